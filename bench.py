@@ -17,7 +17,14 @@ over RCCL, or all-gathered with --traj all_gather + statistics sum, trajectory.p
 collectives still run, in a one-rank RCCL group (--rccl-world1).
 `--dry-run` checks the launch on gloo without a GPU.
 
-Extra objects on the JSON line:
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the
+line's headline fields (metric, value, unit, ms_per_step, ...). `--dump-outputs DIR` also writes what the
+last timed step returned (root visit distributions, root values, the initial inference's outputs) as
+DIR/<name>.npy; inputs, weights and seeds depend on the arguments alone, so two builds can be compared
+output for output. Everything below runs only with `--full`.
+
+Extra objects on the JSON line with `--full` (beside the step's sanity check: tie_stream_errors, search_diag;
+config 5's collect step in 'config5'; configs 1, 3, 4 in 'config1' / 'config3' / 'config4'):
   roofline     - dominant HIP kernel of the step: algorithmic work per launch / its live HIP-event
                  duration vs the peak (fused: fp32 FLOPs vs the fp32 VALU peak — the network runs on
                  v_pk_fma_f32, MFMA utilisation 0 —, plus the L2 weight stream; generic: bytes vs
@@ -85,6 +92,15 @@ def parse():
                         "'config4' objects, each with its roofline and CPU baseline); 'none' skips them")
     p.add_argument("--dry-run", action="store_true",
                    help="launcher check without a GPU: the ranks join a gloo group and rank 0 prints who joined")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also run everything else the line can hold: the step's sanity check, "
+                        "the roofline objects (kernel timing runs of their own), the CPU baselines, config 5's "
+                        "collect step (--secondary) and configs 1, 3, 4 (--configs). Without it the run sets up, "
+                        "warms up, times --steps steps and prints the headline fields")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step returned to its caller (root visit "
+                        "distributions, root values, the initial inference's outputs) as DIR/<name>.npy, float32 / "
+                        "float64 (rank r > 0 of a multi-GPU run: DIR/<name>.rank<r>.npy)")
     return p.parse_args()
 
 
@@ -228,6 +244,9 @@ class GraphStep:
         out = self.step.step()
         self.last = (out["distributions"], out["values"], None)
 
+    def outputs(self):
+        return self.step.out
+
     def tree(self):
         return self.step.roots.tree
 
@@ -255,6 +274,9 @@ class CollectStep:
         self.col.step()
         out = self.col.search.out
         self.last = (out["distributions"], out["values"], None)
+
+    def outputs(self):
+        return self.col.search.out
 
     def finish(self, world):
         """the episodes finished since the last call: packed on the device (lzm_episodes_*) and, under a
@@ -309,6 +331,9 @@ class GpuStep:
             self.last = (t.distributions(), t.values(), t.search_len)
             self._tree = t
             roots.clear()
+
+    def outputs(self):
+        return dict(distributions=self.last[0], values=self.last[1], search_len=self.last[2])
 
     def tree(self):
         return self._tree
@@ -732,6 +757,32 @@ def cpu_baseline(B, S, zero_heads, secs, device):
 BF16_PEAK_TFLOPS = 2500.0  # MI355X dense BF16 = FP16 MFMA (MI355X_MICROARCH.md: the F16 forms take the same cycles; not the 2:1-sparse figure)
 
 
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs: all files of one rank together, their .npy headers included
+NPY_HEADER_BYTES = 256  # allowance per file (numpy writes 128 for these shapes)
+
+
+def dump_outputs(path, outputs, rank):
+    """--dump-outputs: the tensors of the last timed step's output dict as <path>/<name>.npy — floating
+    tensors as float32 (float64 stays), integer ones as float64 (exact). An array over its share of
+    DUMP_MAX_BYTES is stored as a fixed sample: the elements at sorted flat indices drawn once from
+    default_rng(0), the same for every run. Inputs, weights and traverse seeds are seeded by the
+    arguments alone, so two runs with the same arguments write the same step's outputs."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v for k, v in outputs.items() if isinstance(v, torch.Tensor)}
+    share = DUMP_MAX_BYTES // max(1, len(arrays)) - NPY_HEADER_BYTES
+    suffix = f".rank{rank}" if rank else ""
+    written = {}
+    for name, t in sorted(arrays.items()):
+        t = t.detach()
+        a = (t.double() if not t.is_floating_point() or t.dtype == torch.float64 else t.float()).cpu().numpy()
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
+        written[name] = {"shape": list(a.shape), "dtype": str(a.dtype)}
+    return written
+
+
 def make_step(args, workload, model, device, rank):
     B, S = args.envs, args.sims
     if args.path == "fused" and args.step == "graph":
@@ -744,23 +795,57 @@ def make_step(args, workload, model, device, rank):
     return GpuStep(B, S, model, device, args.rng, args.graph, seed=shard_seed(rank), fused=args.path == "fused")
 
 
+# collect steps: an env keeps episode_slots finished episodes between trajectory returns (CollectStep: 8 for the
+# Atari stand-ins, whose episodes last >= 17 (Breakout) / >= 21 (Pong) steps; 64 for CartPole, >= 8 steps), so
+# 100 steps never fill them
+COLLECT_RETURN_EVERY = 100
+# --full's other configs follow --steps up to this many timed steps each (a long headline run does not
+# multiply their time: Pong's collect step takes ~3 ms)
+EXTRA_MAX_STEPS = 1000
+
+
+TRAJ_SUMMED = ("episodes_received", "episodes_all_ranks", "rows_received", "payload_bytes_received", "total_envstep",
+               "collective_ms", "wire_bytes_sent", "wire_bytes_received")
+
+
+def sum_returns(parts):
+    """one trajectory summary of a timed region's returns (CollectStep.finish): the last one's descriptive
+    fields, the TRAJ_SUMMED counts added up (None, no process group, stays None), and their number"""
+    out = dict(parts[-1], returns=len(parts))
+    for k in TRAJ_SUMMED:
+        if out[k] is not None:
+            out[k] = type(out[k])(sum(p[k] for p in parts))
+    if out["collective_ms"] is not None:
+        out["collective_ms"] = round(out["collective_ms"], 3)
+    return out
+
+
 def timed_run(step, steps, warmup, world, device):
     """W untimed steps, then K timed ones between barrier + synchronize pairs; collect mode ends the
-    timed region with the trajectory return. Returns (slowest rank's seconds, trajectory summary)."""
-    for _ in range(warmup):
+    timed region with the trajectory return, and a run longer than COLLECT_RETURN_EVERY steps also returns
+    its trajectories every that many steps, before an env can fill its episode slots (the summary's counts,
+    bytes and collective time are sums over the `returns` returns of the timed region). Returns (slowest
+    rank's seconds, trajectory summary)."""
+    collect = hasattr(step, "finish")
+    for i in range(warmup):
         step()
-    if hasattr(step, "finish"):
+        if collect and (i + 1) % COLLECT_RETURN_EVERY == 0:
+            step.finish(world)
+    if collect:
         step.finish(world)  # (episodes of the warmup steps, untimed)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    parts = []
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for i in range(steps):
         step()
+        if collect and (i + 1) % COLLECT_RETURN_EVERY == 0 and i + 1 < steps:
+            parts.append(step.finish(world))
     # collect mode: the trajectory return ends the timed region (pack the episodes finished in
     # it on the device, return them over RCCL, sum-reduce the collector statistics)
-    traj = step.finish(world) if hasattr(step, "finish") else None
+    traj = sum_returns(parts + [step.finish(world)]) if collect else None
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -893,7 +978,7 @@ def secondary_breakout(args, world, rank, device):
     B, S = args.envs, args.sims
     # enough env steps that episodes (tens of steps) finish inside the timed region and the trajectory
     # return moves real image payloads
-    steps = max(args.steps, 100)
+    steps = min(max(args.steps, 100), EXTRA_MAX_STEPS)
     model = build_conv_model(device, seed=0)
     step = CollectStep(B, S, model, device, args.rng, seed=shard_seed(rank), workload="breakout",
                        dst=0 if args.traj == "gather" else None)
@@ -1003,7 +1088,7 @@ def config1(args, device, cpu):
     B, S = 8, 25
     model = build_model(device, args.zero_heads, seed=0)
     step = GraphStep(B, S, model, device, args.rng, seed=shard_seed(0))
-    steps = max(args.steps, 50)
+    steps = min(max(args.steps, 50), EXTRA_MAX_STEPS)
     el, _ = timed_run(step, steps, args.warmup, 1, device)
     tie, sdiag = check_step(step, S, True)
     out = {"workload": f"CartPole-v0 MuZero (BASELINE.json config 1 shape), {B} envs x {S} sims, MuZeroModelMLP",
@@ -1026,7 +1111,7 @@ def config3(args, device, cpu):
     model = build_ez_model(device, seed=0, zero_heads=args.zero_heads)
     step = CollectStep(B, S, model, device, args.rng, seed=shard_seed(0), workload="pong",
                        dst=0 if args.traj == "gather" else None)
-    steps = max(args.steps, 100)
+    steps = min(max(args.steps, 100), EXTRA_MAX_STEPS)
     world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     el, traj = timed_run(step, steps, args.warmup, world, device)
     tie, sdiag = check_step(step, S, True)
@@ -1060,7 +1145,7 @@ def config4(args, device, cpu):
     ds = torch.from_numpy(starts).to(device)
     m = AlphaZeroMCTS(9, S, 19652, 1.25, 0.3, 0.25, device=device)
     fnet = FusedAZNet(model)
-    steps = max(args.steps, 20)
+    steps = min(max(args.steps, 20), EXTRA_MAX_STEPS)
     with torch.no_grad():
         for _ in range(args.warmup):
             m.search_fused(db, ds, fnet, 1.0, True)
@@ -1122,7 +1207,8 @@ def main():
     if world > 1:
         torch.cuda.set_device(local)
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-    elif args.rccl_world1:
+    elif args.rccl_world1 and (args.full or (args.path == "fused" and args.step == "collect")):
+        # (only where a collect step runs: the headline in --step collect, --full's config 5 / config 3)
         # one-rank RCCL group (a private in-memory store: no rendezvous), so the collect steps' trajectory
         # return runs the 8-GPU node's RCCL calls; the headline search has no collective in its timed region
         torch.cuda.set_device(local)
@@ -1146,17 +1232,19 @@ def main():
     step = make_step(args, wl, model, device, rank)
     el, traj = timed_run(step, args.steps, args.warmup, world, device)
     value = whole_job_rate(B, S, args.steps, world, el)
-    tie_errors, sdiag = check_step(step, S, args.path == "fused")
+    dumped = dump_outputs(args.dump_outputs, step.outputs(), rank) if args.dump_outputs else None
+    full = args.full
+    tie_errors, sdiag = check_step(step, S, args.path == "fused") if full else (None, None)
 
     roofline = None
     cpu = None
-    if rank == 0:
+    if rank == 0 and full:
         roofline = mlp_roofline(step, B, S, device) if wl == "cartpole" else conv_roofline(step, model, B, S, device)
         if world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(B, S, args.zero_heads, args.cpu_baseline_secs, device) if wl == "cartpole" else \
                 cpu_baseline_conv("mz", B, S, model, args.cpu_baseline_secs, device)
     config5 = None
-    if wl == "cartpole" and args.secondary == "breakout" and args.path == "fused":
+    if full and wl == "cartpole" and args.secondary == "breakout" and args.path == "fused":
         del step
         torch.cuda.empty_cache()
         config5 = secondary_breakout(args, world, rank, device)
@@ -1165,7 +1253,7 @@ def main():
                                                         0.5 * args.cpu_baseline_secs, device)
     extra = {}
     wanted = [c for c in args.configs.split(",") if c and c != "none"]
-    if wl == "cartpole" and args.path == "fused" and world == 1:
+    if full and wl == "cartpole" and args.path == "fused" and world == 1:
         # the single-GPU configs of BASELINE.json beside the headline (the SCALE runs, N > 1, skip them)
         for c in wanted:
             fn = {"1": config1, "3": config3, "4": config4}[c]
@@ -1177,7 +1265,7 @@ def main():
         line = {"metric": metric,
                 "value": round(value, 1), "unit": "sims/s", "n_gpus": world, "steps": args.steps,
                 "warmup": args.warmup, "ms_per_step": round(el / args.steps * 1e3, 4), "higher_is_better": True,
-                "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+                "scaling": "weak", "vs_baseline": None, "dtype": "f32", "full": full, "outputs": dumped,
                 "data": "synthetic" if wl == "cartpole" else "synthetic (random-init conv MuZeroModel, synthetic frames)",
                 "config": {"workload": workload_name(wl, B, S, world),
                            "global_batch": world * B, "num_simulations": S, "rng": args.rng,

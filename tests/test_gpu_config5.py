@@ -173,20 +173,41 @@ def test_folded_initial_inference_matches_module_on_gpu():
 
 
 def test_bench_breakout_workload_line(tmp_path):
-    """`bench.py --workload breakout` (config 5's per-GPU shard) prints one line with the conv roofline"""
+    """`bench.py --workload breakout --full` (config 5's per-GPU shard) prints one line with the conv roofline;
+    `--dump-outputs` writes the last timed step's outputs (every root's visits sum to the simulations)"""
     import json
     import os
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--workload", "breakout", "--steps", "2",
-                        "--warmup", "1", "--envs", "32", "--sims", "8", "--no-cpu-baseline", "--step", "collect"],
+                        "--warmup", "1", "--envs", "32", "--sims", "8", "--no-cpu-baseline", "--step", "collect",
+                        "--full", "--dump-outputs", str(tmp_path / "out")],
                        capture_output=True, text=True, timeout=240, cwd=repo)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert "Breakout MuZero" in line["config"]["workload"] and line["value"] > 0
     assert line["roofline"]["kernel"] == "search_conv_kernel" and line["roofline"]["bound"] == "mfma"
     assert line["tie_stream_errors"] == 0 and line["trajectory"]["frame_dtype"] == "uint8"
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    dist, values = np.load(tmp_path / "out" / "distributions.npy"), np.load(tmp_path / "out" / "values.npy")
+    assert dist.shape == (32, 4) and dist.dtype == np.float64 and (dist.sum(axis=1) == 8).all()
+    assert values.shape == (32,) and values.dtype == np.float32 and np.isfinite(values).all()
+
+
+def test_bench_collect_run_returns_trajectories_every_100_steps():
+    """bench.timed_run over a collect step longer than the episode slots can hold (8 per env, Breakout episodes
+    from 17 steps): the trajectories leave every COLLECT_RETURN_EVERY steps, so pack_new never finds a slot
+    overwritten; 230 timed steps = returns after 100, 200 and at the end, and the summary counts all three:
+    every env step, and every episode the envs finished (none can finish in the 2 warm-up steps)"""
+    step = bench.CollectStep(16, 4, _conv_model(), DEV, "glibc", seed=5, workload="breakout", dst=None)
+    el, traj = bench.timed_run(step, 230, 2, 1, DEV)
+    assert el > 0 and traj["returns"] == 3 and traj["frame_dtype"] == "uint8"
+    assert traj["total_envstep"] == 230 * 16
+    finished = int(step.col.ep_count.sum().item())
+    assert finished > 0 and traj["episodes_received"] == finished
+    assert traj["rows_received"] > finished
+    assert bool((step.last[0].sum(dim=1) == 4).all())
 
 
 @pytest.mark.parametrize("kind,B,cin", [("mz", 37, 4), ("ez", 37, 4), ("mz", 300, 4), ("mz", 45, 3), ("mz", 29, 7)])

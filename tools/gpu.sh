@@ -3,7 +3,8 @@
 #   tests:<pytest args, comma-separated>   e.g. tests:tests/test_gpu_config5.py,-k,breakout
 #   alltests                              the whole -m gpu suite
 #   smoke                                 __graft_entry__.smoke()
-#   bench:<bench.py args, comma-separated> one bench line into <out>/bench_<n>.json
+#   bench:<bench.py args, comma-separated> one bench line into <out>/bench_<n>.json (pass --full for the line
+#                                         with roofline, CPU baselines and configs 1, 3, 4, 5; else the headline alone)
 #   conv:<mz|ez>[,args]                   tools/conv_bench.py line
 #   profile                               tools/profile_round.sh into <out>
 #   cmd:<command, comma-separated>        any other command (own timeout 300 s)

@@ -13,5 +13,5 @@ for rep in 1 2; do
     python3 -c "import json;e=json.loads(open('$out/c3_${v}_$rep.json').read().strip().splitlines()[-1]);print('$v', $rep, 'ez', e['value'], e.get('ms_per_search'))" >> $out/summary.txt
   done
 done
-timeout -k 10 300 python bench.py > $out/bench.json 2>&1
+timeout -k 10 300 python bench.py --full > $out/bench.json 2>&1
 cat $out/summary.txt

@@ -19,13 +19,13 @@ for k in mz ez; do
 done
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/trace_conv_mz -o conv_mz --output-format csv -- \
   python3 tools/conv_bench.py --kind mz --searches 3 > $out/trace_conv_mz.log 2>&1
-timeout -k 10 200 python bench.py --no-cpu-baseline --secondary none --rng philox > $out/bench_philox.json 2>&1
-timeout -k 10 200 python bench.py --no-cpu-baseline --secondary none --zero-heads > $out/bench_zero_heads.json 2>&1
-timeout -k 10 200 python bench.py --step collect --secondary none --no-cpu-baseline > $out/bench_collect.json 2>$out/bench_collect.err
-timeout -k 10 300 python bench.py --workload breakout --cpu-baseline-secs 30 > $out/bench_breakout.json 2>$out/bench_breakout.err
+timeout -k 10 200 python bench.py --full --no-cpu-baseline --secondary none --rng philox > $out/bench_philox.json 2>&1
+timeout -k 10 200 python bench.py --full --no-cpu-baseline --secondary none --zero-heads > $out/bench_zero_heads.json 2>&1
+timeout -k 10 200 python bench.py --full --step collect --secondary none --no-cpu-baseline > $out/bench_collect.json 2>$out/bench_collect.err
+timeout -k 10 300 python bench.py --full --workload breakout --cpu-baseline-secs 30 > $out/bench_breakout.json 2>$out/bench_breakout.err
 # config 1 (8 envs x 25 sims): the GPU search at that shape and the pure-Python ptree restatement on
 # this box's host (1 thread, MLP on torch-CPU)
-timeout -k 10 120 python bench.py --envs 8 --sims 25 --no-cpu-baseline --secondary none > $out/bench_c1_gpu.json 2>$out/bench_c1_gpu.err
+timeout -k 10 120 python bench.py --full --envs 8 --sims 25 --no-cpu-baseline --secondary none > $out/bench_c1_gpu.json 2>$out/bench_c1_gpu.err
 timeout -k 10 120 python tools/ptree_bench.py --secs 15 > $out/ptree_c1_cpu.json 2>$out/ptree_c1_cpu.err
 timeout -k 10 150 python tools/phase_timing.py > $out/phase_timing.txt 2>&1
 timeout -k 10 150 python tools/phase_timing.py --zero-heads > $out/phase_timing_zero_heads.txt 2>&1

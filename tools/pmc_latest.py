@@ -35,7 +35,7 @@ def summarise(root, pat):
     req = (per.get("TCC_HIT_sum", 0.0) + per.get("TCC_MISS_sum", 0.0))
     return {
         "kernel": kname,
-        "command": "python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline (one rocprofv3 --kernel-trace --pmc pass per group)",
+        "command": "python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline (one rocprofv3 --kernel-trace --pmc pass per group)",
         "per_dispatch": per,
         "fetch_bytes_corrected": int(fetch),
         "write_bytes": int(write),
