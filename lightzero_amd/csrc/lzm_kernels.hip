@@ -1819,7 +1819,10 @@ int lzm_search_mlp(lzm_handle *h, int hidden, int head_hidden, int support, int 
       res_net(n, weights + round4(kernel_layout(kls, nkl, lay_w, lay_b)), A);
       const char *sm = getenv("LZM_RES_SELECT");
       // measured: 4 < 1 < 0 < 2 < 3; 4 is 1 with the two-action walk for A == 2
-      n.select_mode = sm ? atoi(sm) : (A == 2 ? 4 : 1);
+      // 5 is 4 with the walk on the terms pass's registers: one node per lane of wave 0, so it serves
+      // S + 2 <= 64 (a path is then at most S levels: it fits the wave's lanes); larger searches run mode 4
+      n.select_mode = sm ? atoi(sm) : (A == 2 ? 5 : 1);
+      if (n.select_mode == 5 && (A != 2 || S + 2 > 64 || h->depth_cap < S + 2)) n.select_mode = 4;
       // LZM_RES_SPEC=1 (parity mode): evaluate two-way leaf ties speculatively as a second network
       // row instead of waiting for the look-back (measured slower: every simulation pays the row)
       const char *sl = getenv("LZM_RES_LATE");
@@ -1833,8 +1836,11 @@ int lzm_search_mlp(lzm_handle *h, int hidden, int head_hidden, int support, int 
       const int md = (n.select_mode == 4 && A != 2) ? 1 : n.select_mode;
       void (*fn)(SearchArgs, ResNet) =
           spec                  ? search_res_kernel<2, 1, 0, false>
-          : (md != 1 && md != 4) || !n.spec_depth ? search_res_kernel<1, -1, -1, true>
-          : q.phase             ? (md == 4 ? search_res_kernel<1, 4, -1, true> : search_res_kernel<1, 1, -1, true>)
+          : (md != 1 && md != 4 && md != 5) || !n.spec_depth ? search_res_kernel<1, -1, -1, true>
+          : q.phase             ? (md == 5   ? search_res_kernel<1, 5, -1, true>
+                                   : md == 4 ? search_res_kernel<1, 4, -1, true>
+                                             : search_res_kernel<1, 1, -1, true>)
+          : md == 5             ? (fast ? search_res_kernel<1, 5, 1, false> : search_res_kernel<1, 5, 0, false>)
           : md == 4             ? (fast ? search_res_kernel<1, 4, 1, false> : search_res_kernel<1, 4, 0, false>)
                                 : (fast ? search_res_kernel<1, 1, 1, false> : search_res_kernel<1, 1, 0, false>);
       hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

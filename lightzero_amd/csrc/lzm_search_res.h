@@ -85,6 +85,11 @@ constexpr int kDwinBack = 20;  // draw window [base_prev - kDwinBack, base_prev 
 #ifndef LZM_RES_SPEC_PATH
 #define LZM_RES_SPEC_PATH 1
 #endif
+// LZM_RES_R5_BAR2 (default 0, selection mode 5): keep the barrier between the terms pass and the walk
+// (an A/B switch: with S + 2 <= 64 the pass runs in wave 0 alone, which is also the walk's wave).
+#ifndef LZM_RES_R5_BAR2
+#define LZM_RES_R5_BAR2 0
+#endif
 
 // Part `part` (0..2: coefficient words 11 part .. 11 part + 10) of the window's 64 dot products, added
 // to win (the sums are mod 2^32, so the three waves' LDS adds may land in any order); win must be zero
@@ -341,14 +346,27 @@ __device__ __forceinline__ void support_logits(const float *h, const float4 *P, 
 // children visited, or a single legal child): 0 / 1 = the legal position cselect_child picks,
 // 3 = a tie between the two visited children (a draw decides), 2 = depends on the walk's mean-q
 // (an unvisited child scores the normalised parent mean-q). Same operations as the walk's scores.
+// 4 = a leaf tie: both children unvisited (so unexpanded) with bitwise-equal finite prior scores. An
+// unvisited child scores x + vu with the walk's normalised mean-q vu, so with equal x the two scores
+// are the same float for any non-NaN vu: M = s0 = s1, cselect_child's rule picks position 0 and
+// lists position 1 (s1 >= M - 1e-6) — the tie {0, 1} whatever the mean-q is. (A fresh node has
+// N = visit - 1 = 0, so both priors are pb_c * sqrtf(0) * prior = +0: every fresh node is one.) With
+// a NaN vu the reference picks position 1 without a draw: the walk may use this code only when no
+// NaN can reach vu (terms_finite_a2r); the LDS table dec[] keeps the walk-dependent code 2 for it.
 __device__ __forceinline__ int a2_decision(float4 c0, float4 c1, int n) {
   if (n < 2) return 0;
+  if (!__float_as_int(c0.w) && !__float_as_int(c1.w) && __float_as_int(c0.z) < 0 && __float_as_int(c1.z) < 0 &&
+      __float_as_int(c0.x) == __float_as_int(c1.x) && (__float_as_int(c0.x) & 0x7f800000) != 0x7f800000)
+    return 4;
   if (!__float_as_int(c0.w) || !__float_as_int(c1.w)) return 2;
   const float s0 = c0.x + c0.y, s1 = c1.x + c1.y;
   const float M = fmaxf(s0, s1);
   const int r = (s0 == M) ? 0 : 1;
   return (r == 0 && s1 >= M - 0.000001f) ? 3 : r;
 }
+// the code the LDS table dec[] holds (descend_a2, descend_a2f, speculate_depth_a2: a leaf tie is
+// scored with the mean-q like any node with an unvisited child)
+__device__ __forceinline__ int a2_table_code(int d) { return d == 4 ? 2 : d; }
 
 // ---- selection split in two (MuZero, tree slice in LDS, one root):
 // (1) every expanded node's pUCT terms that do not depend on the walk, one thread per node
@@ -395,7 +413,7 @@ __device__ inline void node_terms(const TreeView &t, int L, int n, float2 *nq, f
       if (j < 2) c01[j] = term;
     }
     nq[L] = make_float2(total_q, __int_as_float(total_v));
-    if (dec) dec[L] = (t.A == 2 && nleg >= 1) ? a2_decision(c01[0], c01[nleg > 1 ? 1 : 0], nleg) : 2;
+    if (dec) dec[L] = (t.A == 2 && nleg >= 1) ? a2_table_code(a2_decision(c01[0], c01[nleg > 1 ? 1 : 0], nleg)) : 2;
   }
 }
 __device__ inline void precompute_terms(const TreeView &t, int nlat, const int *lat2node, float2 *nq, float4 *cs,
@@ -406,15 +424,28 @@ __device__ inline void precompute_terms(const TreeView &t, int nlat, const int *
   }
 }
 
+// A2Rec: one expanded node's record as the register walk (descend_a2r) reads it from the lane that
+// computed it. pk: bits 0-2 a2_decision's code, bit 3 / 4 child 0 / 1 visited, bits 5-6 total_v,
+// then three latents as signed bytes (-1: unexpanded; latents < 64): bits 8-15 the decided child's
+// (code 0 / 1: what the chase follows, one s_bfe_i32), bits 16-23 / 24-31 child 0 / 1's; tq = total_q;
+// x0, y0, x1, y1 = the children's prior score and value term (cs[].x, cs[].y).
+struct A2Rec {
+  int pk;
+  float tq, x0, y0, x1, y1;
+};
+__device__ __forceinline__ int a2rec_pack(int d, bool vis0, bool vis1, int total_v, int l0, int l1) {
+  return d | (vis0 ? 8 : 0) | (vis1 ? 16 : 0) | (total_v << 5) | (((d == 1 ? l1 : l0) & 0xff) << 8) | ((l0 & 0xff) << 16) |
+         (int)((unsigned)(l1 & 0xff) << 24);
+}
 // node_terms for two actions, written for few LDS round trips: a child's slot depends on the latent
 // only (1 + 2 L + legal position; the root, latent 0, takes its legal actions from registers), so
 // both children's records are read with the latent -> node map, the node's visit count next, then
 // the pb_c table row; every read is unconditional and the branches are selects. Same float
-// operations in the same order as node_terms (so the same bits), and also dec[L].
-__device__ inline void precompute_terms_a2(const TreeView &t, int nlat, const int *lat2node, float2 *nq, float4 *cs,
-                                           float4 mm, int players, float disc, int *dec, const int *rleg,
-                                           int nleg_root) {
-  for (int L = threadIdx.x; L < nlat; L += kRT) {
+// operations in the same order as node_terms (so the same bits), and also dec[L] and, when rec is
+// given, the node's record in the calling lane's registers.
+__device__ inline void node_terms_a2(const TreeView &t, int L, const int *lat2node, float2 *nq, float4 *cs, float4 mm,
+                                     int players, float disc, int *dec, const int *rleg, int nleg_root, A2Rec *rec) {
+  {
     const int n = lat2node[L];
     const bool root = L == 0;
     const int nleg = root ? nleg_root : 2;
@@ -424,7 +455,7 @@ __device__ inline void precompute_terms_a2(const TreeView &t, int nlat, const in
     const NodeStat s0 = t.stat[c0], s1 = t.stat[c1];
     const float v0 = t.val[c0], v1 = t.val[c1];
     const int l0 = t.meta[c0].latent, l1 = t.meta[c1].latent;
-    if (n < 0) continue;
+    if (n < 0) return;
     int N = t.stat[n].visit - 1;
     N = N < 0 ? 0 : (N >= t.lut_n ? t.lut_n - 1 : N);
     const float2 Lx = t.lut[N];
@@ -461,8 +492,19 @@ __device__ inline void precompute_terms_a2(const TreeView &t, int nlat, const in
     if (nleg > 0) cs[c0] = t0;
     if (nleg > 1) cs[c1] = t1;
     nq[L] = make_float2(total_q, __int_as_float(total_v));
-    dec[L] = nleg >= 1 ? a2_decision(t0, nleg > 1 ? t1 : t0, nleg) : 2;
+    const int d = nleg >= 1 ? a2_decision(t0, nleg > 1 ? t1 : t0, nleg) : 2;
+    dec[L] = a2_table_code(d);
+    if (rec) {
+      rec->pk = a2rec_pack(d, s0.visit > 0, s1.visit > 0, total_v, l0, l1);
+      rec->tq = total_q; rec->x0 = t0.x; rec->y0 = t0.y; rec->x1 = t1.x; rec->y1 = t1.y;
+    }
   }
+}
+__device__ inline void precompute_terms_a2(const TreeView &t, int nlat, const int *lat2node, float2 *nq, float4 *cs,
+                                           float4 mm, int players, float disc, int *dec, const int *rleg,
+                                           int nleg_root) {
+  for (int L = threadIdx.x; L < nlat; L += kRT)
+    node_terms_a2(t, L, lat2node, nq, cs, mm, players, disc, dec, rleg, nleg_root, nullptr);
 }
 
 // The walk over the precomputed terms (descend_wave's contract and outputs; wave 0).
@@ -967,6 +1009,174 @@ __device__ inline Descent descend_a2f(const TreeView &t, const float2 *nq, const
   return d;
 }
 
+// The NaN guard of descend_a2r's leaf-tie shortcut (wave 0, after the terms pass): every expanded
+// node's total_q and the min-max bounds are finite. The mean-q chain's operands are then sums of
+// finite terms over positive counts, so no NaN reaches a level's vu, and a leaf tie is the tie {0, 1}.
+__device__ __forceinline__ bool terms_finite_a2r(const A2Rec &rc, float4 mm) {
+  const auto fin = [](float v) { return (__float_as_int(v) & 0x7f800000) != 0x7f800000; };
+  return __ballot(!fin(rc.tq)) == 0ull && fin(mm.x) && fin(mm.y) && fin(mm.z);
+}
+
+// The walk on the terms pass's registers (selection mode 5; S + 2 <= 64, so lane L of wave 0 holds
+// the record of the node with latent L): a chase of v_readlane reads with the current latent in a
+// scalar register, no LDS read per level. A decided level (code 0 / 1) only moves the pointer; a
+// leaf tie (code 4, when leaf_ok: terms_finite_a2r) ends the walk with no floating-point work. The
+// mean-q chain is evaluated only where its value is read — a node with an unvisited child (code
+// 2), a tie between visited children (code 3: the resume needs WalkState::parent_q) — by settle():
+// the same divisions, in level order, over the (total_q, total_v) of the path's levels, so the same
+// bits as descend_a2's level-by-level chain. The path is collected in lanes (lane l: level l's
+// latent and action) and stored once. Same outputs as descend_a2f (Descent, TieInfo, at_tie, path,
+// path_act), every lane returns the same values. With !leaf_ok a leaf tie is scored like code 2:
+// the walk then does what descend_a2 does at every level.
+template <bool CLASSIFY, typename Draw>
+__device__ inline Descent descend_a2r(const TreeView &t, const A2Rec &rc, bool leaf_ok, float4 mm, int vtp, int players,
+                                      const int *rleg, int nleg, Draw draw, TieInfo *tie, WalkState *at_tie = nullptr) {
+  const int lane = threadIdx.x & 63;
+  const int dmax = t.depth_cap - 1;
+  const int lat0 = __builtin_amdgcn_readfirstlane(t.meta[0].latent);
+  int lat = lat0, len = 0;
+  int plev = 0, pact = 0;  // lane l: the latent and the action of level l
+  float parent_q = 0.0f;
+  int pend = 0;  // the chain is settled through level pend - 1
+  const auto rl = [](int v, int l) { return __builtin_amdgcn_readlane(v, l); };
+  const auto rlf = [](float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); };
+  const auto child = [](int pk, int j) { return (int)((unsigned)pk << (8 - 8 * j)) >> 24; };  // (signed bytes)
+  const auto decided = [](int pk) { return (int)((unsigned)pk << 16) >> 24; };
+  auto step = [&](int action, int nlat) {  // cross the level at lat
+    plev = lane == len ? lat : plev;
+    pact = lane == len ? action : pact;
+    ++len;
+    lat = nlat;
+  };
+  // the last level crossed (len > 0): the leaf's parent latent and the action taken there
+  const auto plat_of = [&]() { return len > 0 ? rl(plev, len - 1) : -1; };
+  const auto act_of = [&]() { return len > 0 ? rl(pact, len - 1) : -1; };
+  auto settle = [&](int upto) {
+    for (int l = pend; l < upto; ++l) {
+      const int Ls = rl(plev, l);
+      const float tq = rlf(rc.tq, Ls);
+      const int tv = (rl(rc.pk, Ls) >> 5) & 3;
+      parent_q = (l == 0 && tv > 0) ? tq / (float)tv : (parent_q + tq) / (float)(tv + 1);
+    }
+    pend = upto > pend ? upto : pend;
+  };
+  auto flush = [&]() {
+    if (lane == 0) t.path[0] = 0;
+    if (lane < len) {
+      t.path_act[lane] = pact;
+      t.path[lane + 1] = 1 + 2 * plev + pact;
+    }
+  };
+  if (CLASSIFY) tie->status = 0;
+  // A lone wave issues its instructions one after the other, so a level costs what its instruction
+  // count costs (walk_ubench): the decided levels run in a loop of their own (the chase proper: about
+  // fifteen instructions a level, the state two scalars) and only a level the chase stops at (pk, dl: a leaf
+  // tie, an unvisited child, a tie between visited children) takes the general body. The chase needs
+  // no depth check: it crosses expanded nodes only, at most S of them, and depth_cap >= S + 2 (host).
+  int pk = 0, dl = 0;
+  bool stop = false;
+  if (lat >= 0 && len < dmax) {  // the root: legal position j is action rleg[j]
+    pk = rl(rc.pk, lat);
+    dl = pk & 7;
+    if (dl <= 1)
+      step(rleg[dl], decided(pk));
+    else
+      stop = true;
+  }
+  for (;;) {
+    if (!stop && lat >= 0) {
+      for (;;) {
+        pk = rl(rc.pk, lat);
+        dl = pk & 7;
+        if (dl > 1) {
+          stop = true;
+          break;
+        }
+        step(dl, decided(pk));
+        if (lat < 0) break;
+      }
+    }
+    if (!stop || len >= dmax) break;  // a leaf (or the depth cap)
+    stop = false;
+    const bool root = len == 0;
+    int jsel = 0;
+    if (dl == 4 && leaf_ok) {
+      // a leaf tie: the tie {0, 1} whatever the mean-q is (a2_decision)
+      if (CLASSIFY) {
+        flush();
+        const int vt = (players > 1 && (len & 1)) ? ((vtp == 1) ? 2 : 1) : vtp;
+        tie->status = 1;
+        tie->level = len;
+        tie->mask = 3ull;
+        Descent d;
+        d.len = len + 1;
+        d.x = lat;
+        d.action = -1;
+        d.vtp = players > 1 ? ((vt == 1) ? 2 : 1) : vt;
+        d.leaf = -1;
+        return d;
+      }
+      jsel = __builtin_amdgcn_readfirstlane((int)(draw(len) % 2u));
+    } else {
+      settle(len);
+      bool tie2 = dl == 3;
+      float mean_q = 0.0f;
+      if (dl != 3) {  // an unvisited child scores the normalised mean-q (code 2; 4 without leaf_ok)
+        const float delta = mm.x - mm.y;
+        const bool scale = delta > 0;
+        const float div = (delta < mm.z) ? mm.z : delta;
+        const float tq = rlf(rc.tq, lat);
+        const int tv = (pk >> 5) & 3;
+        mean_q = (root && tv > 0) ? tq / (float)tv : (parent_q + tq) / (float)(tv + 1);
+        float vu = mm_norm_fixed(scale, mm.y, div, mean_q);
+        if (vu < 0) vu = 0;
+        if (vu > 1) vu = 1;
+        const float s0 = rlf(rc.x0, lat) + ((pk & 8) ? rlf(rc.y0, lat) : vu);
+        const float s1 = rlf(rc.x1, lat) + ((pk & 16) ? rlf(rc.y1, lat) : vu);
+        const float M = fmaxf(s0, s1);
+        const int j = (s0 == M) ? 0 : 1;
+        jsel = __builtin_amdgcn_readfirstlane(j);
+        tie2 = __builtin_amdgcn_readfirstlane((j == 0 && s1 >= M - 0.000001f) ? 1 : 0) != 0;
+      }
+      if (CLASSIFY && tie2) {
+        const int vt = (players > 1 && (len & 1)) ? ((vtp == 1) ? 2 : 1) : vtp;  // (one flip per level above)
+        const bool all_leaves = ((unsigned)pk >> 16) == 0xffffu;
+        if (at_tie && !all_leaves) {  // (read by the status-2 resume only)
+          const int plat = plat_of(), last_action = act_of();
+          at_tie->node = root ? 0 : 1 + 2 * plat + last_action; at_tie->lat = lat; at_tie->len = len; at_tie->plat = plat;
+          at_tie->last_action = last_action; at_tie->is_root = root; at_tie->vtp = vt; at_tie->parent_q = parent_q;
+        }
+        flush();
+        tie->status = all_leaves ? 1 : 2;
+        tie->level = len;
+        tie->mask = 3ull;
+        Descent d;
+        d.len = len + 1;
+        d.x = lat;
+        d.action = -1;
+        d.vtp = players > 1 ? ((vt == 1) ? 2 : 1) : vt;
+        d.leaf = -1;
+        return d;
+      }
+      if (!CLASSIFY && tie2) jsel = __builtin_amdgcn_readfirstlane((int)(draw(len) % 2u));
+      if (dl != 3) {
+        parent_q = mean_q;
+        pend = len + 1;
+      }
+    }
+    step(root ? rleg[jsel] : jsel, child(pk, jsel));
+  }
+  flush();
+  const int plat = plat_of(), last_action = act_of();
+  Descent d;
+  d.len = len;
+  d.x = plat;
+  d.action = last_action;
+  d.vtp = (players > 1 && (len & 1)) ? ((vtp == 1) ? 2 : 1) : vtp;
+  d.leaf = len == 0 ? 0 : 1 + 2 * plat + last_action;
+  return d;
+}
+
 // descend_terms by one lane: the reference's sequential tie-list scan (cselect_child,
 // cnode.cpp:551-596) over the precomputed terms, no cross-lane operations.
 template <bool CLASSIFY, typename Draw>
@@ -1259,7 +1469,7 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   if (RNG >= 0) p.fast = RNG;
   const ResPlan L = n.plan;
   if (SMODE >= 0) n.select_mode = SMODE;
-  if (SMODE == 4 && RNG == 0 && !STAMPS) n.spec_depth = 1;  // production parity kernel
+  if ((SMODE == 4 || SMODE == 5) && RNG == 0 && !STAMPS) n.spec_depth = 1;  // production parity kernel
   extern __shared__ float4 smem4[];
   float *smem = reinterpret_cast<float *>(smem4);
   const int tid = threadIdx.x, g = blockIdx.x, G = gridDim.x, lane = tid & 63, wid = tid >> 6;
@@ -1424,16 +1634,26 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const uint32_t seed = s_seeds[k];
     if (!LZM_RES_SEEDW1 && !p.fast) seed_state_parallel(seed, s_pow, s_z0);
     // ---- selection, part 1: every expanded node's walk-independent pUCT terms (all threads)
-    // 0: descend_wave; 1: terms + wave walk; 2: terms + lane walk; 3: descend_slice; 4 (default):
-    // terms + descend_small when A <= 2, else as 1
-    const int smode = (n.select_mode == 4 && A != 2) ? 1 : n.select_mode;
+    // 0: descend_wave; 1: terms + wave walk; 2: terms + lane walk; 3: descend_slice; 4: terms + the
+    // two-action walk (descend_a2f) when A == 2, else as 1; 5 (default for A == 2, S + 2 <= 64, chosen
+    // on the host): 4 with the walk on the terms pass's registers (descend_a2r)
+    const bool regwalk = n.select_mode == 5;
+    const int smode = regwalk ? 4 : (n.select_mode == 4 && A != 2) ? 1 : n.select_mode;
+    A2Rec rc = {0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     if (smode == 1 || smode == 2 || smode == 4) {
       __syncthreads();  // the previous simulation's backup (wave 0) and children (wave 1) are complete
-      if (smode == 4)
-        precompute_terms_a2(t, s_nlat + k, L2N, NQ, CS, s_mm, players, p.disc, DEC, rleg, nleg);
-      else
-        precompute_terms(t, s_nlat + k, L2N, NQ, CS, s_mm, players, p.disc, smode == 4 ? DEC : nullptr);
-      __syncthreads();
+      if (regwalk) {
+        // one node per lane, all in wave 0, which alone reads the records (registers) and, after the
+        // walk's barrier, the tables: no barrier between the pass and the walk
+        if (tid < s_nlat + k) node_terms_a2(t, tid, L2N, NQ, CS, s_mm, players, p.disc, DEC, rleg, nleg, &rc);
+        if (LZM_RES_R5_BAR2) __syncthreads();
+      } else {
+        if (smode == 4)
+          precompute_terms_a2(t, s_nlat + k, L2N, NQ, CS, s_mm, players, p.disc, DEC, rleg, nleg);
+        else
+          precompute_terms(t, s_nlat + k, L2N, NQ, CS, s_mm, players, p.disc, smode == 4 ? DEC : nullptr);
+        __syncthreads();
+      }
     }
     LZM_STAMP(12);
     if (wid != 0 && k > 0) res_fetch<kRSlotsD>(res_blk4(n, kRbD), P);  // (see the expand)
@@ -1455,13 +1675,17 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // ---- selection, part 2: the walk (wave 0, one lane per child)
     if (wid == 0) {
       const float4 mm = s_mm;
+      int w_status = 0, w_x = 0;  // (mode 5) the walk's status and x, wave-uniform
       if (p.fast) {
         auto draw = [seed, i](int level) -> uint32_t {
           uint4 o = philox4x32_10(make_uint4((uint32_t)level, (uint32_t)i, 0u, 0u), make_uint2(seed, 0x4c5a4d43u));
           return o.x >> 1;
         };
         Descent d;
-        if (smode == 4) {
+        if (regwalk) {
+          d = descend_a2r<false>(t, rc, terms_finite_a2r(rc, mm), mm, s_vtp, players, rleg, nleg, draw, nullptr);
+          w_x = d.x;
+        } else if (smode == 4) {
           d = descend_a2f<false>(t, NQ, DEC, CS, mm, s_vtp, players, rleg, nleg, draw, nullptr);
         } else if (smode == 1) {
           d = descend_terms<false>(t, NQ, CS, mm, s_vtp, players, draw, nullptr);
@@ -1476,7 +1700,14 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         TieInfo ti;
         auto nodraw = [](int) -> uint32_t { return 0u; };
         Descent d;
-        if (smode == 4) {
+        if (regwalk) {
+          WalkState ws;
+          d = descend_a2r<true>(t, rc, terms_finite_a2r(rc, mm), mm, s_vtp, players, rleg, nleg, nodraw, &ti, &ws);
+          LZM_STAMP(13);
+          if (lane == 0 && ti.status == 2) s_walk = ws;
+          w_status = ti.status;
+          w_x = d.x;
+        } else if (smode == 4) {
           WalkState ws;
           d = descend_a2f<true>(t, NQ, DEC, CS, mm, s_vtp, players, rleg, nleg, nodraw, &ti, &ws);
           LZM_STAMP(13);
@@ -1503,11 +1734,14 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #if LZM_RES_EGATHER
       // gather the leaf's parent latent now, by the walking wave, when the walk's x is final (every
       // status but 2): the walk's barrier then also orders the gather (one barrier fewer)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // lane 0's s_status / s_x to the wave
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      const int stw = __builtin_amdgcn_readfirstlane(s_status);
-      const int x0 = __builtin_amdgcn_readfirstlane(s_x);
+      // (mode 5: straight from the walk's registers, no LDS round trip)
+      if (!regwalk) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // lane 0's s_status / s_x to the wave
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      }
+      const int stw = __builtin_amdgcn_readfirstlane(regwalk ? w_status : s_status);
+      const int x0 = __builtin_amdgcn_readfirstlane(regwalk ? w_x : s_x);
       if (stw != 2 && lane < kRHid / 4)
         reinterpret_cast<float4 *>(X0)[lane + (lane >= kRHid / 8)] =
             reinterpret_cast<const float4 *>(p.pool + ((size_t)max(x0, 0) * B + i) * kRHid)[lane];

@@ -1,5 +1,6 @@
 // Micro-benchmark (diagnostic, not shipped): cycles per level of the resident kernel's selection
-// walk (descend_small<2>, lzm_search_res.h) in isolation, on a synthetic full binary tree in LDS
+// walk (descend_small<2>, descend_a2, descend_a2f, and the register walk descend_a2r as variants 5 and
+// 6: without and with a final settle of the mean-q chain; lzm_search_res.h) in isolation, on a synthetic full binary tree in LDS
 // (depth D, walk ends at a two-way tie among unexpanded children like most real simulations),
 // with NP float4 per lane held live across the walk to emulate the resident kernel's register
 // pressure (its network weights stay in registers for the whole launch).
@@ -31,7 +32,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   for (int e = threadIdx.x; e < CAP; e += 256) cs[e] = gcs[e];
   for (int e = threadIdx.x; e <= NLAT; e += 256) nq[e] = gnq[e];
   __syncthreads();
-  for (int e = threadIdx.x; e <= NLAT; e += 256) dec[e] = a2_decision(cs[1 + 2 * e], cs[2 + 2 * e], 2);
+  for (int e = threadIdx.x; e <= NLAT; e += 256) dec[e] = a2_table_code(a2_decision(cs[1 + 2 * e], cs[2 + 2 * e], 2));
+  // the register walk's record of latent L in lane L of wave 0 (NLAT <= 63), as node_terms_a2 packs it
+  A2Rec rc = {2, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  if (threadIdx.x < NLAT) {
+    const float4 c0 = cs[1 + 2 * threadIdx.x], c1 = cs[2 + 2 * threadIdx.x];
+    const float2 q = nq[threadIdx.x];
+    rc.pk = a2rec_pack(a2_decision(c0, c1, 2), __float_as_int(c0.w) != 0, __float_as_int(c1.w) != 0, __float_as_int(q.y),
+                       __float_as_int(c0.z), __float_as_int(c1.z));
+    rc.tq = q.x; rc.x0 = c0.x; rc.y0 = c0.y; rc.x1 = c1.x; rc.y1 = c1.y;
+  }
   if (threadIdx.x < 2) lg[threadIdx.x] = threadIdx.x;
   if (threadIdx.x == 0) {
     lg[2] = 2;
@@ -58,6 +68,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           ++len;
         }
         acc += len + 1;
+      } else if (V == 5 || V == 6) {
+        // descend_a2r: the chase on registers; 5 ends at the leaf tie without the mean-q, 6 scores the
+        // last node with it (leaf_ok = false: the whole chain settles there, then the two scores)
+        asm volatile("" : "+v"(rc.pk));
+        Descent d = descend_a2r<true>(t, rc, V == 5, mm, vtp, players, rleg, nleg, nodraw, &ti);
+        acc += d.len + ti.status;
       } else {
         Descent d = V == 0 ? descend_small<2, true>(t, nq, cs, mm, vtp, players, rleg, nleg, nodraw, &ti)
                   : V == 1 ? descend_a2<true, decltype(nodraw), 0>(t, nq, dec, cs, mm, vtp, players, rleg, nleg, nodraw, &ti)
@@ -147,6 +163,8 @@ int main() {
   run<0, 1>(dcs, dnq, dc, dout, dpin, G, dmm, dgi);
   run<0, 2>(dcs, dnq, dc, dout, dpin, G, dmm, dgi);
   run<0, 3>(dcs, dnq, dc, dout, dpin, G, dmm, dgi);
+  run<0, 5>(dcs, dnq, dc, dout, dpin, G, dmm, dgi);
+  run<0, 6>(dcs, dnq, dc, dout, dpin, G, dmm, dgi);
 
   return 0;
 }
