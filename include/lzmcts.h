@@ -173,6 +173,17 @@ int lzm_search_set_step(lzm_handle *h, int64_t *count, int64_t base, int increme
  * network: 1 = network-resident (search_res_kernel, lzm_search_res.h: the config-2 shape with one
  * root per workgroup), 0 = weight-streaming (search_mlp_kernel). Host-only, no GPU work. */
 int lzm_search_mlp_kind(int B, int actions, int hidden, int head_hidden, int support, int res_dynamics);
+/* 1 when lzm_mlp_prepare / lzm_search_mlp take this network shape: hidden and head_hidden multiples of 16
+ * up to 1024, support + actions <= 1024, actions <= hidden; 0 otherwise. Host-only, no GPU work. */
+int lzm_search_mlp_supported(int actions, int hidden, int head_hidden, int support);
+/* What lzm_search_mlp(h, ..., num_simulations, ...) launches for this handle as it stands — the function the
+ * launch itself decides with, so the handle's reserved capacities (not num_simulations alone) size the
+ * resident kernel's LDS plan. out int32[4]: {roots per workgroup; kernel: 1 network-resident, 0
+ * weight-streaming, -1 none (the shape, or the LDS it would need, is refused: lzm_search_mlp returns
+ * LZM_ERR_ARG); the resident kernel's selection mode after its downgrades (0 with the streaming kernel);
+ * tree slice in LDS}. Reads the same environment overrides as the launch. Host-only, no GPU work. */
+int lzm_search_mlp_plan(const lzm_handle *h, int num_simulations, int hidden, int head_hidden, int support,
+                        int res_dynamics, int32_t *out);
 /* int32[4]: {integrity errors: look-back spin timeouts and speculation mismatches (must stay 0),
  * slices resolved serially (ties that reached an expanded child, depth unknown until the draw),
  * such ties whose depth was published early (every draw outcome gives the same depth),

@@ -60,6 +60,8 @@ SIGNATURES = {
     "lzm_mlp_packed_floats": [_i, _i, _i, _i, _i],
     "lzm_mlp_kernel_floats": [_i, _i, _i, _i, _i],
     "lzm_search_mlp_kind": [_i, _i, _i, _i, _i, _i],
+    "lzm_search_mlp_supported": [_i, _i, _i, _i],
+    "lzm_search_mlp_plan": [_vp, _i, _i, _i, _i, _i, _vp],
     "lzm_decode_backprop_traverse": [_vp, _i, _f, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp, _i, _f,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "lzm_mlp_initial_inference": [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -1661,6 +1661,72 @@ void res_net(ResNet &n, const float *wres, int A) {
   (void)A;
   n.w = wres;
 }
+// network shapes the search kernels take (lzm_mlp_prepare's K padding, the dense steps' lane maps and
+// the decode's rounds over the support); everything else is refused before any launch
+bool mlp_shape_ok(int H, int A, int F, int V) {
+  return H > 0 && H <= 1024 && F > 0 && F <= 1024 && V > 0 && A > 0 && V + A <= kMaxRounds * kThreads && A <= H &&
+         H % kKC == 0 && F % kKC == 0;
+}
+// LDS plan of search_mlp_kernel with R roots per workgroup (float offsets, 16-B aligned); returns bytes
+size_t plan_stream(SearchArgs &p, const lzm_handle *h, int R, int S, int H, int A, int F, int V) {
+  size_t o = 0;
+  const size_t tree_floats = (size_t)h->cap * R * 4;
+  p.tree_in_lds = (2 * tree_floats * sizeof(float) <= 96 * 1024) ? 1 : 0;
+  p.off_stat = o; if (p.tree_in_lds) o += tree_floats;
+  p.off_meta = o; if (p.tree_in_lds) o += tree_floats;
+  p.off_lut = o; if (p.tree_in_lds) o += round4((size_t)2 * h->lut_n);
+  p.off_legal = o; if (p.tree_in_lds) o += round4((size_t)R * A + R);
+  p.off_val = o; if (p.tree_in_lds) o += round4((size_t)h->cap * R);
+  // pUCT visit table rows: all of lut when the triangle fits 32 KB (descent falls back to dividing)
+  p.pbt_rows = (p.tree_in_lds && (size_t)h->lut_n * (h->lut_n + 1) / 2 <= 8192) ? h->lut_n : 0;
+  p.off_pbt = o; o += round4((size_t)p.pbt_rows * (p.pbt_rows + 1) / 2);
+  p.off_path = o; o += round4((size_t)h->depth_cap * R);
+  p.off_pact = o; o += round4((size_t)h->depth_cap * R);
+  // transposed activations [k][r], 4-float pad per kKC rows (tpos in lzm_search_mlp.h)
+  auto tfl = [R](int K) { return (size_t)((K + kKC - 1) / kKC) * (kKC * R + 4); };
+  p.off_x0 = o; o += round4(tfl((H + A + kKC - 1) / kKC * kKC));  // [latent; one-hot] rows, zero-padded
+  p.off_x1 = o; o += round4(tfl(H));          // also the policy logits [r][A]
+  p.off_x2 = o; o += round4(tfl(H));
+  p.off_n = o; o += round4(tfl(H));
+  p.off_h = o; o += round4(tfl(2 * F));        // [value hidden; policy hidden] (merged layer)
+  p.off_logit = o; if (V < kThreads) o += round4((size_t)(V + 1) * R);  // wide supports decode from registers
+  p.off_part = o;  // (unused: split-K partials meet through DPP)
+  p.off_misc = o; o += round4((size_t)S + 32);  // staged seeds[S] + 16807^i table
+  return o * sizeof(float);
+}
+// What lzm_search_mlp launches for this handle, network shape and search length: the one decision
+// behind the launch and lzm_search_mlp_plan. kind: 1 network-resident, 0 weight-streaming, -1 none
+// (the shape, or the LDS the streaming kernel would need for it, is refused). mode: the resident
+// kernel's selection mode after its downgrades (0 for the streaming kernel). The LDS offsets of the
+// chosen kernel are left in p (and n.plan).
+struct MlpPlan {
+  int R, kind, mode, tree_in_lds;
+  size_t lds;
+};
+MlpPlan mlp_plan(const lzm_handle *h, int H, int F, int V, int res_dynamics, int S, SearchArgs &p, ResNet &n) {
+  const int A = h->A;
+  MlpPlan pl{roots_per_wg(h->B), -1, 0, 0, 0};
+  if (!mlp_shape_ok(H, A, F, V)) return pl;
+  if (pl.R == 1 && res_enabled() && res_shape_ok(H, A, F, V, res_dynamics)) {
+    pl.lds = plan_res(p, n, h, S, A);
+    if (pl.lds) {
+      const char *sm = getenv("LZM_RES_SELECT");
+      // measured: 4 < 1 < 0 < 2 < 3 (DESIGN.md 5.0); 4 is 1 with the two-action walk for A == 2
+      // 5 is 4 with the walk on the terms pass's registers: one node per lane of wave 0, so it serves
+      // S + 2 <= 64 (a path is then at most S levels: it fits the wave's lanes); larger searches run mode 4
+      n.select_mode = sm ? atoi(sm) : (A == 2 ? 5 : 1);
+      if (n.select_mode == 5 && (A != 2 || S + 2 > 64 || h->depth_cap < S + 2)) n.select_mode = 4;
+      pl.kind = 1;
+      pl.mode = (n.select_mode == 4 && A != 2) ? 1 : n.select_mode;
+      pl.tree_in_lds = 1;
+      return pl;
+    }
+  }
+  pl.lds = plan_stream(p, h, pl.R, S, H, A, F, V);
+  pl.tree_in_lds = p.tree_in_lds;
+  pl.kind = pl.lds <= kMaxLds ? 0 : -1;
+  return pl;
+}
 }  // namespace
 
 extern "C" {
@@ -1742,6 +1808,33 @@ int lzm_search_mlp_kind(int B, int actions, int hidden, int head_hidden, int sup
              : 0;
 }
 
+int lzm_search_mlp_supported(int actions, int hidden, int head_hidden, int support) {
+  return mlp_shape_ok(hidden, actions, head_hidden, support) ? 1 : 0;
+}
+
+int lzm_search_mlp_plan(const lzm_handle *h, int num_simulations, int hidden, int head_hidden, int support,
+                        int res_dynamics, int32_t *out) {
+  if (!h || !out || num_simulations <= 0) {
+    set_err("lzm_search_mlp_plan: null argument or no simulations");
+    return LZM_ERR_ARG;
+  }
+  if (num_simulations > h->sims_cap) {
+    snprintf(g_err, sizeof(g_err), "lzm_search_mlp_plan: %d simulations > reserved %d (lzm_reserve)", num_simulations,
+             h->sims_cap);
+    return LZM_ERR_CAPACITY;
+  }
+  SearchArgs p;
+  memset(&p, 0, sizeof(p));
+  ResNet n;
+  memset(&n, 0, sizeof(n));
+  const MlpPlan pl = mlp_plan(h, hidden, head_hidden, support, res_dynamics, num_simulations, p, n);
+  out[0] = pl.R;
+  out[1] = (h->flags & LZM_TREE_EZ) ? -1 : pl.kind;
+  out[2] = pl.mode;
+  out[3] = pl.tree_in_lds;
+  return LZM_OK;
+}
+
 int lzm_search_mlp(lzm_handle *h, int hidden, int head_hidden, int support, int res_dynamics, const float *weights,
                    int num_simulations, int pb_c_base, float pb_c_init, float discount, float *minmax,
                    const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool, int32_t *rec_x, int32_t *rec_a,
@@ -1759,8 +1852,7 @@ int lzm_search_mlp(lzm_handle *h, int hidden, int head_hidden, int support, int 
     return LZM_ERR_ARG;
   }
   const int H = hidden, F = head_hidden, V = support, A = h->A, S = num_simulations;
-  if (H <= 0 || H > 1024 || F <= 0 || F > 1024 || V <= 0 || V + A > kMaxRounds * kThreads || A > H || H % kKC != 0 ||
-      F % kKC != 0) {
+  if (!mlp_shape_ok(H, A, F, V)) {
     set_err("lzm_search_mlp: unsupported network shape (hidden and head widths must be multiples of 16)");
     return LZM_ERR_ARG;
   }
@@ -1770,7 +1862,12 @@ int lzm_search_mlp(lzm_handle *h, int hidden, int head_hidden, int support, int 
   }
   int rc = fill_lut(h, pb_c_base, pb_c_init);
   if (rc != LZM_OK) return rc;
-  const int R = roots_per_wg(h->B);
+  SearchArgs p;
+  memset(&p, 0, sizeof(p));
+  ResNet n;
+  memset(&n, 0, sizeof(n));
+  const MlpPlan plan = mlp_plan(h, H, F, V, res_dynamics, S, p, n);
+  const int R = plan.R;
   const int G = (h->B + R - 1) / R;
   const bool fast = (h->flags & LZM_RNG_FAST) != 0;
   if (!fast) {
@@ -1780,9 +1877,6 @@ int lzm_search_mlp(lzm_handle *h, int hidden, int head_hidden, int support, int 
   rc = ensure_flags(h, S, G);
   if (rc != LZM_OK) return rc;
 
-  SearchArgs p;
-  memset(&p, 0, sizeof(p));
-  LayerShape shp[12];
   KLayer kls[12];
   int nkl = 0;
   size_t lay_w[12], lay_b[12];
@@ -1796,7 +1890,6 @@ int lzm_search_mlp(lzm_handle *h, int hidden, int head_hidden, int support, int 
     mlp_shapes(H, A, F, V, s);
     nkl = kernel_layers(s, res_dynamics, kls);
     kernel_layout(kls, nkl, lay_w, lay_b);
-    for (int l = 0; l < 12; ++l) shp[l] = s[l];
   }
   p.coef = h->coef; p.coef_positions = h->coef_positions; p.pow16807 = h->pow16807;
   p.flags = h->lb_flags; p.epoch = h->epoch; p.diag = h->search_diag; p.fast = fast ? 1 : 0;
@@ -1807,77 +1900,43 @@ int lzm_search_mlp(lzm_handle *h, int hidden, int head_hidden, int support, int 
   p.phase = h->phase;
   p.diag_mode = getenv("LZM_DIAG_MODE") ? atoi(getenv("LZM_DIAG_MODE")) : 0;  // timing experiments only
   p.rec_x = rec_x; p.rec_a = rec_a; p.rec_len = rec_len; p.rec_dec = rec_decoded; p.rec_logits = rec_logits;
-  if (R == 1 && res_enabled() && res_shape_ok(H, A, F, V, res_dynamics)) {
+  if (plan.kind == 1) {
     // the network-resident kernel (lzm_search_res.h); its weights follow the generic layout
     SearchArgs q = p;
     q.step_count = h->step_count; q.step_inc = h->step_inc; q.step_base = h->step_base; q.mm_fresh = h->step_fresh; q.mm_delta = h->step_delta;
     q.out_dist = h->step_dist; q.out_values = h->step_vals;
-    ResNet n;
-    memset(&n, 0, sizeof(n));
-    const size_t lds = plan_res(q, n, h, S, A);
-    if (lds) {
-      res_net(n, weights + round4(kernel_layout(kls, nkl, lay_w, lay_b)), A);
-      const char *sm = getenv("LZM_RES_SELECT");
-      // measured: 4 < 1 < 0 < 2 < 3 (DESIGN.md 5.0); 4 is 1 with the two-action walk for A == 2
-      // 5 is 4 with the walk on the terms pass's registers: one node per lane of wave 0, so it serves
-      // S + 2 <= 64 (a path is then at most S levels: it fits the wave's lanes); larger searches run mode 4
-      n.select_mode = sm ? atoi(sm) : (A == 2 ? 5 : 1);
-      if (n.select_mode == 5 && (A != 2 || S + 2 > 64 || h->depth_cap < S + 2)) n.select_mode = 4;
-      // LZM_RES_SPEC=1 (parity mode): evaluate two-way leaf ties speculatively as a second network
-      // row instead of waiting for the look-back (measured slower: every simulation pays the row)
-      const char *sl = getenv("LZM_RES_LATE");
-      n.late_draw = sl ? atoi(sl) : 1;
-      const char *sd = getenv("LZM_RES_SPEC_DEPTH");
-      n.spec_depth = sd ? atoi(sd) : 1;
-      const char *se = getenv("LZM_RES_SPEC");
-      const bool spec = !fast && se && atoi(se) == 1;
-      // production: selection mode, RNG and stamps fixed at compile time (modes 1 and 4); phase
-      // timing compiles the stamps in; the other selection modes (experiments) read it at run time
-      const int md = (n.select_mode == 4 && A != 2) ? 1 : n.select_mode;
-      void (*fn)(SearchArgs, ResNet) =
-          spec                  ? search_res_kernel<2, 1, 0, false>
-          : (md != 1 && md != 4 && md != 5) || !n.spec_depth ? search_res_kernel<1, -1, -1, true>
-          : q.phase             ? (md == 5   ? search_res_kernel<1, 5, -1, true>
-                                   : md == 4 ? search_res_kernel<1, 4, -1, true>
-                                             : search_res_kernel<1, 1, -1, true>)
-          : md == 5             ? (fast ? search_res_kernel<1, 5, 1, false> : search_res_kernel<1, 5, 0, false>)
-          : md == 4             ? (fast ? search_res_kernel<1, 4, 1, false> : search_res_kernel<1, 4, 0, false>)
-                                : (fast ? search_res_kernel<1, 1, 1, false> : search_res_kernel<1, 1, 0, false>);
-      hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e == hipSuccess) {
-        hipLaunchKernelGGL(fn, dim3(G), dim3(kRT), lds, (hipStream_t)stream, q, n);
-        e = hipGetLastError();
-      }
-      LZM_HIP(e);
-      LZM_CHECK_LAUNCH();
-      return LZM_OK;
+    const size_t lds = plan.lds;
+    res_net(n, weights + round4(kernel_layout(kls, nkl, lay_w, lay_b)), A);
+    // LZM_RES_SPEC=1 (parity mode): evaluate two-way leaf ties speculatively as a second network
+    // row instead of waiting for the look-back (measured slower: every simulation pays the row)
+    const char *sl = getenv("LZM_RES_LATE");
+    n.late_draw = sl ? atoi(sl) : 1;
+    const char *sd = getenv("LZM_RES_SPEC_DEPTH");
+    n.spec_depth = sd ? atoi(sd) : 1;
+    const char *se = getenv("LZM_RES_SPEC");
+    const bool spec = !fast && se && atoi(se) == 1;
+    // production: selection mode, RNG and stamps fixed at compile time (modes 1 and 4); phase
+    // timing compiles the stamps in; the other selection modes (experiments) read it at run time
+    const int md = plan.mode;
+    void (*fn)(SearchArgs, ResNet) =
+        spec                  ? search_res_kernel<2, 1, 0, false>
+        : (md != 1 && md != 4 && md != 5) || !n.spec_depth ? search_res_kernel<1, -1, -1, true>
+        : q.phase             ? (md == 5   ? search_res_kernel<1, 5, -1, true>
+                                 : md == 4 ? search_res_kernel<1, 4, -1, true>
+                                           : search_res_kernel<1, 1, -1, true>)
+        : md == 5             ? (fast ? search_res_kernel<1, 5, 1, false> : search_res_kernel<1, 5, 0, false>)
+        : md == 4             ? (fast ? search_res_kernel<1, 4, 1, false> : search_res_kernel<1, 4, 0, false>)
+                              : (fast ? search_res_kernel<1, 1, 1, false> : search_res_kernel<1, 1, 0, false>);
+    hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(fn, dim3(G), dim3(kRT), lds, (hipStream_t)stream, q, n);
+      e = hipGetLastError();
     }
+    LZM_HIP(e);
+    LZM_CHECK_LAUNCH();
+    return LZM_OK;
   }
-  // dynamic LDS plan (float offsets, 16-B aligned)
-  size_t o = 0;
-  const size_t tree_floats = (size_t)h->cap * R * 4;
-  p.tree_in_lds = (2 * tree_floats * sizeof(float) <= 96 * 1024) ? 1 : 0;
-  p.off_stat = o; if (p.tree_in_lds) o += tree_floats;
-  p.off_meta = o; if (p.tree_in_lds) o += tree_floats;
-  p.off_lut = o; if (p.tree_in_lds) o += round4((size_t)2 * h->lut_n);
-  p.off_legal = o; if (p.tree_in_lds) o += round4((size_t)R * A + R);
-  p.off_val = o; if (p.tree_in_lds) o += round4((size_t)h->cap * R);
-  // pUCT visit table rows: all of lut when the triangle fits 32 KB (descent falls back to dividing)
-  p.pbt_rows = (p.tree_in_lds && (size_t)h->lut_n * (h->lut_n + 1) / 2 <= 8192) ? h->lut_n : 0;
-  p.off_pbt = o; o += round4((size_t)p.pbt_rows * (p.pbt_rows + 1) / 2);
-  p.off_path = o; o += round4((size_t)h->depth_cap * R);
-  p.off_pact = o; o += round4((size_t)h->depth_cap * R);
-  // transposed activations [k][r], 4-float pad per kKC rows (tpos in lzm_search_mlp.h)
-  auto tfl = [R](int K) { return (size_t)((K + kKC - 1) / kKC) * (kKC * R + 4); };
-  p.off_x0 = o; o += round4(tfl(shp[0].K));  // [latent; one-hot] rows, zero-padded
-  p.off_x1 = o; o += round4(tfl(H));          // also the policy logits [r][A]
-  p.off_x2 = o; o += round4(tfl(H));
-  p.off_n = o; o += round4(tfl(H));
-  p.off_h = o; o += round4(tfl(2 * F));        // [value hidden; policy hidden] (merged layer)
-  p.off_logit = o; if (V < kThreads) o += round4((size_t)(V + 1) * R);  // wide supports decode from registers
-  p.off_part = o;  // (unused: split-K partials meet through DPP)
-  p.off_misc = o; o += round4((size_t)S + 32);  // staged seeds[S] + 16807^i table
-  const size_t lds = o * sizeof(float);
+  const size_t lds = plan.lds;  // (plan_stream left the streaming kernel's LDS offsets in p)
   build_schedule(p, kls, nkl, lay_w, lay_b, weights, res_dynamics, A, V, F, R);
   if (lds > kMaxLds) {
     snprintf(g_err, sizeof(g_err), "lzm_search_mlp: %zu B of LDS needed (network too wide)", lds);

@@ -109,6 +109,9 @@ def describe(model):
 
 def pack_muzero_mlp(model, device):
     layers, dims = describe(model)
+    # the kernels' own limits (widths, support + actions, actions <= hidden), asked of the library
+    if not _lib.load().lzm_search_mlp_supported(dims["actions"], dims["hidden"], dims["head_hidden"], dims["support"]):
+        raise NotPackable("network shape outside the search kernels' range: {}".format(dims))
     parts = []
     for (W, b), _ in layers:
         parts.append(W.t().contiguous().reshape(-1))

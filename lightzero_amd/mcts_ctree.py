@@ -262,9 +262,11 @@ class MuZeroMCTSCtree(object):
     def _categorical(self):
         return bool(self._cfg.model.get('categorical_distribution', True))
 
-    def _fused(self, model, t):
+    def _fused(self, model, t, S=None):
         """(packed weights, dims) when the whole search can run as one lzm_search_mlp launch:
-        a MuZeroModelMLP-shaped network with categorical heads, eval-mode BatchNorm and ReLU."""
+        a MuZeroModelMLP-shaped network with categorical heads, eval-mode BatchNorm and ReLU, of a
+        shape the kernels take on this tree for S simulations (default: the tree's reserved capacity),
+        by the library's own launch plan (lzm_search_mlp_supported, lzm_search_mlp_plan)."""
         if not self._cfg.get('fused_search', True) or not self._categorical() or t.ez:
             return None
         try:
@@ -273,6 +275,8 @@ class MuZeroMCTSCtree(object):
             return None
         if dims["actions"] != t.A or dims["support"] != 2 * int(self._cfg.model.support_scale) + 1:
             return None
+        if t.search_mlp_plan(dims, t.sims_capacity if S is None else S)["kernel"] is None:
+            return None  # (the streaming kernel's LDS need at this width and tree size)
         return packed, dims
 
     def _fused_conv(self, model, t, shape):
@@ -360,7 +364,7 @@ class MuZeroMCTSCtree(object):
             shape = lat0.shape[1:]
             row = int(np.prod(shape)) if len(shape) else 1
             rec = _Recorder(S, B, t.A, dev) if getattr(self, "record", False) else None
-            fz = self._fused(model, t)
+            fz = self._fused(model, t, S)
             cz = self._fused_conv(model, t, shape) if fz is None else None
             graph = fz is None and cz is None and rec is None and self._cfg.get('use_hip_graph', False)
             gkey = _graph_key(t, model, B, S, shape) if graph else None

@@ -199,6 +199,16 @@ class DeviceTree:
              ptr(vtp_in), ptr(pool), r("x"), r("action"), r("search_len"), r("decoded"), r("policy_logits"),
              stream_ptr(stream))
 
+    def search_mlp_plan(self, dims, S):
+        """What search_mlp(dims, ..., S) launches on this handle as it stands (lzm_search_mlp_plan; host
+        only): dict(roots_per_wg, kernel 'resident' / 'streaming' / None when the kernels refuse the
+        shape, mode: the resident kernel's selection mode, tree_in_lds)."""
+        out = (ctypes.c_int32 * 4)()
+        call("lzm_search_mlp_plan", self.h, int(S), dims["hidden"], dims["head_hidden"], dims["support"],
+             int(dims["res"]), out)
+        return dict(roots_per_wg=out[0], kernel={1: "resident", 0: "streaming"}.get(out[1]), mode=out[2],
+                    tree_in_lds=bool(out[3]))
+
     def search_conv(self, net, S, minmax, seeds, vtp_in, pool, pb_c_base=19652, pb_c_init=1.25, discount=0.997,
                     categorical=True, rec=None, stream=None):
         """One launch for the whole search of a conv MuZeroModel (lzm_search_conv; net: a native

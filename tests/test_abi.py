@@ -169,3 +169,19 @@ def test_representation_entry_points_validate_arguments_on_the_host():
     assert L.lzm_conv_resnet8_p(1, 9, 1, 16, p16, p16, p16, p16, None, None) == err  # more than 8
     assert L.lzm_conv_resnet8_p(1, 2, 1, 33, p16, p16, p16, p16, None, None) == err  # head channels
     assert L.lzm_conv_resnet8_p(1, 2, 1, 16, p16, p4, p16, p16, None, None) == err  # input alignment
+
+
+def test_search_mlp_shape_and_plan_queries_validate_on_the_host():
+    """lzm_search_mlp_supported states the MLP search kernels' shape limits (host only, no GPU needed);
+    lzm_search_mlp_plan refuses a null handle before touching it"""
+    import ctypes
+    L = _lib.load()
+    ok = L.lzm_search_mlp_supported  # (actions, hidden, head_hidden, support)
+    assert ok(2, 128, 32, 601) == 1 and ok(1, 64, 32, 1023) == 1 and ok(16, 16, 16, 21) == 1
+    assert ok(2, 1024, 1024, 601) == 1
+    assert ok(2, 100, 32, 601) == 0 and ok(2, 64, 24, 601) == 0  # widths: multiples of 16
+    assert ok(2, 64, 32, 1201) == 0 and ok(2, 64, 32, 1023) == 0  # support + actions <= 1024
+    assert ok(17, 16, 16, 21) == 0  # actions <= hidden
+    assert ok(2, 1040, 32, 601) == 0 and ok(2, 64, 1040, 601) == 0 and ok(0, 64, 32, 601) == 0
+    out = (ctypes.c_int32 * 4)()
+    assert L.lzm_search_mlp_plan(None, 10, 128, 32, 601, 1, out) == -1  # LZM_ERR_ARG

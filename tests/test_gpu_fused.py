@@ -23,12 +23,16 @@ from tests.test_gpu_numerics import torch_inverse_scalar_transform  # noqa: E402
 DEV = torch.device("cuda", 0)
 
 
-def make_model(A, H, zero_heads, seed=0, support_scale=300):
+def make_model(A, H, zero_heads, seed=0, support_scale=300, res=True, head_hidden=None, group=None):
     from lightzero_amd.model_mlp import MuZeroModelMLP
     torch.manual_seed(seed)
+    heads = {} if head_hidden is None else dict(fc_reward_layers=(head_hidden,), fc_value_layers=(head_hidden,),
+                                                fc_policy_layers=(head_hidden,))
     m = MuZeroModelMLP(observation_shape=4, action_space_size=A, latent_state_dim=H, categorical_distribution=True,
                        reward_support_size=2 * support_scale + 1, value_support_size=2 * support_scale + 1,
-                       last_linear_layer_init_zero=zero_heads, norm_type='BN', res_connection_in_dynamics=True)
+                       last_linear_layer_init_zero=zero_heads, norm_type='BN', res_connection_in_dynamics=res, **heads)
+    if group is not None:  # (latent widths the default SimNorm group of 8 does not divide)
+        m.representation_network.sim_norm.dim = group
     g = torch.Generator().manual_seed(seed + 1)
     for mod in m.modules():
         if isinstance(mod, torch.nn.BatchNorm1d):
@@ -38,11 +42,16 @@ def make_model(A, H, zero_heads, seed=0, support_scale=300):
     return m.to(DEV).eval()
 
 
-def fused_search(B, S, A, H, zero_heads, players, fast, seed, support_scale=300):
+def fused_search(B, S, A, H, zero_heads, players, fast, seed, support_scale=300, tree_sims=None, fused=True,
+                 **model_kw):
+    """tree_sims: run on a fresh tree handle of that simulation capacity (closed afterwards) instead of a
+    pooled one of the default capacity: the handle's capacity sizes the resident kernel's LDS plan, so it
+    decides which kernel runs (res["plan"], DeviceTree.search_mlp_plan). fused=False: the model is
+    expected to take the generic per-simulation path. model_kw: further make_model arguments."""
     from lightzero_amd.mcts_ctree import MuZeroMCTSCtree
-    from lightzero_amd.tree import SequentialSeeds, set_seed_source
+    from lightzero_amd.tree import DeviceTree, SequentialSeeds, set_seed_source
     from lightzero_amd.utils import EasyDict
-    model = make_model(A, H, zero_heads, seed, support_scale)
+    model = make_model(A, H, zero_heads, seed, support_scale, **model_kw)
     rng = np.random.default_rng(seed)
     obs = torch.from_numpy(rng.normal(size=(B, 4)).astype(np.float32)).to(DEV)
     with torch.no_grad():
@@ -59,19 +68,28 @@ def fused_search(B, S, A, H, zero_heads, players, fast, seed, support_scale=300)
         mcts = cls(cfg)
         mcts.record = True
         roots = cls.roots(B, [list(range(A))] * B)
+        if tree_sims is not None:
+            roots.tree = DeviceTree(B, A, tree_sims, fast_rng=fast, device=DEV)
         roots.prepare(float(NOISE_W), [n.tolist() for n in noises], [0.0] * B, logits0.tolist(), to_play)
         set_seed_source(SequentialSeeds(seed))
         try:
             mcts.search(roots, model, out.latent_state, to_play)
         finally:
             set_seed_source(None)
-        assert mcts._fused(model, roots.tree) is not None, "model should take the fused path"
+        fz = mcts._fused(model, roots.tree, S)
+        assert (fz is not None) == fused, "model should take the {} path".format("fused" if fused else "generic")
+        assert mcts.last_path == ("fused-mlp" if fused else "generic")
         rec = mcts.last_record.numpy()
         t = roots.tree
         res = dict(rec=rec, dist=t.distributions().cpu().numpy(), values=t.values().cpu().numpy(),
                    traj=t.trajectories(S + 2).cpu().numpy(), pool=mcts._buf.pool.clone(), diag=t.search_diagnostics(),
-                   model=model, logits0=logits0, noises=noises, to_play=np.array(to_play, np.int32))
-        roots.clear()
+                   model=model, logits0=logits0, noises=noises, to_play=np.array(to_play, np.int32),
+                   plan=t.search_mlp_plan(fz[1], S) if fused else None, path=mcts.last_path)
+        if tree_sims is None:
+            roots.clear()
+        else:
+            roots.tree = None
+            t.close()
         return res
     finally:
         cls.rng_mode = old

@@ -68,7 +68,7 @@ def midwalk_settles(rec):
     return n
 
 
-def oracle_mismatch(r, B, S, fast=False, legal=None):
+def oracle_mismatch(r, B, S, fast=False, legal=None, A=A):
     """None when the search r equals the oracle fed r's recorded network outputs, else what differs."""
     rec = r["rec"]
     ot = OracleTree(B, A, S, fast_rng=fast)

@@ -81,3 +81,34 @@ def test_fused_initial_inference_matches_module(B, random_heads):
         got2 = fi.initial_inference(obs)
     assert fi.flat is flat
     torch.testing.assert_close(got2.policy_logits, ref2.policy_logits, rtol=1e-4, atol=1e-5)
+
+
+def _wide_model(O=4, H=64, F=16, V=21, A=2, group=8):
+    from lightzero_amd.model_mlp import MuZeroModelMLP
+    m = MuZeroModelMLP(observation_shape=O, action_space_size=A, latent_state_dim=H, fc_reward_layers=(F,),
+                       fc_value_layers=(F,), fc_policy_layers=(F,), reward_support_size=V, value_support_size=V,
+                       res_connection_in_dynamics=True)
+    m.representation_network.sim_norm.dim = group  # (describe_initial reads the group from the instance)
+    return m.eval()
+
+
+@pytest.mark.parametrize("over", [dict(O=1025), dict(H=1032), dict(V=1025), dict(A=1025), dict(F=257), dict(H=96, group=5),
+                                  dict(group=0)])
+def test_describe_initial_refuses_one_over_each_limit(over):
+    """lzm_mlp_initial_inference takes widths up to 1024, head hidden up to 256 and a group dividing H: one
+    past each raises NotPackable, so callers keep the module (fused_initial_or_none)"""
+    from lightzero_amd.fused import NotPackable
+    from lightzero_amd.initial import fused_initial_or_none
+    m = _wide_model(**over)
+    with pytest.raises(NotPackable):
+        describe_initial(m)
+    assert fused_initial_or_none(m) is None
+
+
+def test_describe_initial_accepts_the_limits_themselves():
+    for at in (dict(O=1024), dict(H=1024), dict(V=1024), dict(A=1024), dict(F=256), dict(H=96, group=96)):
+        dims = describe_initial(_wide_model(**at))[1]
+        for k, name in (("O", "obs"), ("H", "hidden"), ("V", "support"), ("A", "actions"), ("F", "head_hidden"),
+                        ("group", "group")):
+            if k in at:
+                assert dims[name] == at[k]
