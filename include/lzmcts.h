@@ -357,6 +357,8 @@ int lzm_az_finish(int B, int S, void *ws, double temperature, int sample, uint32
 /* test access: node visit / value_sum / first-child rows [B][1 + 9 (S + 1)] and node counts [B] (any may be NULL) */
 int lzm_az_export_tree(int B, int S, void *ws, int32_t *visit, float *vsum, int32_t *first, int32_t *nnodes,
                        void *stream);
+/* test access: the nodes' priors (the root's children after the noise mix), float [B][1 + 9 (S + 1)] */
+int lzm_az_export_priors(int B, int S, void *ws, float *prior, void *stream);
 
 /* ---- fused AlphaZero search: the TicTacToe config's AlphaZeroModel (alphazero_model.py:14-330; 16 channels,
  * num_res_blocks 1 or 2, head width 8, 9 actions, scalar value) evaluated inside the search kernel; one
@@ -379,6 +381,12 @@ int lzm_az_search_fused(int B, int S, void *ws, int nres, const float *weights, 
                         const int32_t *start_index, int with_noise, double noise_weight, double temperature,
                         int sample, uint32_t seed, const int64_t *counter, int32_t *visits, double *probs,
                         int32_t *action, int export_tree, void *stream);
+/* What lzm_az_search_fused(B, S, .., nres, ..) would launch as the process stands (the launch's own choice,
+ * LZM_AZ_BOARDS_PER_WG included; nothing is launched). out int32[4]: boards per workgroup; workgroups; the
+ * workgroups of that instantiation one CU holds at once (0: its trees do not fit in LDS; -1: the occupancy
+ * query failed and the choice assumed 1); dynamic LDS bytes per workgroup. Bad arguments (B <= 0, S <= 0,
+ * nres not 1 / 2, null out) return LZM_ERR_ARG before any HIP call. */
+int lzm_az_fused_plan(int B, int S, int nres, int32_t *out);
 
 /* ---- convolutional recurrent trunk (configs 3 / 5: conv MuZeroModel / EfficientZeroModel) --------
  * The conv part of recurrent_inference (muzero_model.py:505-530, efficientzero_model.py:526-574,

@@ -126,10 +126,12 @@ SIGNATURES = {
     "lzm_az_step": [_i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _d, _vp, _vp],
     "lzm_az_finish": [_i, _i, _vp, _d, _i, _u32, _vp, _vp, _vp, _vp, _vp],
     "lzm_az_export_tree": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "lzm_az_export_priors": [_i, _i, _vp, _vp, _vp],
     "lzm_az_net_floats": [_i],
     "lzm_az_net_prepare": [_i, _vp, _vp],
     "lzm_az_net_eval": [_i, _vp, _vp, _i, _vp, _vp, _vp],
     "lzm_az_search_fused": [_i, _i, _vp, _i, _vp, _vp, _vp, _i, _d, _d, _i, _u32, _vp, _vp, _vp, _vp, _i, _vp],
+    "lzm_az_fused_plan": [_i, _i, _i, _vp],
     "lzm_conv_trunk_floats": [_i, _i],
     "lzm_conv_trunk_prepare": [_i, _i, _i, _i, _vp, _vp],
     "lzm_conv_trunk": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -12,8 +12,10 @@ callback (policy/alphazero.py:371-380): the simulate env lives inside the kernel
 Per search: lzm_az_begin, network(roots), lzm_az_step(-1), then S x (network(leaves),
 lzm_az_step(k)), lzm_az_finish; with ``graph=True`` that whole sequence is one HIP graph per batch
 size. Visit counts and action_probs are identical to the reference's for the same network outputs
-(tests/test_gpu_alphazero.py against tests/golden/az_*.npz). The sampled action uses a Philox draw
-(the reference uses std::random_device, which has no reproducible stream).
+(tests/test_gpu_alphazero.py against tests/golden/az_*.npz with the scripted policy; tests/test_gpu_az_oracle.py
+with a real-valued network: whole trees of both paths against the restatement fed the fused network's own
+outputs, bit for bit). The sampled action uses a Philox draw (the reference uses std::random_device, which
+has no reproducible stream); tests/test_gpu_az_oracle.py restates the draw on the host.
 """
 import ctypes
 
@@ -197,6 +199,14 @@ class AlphaZeroMCTS:
         self._count.add_(1)
         return c["action"], c["probs"]
 
+    def fused_plan(self, B, net):
+        """What search_fused launches for B boards as the process stands (lzm_az_fused_plan; host only):
+        dict(rows: boards per workgroup, workgroups, per_cu: workgroups one CU holds (-1: the occupancy
+        query failed and 1 was assumed), lds_bytes)."""
+        out = (ctypes.c_int32 * 4)()
+        call("lzm_az_fused_plan", int(B), self.num_simulations, net.nres, out)
+        return dict(rows=out[0], workgroups=out[1], per_cu=out[2], lds_bytes=out[3])
+
     # ------------------------------------------------------------------ public API
     def get_next_actions(self, boards, start_player_index, compute_policy_value, temperature=1.0, sample=True):
         """boards [B, 9] (or [B, 3, 3]) with 0 empty / 1 / 2 stones, start_player_index [B] (0: player 1
@@ -233,6 +243,14 @@ class AlphaZeroMCTS:
                torch.empty((B, cap), dtype=torch.int32, device=self.device),
                torch.empty(B, dtype=torch.int32, device=self.device)]
         call("lzm_az_export_tree", B, self.num_simulations, ptr(c["ws"]), *[ptr(t) for t in out], stream_ptr())
+        return out
+
+    def export_priors(self, B):
+        """the nodes' priors, float32 [B, cap] (rows as export_tree's; the root's children after the noise mix)"""
+        c = self._buffers(B)
+        cap = 1 + ACTIONS * (self.num_simulations + 1)
+        out = torch.empty((B, cap), dtype=torch.float32, device=self.device)
+        call("lzm_az_export_priors", B, self.num_simulations, ptr(c["ws"]), ptr(out), stream_ptr())
         return out
 
 

@@ -2402,6 +2402,17 @@ int lzm_az_export_tree(int B, int S, void *ws, int32_t *visit, float *vsum, int3
   return LZM_OK;
 }
 
+int lzm_az_export_priors(int B, int S, void *ws, float *prior, void *stream) {
+  if (!az_args_ok(B, S, ws, "lzm_az_export_priors") || !prior) {
+    if (B > 0 && S > 0 && S <= (1 << 20) && ws) set_err("lzm_az_export_priors: null output");
+    return LZM_ERR_ARG;
+  }
+  AzTree t;
+  az_carve(B, S, ws, &t);
+  LZM_HIP(hipMemcpyAsync(prior, t.prior, (size_t)B * t.cap * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return LZM_OK;
+}
+
 }  // extern "C"
 
 // ---- fused AlphaZero search (lzm_az_fused.h)
@@ -2424,22 +2435,31 @@ static int az_fused_attr(bool stamps) {
   return LZM_OK;
 }
 
-// workgroups of R boards that one CU holds at once (0: the trees do not fit in LDS)
+// workgroups of R boards that one CU holds at once (0: the trees do not fit in LDS). *assumed: the occupancy
+// query failed and one workgroup per CU is assumed (lzm_az_fused_plan reports it)
 template <int R, int NRES>
-static int az_fused_per_cu(int cap, int S, bool stamps) {
+static int az_fused_per_cu(int cap, int S, bool stamps, bool *assumed = nullptr) {
+  if (assumed) *assumed = false;
   const size_t lds = az_fused_lds<R>(cap, S);
   if (lds > 160 * 1024) return 0;
   static size_t memo_lds[2] = {0, 0};
   static int memo[2] = {0, 0};
-  if (memo_lds[stamps] == lds) return memo[stamps];
+  static bool memo_assumed[2] = {false, false};
+  if (memo_lds[stamps] == lds) {
+    if (assumed) *assumed = memo_assumed[stamps];
+    return memo[stamps];
+  }
   if (az_fused_attr<R, NRES>(stamps) != LZM_OK) return 0;
   int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, stamps ? (const void *)az_search_fused_kernel<R, NRES, true>
+  const bool failed =
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, stamps ? (const void *)az_search_fused_kernel<R, NRES, true>
                                                                    : (const void *)az_search_fused_kernel<R, NRES, false>,
-                                                   kAzfThreads, lds) != hipSuccess)
-    per_cu = 1;
+                                                   kAzfThreads, lds) != hipSuccess;
+  if (failed) per_cu = 1;
   memo_lds[stamps] = lds;
   memo[stamps] = per_cu;
+  memo_assumed[stamps] = failed;
+  if (assumed) *assumed = failed;
   return per_cu;
 }
 
@@ -2459,6 +2479,29 @@ static int az_fused_rows(int B, int cap, int S, bool stamps) {
     if ((B + r - 1) / r <= occ[i] * cus) return r;
   }
   return best ? best : 1;
+}
+
+// lzm_az_fused_plan: what az_fused_rows picks and what that instantiation needs
+template <int NRES>
+static int az_fused_plan(int B, int cap, int S, bool stamps, int32_t *out) {
+  const int R = az_fused_rows<NRES>(B, cap, S, stamps);
+  bool assumed = false;
+  int per_cu = 0;
+  size_t lds = 0;
+  switch (R) {
+    case 1: per_cu = az_fused_per_cu<1, NRES>(cap, S, stamps, &assumed); lds = az_fused_lds<1>(cap, S); break;
+    case 2: per_cu = az_fused_per_cu<2, NRES>(cap, S, stamps, &assumed); lds = az_fused_lds<2>(cap, S); break;
+    case 4: per_cu = az_fused_per_cu<4, NRES>(cap, S, stamps, &assumed); lds = az_fused_lds<4>(cap, S); break;
+    case 8: per_cu = az_fused_per_cu<8, NRES>(cap, S, stamps, &assumed); lds = az_fused_lds<8>(cap, S); break;
+    default:
+      set_err("lzm_az_fused_plan: boards per workgroup must be 1, 2, 4 or 8");
+      return LZM_ERR_ARG;
+  }
+  out[0] = R;
+  out[1] = (B + R - 1) / R;
+  out[2] = assumed ? -1 : per_cu;
+  out[3] = (int32_t)lds;
+  return LZM_OK;
 }
 
 template <int R, int NRES>
@@ -2586,6 +2629,20 @@ int lzm_az_search_fused(int B, int S, void *ws, int nres, const float *weights, 
   const int R = nres == 1 ? az_fused_rows<1>(B, a.cap, S, a.stamps != nullptr) : az_fused_rows<2>(B, a.cap, S, a.stamps != nullptr);
   hipStream_t s = (hipStream_t)stream;
   return nres == 1 ? az_launch_fused_r<1>(R, a, s) : az_launch_fused_r<2>(R, a, s);
+}
+
+int lzm_az_fused_plan(int B, int S, int nres, int32_t *out) {
+  if (B <= 0 || S <= 0 || S > (1 << 20) || (nres != 1 && nres != 2) || !out) {
+    set_err("lzm_az_fused_plan: need B > 0, 0 < num_simulations <= 2^20, num_res_blocks 1 or 2 and an output buffer");
+    return LZM_ERR_ARG;
+  }
+  if (1 + kAzCells * (S + 1) >= 0xffff) {
+    set_err("lzm_az_fused_plan: num_simulations too large for the LDS tree (16-bit node index)");
+    return LZM_ERR_CAPACITY;
+  }
+  const int cap = 1 + kAzCells * (S + 1);
+  const bool stamps = g_az_stamps != nullptr;
+  return nres == 1 ? az_fused_plan<1>(B, cap, S, stamps, out) : az_fused_plan<2>(B, cap, S, stamps, out);
 }
 
 

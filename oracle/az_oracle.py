@@ -55,23 +55,47 @@ def ucb(parent, child, base, init):
     return pb_c * float(child.prior) + float(child.value())
 
 
-def expand(node, env, pv):
+def expand(node, env, pv, order=None):
     priors, value = pv(env.board.reshape(-1), env.legal_actions)
     legal = set(env.legal_actions)
     for a in sorted(priors):
         if a in legal:
             node.children[a] = Node(node, priors[a])
+    if order is not None:
+        order.append(node)
     return value
 
 
+def flatten(root, order, priors=False):
+    """The tree in the device's layout (lightzero_amd/csrc/lzm_az.h): node 0 is the root, every expansion
+    (`order`: the expanded nodes in expansion order) appends the node's children contiguously in action
+    order. Returns (visit int32 [n], value_sum float32 [n], first int32 [n] (-1: leaf), n); with priors
+    also prior_p float32 [n] as a fifth element (the root's children after the noise mix)."""
+    nodes, first = [root], {}
+    for node in order:
+        if node.children:
+            first[id(node)] = len(nodes)
+            nodes.extend(node.children[a] for a in sorted(node.children))
+    n = len(nodes)
+    visit = np.array([x.visit for x in nodes], np.int32)
+    vsum = np.array([x.value_sum for x in nodes], np.float32)
+    fst = np.array([first.get(id(x), -1) for x in nodes], np.int32)
+    if priors:
+        return visit, vsum, fst, n, np.array([x.prior for x in nodes], np.float32)
+    return visit, vsum, fst, n
+
+
 def search(board, start_player_index, sims, pv, sample, base=19652.0, init=1.25, alpha=0.3, frac=0.25, table=None,
-           return_values=False):
+           return_values=False, return_tree=False):
     """Root visit counts [9] of MCTS.get_next_action (the action_probs it returns x sims at T=1);
-    with return_values also the root children's value_sum float32 [9] and the root's (visit, value_sum)."""
+    with return_values also the root children's value_sum float32 [9] and the root's (visit, value_sum);
+    with return_tree the whole tree follows as one more element (`flatten`; return_tree="priors": with the
+    nodes' priors)."""
     env = SimTicTacToe()
     root = Node()
+    order = [] if return_tree else None
     env.reset(start_player_index, board)
-    expand(root, env, pv)
+    expand(root, env, pv, order)
     if sample:
         tab = noise_table(alpha) if table is None else table
         acts = sorted(root.children)
@@ -96,7 +120,7 @@ def search(board, start_player_index, sims, pv, sample, base=19652.0, init=1.25,
             node = child
         done, winner = env.get_done_winner()
         if not done:
-            leaf = expand(node, env, pv)
+            leaf = expand(node, env, pv, order)
         else:
             leaf = 0.0 if winner == -1 else (1.0 if env.current_player == winner else -1.0)
         node.update_recursive(-leaf)
@@ -105,6 +129,7 @@ def search(board, start_player_index, sims, pv, sample, base=19652.0, init=1.25,
     for a, c in root.children.items():
         visits[a] = c.visit
         vsums[a] = c.value_sum
-    if return_values:
-        return visits, vsums, (root.visit, root.value_sum)
-    return visits
+    out = (visits, vsums, (root.visit, root.value_sum)) if return_values else (visits,)
+    if return_tree:
+        out += (flatten(root, order, priors=(return_tree == "priors")),)
+    return out if len(out) > 1 else visits

@@ -267,6 +267,76 @@ def az_scripted_pv_torch(state):
     return priors, value
 
 
+def az_reachable_states(roots):
+    """Every non-terminal (board tuple [9], player to move 1 / 2) reachable from the root (board,
+    start_player_index) pairs, the roots included, in breadth-first order without repeats. From the empty
+    board with player 1 to move these are TicTacToe's 4,520 non-terminal positions."""
+    from collections import deque
+    from oracle.tictactoe import done_winner
+    seen, out, queue = set(), [], deque()
+    for board, start in roots:
+        key = (tuple(int(c) for c in np.asarray(board).reshape(-1)), 1 if int(start) == 0 else 2)
+        if key not in seen and not done_winner(key[0])[0]:
+            seen.add(key)
+            queue.append(key)
+    while queue:
+        key = queue.popleft()
+        out.append(key)
+        board, player = key
+        for a in range(9):
+            if board[a] != 0:
+                continue
+            nxt = (board[:a] + (player,) + board[a + 1:], 3 - player)
+            if nxt not in seen and not done_winner(nxt[0])[0]:
+                seen.add(nxt)
+                queue.append(nxt)
+    return out
+
+
+def az_encode_states(states):
+    """float32 [n, 3, 3, 3]: SimTicTacToe.current_state()'s scaled form (the network input) of each
+    (board, player to move)"""
+    from oracle.tictactoe import SimTicTacToe
+    env = SimTicTacToe(scale=True)
+    out = np.zeros((len(states), 3, 3, 3), np.float32)
+    for i, (board, player) in enumerate(states):
+        env.reset(player - 1, np.asarray(board, np.int32))
+        out[i] = env.current_state()[1]
+    return out
+
+
+class AzTablePolicy:
+    """The oracle's policy-value function as a table of the fused network's own outputs: every state the
+    searches from `roots` can meet, evaluated in ONE FusedAZNet.compute_policy_value call (lzm_az_net_eval
+    gives a state the same bits wherever it sits in a batch, and the same bits as the network inside the
+    fused search kernel), kept as float32 on the host, keyed by (board code, player to move)."""
+
+    def __init__(self, net, roots):
+        import torch
+        from oracle.tictactoe import board_code
+        self.states = az_reachable_states(roots)
+        x = torch.from_numpy(az_encode_states(self.states)).cuda()
+        with torch.no_grad():
+            probs, value = net.compute_policy_value(x)
+        self.probs = probs.cpu().numpy().astype(np.float32, copy=False)
+        self.value = value.cpu().numpy().reshape(-1).astype(np.float32, copy=False)
+        self.index = {(board_code(b), p): i for i, (b, p) in enumerate(self.states)}
+
+    def pv(self, board, start_player_index):
+        """pv(board, legal) for az_oracle.search from this root: the player to move follows from the root's
+        and the stones placed since"""
+        from oracle.tictactoe import board_code
+        n0 = int(np.count_nonzero(board))
+        p0 = 1 if int(start_player_index) == 0 else 2
+
+        def pv(b, legal):
+            player = p0 if (int(np.count_nonzero(b)) - n0) % 2 == 0 else 3 - p0
+            i = self.index[(board_code(b), player)]
+            row = self.probs[i]
+            return {int(a): row[a] for a in legal}, self.value[i]
+        return pv
+
+
 def tie_list(scores):
     """cselect_child's order-dependent tie list (cnode.cpp:551-596) over one level's scores, in float32:
     scan in action order from max_score = FLOAT_MIN (-1e6); a score above the max restarts the list,

@@ -185,3 +185,24 @@ def test_search_mlp_shape_and_plan_queries_validate_on_the_host():
     assert ok(2, 1040, 32, 601) == 0 and ok(2, 64, 1040, 601) == 0 and ok(0, 64, 32, 601) == 0
     out = (ctypes.c_int32 * 4)()
     assert L.lzm_search_mlp_plan(None, 10, 128, 32, 601, 1, out) == -1  # LZM_ERR_ARG
+
+
+def test_az_fused_plan_validates_on_the_host():
+    """lzm_az_fused_plan refuses a residual-block count the fused network does not have, a null output, an
+    empty batch and no simulations before any HIP call (LZM_ERR_ARG, no GPU needed), and leaves `out` alone"""
+    import ctypes
+    L = _lib.load()
+    err = -1  # LZM_ERR_ARG
+    out = (ctypes.c_int32 * 4)(7, 7, 7, 7)
+    assert L.lzm_az_fused_plan(512, 100, 0, out) == err
+    assert L.lzm_az_fused_plan(512, 100, 3, out) == err
+    assert L.lzm_az_fused_plan(512, 100, 1, None) == err
+    assert L.lzm_az_fused_plan(0, 100, 1, out) == err
+    assert L.lzm_az_fused_plan(-5, 100, 2, out) == err
+    assert L.lzm_az_fused_plan(512, 0, 1, out) == err
+    assert b"lzm_az_fused_plan" in L.lzm_last_error()
+    assert list(out) == [7, 7, 7, 7]
+    # lzm_az_export_priors (test access beside lzm_az_export_tree): no workspace, no output
+    assert L.lzm_az_export_priors(4, 10, None, out, None) == err
+    assert L.lzm_az_export_priors(0, 10, out, out, None) == err
+    assert L.lzm_az_export_priors(4, 10, out, None, None) == err

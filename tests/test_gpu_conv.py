@@ -507,6 +507,30 @@ def test_ez_residency_refusal_falls_back_to_generic_with_same_results(monkeypatc
     assert mcts.residency_fallbacks == 1
 
 
+def _stream_beside_current():
+    """A pooled stream whose kernels run WHILE the current stream's do. A process has few hardware queues
+    (GPU_MAX_HW_QUEUES), so some pooled streams share the current stream's queue: a kernel on one of those only
+    delays what the current stream launches next instead of holding CUs beside it, and which pooled stream a
+    test gets depends on how many the tests before it took. Probed per candidate: a 30 ms one-CU hold on it, a
+    small kernel on the current stream; the two ran side by side when the small kernel is done first."""
+    from lightzero_amd import _lib
+    x = torch.zeros(64, device=DEV)
+    for _ in range(8):
+        s = torch.cuda.Stream(device=DEV)
+        torch.cuda.synchronize()
+        held = torch.cuda.Event()
+        with torch.cuda.stream(s):
+            _lib.call("lzm_debug_hold_cus", 1, 30000, _lib.stream_ptr(s))
+            held.record(s)
+        x.add_(1)
+        torch.cuda.current_stream(DEV).synchronize()
+        beside = not held.query()
+        torch.cuda.synchronize()
+        if beside:
+            return s
+    raise AssertionError("none of 8 pooled streams runs beside the current stream")
+
+
 def test_ez_handoff_timeout_falls_back_to_generic_with_same_results():
     """another stream's kernel holds most CUs while the one-launch EZ search launches eagerly (the
     static occupancy bound accepted the grid): the resident workgroups' hand-off waits give up after 200 ms
@@ -524,7 +548,7 @@ def test_ez_handoff_timeout_falls_back_to_generic_with_same_results():
                         model=dict(support_scale=50, categorical_distribution=True)))
     mcts = EfficientZeroMCTSCtree(cfg)
     cus = torch.cuda.get_device_properties(DEV).multi_processor_count
-    hog = torch.cuda.Stream(device=DEV)
+    hog = _stream_beside_current()
     torch.cuda.synchronize()
     with torch.cuda.stream(hog):
         _lib.call("lzm_debug_hold_cus", cus - 40, 700000, _lib.stream_ptr(hog))  # 700 ms on all but 40 CUs
