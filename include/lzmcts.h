@@ -517,6 +517,27 @@ int lzm_search_conv_ez(lzm_handle *h, int num_simulations, int pb_c_base, float 
                        int32_t *rec_a, int32_t *rec_len, float *rec_decoded, float *rec_logits, int32_t *rec_reset,
                        void *stream);
 
+/* 1 when lzm_conv_heads takes these head shapes (Kr <= 1024 and a multiple of 4, head planes <= 2048, K per
+ * head <= 1024 and a multiple of 4, supports and actions <= 1024), else 0; host only. conv_infer.pack_heads asks
+ * it before it hands a network's heads to the kernel. */
+int lzm_conv_heads_supported(int Kr, int Khd, int off_policy, int Vr, int Vv, int A);
+
+/* What lzm_search_conv (ez = 0: H and horizon unused, Kr = r_ch * 64) or lzm_search_conv_ez (ez = 1: Kr unused)
+ * would do for this handle, network shape and search length as the process stands, by the function the
+ * launches themselves decide with; host only, launches nothing. out int32 [8]:
+ *   [0] the code the launch would return: LZM_OK it runs, LZM_ERR_ARG the shape or the LDS the tree needs is
+ *       refused, LZM_ERR_CAPACITY more simulations than reserved, LZM_ERR_RESIDENCY (EfficientZero) the grid
+ *       cannot be co-resident (lzm_last_error says which);
+ *   [1] workgroups; [2] LSTM tiles T (EfficientZero); [3] dynamic LDS bytes; [4] head half-heads kept in LDS
+ *   (MuZero, LZM_CONV_PIN); [5] rows of the pb_c table in LDS (EfficientZero; 0: the walk divides);
+ *   [6] rounds of 768 columns the output layer takes (MuZero: all Vr + Vv + A columns; EfficientZero: the
+ *   Vv + A value | policy columns, 0 standing for the one-column-per-thread form taken up to 256 columns);
+ *   [7] 1 when the EfficientZero reward output (Vr columns) takes the one-column-per-thread form.
+ * Returns LZM_ERR_ARG for a null handle or output or num_simulations <= 0, before any HIP call. */
+int lzm_search_conv_plan(const lzm_handle *h, int num_simulations, int ez, int H, int horizon, int n_dres, int n_pres,
+                         int r_ch, int h_ch, int Kr, int Khd, int off_policy, int Vr, int Vv, int categorical,
+                         int32_t *out);
+
 /* lzm_decode_backprop of simulation `cur` fused with lzm_traverse of the next simulation (parity /
  * glibc mode only): one launch in which the wave that backs up root i then walks root i again
  * (same requests, draws and outputs as the two separate calls). Replaces the pair
@@ -544,6 +565,13 @@ int lzm_seed_sequence(const int64_t *count, int64_t base, int S, int32_t *seeds,
 /* Verdict words for the following lzm_decode_backprop(_traverse) calls on this handle: written by
  * lzm_conv_heads(norm_words) for the same outputs; null restores the decode's own check launch. */
 int lzm_set_norm_words(lzm_handle *h, const int32_t *words);
+
+/* Length of the value logit rows read by the following lzm_decode_backprop(_traverse) calls on this handle
+ * when it differs from their support_len (the reward rows' length): a network whose value and reward supports
+ * differ. 0 (the default): the same length. Host state only, and it PERSISTS on the handle across searches until
+ * it is set again: a caller that shares handles sets it before every decode whose lengths may differ from the
+ * last one's (lightzero_amd.tree.DeviceTree does, and clears it when a pooled handle changes owner). */
+int lzm_set_value_support(lzm_handle *h, int value_support_len);
 
 /* ReZero search-with-reuse inputs for the following lzm_traverse / lzm_backprop /
  * lzm_decode_backprop(_traverse) calls on this handle (device arrays [B], kept by pointer; null /

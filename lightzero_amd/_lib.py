@@ -86,6 +86,9 @@ SIGNATURES = {
     "lzm_conv_heads_prepare": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f,
                                _vp, _vp, _vp],
     "lzm_set_norm_words": [_vp, _vp],
+    "lzm_conv_heads_supported": [_i, _i, _i, _i, _i, _i],
+    "lzm_set_value_support": [_vp, _i],
+    "lzm_search_conv_plan": [_vp] + [_i] * 14 + [_vp],
     "lzm_seed_sequence": [_vp, _i64, _i, _vp, _vp],
     "lzm_get_root_outputs": [_vp, _vp, _vp, _vp],
     "lzm_mlp_prepare": [_i, _i, _i, _i, _i, _vp, _vp, _vp],

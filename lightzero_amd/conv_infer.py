@@ -128,15 +128,18 @@ def fold_tensors(model):
 
 def pack_heads(t, hv):
     """lzm_conv_heads layouts (csrc/lzm_heads.h) of the folded head MLPs (fold_tensors' t; hv: value head
-    channels), or None if they do not fit the kernel: w1t [3][8][32][32][4] over the three hidden layers
+    channels), or None if they do not fit the kernel (hidden width 32 per head, K per head <= 1024, supports and
+    actions <= 1024: such a network's heads run as the folded torch Linears): w1t [3][8][32][32][4] over the three hidden layers
     (reward from r, value / policy from the value / policy planes), w2t [32][Vr + Vv + A] (and w2q [8][N2][4],
     k4-major float4s, for the one-launch search lzm_search_conv)."""
     rw1, vw1 = t["rh_w1"], t["ph_w1"]
     Kr, fv = rw1.shape[1], hv * 64
     Khd = vw1.shape[1]
     fp = Khd - fv
-    if rw1.shape[0] != 32 or vw1.shape[0] != 64 or Kr > 1024 or fv > 1024 or fp > 1024 or fp <= 0 \
-            or Kr % 4 or fv % 4 or Khd > 2048:
+    Vr, Vv, A = t["rh_w2"].shape[0], t["v_w2"].shape[0], t["p_w2"].shape[0]
+    # the kernels' hidden width is 32 per head; the rest is the library's own rule (lzm_conv_heads_supported)
+    if rw1.shape[0] != 32 or vw1.shape[0] != 64 or t["v_w2"].shape[1] != 32 or t["p_w2"].shape[1] != 32 \
+            or not _lib.load().lzm_conv_heads_supported(int(Kr), int(Khd), int(fv), int(Vr), int(Vv), int(A)):
         return None
     dev = rw1.device
     W = torch.zeros(96, 1024, dtype=torch.float32, device=dev)
@@ -149,8 +152,7 @@ def pack_heads(t, hv):
     w2t = w2c.t().contiguous()
     w2q = w2c.reshape(-1, 8, 4).permute(1, 0, 2).contiguous()  # [8][N2][4] (the one-launch search)
     b2 = torch.cat([t["rh_b2"], t["v_b2"], t["p_b2"]]).contiguous()
-    return dict(w1t=w1t, b1=b1, w2t=w2t, w2q=w2q, b2=b2, Kr=Kr, Khd=Khd, off_policy=fv, Vr=t["rh_w2"].shape[0],
-                Vv=t["v_w2"].shape[0], A=t["p_w2"].shape[0])
+    return dict(w1t=w1t, b1=b1, w2t=w2t, w2q=w2q, b2=b2, Kr=Kr, Khd=Khd, off_policy=fv, Vr=Vr, Vv=Vv, A=A)
 
 
 class FoldedConvNet:
@@ -219,6 +221,8 @@ class FoldedConvNet:
         L = _lib.load()
         prec = self.PRECISIONS[self.precision]
         n = L.lzm_conv_trunk_floats_p(self.n_dres, self.n_pres, prec)
+        if n < 0:  # more residual blocks than the trunk kernel takes (8 per network): the folded torch path
+            return
         host = np.zeros(n, np.float32)
         self.r_ch, self.h_ch = int(t["rw_w"].shape[0]), int(t["head_w"].shape[0])
         _lib.check(L.lzm_conv_trunk_prepare_p(prec, self.n_dres, self.n_pres, self.r_ch, self.h_ch,

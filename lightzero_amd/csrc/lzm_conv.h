@@ -115,12 +115,25 @@ __device__ __forceinline__ cvf16 conv_tile(const float *in, const float4 *__rest
 #pragma unroll
     for (int c2 = 0; c2 < 32; ++c2) a[c2] = in[abase + 2 * c2 * kCvCS + toff];
     __builtin_amdgcn_sched_barrier(0);
+    // blocked summation: each tap's 64 input channels go into two fresh accumulators (16 MFMA steps each) that
+    // are then added to the running sum — 16 + 2 x TAPS roundings along any path instead of 32 x TAPS in one
+    // chain (K = 576: the single chain's relative error measured 1.5 times torch-f32's in the median, over
+    // _check's bounds at three shapes of tests/test_gpu_conv_numerics.py). One accumulator per tap, which spills
+    // nothing, still misses the bound at one shape. Cost of this form: 46 spilled VGPRs (140 B of scratch per
+    // lane), 59.5 -> 70.8 us per launch at 256 envs; this is the non-default precision (LZM_CONV_F32).
+    cvf16 part[2];
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) part[hf][r] = 0.f;
+    }
 #pragma unroll
     for (int c2 = 0; c2 < 32; ++c2) {
       const float4 wq = wr[tap % 3][c2 >> 2];
       const float b = (c2 & 3) == 0 ? wq.x : (c2 & 3) == 1 ? wq.y : (c2 & 3) == 2 ? wq.z : wq.w;
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c2], b, acc, 0, 0, 0);
+      part[c2 >> 4] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c2], b, part[c2 >> 4], 0, 0, 0);
     }
+    acc += part[0] + part[1];
     __builtin_amdgcn_sched_barrier(0);
   }
   return acc;

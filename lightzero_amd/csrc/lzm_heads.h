@@ -33,7 +33,8 @@ constexpr int kHdParts = 8;    // K split of the first layer, one per 32-lane ha
 constexpr int kHdKMax = 1024;  // K per head (8 parts of 128)
 constexpr int kHdRMax = 1024;  // reward input width
 constexpr int kHdHMax = 2048;  // head planes width
-constexpr int kHdCols = 3;     // output columns per thread: supports up to 768
+constexpr int kHdCols = 3;     // output columns per thread: supports up to 768 (the Atari heads)
+constexpr int kHdColsWide = 4; // the wide instantiation: supports up to 1024, what the one-launch searches take
 
 struct HeadsArgs {
   int B, Kr, Khd;
@@ -53,6 +54,7 @@ struct HeadsArgs {
   int prep_on;
 };
 
+template <int COLS>
 __global__ __launch_bounds__(kHdThreads) void conv_heads_kernel(HeadsArgs p) {
   __shared__ float4 s_in4[kHdEnvs * kHdKMax / 4];
   __shared__ float s_part[kHdParts][kHdEnvs][32];
@@ -79,9 +81,9 @@ __global__ __launch_bounds__(kHdThreads) void conv_heads_kernel(HeadsArgs p) {
   const int N2 = p.Vr + p.Vv + p.A;
   const int j0 = head == 0 ? 0 : (head == 1 ? p.Vr : p.Vr + p.Vv);
   const int wd = head == 0 ? p.Vr : (head == 1 ? p.Vv : p.A);
-  float w2[kHdCols][32], b2[kHdCols];
+  float w2[COLS][32], b2[COLS];
 #pragma unroll
-  for (int cc = 0; cc < kHdCols; ++cc) {
+  for (int cc = 0; cc < COLS; ++cc) {
     const int jj = tid + cc * kHdThreads;
     const bool live = jj < wd;
 #pragma unroll
@@ -145,7 +147,7 @@ __global__ __launch_bounds__(kHdThreads) void conv_heads_kernel(HeadsArgs p) {
     s_hid[e][cc] = fmaxf(s + p.b1[head * 32 + cc], 0.0f);
   }
   __syncthreads();
-  // ---- output layer: kHdCols columns of this head per thread, 32-deep dot per env
+  // ---- output layer: COLS columns of this head per thread, 32-deep dot per env
   float *out = head == 0 ? p.reward : (head == 1 ? p.value : p.policy);
   const bool prep = p.prep_on && head == 2;  // (block-uniform)
   __shared__ float s_lg[kHdEnvs][kHdThreads];
@@ -153,7 +155,7 @@ __global__ __launch_bounds__(kHdThreads) void conv_heads_kernel(HeadsArgs p) {
 #pragma unroll
   for (int e = 0; e < kHdEnvs; ++e) rsum[e] = 0.0f;
 #pragma unroll
-  for (int cc = 0; cc < kHdCols; ++cc) {
+  for (int cc = 0; cc < COLS; ++cc) {
     const int jj = tid + cc * kHdThreads;
     if (jj >= wd) break;
     float acc[kHdEnvs];

@@ -397,7 +397,7 @@ struct DecodeArgs {
   const float *next_latent;
   float *pool_slot;
   long long row_elems;
-  int V, categorical, cur, horizon;
+  int V, Vv, categorical, cur, horizon;  // V: reward support length, Vv: value support length
   float disc;
   float *out_decoded;  // [B][2] {reward, value} after h^-1, optional
   const int32_t *reuse_action;  // optional: search-with-reuse, see reuse_leaf
@@ -410,14 +410,14 @@ struct DecodeArgs {
 // (4 rows) overwrites its own verdict words part[2 * block + head] (1: no row of that head in the
 // block fails), so nothing has to be cleared between calls; consumers AND the words (norm_ok).
 __global__ __launch_bounds__(256) void normalized_check_kernel(const float *a, const float *b, int rows, int V,
-                                                               int32_t *part) {
+                                                               int Vb, int32_t *part) {
   __shared__ int s_ok[2];
   if (threadIdx.x == 0) s_ok[0] = s_ok[1] = 1;
   __syncthreads();
   const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if (w < 2 * rows) {
-    const float *row = (w < rows) ? a + (size_t)w * V : b + (size_t)(w - rows) * V;
-    const float s = wave_row_sum(row, V);
+    const float *row = (w < rows) ? a + (size_t)w * V : b + (size_t)(w - rows) * Vb;
+    const float s = wave_row_sum(row, w < rows ? V : Vb);
     if ((threadIdx.x & 63) == 0 && !(fabsf(s - 1.0f) <= 1e-5f + 1e-5f)) atomicAnd(&s_ok[w < rows ? 0 : 1], 0);
   }
   __syncthreads();
@@ -446,10 +446,10 @@ __device__ inline void decode_root(const DecodeArgs &p, const int32_t *norm_part
   if (p.categorical) {
     const int np = norm_parts(t.B);
     r = wave_support_expectation(p.reward_logits + (size_t)i * p.V, p.V, !norm_ok(norm_part, np, 0));
-    v = wave_support_expectation(p.value_logits + (size_t)i * p.V, p.V, !norm_ok(norm_part, np, 1));
+    v = wave_support_expectation(p.value_logits + (size_t)i * p.Vv, p.Vv, !norm_ok(norm_part, np, 1));
   } else {
     r = p.reward_logits[(size_t)i * p.V];
-    v = p.value_logits[(size_t)i * p.V];
+    v = p.value_logits[(size_t)i * p.Vv];
   }
   r = h_inverse(r);
   v = h_inverse(v);
@@ -786,6 +786,7 @@ struct lzm_handle {
   int step_seeds_n = 0;
   unsigned long long *phase = nullptr;     // [64] diagnostic phase cycles (LZM_PHASE_TIMING=1)
   const int32_t *ext_norm = nullptr;       // lzm_set_norm_words: verdict words written by lzm_conv_heads
+  int value_support = 0;                   // lzm_set_value_support: the value rows' length when it differs (0: same)
   const int32_t *reuse_action = nullptr;   // lzm_set_reuse: search-with-reuse inputs (device, [B])
   const float *reuse_value = nullptr;
   // lzm_search_conv_ez's hand-off workspace (LSTM input rows, outputs, split-K partials, flags)
@@ -1170,9 +1171,9 @@ int lzm_backprop(lzm_handle *h, int cur, float discount, float *minmax, const fl
 }
 
 static int launch_norm_check(lzm_handle *hflag_owner, int32_t *flag, const float *a, const float *b, int rows, int V,
-                             hipStream_t s) {
+                             int Vb, hipStream_t s) {
   (void)hflag_owner;
-  hipLaunchKernelGGL(normalized_check_kernel, dim3(norm_parts(rows)), dim3(256), 0, s, a, b, rows, V, flag);
+  hipLaunchKernelGGL(normalized_check_kernel, dim3(norm_parts(rows)), dim3(256), 0, s, a, b, rows, V, Vb, flag);
   LZM_CHECK_LAUNCH();
   return LZM_OK;
 }
@@ -1185,7 +1186,8 @@ int lzm_decode_backprop(lzm_handle *h, int cur, float discount, float *minmax, c
     set_err("lzm_decode_backprop: null argument");
     return LZM_ERR_ARG;
   }
-  if (categorical && support_len % 2 == 0) {
+  const int value_len = h->value_support > 0 ? h->value_support : support_len;
+  if (categorical && (support_len % 2 == 0 || value_len % 2 == 0)) {
     set_err("lzm_decode_backprop: categorical support length must be odd (2*support_scale+1)");
     return LZM_ERR_ARG;
   }
@@ -1193,7 +1195,7 @@ int lzm_decode_backprop(lzm_handle *h, int cur, float discount, float *minmax, c
   if (rc != LZM_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (categorical && !h->ext_norm) {
-    rc = launch_norm_check(h, h->norm_flag, reward_logits, value_logits, h->B, support_len, s);
+    rc = launch_norm_check(h, h->norm_flag, reward_logits, value_logits, h->B, support_len, value_len, s);
     if (rc != LZM_OK) return rc;
   }
   DecodeArgs p;
@@ -1201,7 +1203,7 @@ int lzm_decode_backprop(lzm_handle *h, int cur, float discount, float *minmax, c
   p.minmax = (float4 *)minmax;
   p.reward_logits = reward_logits; p.value_logits = value_logits; p.policy_logits = policy_logits;
   p.to_play = to_play; p.out_is_reset = out_is_reset; p.next_latent = next_latent; p.pool_slot = pool_slot;
-  p.row_elems = row_elems; p.V = support_len; p.categorical = categorical; p.cur = cur; p.horizon = lstm_horizon;
+  p.row_elems = row_elems; p.V = support_len; p.Vv = value_len; p.categorical = categorical; p.cur = cur; p.horizon = lstm_horizon;
   p.disc = discount; p.out_decoded = out_decoded;
   p.reuse_action = h->reuse_action; p.reuse_value = h->reuse_value;
   dim3 g((h->B * 64 + 255) / 256), b(256);
@@ -1224,7 +1226,8 @@ int lzm_decode_backprop_traverse(lzm_handle *h, int cur, float discount, float *
     set_err("lzm_decode_backprop_traverse: null argument");
     return LZM_ERR_ARG;
   }
-  if (categorical && support_len % 2 == 0) {
+  const int value_len = h->value_support > 0 ? h->value_support : support_len;
+  if (categorical && (support_len % 2 == 0 || value_len % 2 == 0)) {
     set_err("lzm_decode_backprop_traverse: categorical support length must be odd (2*support_scale+1)");
     return LZM_ERR_ARG;
   }
@@ -1246,7 +1249,7 @@ int lzm_decode_backprop_traverse(lzm_handle *h, int cur, float discount, float *
   if (rc != LZM_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (categorical && !h->ext_norm) {
-    rc = launch_norm_check(h, h->norm_flag, reward_logits, value_logits, h->B, support_len, s);
+    rc = launch_norm_check(h, h->norm_flag, reward_logits, value_logits, h->B, support_len, value_len, s);
     if (rc != LZM_OK) return rc;
   }
   DecodeArgs p;
@@ -1254,7 +1257,7 @@ int lzm_decode_backprop_traverse(lzm_handle *h, int cur, float discount, float *
   p.minmax = (float4 *)minmax;
   p.reward_logits = reward_logits; p.value_logits = value_logits; p.policy_logits = policy_logits;
   p.to_play = to_play; p.out_is_reset = out_is_reset; p.next_latent = next_latent; p.pool_slot = pool_slot;
-  p.row_elems = row_elems; p.V = support_len; p.categorical = categorical; p.cur = cur; p.horizon = lstm_horizon;
+  p.row_elems = row_elems; p.V = support_len; p.Vv = value_len; p.categorical = categorical; p.cur = cur; p.horizon = lstm_horizon;
   p.disc = discount; p.out_decoded = out_decoded;
   p.reuse_action = h->reuse_action; p.reuse_value = h->reuse_value;
   TraverseLbArgs q;
@@ -1293,7 +1296,7 @@ int lzm_inverse_scalar_transform(const float *logits, int rows, int V, int categ
     }
   }
   if (categorical)
-    hipLaunchKernelGGL(normalized_check_kernel, dim3(norm_parts(rows)), dim3(256), 0, s, logits, logits, rows, V,
+    hipLaunchKernelGGL(normalized_check_kernel, dim3(norm_parts(rows)), dim3(256), 0, s, logits, logits, rows, V, V,
                        g_scratch_flag);
   hipLaunchKernelGGL(inverse_transform_kernel, dim3((rows * 64 + 255) / 256), dim3(256), 0, s, logits, rows, V,
                      categorical, g_scratch_flag, out);
@@ -2875,18 +2878,28 @@ int lzm_conv_trunk(int B, int n_dres, int n_pres, int r_ch, int h_ch, const floa
 
 }  // extern "C"
 
+// the head shapes lzm_conv_heads takes (pred_only: no reward head, Kr unused): what conv_infer.pack_heads asks
+// through lzm_conv_heads_supported before it hands a network's heads to the kernel
+static bool heads_shape_ok(bool pred_only, int Kr, int Khd, int off_policy, int Vr, int Vv, int A) {
+  constexpr int kMaxCols = kHdColsWide * kHdThreads;
+  return (pred_only || (Kr > 0 && Kr <= kHdRMax && !(Kr & 3))) && Khd > 0 && Khd <= kHdHMax && off_policy > 0 &&
+         off_policy < Khd && Khd - off_policy <= kHdKMax && off_policy <= kHdKMax && Vr > 0 && Vv > 0 && A > 0 &&
+         Vr <= kMaxCols && Vv <= kMaxCols && A <= kMaxCols && !(Khd & 3) && !(off_policy & 3);
+}
+extern "C" int lzm_conv_heads_supported(int Kr, int Khd, int off_policy, int Vr, int Vv, int A) {
+  return heads_shape_ok(false, Kr, Khd, off_policy, Vr, Vv, A) ? 1 : 0;
+}
+
 extern "C" int lzm_conv_heads(int B, int Kr, int Khd, int off_policy, const float *r, const float *r_scale,
                               const float *r_shift, const float *hd, const float *w1t, const float *b1,
                               const float *w2t, const float *b2, int Vr, int Vv, int A, float *reward, float *value,
                               float *policy, int32_t *norm_words, void *stream) {
   // r == NULL: the prediction heads only (value, policy: initial_inference), reward / norm_words unused
   const bool pred_only = !r;
-  if (B <= 0 || (!pred_only && (Kr <= 0 || Kr > kHdRMax || (Kr & 3) || !reward)) || Khd <= 0 || Khd > kHdHMax ||
-      off_policy <= 0 || off_policy >= Khd || Khd - off_policy > kHdKMax || off_policy > kHdKMax || Vr <= 0 ||
-      Vv <= 0 || A <= 0 || Vr > kHdCols * kHdThreads || Vv > kHdCols * kHdThreads || A > kHdCols * kHdThreads ||
-      !hd || !w1t || !b1 || !w2t || !b2 || !value || !policy || (!r_scale) != (!r_shift) || ((uintptr_t)w1t & 15) ||
-      (Khd & 3) || (off_policy & 3)) {
-    set_err("lzm_conv_heads: bad arguments (Kr <= 1024, head planes <= 2048, K per head <= 1024, supports <= 768, 16-B aligned w1t)");
+  if (B <= 0 || !heads_shape_ok(pred_only, Kr, Khd, off_policy, Vr, Vv, A) || (!pred_only && !reward) || !hd || !w1t ||
+      !b1 || !w2t || !b2 || !value || !policy || (!r_scale) != (!r_shift) || ((uintptr_t)w1t & 15)) {
+    set_err("lzm_conv_heads: bad arguments (Kr <= 1024, head planes <= 2048, K per head <= 1024, supports and actions "
+            "<= 1024, 16-B aligned w1t)");
     return LZM_ERR_ARG;
   }
   HeadsArgs p;
@@ -2901,8 +2914,12 @@ extern "C" int lzm_conv_heads(int B, int Kr, int Khd, int off_policy, const floa
   p.norm_words = pred_only ? nullptr : norm_words; p.norm_nparts = norm_parts(B);
   p.head0 = pred_only ? 1 : 0;
   p.prep_on = 0;
-  hipLaunchKernelGGL(conv_heads_kernel, dim3((B + kHdEnvs - 1) / kHdEnvs, pred_only ? 2 : 3), dim3(kHdThreads), 0,
-                     (hipStream_t)stream, p);
+  // three output columns per thread (the Atari supports); the four-column instantiation past 768
+  const dim3 grid((B + kHdEnvs - 1) / kHdEnvs, pred_only ? 2 : 3);
+  if (std::max(Vr, std::max(Vv, A)) <= kHdCols * kHdThreads)
+    hipLaunchKernelGGL(conv_heads_kernel<kHdCols>, grid, dim3(kHdThreads), 0, (hipStream_t)stream, p);
+  else
+    hipLaunchKernelGGL(conv_heads_kernel<kHdColsWide>, grid, dim3(kHdThreads), 0, (hipStream_t)stream, p);
   LZM_CHECK_LAUNCH();
   return LZM_OK;
 }
@@ -2920,10 +2937,9 @@ extern "C" int lzm_conv_heads_prepare(lzm_handle *h, int B, int Khd, int off_pol
             "to_play required");
     return LZM_ERR_ARG;
   }
-  if (B <= 0 || Khd <= 0 || Khd > kHdHMax || off_policy <= 0 || off_policy >= Khd || Khd - off_policy > kHdKMax ||
-      off_policy > kHdKMax || Vr <= 0 || Vv <= 0 || Vv > kHdCols * kHdThreads || !hd || !w1t || !b1 || !w2t || !b2 ||
-      !value || !policy || ((uintptr_t)w1t & 15) || (Khd & 3) || (off_policy & 3)) {
-    set_err("lzm_conv_heads_prepare: bad arguments (head planes <= 2048, K per head <= 1024, supports <= 768, "
+  if (B <= 0 || !heads_shape_ok(true, 0, Khd, off_policy, Vr, Vv, A) || !hd || !w1t || !b1 || !w2t || !b2 || !value ||
+      !policy || ((uintptr_t)w1t & 15)) {
+    set_err("lzm_conv_heads_prepare: bad arguments (head planes <= 2048, K per head <= 1024, supports <= 1024, "
             "16-B aligned w1t)");
     return LZM_ERR_ARG;
   }
@@ -2944,10 +2960,98 @@ extern "C" int lzm_conv_heads_prepare(lzm_handle *h, int B, int Khd, int off_pol
   q.legal_in = legal; q.count_in = count; q.to_play = to_play; q.noises = noises; q.rewards = rewards;
   q.logits = policy; q.noise_weight = noise_weight; q.B = h->B; q.A = h->A;
   p.prep_on = 1;
-  hipLaunchKernelGGL(conv_heads_kernel, dim3((B + kHdEnvs - 1) / kHdEnvs, 2), dim3(kHdThreads), 0, (hipStream_t)stream,
-                     p);
+  const dim3 grid((B + kHdEnvs - 1) / kHdEnvs, 2);
+  if (Vv <= kHdCols * kHdThreads)  // (A <= 256 here)
+    hipLaunchKernelGGL(conv_heads_kernel<kHdCols>, grid, dim3(kHdThreads), 0, (hipStream_t)stream, p);
+  else
+    hipLaunchKernelGGL(conv_heads_kernel<kHdColsWide>, grid, dim3(kHdThreads), 0, (hipStream_t)stream, p);
   LZM_CHECK_LAUNCH();
   return LZM_OK;
+}
+
+// What the one-launch conv searches do for a handle, a network shape and a search length: the one decision
+// behind lzm_search_conv / lzm_search_conv_ez and lzm_search_conv_plan. rc is what the launch returns for this
+// request (LZM_OK: it runs; the message is in g_err otherwise); the LDS offsets are left in p.
+struct ConvPlan {
+  int rc, G, T, npin, pbt_rows, out_rounds, r_one_round;
+  size_t lds;
+};
+// lower bits shared by both kinds: tree, walk and head buffers after the activation buffers (float offsets)
+static size_t conv_plan_lds(const lzm_handle *h, int S, int Kr, int Khd, int Vr, int Vv, size_t o, ConvSearchArgs &p) {
+  p.off_stat = (int)o; o += (size_t)h->cap * 4;
+  p.off_meta = (int)o; o += (size_t)h->cap * 4;
+  p.off_val = (int)o; o += round4((size_t)h->cap);
+  p.off_lut = (int)o; o += round4((size_t)2 * h->lut_n);
+  p.off_legal = (int)o; o += round4((size_t)h->A + 1);
+  p.off_path = (int)o; o += round4((size_t)h->depth_cap);
+  p.off_pact = (int)o; o += round4((size_t)h->depth_cap);
+  p.off_pbt = (int)o; o += round4((size_t)p.pbt_rows * (p.pbt_rows + 1) / 2);
+  p.off_r = (int)o; o += round4((size_t)Kr);
+  p.off_hd = (int)o; o += round4((size_t)Khd);
+  p.off_hid = (int)o; o += 96;
+  p.off_part = (int)o; o += 3 * kHdParts * 32;
+  p.off_lg = (int)o; o += round4((size_t)Vr + Vv + h->A);
+  p.off_seed = (int)o; o += round4((size_t)S + 32);
+  p.off_lmax = (int)o; o += round4((size_t)S + 1);
+  return o;
+}
+static bool conv_shape_ok(int n_dres, int n_pres, int r_ch, int h_ch, int Khd, int off_policy, int Vr, int Vv,
+                          int categorical) {
+  return lzm_conv_trunk_floats_p(n_dres, n_pres, LZM_CONV_SPLIT) >= 0 && r_ch > 0 && r_ch <= 32 &&
+         h_ch > 0 && h_ch <= 32 && Khd == h_ch * 64 && off_policy > 0 && off_policy < Khd && off_policy <= kHdKMax &&
+         Khd - off_policy <= kHdKMax && !(off_policy % 128) && !(Khd % 128) && Vr > 0 && Vv > 0 && Vr <= 1024 &&
+         Vv <= 1024 && (categorical || (Vr == 1 && Vv == 1));
+}
+static ConvPlan conv_plan_mz(const lzm_handle *h, int S, int n_dres, int n_pres, int r_ch, int h_ch, int Kr, int Khd,
+                             int off_policy, int Vr, int Vv, int categorical, ConvSearchArgs &p) {
+  ConvPlan pl{LZM_ERR_ARG, 0, 0, 0, 0, 0, 0, 0};
+  if (h->flags & LZM_TREE_EZ) {
+    set_err("lzm_search_conv: MuZero trees only");
+    return pl;
+  }
+  if (!conv_shape_ok(n_dres, n_pres, r_ch, h_ch, Khd, off_policy, Vr, Vv, categorical) || Kr != r_ch * 64 ||
+      (Kr % 128)) {
+    set_err("lzm_search_conv: unsupported network shape (64x8x8 latent, <= 8 residual blocks per network, <= 32 "
+            "reward / head planes, K per head a multiple of 128 and <= 1024, supports <= 1024)");
+    return pl;
+  }
+  if (S > h->sims_cap) {
+    snprintf(g_err, sizeof(g_err), "lzm_search_conv: %d simulations > reserved %d (lzm_reserve)", S, h->sims_cap);
+    pl.rc = LZM_ERR_CAPACITY;
+    return pl;
+  }
+  // one workgroup per root; roots beyond the CUs queue behind the first ones (their look-back waits only on
+  // lower roots: lzm_search_conv.h sc_lookback)
+  if (h->B > kScMaxRoots) {
+    snprintf(g_err, sizeof(g_err), "lzm_search_conv: %d roots > %d", h->B, kScMaxRoots);
+    return pl;
+  }
+  // dynamic LDS plan (float offsets, 16-B aligned): the two split-fp16 activation buffers first
+  p.pbt_rows = 0;  // (no pb_c table: the MuZero conv walk divides, same bits)
+  size_t o = conv_plan_lds(h, S, Kr, Khd, Vr, Vv, (size_t)2 * kBxBuf / 2, p);
+  if (o * sizeof(float) > kMaxLds) {
+    snprintf(g_err, sizeof(g_err), "lzm_search_conv: %zu B of LDS needed (tree too large: lower num_simulations)",
+             o * sizeof(float));
+    return pl;
+  }
+  // the head hidden layers' first half-head resident in LDS when it fits and every root has a CU of its own
+  // (more roots than CUs: the smaller footprint lets two workgroups share one)
+  constexpr size_t kPinFloats = (size_t)kHdParts * 16 * 32 * 4;
+  const char *pin_env = getenv("LZM_CONV_PIN");
+  const int pin_max = pin_env ? atoi(pin_env) : 1;
+  p.off_wpin = (int)o;
+  p.npin = 0;
+  while (p.npin < pin_max && p.npin < 6 && h->B <= device_cus() && (o + kPinFloats) * sizeof(float) <= kMaxLds) {
+    o += kPinFloats;
+    ++p.npin;
+  }
+  pl.rc = LZM_OK;
+  pl.G = h->B;
+  pl.npin = p.npin;
+  pl.out_rounds = sc_out_rounds(Vr + Vv + h->A);
+  pl.r_one_round = 0;
+  pl.lds = o * sizeof(float);
+  return pl;
 }
 
 // Whole-search launch for the conv MuZero networks (lzm_search_conv.h): one workgroup per root,
@@ -2966,29 +3070,14 @@ extern "C" int lzm_search_conv(lzm_handle *h, int num_simulations, int pb_c_base
     set_err("lzm_search_conv: null argument or no simulations");
     return LZM_ERR_ARG;
   }
-  if (h->flags & LZM_TREE_EZ) {
-    set_err("lzm_search_conv: MuZero trees only");
+  if (((uintptr_t)trunk_w | (uintptr_t)actmap | (uintptr_t)w1t | (uintptr_t)w2q | (uintptr_t)latent_pool) & 15) {
+    set_err("lzm_search_conv: weights and pool must be 16-byte aligned");
     return LZM_ERR_ARG;
   }
-  if (n_dres < 0 || n_pres < 0 || r_ch <= 0 || r_ch > 32 || h_ch <= 0 || h_ch > 32 || Kr != r_ch * 64 ||
-      Khd != h_ch * 64 || off_policy <= 0 || off_policy >= Khd || off_policy > kHdKMax || Khd - off_policy > kHdKMax ||
-      (off_policy % 128) || (Kr % 128) || (Khd % 128) || Vr <= 0 || Vv <= 0 || Vr > 1024 || Vv > 1024 ||
-      (!categorical && (Vr != 1 || Vv != 1)) ||
-      (((uintptr_t)trunk_w | (uintptr_t)actmap | (uintptr_t)w1t | (uintptr_t)w2q | (uintptr_t)latent_pool) & 15)) {
-    set_err("lzm_search_conv: unsupported network shape (64x8x8 latent, <= 32 reward / head planes, K per head a "
-            "multiple of 128 and <= 1024, supports <= 1024, 16-B aligned weights and pool)");
-    return LZM_ERR_ARG;
-  }
-  if (S > h->sims_cap) {
-    snprintf(g_err, sizeof(g_err), "lzm_search_conv: %d simulations > reserved %d (lzm_reserve)", S, h->sims_cap);
-    return LZM_ERR_CAPACITY;
-  }
-  // one workgroup per root; roots beyond the CUs queue behind the first ones (their look-back waits only on
-  // lower roots: lzm_search_conv.h sc_lookback)
-  if (h->B > kScMaxRoots) {
-    snprintf(g_err, sizeof(g_err), "lzm_search_conv: %d roots > %d", h->B, kScMaxRoots);
-    return LZM_ERR_ARG;
-  }
+  ConvSearchArgs p;
+  memset(&p, 0, sizeof(p));
+  const ConvPlan plan = conv_plan_mz(h, S, n_dres, n_pres, r_ch, h_ch, Kr, Khd, off_policy, Vr, Vv, categorical, p);
+  if (plan.rc != LZM_OK) return plan.rc;
   int rc = fill_lut(h, pb_c_base, pb_c_init);
   if (rc != LZM_OK) return rc;
   const bool fast = (h->flags & LZM_RNG_FAST) != 0;
@@ -2998,8 +3087,6 @@ extern "C" int lzm_search_conv(lzm_handle *h, int num_simulations, int pb_c_base
   }
   rc = ensure_flags(h, S, h->B);
   if (rc != LZM_OK) return rc;
-  ConvSearchArgs p;
-  memset(&p, 0, sizeof(p));
   p.stat = h->stat; p.meta = h->meta; p.legal = h->legal; p.nlegal = h->nlegal;
   p.path = h->path; p.path_act = h->path_act; p.pathlen = h->pathlen; p.lut = h->lut;
   p.B = h->B; p.A = h->A; p.cap = h->cap; p.lut_n = h->lut_n; p.depth_cap = h->depth_cap;
@@ -3012,41 +3099,7 @@ extern "C" int lzm_search_conv(lzm_handle *h, int num_simulations, int pb_c_base
   p.rec_x = rec_x; p.rec_a = rec_a; p.rec_len = rec_len; p.rec_dec = rec_decoded; p.rec_logits = rec_logits;
   p.step_count = h->step_count; p.step_base = h->step_base; p.step_inc = h->step_inc; p.step_fresh = h->step_fresh;
   p.step_delta = h->step_delta; p.out_dist = h->step_dist; p.out_values = h->step_vals;
-  // dynamic LDS plan (float offsets, 16-B aligned): the two split-fp16 activation buffers first
-  size_t o = (size_t)2 * kBxBuf / 2;
-  p.off_stat = (int)o; o += (size_t)h->cap * 4;
-  p.off_meta = (int)o; o += (size_t)h->cap * 4;
-  p.off_val = (int)o; o += round4((size_t)h->cap);
-  p.off_lut = (int)o; o += round4((size_t)2 * h->lut_n);
-  p.off_legal = (int)o; o += round4((size_t)h->A + 1);
-  p.off_path = (int)o; o += round4((size_t)h->depth_cap);
-  p.off_pact = (int)o; o += round4((size_t)h->depth_cap);
-  p.pbt_rows = 0;  // (no pb_c table: the MuZero conv walk divides, same bits)
-  p.off_pbt = (int)o;
-  p.off_r = (int)o; o += round4((size_t)Kr);
-  p.off_hd = (int)o; o += round4((size_t)Khd);
-  p.off_hid = (int)o; o += 96;
-  p.off_part = (int)o; o += 3 * kHdParts * 32;
-  p.off_lg = (int)o; o += round4((size_t)Vr + Vv + h->A);
-  p.off_seed = (int)o; o += round4((size_t)S + 32);
-  p.off_lmax = (int)o; o += round4((size_t)S + 1);
-  if (o * sizeof(float) > kMaxLds) {
-    snprintf(g_err, sizeof(g_err), "lzm_search_conv: %zu B of LDS needed (tree too large: lower num_simulations)",
-             o * sizeof(float));
-    return LZM_ERR_ARG;
-  }
-  // the head hidden layers' first half-head resident in LDS when it fits and every root has a CU of its own
-  // (more roots than CUs: the smaller footprint lets two workgroups share one)
-  constexpr size_t kPinFloats = (size_t)kHdParts * 16 * 32 * 4;
-  const char *pin_env = getenv("LZM_CONV_PIN");
-  const int pin_max = pin_env ? atoi(pin_env) : 1;
-  p.off_wpin = (int)o;
-  p.npin = 0;
-  while (p.npin < pin_max && p.npin < 6 && h->B <= device_cus() && (o + kPinFloats) * sizeof(float) <= kMaxLds) {
-    o += kPinFloats;
-    ++p.npin;
-  }
-  const size_t lds = o * sizeof(float);
+  const size_t lds = plan.lds;
   const bool stamps = getenv("LZM_PHASE_TIMING") && atoi(getenv("LZM_PHASE_TIMING")) > 0;
   if (stamps && !h->phase) {
     LZM_HIP(hipMalloc(&h->phase, (64 + 1024) * sizeof(unsigned long long)));
@@ -3061,6 +3114,113 @@ extern "C" int lzm_search_conv(lzm_handle *h, int num_simulations, int pb_c_base
     e = hipGetLastError();
   }
   LZM_HIP(e);
+  return LZM_OK;
+}
+
+using ConvEzFn = decltype(&search_conv_ez_kernel<kBxAheadEz, false, false>);
+static ConvEzFn conv_ez_kernel_fn(bool fast, bool stamps) {
+  return stamps ? (fast ? search_conv_ez_kernel<kBxAheadEz, true, true> : search_conv_ez_kernel<kBxAheadEz, false, true>)
+                : (fast ? search_conv_ez_kernel<kBxAheadEz, true> : search_conv_ez_kernel<kBxAheadEz, false>);
+}
+static bool conv_stamps() { return getenv("LZM_PHASE_TIMING") && atoi(getenv("LZM_PHASE_TIMING")) > 0; }
+
+// conv_plan_mz's EfficientZero twin. The shape, capacity and grid checks touch no HIP state; a request that
+// passes them is then measured against the occupancy of the kernel it would launch (residency = true).
+static ConvPlan conv_plan_ez(const lzm_handle *h, int S, int H, int horizon, int n_dres, int n_pres, int r_ch, int h_ch,
+                             int Khd, int off_policy, int Vr, int Vv, int categorical, ConvSearchArgs &p) {
+  ConvPlan pl{LZM_ERR_ARG, 0, 0, 0, 0, 0, 0, 0};
+  if (!(h->flags & LZM_TREE_EZ)) {
+    set_err("lzm_search_conv_ez: EfficientZero trees only");
+    return pl;
+  }
+  const int Kx = r_ch * 64 + H;
+  if (!conv_shape_ok(n_dres, n_pres, r_ch, h_ch, Khd, off_policy, Vr, Vv, categorical) || H <= 0 || H % kLsUnits ||
+      H % 128 || H > kHdKMax || H / kLsUnits > 64 || Kx % (2 * kLsKc) || horizon <= 0 || S > 4094) {
+    set_err("lzm_search_conv_ez: unsupported network shape (64x8x8 latent, <= 8 residual blocks per network, <= 32 "
+            "reward / head planes, K per head a multiple of 128 and <= 1024, supports <= 1024, LSTM width a multiple "
+            "of 128, (r_ch * 64 + H) % 128 == 0, horizon > 0) or more than 4094 simulations");
+    return pl;
+  }
+  if (S > h->sims_cap) {
+    snprintf(g_err, sizeof(g_err), "lzm_search_conv_ez: %d simulations > reserved %d (lzm_reserve)", S, h->sims_cap);
+    pl.rc = LZM_ERR_CAPACITY;
+    return pl;
+  }
+  // LZM_RESIDENCY_CUS=<n> caps the CU count this check assumes (tests: force the refusal)
+  int cus = device_cus();
+  if (const char *ov = getenv("LZM_RESIDENCY_CUS"))
+    if (atoi(ov) > 0) cus = std::min(cus, atoi(ov));
+  const int B = h->B, nmb = (B + kLsRows - 1) / kLsRows, T = nmb * (H / kLsUnits), G = std::max(B, 2 * T);
+  pl.G = G;
+  pl.T = T;
+  p.nmb = nmb; p.T = T;
+  if (B > 256 || G > cus) {
+    snprintf(g_err, sizeof(g_err),
+             "lzm_search_conv_ez: %d workgroups (%d roots, %d LSTM tiles x 2) > min(%d CUs) or B > 256 (the grid is "
+             "co-resident)", G, B, T, cus);
+    pl.rc = LZM_ERR_RESIDENCY;
+    return pl;
+  }
+  // dynamic LDS plan (float offsets, 16-B aligned): the activation buffers / LSTM stage buffers first
+  p.pbt_rows = ((size_t)h->lut_n * (h->lut_n + 1) / 2 <= 4096) ? h->lut_n : 0;
+  const size_t o = conv_plan_lds(h, S, H, Khd, Vr, Vv, std::max((size_t)2 * kBxBuf / 2, (size_t)kLsLdsBytes / 4), p);
+  pl.lds = o * sizeof(float);
+  pl.pbt_rows = p.pbt_rows;
+  pl.out_rounds = sc_one_round(Vv + h->A) ? 0 : sc_out_rounds(Vv + h->A);
+  pl.r_one_round = sc_one_round(Vr) ? 1 : 0;
+  if (pl.lds > kMaxLds) {
+    snprintf(g_err, sizeof(g_err), "lzm_search_conv_ez: %zu B of LDS needed (tree too large: lower num_simulations)",
+             pl.lds);
+    return pl;
+  }
+  // The roots wait on LSTM tiles and the tiles on roots inside the launch, so every workgroup must be
+  // resident at once. The check is static: resident workgroups per CU at this LDS / register use (the
+  // occupancy API) x the CUs must cover the grid, else LZM_ERR_RESIDENCY and nothing ran (the caller takes
+  // the generic per-simulation path). It cannot see other work on the GPU (a learner on another stream, a
+  // second rank on the same GPU): every hand-off wait in the kernel is bounded and a timeout is counted in
+  // the tree's error word (lzm_check_errors raises), never a hang. The launch is a plain one, eager and
+  // captured alike: the cooperative launch it replaced applies the same static occupancy check (it is
+  // not a residency guarantee against other streams), cannot be captured into a HIP graph, and its
+  // runtime state was the one difference from the MuZero conv search in the EZ trace that faulted in
+  // exit() after rocprofv3 finalised (profiles/r05/README.md).
+  const void *fn = (const void *)conv_ez_kernel_fn((h->flags & LZM_RNG_FAST) != 0, conv_stamps());
+  int per_cu = 0;
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kScThreads, pl.lds) != hipSuccess) {
+    set_err("lzm_search_conv_ez: the occupancy query failed");
+    pl.rc = LZM_ERR_HIP;
+    return pl;
+  }
+  if ((long long)per_cu * cus < G) {
+    snprintf(g_err, sizeof(g_err), "lzm_search_conv_ez: %d workgroups > %d resident (%d per CU x %d CUs)", G,
+             per_cu * cus, per_cu, cus);
+    pl.rc = LZM_ERR_RESIDENCY;
+    return pl;
+  }
+  pl.rc = LZM_OK;
+  return pl;
+}
+
+// What lzm_search_conv (ez = 0: H and horizon ignored, Kr = r_ch * 64) or lzm_search_conv_ez (ez = 1: Kr ignored)
+// would do for this request as the process stands, by the launches' own decision (conv_plan_mz / conv_plan_ez);
+// launches nothing. out[8]: {rc the launch would return (LZM_OK: it runs), workgroups, LSTM tiles, dynamic LDS
+// bytes, pinned head half-heads, pb_c table rows, rounds of the value | policy (MuZero: whole) output loop
+// (0 = EfficientZero's single-round form), 1 if the EfficientZero reward output takes the single-round form}.
+extern "C" int lzm_search_conv_plan(const lzm_handle *h, int num_simulations, int ez, int H, int horizon, int n_dres,
+                                    int n_pres, int r_ch, int h_ch, int Kr, int Khd, int off_policy, int Vr, int Vv,
+                                    int categorical, int32_t *out) {
+  if (!h || !out || num_simulations <= 0) {
+    set_err("lzm_search_conv_plan: null argument or no simulations");
+    return LZM_ERR_ARG;
+  }
+  ConvSearchArgs p;
+  memset(&p, 0, sizeof(p));
+  const ConvPlan pl = ez ? conv_plan_ez(h, num_simulations, H, horizon, n_dres, n_pres, r_ch, h_ch, Khd, off_policy,
+                                        Vr, Vv, categorical, p)
+                         : conv_plan_mz(h, num_simulations, n_dres, n_pres, r_ch, h_ch, Kr, Khd, off_policy, Vr, Vv,
+                                        categorical, p);
+  out[0] = pl.rc; out[1] = pl.G; out[2] = pl.T; out[3] = (int32_t)pl.lds; out[4] = pl.npin; out[5] = pl.pbt_rows;
+  out[6] = pl.out_rounds; out[7] = pl.r_one_round;
   return LZM_OK;
 }
 
@@ -3084,38 +3244,17 @@ extern "C" int lzm_search_conv_ez(lzm_handle *h, int num_simulations, int pb_c_b
     set_err("lzm_search_conv_ez: null argument or no simulations");
     return LZM_ERR_ARG;
   }
-  if (!(h->flags & LZM_TREE_EZ)) {
-    set_err("lzm_search_conv_ez: EfficientZero trees only");
+  if (((uintptr_t)trunk_w | (uintptr_t)actmap | (uintptr_t)w1t | (uintptr_t)w2q | (uintptr_t)latent_pool |
+       (uintptr_t)hpool | (uintptr_t)cpool | (uintptr_t)lstm_frag | (uintptr_t)vp_s | (uintptr_t)vp_t) & 15) {
+    set_err("lzm_search_conv_ez: weights and pools must be 16-byte aligned");
     return LZM_ERR_ARG;
   }
-  const int Kx = r_ch * 64 + H;
-  if (n_dres < 0 || n_pres < 0 || r_ch <= 0 || r_ch > 32 || h_ch <= 0 || h_ch > 32 || Khd != h_ch * 64 ||
-      off_policy <= 0 || off_policy >= Khd || off_policy > kHdKMax || Khd - off_policy > kHdKMax || (off_policy % 128) ||
-      (Khd % 128) || H <= 0 || H % kLsUnits || H % 128 || H > kHdKMax || H / kLsUnits > 64 || Kx % (2 * kLsKc) ||
-      horizon <= 0 || Vr <= 0 || Vv <= 0 || Vr > 1024 || Vv > 1024 || (!categorical && (Vr != 1 || Vv != 1)) ||
-      S > 4094 ||
-      (((uintptr_t)trunk_w | (uintptr_t)actmap | (uintptr_t)w1t | (uintptr_t)w2q | (uintptr_t)latent_pool |
-        (uintptr_t)hpool | (uintptr_t)cpool | (uintptr_t)lstm_frag | (uintptr_t)vp_s | (uintptr_t)vp_t) & 15)) {
-    set_err("lzm_search_conv_ez: unsupported network shape (64x8x8 latent, <= 32 reward / head planes, K per head a "
-            "multiple of 128 and <= 1024, LSTM width a multiple of 128, (r_ch * 64 + H) % 128 == 0, horizon > 0, "
-            "16-B aligned weights and pools) or more than 4094 simulations");
-    return LZM_ERR_ARG;
-  }
-  if (S > h->sims_cap) {
-    snprintf(g_err, sizeof(g_err), "lzm_search_conv_ez: %d simulations > reserved %d (lzm_reserve)", S, h->sims_cap);
-    return LZM_ERR_CAPACITY;
-  }
-  // LZM_RESIDENCY_CUS=<n> caps the CU count this check assumes (tests: force the refusal)
-  int cus = device_cus();
-  if (const char *ov = getenv("LZM_RESIDENCY_CUS"))
-    if (atoi(ov) > 0) cus = std::min(cus, atoi(ov));
-  const int B = h->B, nmb = (B + kLsRows - 1) / kLsRows, T = nmb * (H / kLsUnits), G = std::max(B, 2 * T);
-  if (B > 256 || G > cus) {
-    snprintf(g_err, sizeof(g_err),
-             "lzm_search_conv_ez: %d workgroups (%d roots, %d LSTM tiles x 2) > min(%d CUs) or B > 256 (the grid is "
-             "co-resident)", G, B, T, cus);
-    return LZM_ERR_RESIDENCY;
-  }
+  ConvSearchArgs p;
+  memset(&p, 0, sizeof(p));
+  const ConvPlan plan = conv_plan_ez(h, S, H, horizon, n_dres, n_pres, r_ch, h_ch, Khd, off_policy, Vr, Vv,
+                                     categorical, p);
+  if (plan.rc != LZM_OK) return plan.rc;
+  const int Kx = r_ch * 64 + H, B = h->B, T = plan.T, G = plan.G;
   int rc = fill_lut(h, pb_c_base, pb_c_init);
   if (rc != LZM_OK) return rc;
   const bool fast = (h->flags & LZM_RNG_FAST) != 0;
@@ -3139,8 +3278,6 @@ extern "C" int lzm_search_conv_ez(lzm_handle *h, int num_simulations, int pb_c_b
   }
   float *wsf = reinterpret_cast<float *>(h->ez_ws);
   unsigned long long *wsl = reinterpret_cast<unsigned long long *>(wsf + f_xin + f_h1 + f_part);
-  ConvSearchArgs p;
-  memset(&p, 0, sizeof(p));
   p.stat = h->stat; p.meta = h->meta; p.legal = h->legal; p.nlegal = h->nlegal;
   p.path = h->path; p.path_act = h->path_act; p.pathlen = h->pathlen; p.lut = h->lut;
   p.B = B; p.A = h->A; p.cap = h->cap; p.lut_n = h->lut_n; p.depth_cap = h->depth_cap;
@@ -3159,58 +3296,14 @@ extern "C" int lzm_search_conv_ez(lzm_handle *h, int num_simulations, int pb_c_b
   p.Kx = Kx; p.H = H; p.horizon = horizon; p.hpool = hpool; p.cpool = cpool;
   p.lwfrag = reinterpret_cast<const uint16_t *>(lstm_frag); p.lwinv = lstm_frag + ls_frag_floats(Kx, H);
   p.lbias = lstm_bias; p.vp_s = vp_s; p.vp_t = vp_t;
-  p.nmb = nmb; p.T = T;
-  // dynamic LDS plan (float offsets, 16-B aligned): the activation buffers / LSTM stage buffers first
-  size_t o = std::max((size_t)2 * kBxBuf / 2, (size_t)kLsLdsBytes / 4);
-  p.off_stat = (int)o; o += (size_t)h->cap * 4;
-  p.off_meta = (int)o; o += (size_t)h->cap * 4;
-  p.off_val = (int)o; o += round4((size_t)h->cap);
-  p.off_lut = (int)o; o += round4((size_t)2 * h->lut_n);
-  p.off_legal = (int)o; o += round4((size_t)h->A + 1);
-  p.off_path = (int)o; o += round4((size_t)h->depth_cap);
-  p.off_pact = (int)o; o += round4((size_t)h->depth_cap);
-  p.pbt_rows = ((size_t)h->lut_n * (h->lut_n + 1) / 2 <= 4096) ? h->lut_n : 0;
-  p.off_pbt = (int)o; o += round4((size_t)p.pbt_rows * (p.pbt_rows + 1) / 2);
-  p.off_r = (int)o; o += round4((size_t)H);
-  p.off_hd = (int)o; o += round4((size_t)Khd);
-  p.off_hid = (int)o; o += 96;
-  p.off_part = (int)o; o += 3 * kHdParts * 32;
-  p.off_lg = (int)o; o += round4((size_t)Vr + Vv + h->A);
-  p.off_seed = (int)o; o += round4((size_t)S + 32);
-  p.off_lmax = (int)o; o += round4((size_t)S + 1);
-  const size_t lds = o * sizeof(float);
-  if (lds > kMaxLds) {
-    snprintf(g_err, sizeof(g_err), "lzm_search_conv_ez: %zu B of LDS needed (tree too large: lower num_simulations)",
-             lds);
-    return LZM_ERR_ARG;
-  }
-  const bool stamps = getenv("LZM_PHASE_TIMING") && atoi(getenv("LZM_PHASE_TIMING")) > 0;
+  const size_t lds = plan.lds;
+  const bool stamps = conv_stamps();
   if (stamps && !h->phase) {
     LZM_HIP(hipMalloc(&h->phase, (64 + 1024) * sizeof(unsigned long long)));
     LZM_HIP(hipMemset(h->phase, 0, (64 + 1024) * sizeof(unsigned long long)));
   }
   p.stamps = stamps ? h->phase : nullptr;
-  auto fn = stamps ? (fast ? search_conv_ez_kernel<kBxAheadEz, true, true> : search_conv_ez_kernel<kBxAheadEz, false, true>)
-                   : (fast ? search_conv_ez_kernel<kBxAheadEz, true> : search_conv_ez_kernel<kBxAheadEz, false>);
-  LZM_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  // The roots wait on LSTM tiles and the tiles on roots inside the launch, so every workgroup must be
-  // resident at once. The check is static: resident workgroups per CU at this LDS / register use (the
-  // occupancy API) x the CUs must cover the grid, else LZM_ERR_RESIDENCY and nothing ran (the caller takes
-  // the generic per-simulation path). It cannot see other work on the GPU (a learner on another stream, a
-  // second rank on the same GPU): every hand-off wait in the kernel is bounded and a timeout is counted in
-  // the tree's error word (lzm_check_errors raises), never a hang. The launch is a plain one, eager and
-  // captured alike: the cooperative launch it replaced applies the same static occupancy check (it is
-  // not a residency guarantee against other streams), cannot be captured into a HIP graph, and its
-  // runtime state was the one difference from the MuZero conv search in the EZ trace that faulted in
-  // exit() after rocprofv3 finalised (profiles/r05/README.md).
-  int per_cu = 0;
-  LZM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)fn, kScThreads, lds));
-  if ((long long)per_cu * cus < G) {
-    snprintf(g_err, sizeof(g_err), "lzm_search_conv_ez: %d workgroups > %d resident (%d per CU x %d CUs)", G,
-             per_cu * cus, per_cu, cus);
-    return LZM_ERR_RESIDENCY;
-  }
-  hipLaunchKernelGGL(fn, dim3(G), dim3(kScThreads), lds, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(conv_ez_kernel_fn(fast, stamps), dim3(G), dim3(kScThreads), lds, (hipStream_t)stream, p);
   LZM_CHECK_LAUNCH();
   return LZM_OK;
 }
@@ -3397,6 +3490,15 @@ extern "C" int lzm_set_reuse(lzm_handle *h, const int32_t *true_action, const fl
   }
   h->reuse_action = true_action;
   h->reuse_value = reuse_value;
+  return LZM_OK;
+}
+
+extern "C" int lzm_set_value_support(lzm_handle *h, int value_support_len) {
+  if (!h || value_support_len < 0) {
+    set_err("lzm_set_value_support: null handle or negative length");
+    return LZM_ERR_ARG;
+  }
+  h->value_support = value_support_len;
   return LZM_OK;
 }
 

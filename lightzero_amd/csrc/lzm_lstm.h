@@ -251,8 +251,22 @@ __global__ __launch_bounds__(kLsThreads) void ez_lstm_gemm_cell_kernel(LstmArgs 
 #pragma unroll
   for (int t = 0; t < 2; ++t) acc[t] = bxf4{0.f, 0.f, 0.f, 0.f};
   const int ar = lane & 15, ag = lane >> 4;
+  // Without the split-K hand-off the workgroup still sums the two K halves apart, each from zero, and adds them
+  // at the end: the split form's order, so the same bits with and without a workspace, and half the chain length
+  // (one chain over K = 1,152 measured 1.5 times torch-f32's error). K not a multiple of 128: one chain.
+  const int nhalf = (p.splitk == 1 && K % (2 * kLsKc) == 0) ? nst / 2 : -1;
+  bxf4 lo[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) lo[t] = bxf4{0.f, 0.f, 0.f, 0.f};
   auto stage = [&](int s, auto par) __attribute__((always_inline)) {
     constexpr int PAR = decltype(par)::value;
+    if (s == nhalf) {  // (uniform) the lower half is complete: the upper half starts from zero
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        lo[t] = acc[t];
+        acc[t] = bxf4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
     __syncthreads();
     if (s + 2 < nst) {
       if constexpr (PAR == 0)
@@ -291,6 +305,10 @@ __global__ __launch_bounds__(kLsThreads) void ez_lstm_gemm_cell_kernel(LstmArgs 
   for (int s = 0; s < nst; s += 2) {
     stage(s, I0());
     if (s + 1 < nst) stage(s + 1, I1());
+  }
+  if (nhalf >= 0) {  // (uniform; the split form's final add: lower + upper)
+#pragma unroll
+    for (int t = 0; t < 2; ++t) acc[t] = lo[t] + acc[t];
   }
   stamp(2);
   if (bad && p.range_err) atomicAdd(p.range_err, 1);

@@ -40,6 +40,12 @@ namespace lzm {
 
 constexpr int kScThreads = 256;
 constexpr int kScMaxRoots = 1024;  // search_conv_kernel: roots per launch (one workgroup each, queued past the CUs)
+// The head output layers: n columns take the single-round form (sc_head_out1_rs, one column per thread) when they
+// fit one round of the workgroup, else rounds of three columns per thread (sc_head_out and the MuZero kernel's
+// loop). The kernels and the host's launch plan (lzm_search_conv_plan) both ask here.
+constexpr int kScOutCols = 3 * kScThreads;
+__host__ __device__ constexpr bool sc_one_round(int n) { return n <= kScThreads; }
+__host__ __device__ constexpr int sc_out_rounds(int n) { return (n + kScOutCols - 1) / kScOutCols; }
 
 struct ConvSearchArgs {
   // tree (HBM, whole batch; the kernel stages root b's slice)
@@ -226,7 +232,7 @@ __device__ __forceinline__ float sc_decode_row(const float *row, int V, float *r
 // [0, N2) into ranges gives the same bits.
 __device__ __forceinline__ void sc_head_out(const ConvSearchArgs &p, const float *lhid, float *llg, int N2, int jlo,
                                             int jhi, int tid) {
-  for (int j0 = jlo; j0 < jhi; j0 += 3 * kScThreads) {
+  for (int j0 = jlo; j0 < jhi; j0 += kScOutCols) {
     float4 w2[3][8];
     float b2[3];
 #pragma unroll
@@ -685,7 +691,7 @@ __global__ __launch_bounds__(kScThreads) __attribute__((amdgpu_waves_per_eu(1, 1
     // reads 64 consecutive columns' float4s, 1 KiB contiguous), up to three columns per thread per
     // round with every load of the round in flight; the FMA order of conv_heads_kernel (k = 0 .. 31
     // from zero, then + bias)
-    for (int j0 = 0; j0 < N2; j0 += 3 * kScThreads) {
+    for (int j0 = 0; j0 < N2; j0 += kScOutCols) {
       float4 w2[3][8];
       float b2[3];
 #pragma unroll
@@ -1111,7 +1117,7 @@ __global__ __launch_bounds__(kScThreads) __attribute__((amdgpu_waves_per_eu(1, 1
       sc_head_hidden_rs(lhd + p.off_policy, p.Khd - p.off_policy, p.w1t, 2, tid < 32 ? p.b1[64 + tid] : 0.0f, lpart,
                      lhid + 64, tid);
       stamp(3);
-      if (N2 - p.Vr <= kScThreads)
+      if (sc_one_round(N2 - p.Vr))
         sc_head_out1_rs(p, lhid, llg, N2, p.Vr, N2, tid);
       else
         sc_head_out(p, lhid, llg, N2, p.Vr, N2, tid);
@@ -1249,7 +1255,7 @@ __global__ __launch_bounds__(kScThreads) __attribute__((amdgpu_waves_per_eu(1, 1
         }
         __syncthreads();
         sc_head_hidden_rs(lr, p.Kr, p.w1t, 0, tid < 32 ? p.b1[tid] : 0.0f, lpart, lhid, tid);
-        if (p.Vr <= kScThreads)
+        if (sc_one_round(p.Vr))
           sc_head_out1_rs(p, lhid, llg, N2, 0, p.Vr, tid);
         else
           sc_head_out(p, lhid, llg, N2, 0, p.Vr, tid);

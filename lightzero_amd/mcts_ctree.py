@@ -104,17 +104,6 @@ class _SearchBuffers:
         return self
 
 
-_CUS = {}
-
-
-def _device_cus(device):
-    """compute units of `device` (the one-launch conv search needs one co-resident workgroup per root)"""
-    key = str(device)
-    if key not in _CUS:
-        _CUS[key] = torch.cuda.get_device_properties(device).multi_processor_count
-    return _CUS[key]
-
-
 def _step_net(mcts, model):
     """the BN-folded recurrent step for the conv MuZeroModel / EfficientZeroModel family
     (conv_infer.FoldedConvNet, cfg.fold_network, default on), else the model itself"""
@@ -279,24 +268,24 @@ class MuZeroMCTSCtree(object):
             return None  # (the streaming kernel's LDS need at this width and tree size)
         return packed, dims
 
-    def _fused_conv(self, model, t, shape):
-        """The native split-precision FoldedConvNet when the whole search can run as one lzm_search_conv
-        launch (conv MuZeroModel, 64 x 8 x 8 latent, packed heads with K multiples of 128, one workgroup
-        per root, up to 1024 roots: past the CU count they queue); None otherwise (the generic
-        per-simulation path). cfg.fused_search (default on) and
-        LZM_FUSED_CONV=0 turn it off."""
+    def _fused_conv(self, model, t, shape, S=None):
+        """The native split-precision FoldedConvNet when the whole search of S simulations (default: the tree's
+        reserved capacity) can run as one lzm_search_conv launch: a conv MuZeroModel with a 64 x 8 x 8 latent
+        whose trunk and heads are packed, of a shape and tree size the launch itself accepts — asked of the
+        library (DeviceTree.search_conv_plan: head K multiples of 128, supports <= 1024, up to 1024 roots, the
+        tree in the workgroup's LDS); None otherwise (the generic per-simulation path). cfg.fused_search
+        (default on) and LZM_FUSED_CONV=0 turn it off."""
+        self.last_plan = None  # (the plan of this search, when the library is asked)
         if not self._cfg.get('fused_search', True) or t.ez or os.environ.get("LZM_FUSED_CONV", "1") == "0":
-            return None
-        if tuple(shape) != (64, 8, 8) or t.B > 1024:  # (lzm_search_conv: kScMaxRoots)
             return None
         net = _step_net(self, model)
         hp = getattr(net, "heads", None)
-        if getattr(net, "native", None) is None or hp is None or getattr(net, "precision", None) != "split" \
-                or getattr(net, "ez", True):
+        if tuple(shape) != (64, 8, 8) or getattr(net, "native", None) is None or hp is None \
+                or getattr(net, "precision", None) != "split" or getattr(net, "ez", True) or hp["A"] != t.A:
             return None
-        if hp["Kr"] % 128 or hp["Khd"] % 128 or hp["off_policy"] % 128 or hp["A"] != t.A:
-            return None
-        return net
+        plan = t.search_conv_plan(net, t.sims_capacity if S is None else S, categorical=self._categorical())
+        self.last_plan = plan
+        return net if plan["supported"] else None
 
     def _loop(self, t, model, buf, mm, vtp_in, seeds, S, row, rec=None, infer=None, net=None):
         """The S simulations (mcts_ctree.py:255-321), all enqueued on the current stream.
@@ -365,7 +354,7 @@ class MuZeroMCTSCtree(object):
             row = int(np.prod(shape)) if len(shape) else 1
             rec = _Recorder(S, B, t.A, dev) if getattr(self, "record", False) else None
             fz = self._fused(model, t, S)
-            cz = self._fused_conv(model, t, shape) if fz is None else None
+            cz = self._fused_conv(model, t, shape, S) if fz is None else None
             graph = fz is None and cz is None and rec is None and self._cfg.get('use_hip_graph', False)
             gkey = _graph_key(t, model, B, S, shape) if graph else None
             entry = self._graphs.get(gkey, model, t) if graph else None
@@ -540,28 +529,31 @@ class EfficientZeroMCTSCtree(object):
     def roots(cls: int, active_collect_env_num: int, legal_actions: List[Any]) -> "ez_tree.Roots":
         return ez_tree.Roots(active_collect_env_num, legal_actions, fast_rng=(cls.rng_mode == 'philox'))
 
-    def _fused_conv(self, model, t, shape, Hl):
-        """The native split-precision FoldedConvNet (with the fused LSTM step packed) when the whole search
-        can run as one lzm_search_conv_ez launch: conv EfficientZeroModel, 64 x 8 x 8 latent, head K
-        multiples of 128, LSTM width a multiple of 128, max(B, 2 T) workgroups co-resident (T = ceil(B / 64)
-        * H / 16 LSTM tiles); None otherwise (the generic per-simulation path). cfg.fused_search (default
-        on) and LZM_FUSED_CONV=0 turn it off."""
+    def _fused_conv(self, model, t, shape, Hl, S=None):
+        """The native split-precision FoldedConvNet (with the fused LSTM step packed) when the whole search of
+        S simulations (default: the tree's reserved capacity) is one the lzm_search_conv_ez launch takes: a
+        conv EfficientZeroModel with a 64 x 8 x 8 latent whose trunk, heads and LSTM are packed, of a shape and
+        tree size the launch accepts — asked of the library (DeviceTree.search_conv_plan: head K multiples of
+        128, supports <= 1024, LSTM width a multiple of 128, the tree in LDS); None otherwise (the generic
+        per-simulation path). A plan refused for co-residency only (max(B, 2 T) workgroups, T = ceil(B / 64) *
+        H / 16 LSTM tiles, against the CUs and the kernel's occupancy) still returns the network: an eager
+        search() launches, is refused with ResidencyError before anything runs, and counts the fallback; a
+        captured one takes the generic path without launching.
+        cfg.fused_search (default on) and LZM_FUSED_CONV=0 turn it off."""
+        self.last_plan = None  # (the plan of this search, when the library is asked)
         if not self._cfg.get('fused_search', True) or not t.ez or os.environ.get("LZM_FUSED_CONV", "1") == "0":
-            return None
-        if tuple(shape) != (64, 8, 8) or Hl % 128 or Hl > 1024 or Hl // 16 > 64:
-            return None
-        tiles = -(-t.B // 64) * (Hl // 16)
-        if t.B > 256 or max(t.B, 2 * tiles) > _device_cus(t.device):
             return None
         net = _step_net(self, model)
         hp = getattr(net, "heads", None)
-        if getattr(net, "native", None) is None or hp is None or getattr(net, "precision", None) != "split" \
-                or not getattr(net, "ez", False) or getattr(net, "lstm_frag", None) is None:
+        if tuple(shape) != (64, 8, 8) or getattr(net, "native", None) is None or hp is None \
+                or getattr(net, "precision", None) != "split" or not getattr(net, "ez", False) \
+                or getattr(net, "lstm_frag", None) is None or hp["A"] != t.A or hp["Kr"] != Hl:
             return None
-        if hp["Khd"] % 128 or hp["off_policy"] % 128 or hp["A"] != t.A or hp["Kr"] != Hl \
-                or (net.r_ch * 64 + Hl) % 128:
-            return None
-        return net
+        plan = t.search_conv_plan(net, t.sims_capacity if S is None else S, H=Hl,
+                                  horizon=int(self._cfg.lstm_horizon_len),
+                                  categorical=bool(self._cfg.model.get('categorical_distribution', True)))
+        self.last_plan = plan
+        return net if plan["supported"] or plan["code"] == _lib.LZM_ERR_RESIDENCY else None
 
     def _loop(self, t, model, buf, S, row, Hl, rec=None, net=None, infer=None):
         """The S simulations (mcts_ctree.py:756-827), all enqueued on the current stream. infer: optional
@@ -645,8 +637,16 @@ class EfficientZeroMCTSCtree(object):
             hh0 = _latent_tensor(reward_hidden_state_roots[1], dev).reshape(B, -1)
             Hl = hc0.shape[1]
             rec = None
+            cz = self._fused_conv(model, t, shape, Hl, S)
+            # A grid the plan refuses for co-residency is not launched where a fallback after the refusal is
+            # not possible: when this search captures the generic path itself (use_hip_graph), and inside a
+            # caller's stream capture (collect.py's graph), which then captures the generic path instead of
+            # raising. (The plan is a host query; eagerly the launch is tried, refused and counted.)
+            refused = cz is not None and not self.last_plan["supported"]
             graph = self._cfg.get('use_hip_graph', False) and not getattr(self, "record", False) \
-                and self._fused_conv(model, t, shape, Hl) is None
+                and (cz is None or refused)
+            if graph or (refused and torch.cuda.is_current_stream_capturing()):
+                cz = None
             gkey = _graph_key(t, model, B, S, shape, (Hl, Hl)) if graph else None
             entry = self._graphs.get(gkey, model, t) if graph else None
             buf = entry.buf if entry is not None else (_SearchBuffers() if graph else self._buf).get(
@@ -656,7 +656,6 @@ class EfficientZeroMCTSCtree(object):
             buf.extra[0][0].copy_(hc0)
             buf.extra[1][0].copy_(hh0)
             buf.vtp_in.copy_(_to_play_tensor(to_play_batch, B, dev))
-            cz = self._fused_conv(model, t, shape, Hl)
             recording = getattr(self, "record", False)
             # the one-launch search runs the collect step's glue in its kernel (lzm_search_set_step: seeds
             # from the step counter, fresh min-max bounds, root outputs, the counter increment)
@@ -678,7 +677,8 @@ class EfficientZeroMCTSCtree(object):
                 # the conv network's whole search, reward LSTM included, in one launch (lzm_search_conv_ez);
                 # the launch needs its whole grid co-resident: when the occupancy bound refuses it, nothing
                 # ran and the generic per-simulation path runs instead — eagerly only: inside a stream
-                # capture the refusal is raised (the caller captures a different graph, not a fallback)
+                # capture a plan-refused grid never gets here (cz was dropped above), and a refusal the plan
+                # did not foresee is raised (no fallback inside a capture)
                 cfg = self._cfg
                 if step_in_kernel:
                     t.set_step(step["count"], int(step["base"]), step.get("increment", True), step["dist"],

@@ -168,10 +168,19 @@ class DeviceTree:
         call("lzm_backprop", self.h, int(cur), float(discount), ptr(minmax), ptr(rewards), ptr(values), ptr(logits),
              ptr(to_play), ptr(is_reset), stream_ptr(stream))
 
+    def _value_support(self, Vv, V):
+        """the value rows' length for the decode when it differs from the reward rows' (lzm_set_value_support;
+        host state, set only when it changes)"""
+        want = 0 if Vv == V else int(Vv)
+        if want != getattr(self, "_vsupport", 0):
+            call("lzm_set_value_support", self.h, want)
+            self._vsupport = want
+
     def decode_backprop(self, cur, discount, minmax, reward_logits, value_logits, categorical, policy_logits, to_play,
                         lstm_horizon=0, out_is_reset=None, next_latent=None, pool_slot=None, row_elems=0,
                         out_decoded=None, stream=None):
         V = reward_logits.shape[-1] if categorical else 1
+        self._value_support(value_logits.shape[-1] if categorical else 1, V)
         call("lzm_decode_backprop", self.h, int(cur), float(discount), ptr(minmax), ptr(reward_logits),
              ptr(value_logits), int(V), int(bool(categorical)), ptr(policy_logits), ptr(to_play), int(lstm_horizon),
              ptr(out_is_reset), ptr(next_latent), ptr(pool_slot), int(row_elems), ptr(out_decoded), stream_ptr(stream))
@@ -183,6 +192,7 @@ class DeviceTree:
         """decode_backprop of simulation `cur` and the traverse of the next one in one launch (parity
         mode); the traverse outputs overwrite x / y / action / vtp / search_len."""
         V = reward_logits.shape[-1] if categorical else 1
+        self._value_support(value_logits.shape[-1] if categorical else 1, V)
         call("lzm_decode_backprop_traverse", self.h, int(cur), float(discount), ptr(minmax), ptr(reward_logits),
              ptr(value_logits), int(V), int(bool(categorical)), ptr(policy_logits), ptr(to_play), int(lstm_horizon),
              ptr(out_is_reset), ptr(next_latent), ptr(pool_slot), int(row_elems), ptr(out_decoded), int(pb_c_base),
@@ -208,6 +218,27 @@ class DeviceTree:
              int(dims["res"]), out)
         return dict(roots_per_wg=out[0], kernel={1: "resident", 0: "streaming"}.get(out[1]), mode=out[2],
                     tree_in_lds=bool(out[3]))
+
+    def search_conv_plan(self, net, S, H=0, horizon=1, categorical=True):
+        """What search_conv (MuZero trees) / search_conv_ez (EfficientZero trees; H: the LSTM width, horizon:
+        lstm_horizon_len) launches for the native FoldedConvNet `net` and S simulations on this handle as the
+        process stands (lzm_search_conv_plan: the launches' own decision; host only, nothing is launched):
+        dict(supported, code: the launch's return code (0 runs, _lib.LZM_ERR_RESIDENCY the EfficientZero grid
+        cannot be co-resident), reason: the library's message when refused, workgroups, lstm_tiles, lds_bytes,
+        pinned: head half-heads kept in LDS, pbt_rows: pb_c table rows in LDS (0: the walk divides),
+        out_rounds: rounds of 768 output columns (MuZero: Vr + Vv + A; EfficientZero: Vv + A, 0 when
+        out_one_round), out_one_round / reward_one_round: EfficientZero's one-column-per-thread forms of the
+        value | policy and the reward output (up to 256 columns))."""
+        hp = net.heads
+        out = (ctypes.c_int32 * 8)()
+        call("lzm_search_conv_plan", self.h, int(S), int(self.ez), int(H), int(horizon), int(net.n_dres),
+             int(net.n_pres), int(net.r_ch), int(net.h_ch), int(hp["Kr"]), int(hp["Khd"]), int(hp["off_policy"]),
+             int(hp["Vr"]), int(hp["Vv"]), int(bool(categorical)), out)
+        reason = None if out[0] == 0 else _lib.load().lzm_last_error().decode()
+        return dict(supported=out[0] == 0, code=out[0], reason=reason, workgroups=out[1], lstm_tiles=out[2],
+                    lds_bytes=out[3], pinned=out[4], pbt_rows=out[5], out_rounds=out[6],
+                    out_one_round=bool(self.ez and out[6] == 0),
+                    reward_one_round=bool(out[7]))
 
     def search_conv(self, net, S, minmax, seeds, vtp_in, pool, pb_c_base=19652, pb_c_init=1.25, discount=0.997,
                     categorical=True, rec=None, stream=None):
@@ -340,6 +371,7 @@ class TreePool:
             # (ADVICE r03); acquiring happens between searches, never inside a graph capture
             if not torch.cuda.is_current_stream_capturing():
                 t.reset_errors()
+            t._value_support(0, 0)  # (the previous owner's value support length: host state on the handle)
         return t
 
     def release(self, t):

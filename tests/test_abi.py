@@ -206,3 +206,31 @@ def test_az_fused_plan_validates_on_the_host():
     assert L.lzm_az_export_priors(4, 10, None, out, None) == err
     assert L.lzm_az_export_priors(0, 10, out, out, None) == err
     assert L.lzm_az_export_priors(4, 10, out, None, None) == err
+
+
+def test_conv_plan_and_head_shape_queries_validate_on_the_host():
+    """lzm_conv_heads_supported states lzm_conv_heads' shape limits (host only, no GPU needed);
+    lzm_search_conv_plan refuses a null handle, a null output and no simulations before any HIP call
+    (LZM_ERR_ARG) and leaves `out` alone; lzm_set_value_support refuses a null handle"""
+    import ctypes
+    L = _lib.load()
+    ok = L.lzm_conv_heads_supported  # (Kr, Khd, off_policy, Vr, Vv, A)
+    assert ok(1024, 2048, 1024, 601, 601, 4) == 1 and ok(512, 2048, 1024, 101, 101, 6) == 1
+    assert ok(128, 256, 128, 1, 1, 1) == 1 and ok(128, 1024, 384, 1024, 769, 18) == 1
+    assert ok(1024, 2048, 1024, 1025, 601, 4) == 0 and ok(1024, 2048, 1024, 601, 1201, 4) == 0  # supports <= 1024
+    assert ok(1024, 2048, 1024, 601, 601, 1025) == 0 and ok(1024, 2048, 1024, 601, 601, 0) == 0
+    assert ok(1088, 2048, 1024, 601, 601, 4) == 0 and ok(126, 2048, 1024, 601, 601, 4) == 0  # Kr <= 1024, % 4
+    assert ok(1024, 2112, 1024, 601, 601, 4) == 0  # head planes <= 2048
+    assert ok(1024, 1280, 128, 601, 601, 4) == 0 and ok(1024, 1280, 1152, 601, 601, 4) == 0  # K per head <= 1024
+    assert ok(1024, 256, 256, 601, 601, 4) == 0 and ok(1024, 256, 0, 601, 601, 4) == 0  # both heads non-empty
+    err = -1  # LZM_ERR_ARG
+    out = (ctypes.c_int32 * 8)(*([7] * 8))
+    fake = ctypes.c_void_p(16)  # never dereferenced: the null checks come first
+    shape = (0, 0, 1, 1, 1, 16, 32, 1024, 2048, 1024, 601, 601, 1)
+    assert L.lzm_search_conv_plan(None, 10, *shape, out) == err
+    assert b"lzm_search_conv_plan" in L.lzm_last_error()
+    assert L.lzm_search_conv_plan(fake, 10, *shape, None) == err
+    assert L.lzm_search_conv_plan(fake, 0, *shape, out) == err
+    assert L.lzm_search_conv_plan(fake, -3, *shape, out) == err
+    assert list(out) == [7] * 8
+    assert L.lzm_set_value_support(None, 21) == err

@@ -24,10 +24,12 @@ from tests.test_gpu_numerics import torch_inverse_scalar_transform  # noqa: E402
 DEV = torch.device("cuda", 0)
 
 
-def conv_model(kind, seed=0, zero_heads=False):
+def conv_model(kind, seed=0, zero_heads=False, factory=None):
+    """factory: optional callable(last_linear_layer_init_zero=...) building another network of the family"""
     from lightzero_amd.model_conv import atari_efficientzero_model, atari_muzero_model
     torch.manual_seed(seed)
-    m = (atari_efficientzero_model if kind == "ez" else atari_muzero_model)(last_linear_layer_init_zero=zero_heads)
+    factory = factory or (atari_efficientzero_model if kind == "ez" else atari_muzero_model)
+    m = factory(last_linear_layer_init_zero=zero_heads)
     g = torch.Generator().manual_seed(seed + 1)
     for mod in m.modules():  # non-trivial eval-mode BatchNorm statistics
         if isinstance(mod, (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d)):
@@ -39,75 +41,125 @@ def conv_model(kind, seed=0, zero_heads=False):
     return m.to(DEV).eval()
 
 
-def run_search(kind, B, S, seed, graph=False, record=True, model=None, mcts=None, fused=True, rng="glibc"):
+def run_search(kind, B, S, seed, graph=False, record=True, model=None, mcts=None, fused=True, rng="glibc",
+               horizon=5, discount=0.997, legal=None, to_play=None, categorical=True, scales=None, direct=False, check=False, fresh_tree=False):
+    """horizon: lstm_horizon_len; legal: per-root legal action lists (default: every action); to_play: per-root
+    players (default -1: one player); categorical / scales = (reward, value) support scales: the heads' kind
+    (default: categorical with the Atari scale of `kind` for both); direct: the search is fed random
+    non-negative root latents, random root logits and (EZ) a random root LSTM state instead of the
+    representation network's outputs; check: also read (and clear) the tree's sticky error words, raising on
+    a timed-out look-back, a draw outside the coefficient table or a split-range error; fresh_tree: the roots
+    get a tree created for them (64 simulations reserved, as a first search's) instead of one from the handle pool,
+    whose reserved capacity depends on the searches that used it before."""
     from lightzero_amd.mcts_ctree import EfficientZeroMCTSCtree, MuZeroMCTSCtree
     from lightzero_amd.tree import SequentialSeeds, set_seed_source
     from lightzero_amd.utils import EasyDict
     model = conv_model(kind, seed) if model is None else model
     A = model.action_space_size
     scale = 50 if kind == "ez" else 300
-    rng = np.random.default_rng(seed)
-    obs = torch.from_numpy(rng.integers(0, 256, size=(B, 4, 64, 64)).astype(np.float32) / 255.0).to(DEV)
-    with torch.no_grad():
-        out = model.initial_inference(obs)
-    noises = rng.dirichlet([0.3] * A, size=B).astype(np.float32)
-    logits0 = out.policy_logits.float().cpu().numpy()
-    cfg = EasyDict(dict(num_simulations=S, discount_factor=0.997, device=DEV, lstm_horizon_len=5,
+    scales = (scale, scale) if scales is None else tuple(scales)
+    rng_np = np.random.default_rng(seed)
+    if direct:
+        lat0 = torch.from_numpy(np.maximum(rng_np.standard_normal((B, 64, 8, 8)), 0).astype(np.float32)).to(DEV)
+        logits0 = rng_np.standard_normal((B, A)).astype(np.float32)
+        hidden0 = None
+        if kind == "ez":
+            H = model.lstm_hidden_size
+            hidden0 = tuple(torch.from_numpy((0.5 * rng_np.standard_normal((1, B, H))).astype(np.float32)).to(DEV)
+                            for _ in range(2))
+    else:
+        obs = torch.from_numpy(rng_np.integers(0, 256, size=(B, 4, 64, 64)).astype(np.float32) / 255.0).to(DEV)
+        with torch.no_grad():
+            out = model.initial_inference(obs)
+        lat0, hidden0 = out.latent_state, getattr(out, "reward_hidden_state", None)
+        logits0 = out.policy_logits.float().cpu().numpy()
+    noises = rng_np.dirichlet([0.3] * A, size=B).astype(np.float32)
+    cfg = EasyDict(dict(num_simulations=S, discount_factor=discount, device=DEV, lstm_horizon_len=horizon,
                         use_hip_graph=graph, fused_search=fused,
-                        model=dict(support_scale=scale, categorical_distribution=True)))
+                        model=dict(support_scale=scales[0], categorical_distribution=categorical)))
     cls = EfficientZeroMCTSCtree if kind == "ez" else MuZeroMCTSCtree
     mcts = cls(cfg) if mcts is None else mcts
     mcts.record = record
+    legal = [list(range(A))] * B if legal is None else [list(l) for l in legal]
+    to_play = [-1] * B if to_play is None else [int(p) for p in to_play]
     old_mode = cls.rng_mode
     cls.rng_mode = rng
     try:
-        roots = cls.roots(B, [list(range(A))] * B)
+        roots = cls.roots(B, legal)
     finally:
         cls.rng_mode = old_mode
-    roots.prepare(0.25, [n.tolist() for n in noises], [0.0] * B, logits0.tolist(), [-1] * B)
+    if fresh_tree:
+        from lightzero_amd.tree import DeviceTree
+        roots.tree = DeviceTree(B, A, 64, ez=(kind == "ez"), fast_rng=(rng == "philox"), device=DEV)
+    roots.prepare(0.25, [n.tolist() for n in noises], [0.0] * B, logits0.tolist(), to_play)
     set_seed_source(SequentialSeeds(seed))
     try:
         if kind == "ez":
-            mcts.search(roots, model, out.latent_state, out.reward_hidden_state, [-1] * B)
+            mcts.search(roots, model, lat0, hidden0, to_play)
         else:
-            mcts.search(roots, model, out.latent_state, [-1] * B)
+            mcts.search(roots, model, lat0, to_play)
     finally:
         set_seed_source(None)
     t = roots.tree
     res = dict(dist=t.distributions().cpu().numpy(), values=t.values().cpu().numpy(),
                traj=t.trajectories(S + 2).cpu().numpy(), noises=noises, logits0=logits0, model=model,
-               lat0=out.latent_state, hidden0=getattr(out, "reward_hidden_state", None), A=A, scale=scale)
+               lat0=lat0, hidden0=hidden0, A=A, scale=scales[0], scales=scales, categorical=categorical,
+               horizon=horizon, discount=discount, legal=legal, to_play=to_play,
+               errors=t.check_errors() if check else None)
     res["rec"] = None if mcts.last_record is None else mcts.last_record.numpy() | (
         {"is_reset": mcts.last_record.is_reset.cpu().numpy()} if kind == "ez" else {})
     res["path"] = getattr(mcts, "last_path", None)
+    res["plan"] = getattr(mcts, "last_plan", None)
     roots.clear()
     return res
 
 
 def oracle_replay(kind, res, B, S):
+    """the search's horizon, discount, legal sets and players are taken from `res` (run_search's arguments)"""
     rec, A = res["rec"], res["A"]
+    horizon, disc = res.get("horizon", 5), np.float32(res.get("discount", DISC))
+    to_play = np.asarray(res.get("to_play", [-1] * B), np.int32)
     ot = OracleTree(B, A, S, ez=(kind == "ez"))
+    if res.get("legal") is not None:
+        la = np.full((B, A), -1, np.int32)
+        for i, l in enumerate(res["legal"]):
+            la[i, :len(l)] = l
+        ot.set_legal(la, np.array([len(l) for l in res["legal"]], np.int32))
     ot.set_delta(VDM)
-    ot.prepare(NOISE_W, res["noises"], np.zeros(B, np.float32), res["logits0"], np.full(B, -1, np.int32))
+    ot.prepare(NOISE_W, res["noises"], np.zeros(B, np.float32), res["logits0"], to_play)
     for k in range(S):
-        x, y, a, vtp, slen = ot.traverse(PB_C_BASE, PB_C_INIT, DISC, int(rec["seeds"][k]), np.full(B, -1, np.int32))
+        x, y, a, vtp, slen = ot.traverse(PB_C_BASE, PB_C_INIT, disc, int(rec["seeds"][k]), to_play)
         assert np.array_equal(x, rec["x"][k]), f"sim {k}: latent index differs"
         assert np.array_equal(a, rec["action"][k]), f"sim {k}: action differs"
         assert np.array_equal(slen, rec["search_len"][k]), f"sim {k}: search_len differs"
         is_reset = None
         if kind == "ez":
-            is_reset = (slen % 5 == 0).astype(np.int32)
+            is_reset = (slen % horizon == 0).astype(np.int32)
             assert np.array_equal(is_reset, rec["is_reset"][k]), f"sim {k}: is_reset differs"
-        ot.backprop(k + 1, DISC, rec["decoded"][k][:, 0], rec["decoded"][k][:, 1], rec["policy_logits"][k], vtp,
+        ot.backprop(k + 1, disc, rec["decoded"][k][:, 0], rec["decoded"][k][:, 1], rec["policy_logits"][k], vtp,
                     is_reset)
     assert np.array_equal(res["dist"], ot.distributions())
     assert np.array_equal(res["values"], ot.values())
     assert np.array_equal(res["traj"], ot.trajectories(S + 2))
 
 
+def torch_h_inverse(x, eps=0.001):
+    """fp32 h^-1 of scaling_transform.py:118-128 (what InverseScalarTransform applies to a scalar head)"""
+    tmp = (torch.sqrt(1 + 4 * eps * (torch.abs(x) + 1 + eps)) - 1) / (2 * eps)
+    return torch.sign(x) * (tmp * tmp - 1)
+
+
 def torch_replay(kind, res, B, S):
-    """the decoded values the kernel consumed == torch InverseScalarTransform of the same net outputs"""
-    rec, model, scale = res["rec"], res["model"], res["scale"]
+    """the decoded values the kernel consumed == torch InverseScalarTransform of the same net outputs
+    (scalar heads: h^-1 of the module's raw outputs), at each head's own support scale"""
+    rec, model = res["rec"], res["model"]
+    rscale, vscale = res.get("scales", (res["scale"], res["scale"]))
+    cat = res.get("categorical", True)
+
+    def decode(logits, scale):
+        if cat:
+            return torch_inverse_scalar_transform(logits, scale).squeeze(1)
+        return torch_h_inverse(logits.float()).reshape(-1)
     pool = [res["lat0"].float()]
     if kind == "ez":
         hpool = [(res["hidden0"][0].reshape(B, -1).float(), res["hidden0"][1].reshape(B, -1).float())]
@@ -128,10 +180,8 @@ def torch_replay(kind, res, B, S):
                 out = model.recurrent_inference(lat, act)
                 r_logits = out.reward
             dec = torch.from_numpy(rec["decoded"][k]).to(DEV)
-            torch.testing.assert_close(dec[:, 0], torch_inverse_scalar_transform(r_logits, scale).squeeze(1),
-                                       rtol=1e-4, atol=1e-5 * scale)
-            torch.testing.assert_close(dec[:, 1], torch_inverse_scalar_transform(out.value, scale).squeeze(1),
-                                       rtol=1e-4, atol=1e-5 * scale)
+            torch.testing.assert_close(dec[:, 0], decode(r_logits, rscale), rtol=1e-4, atol=1e-5 * rscale)
+            torch.testing.assert_close(dec[:, 1], decode(out.value, vscale), rtol=1e-4, atol=1e-5 * vscale)
             torch.testing.assert_close(torch.from_numpy(rec["policy_logits"][k]).to(DEV), out.policy_logits.float(),
                                        rtol=1e-4, atol=1e-5)
             pool.append(out.latent_state.float())
@@ -475,8 +525,10 @@ def test_search_bf16x3_vs_f32_trunk(kind, monkeypatch):
 def test_ez_residency_refusal_falls_back_to_generic_with_same_results(monkeypatch):
     """lzm_search_conv_ez refuses a grid its static co-residency bound cannot hold (LZM_RESIDENCY_CUS caps
     the CU count it assumes) with LZM_ERR_RESIDENCY before running anything; EfficientZeroMCTSCtree.search
-    then runs the generic path eagerly: the same visit counts, values and trajectories. Inside a stream
-    capture the refusal is raised instead."""
+    then runs the generic path eagerly: the same visit counts, values and trajectories. Inside a caller's
+    stream capture no fallback after a refused launch is possible, so search() asks the launch's plan first
+    (lzm_search_conv_plan, the same refusal), launches nothing and captures the generic path: no exception, no
+    fallback counted, and the replayed graph gives the eager generic search's results."""
     from lightzero_amd import _lib
     from lightzero_amd.mcts_ctree import EfficientZeroMCTSCtree
     from lightzero_amd.utils import EasyDict
@@ -492,19 +544,45 @@ def test_ez_residency_refusal_falls_back_to_generic_with_same_results(monkeypatc
     assert b["path"] == "generic (co-residency refused)" and mcts.residency_fallbacks == 1
     for key in ("dist", "values", "traj"):
         assert np.array_equal(a[key], b[key]), key
-    # captured: raised, not a fallback inside the capture
-    roots = EfficientZeroMCTSCtree.roots(B, [list(range(6))] * B)
-    roots.prepare_no_noise([0.0] * B, a["logits0"].tolist(), [-1] * B)
+    # captured: the generic path, not a launch that is refused inside the capture
+    captured_search_equals_eager_generic(mcts, model, B, S, a["logits0"], a["lat0"], a["hidden0"])
+    assert mcts.residency_fallbacks == 1 and mcts.last_path == "generic"
+    assert mcts.last_plan["code"] == _lib.LZM_ERR_RESIDENCY
+
+
+def captured_search_equals_eager_generic(mcts, model, B, S, logits0, lat0, hidden0):
+    """EfficientZeroMCTSCtree.search of `mcts` inside a caller's stream capture (device seeds and players, roots
+    prepared without noise): no exception; the replayed graph's visit counts, root values and trajectories equal
+    an eager generic search (fused_search off) from the same roots and seeds"""
+    from lightzero_amd.mcts_ctree import EfficientZeroMCTSCtree
+    from lightzero_amd.utils import EasyDict
+    A = logits0.shape[1]
     seeds = torch.arange(S, dtype=torch.int32, device=DEV)
     to_play = torch.full((B,), -1, dtype=torch.int32, device=DEV)
-    roots.tree.reserve(S)  # (no allocation or host copy inside the capture)
-    roots.tree.set_pb_c(19652, 1.25)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with pytest.raises(_lib.ResidencyError):
-        with torch.cuda.graph(g):
-            mcts.search(roots, model, a["lat0"], a["hidden0"], to_play, seeds=seeds)
-    assert mcts.residency_fallbacks == 1
+    cfg = EasyDict(dict(mcts._cfg))
+    cfg.fused_search = False
+    runs = []
+    for m, capture in ((EfficientZeroMCTSCtree(cfg), False), (mcts, True)):
+        roots = EfficientZeroMCTSCtree.roots(B, [list(range(A))] * B)
+        roots.prepare_no_noise([0.0] * B, logits0.tolist(), [-1] * B)
+        roots.tree.reserve(S)  # (no allocation or host copy inside the capture)
+        roots.tree.set_pb_c(19652, 1.25)
+        torch.cuda.synchronize()
+        if capture:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                m.search(roots, model, lat0, hidden0, to_play, seeds=seeds)
+            g.replay()
+        else:
+            m.search(roots, model, lat0, hidden0, to_play, seeds=seeds)
+        torch.cuda.synchronize()
+        t = roots.tree
+        runs.append((t.distributions().cpu().numpy(), t.values().cpu().numpy(), t.trajectories(S + 2).cpu().numpy()))
+        assert t.check_errors() is not None
+        roots.clear()
+    for x, y in zip(*runs):
+        assert np.array_equal(x, y)
+    assert (runs[1][0].sum(axis=1) == S).all()
 
 
 def _stream_beside_current():
