@@ -1713,14 +1713,17 @@ MlpPlan mlp_plan(const lzm_handle *h, int H, int F, int V, int res_dynamics, int
   if (pl.R == 1 && res_enabled() && res_shape_ok(H, A, F, V, res_dynamics)) {
     pl.lds = plan_res(p, n, h, S, A);
     if (pl.lds) {
+      // the selection mode (lzm_search_res.h, the simulation loop): 1 the wave walk; 4 the two-action
+      // walk for A == 2; 5 is 4 with the walk on the terms pass's registers: one node per lane of wave
+      // 0, so it serves S + 2 <= 64 (a path is then at most S levels: it fits the wave's lanes); larger
+      // searches run mode 4. LZM_RES_SELECT = 1, 4 or 5 asks for a mode; any other value is ignored.
       const char *sm = getenv("LZM_RES_SELECT");
-      // measured: 4 < 1 < 0 < 2 < 3; 4 is 1 with the two-action walk for A == 2
-      // 5 is 4 with the walk on the terms pass's registers: one node per lane of wave 0, so it serves
-      // S + 2 <= 64 (a path is then at most S levels: it fits the wave's lanes); larger searches run mode 4
-      n.select_mode = sm ? atoi(sm) : (A == 2 ? 5 : 1);
-      if (n.select_mode == 5 && (A != 2 || S + 2 > 64 || h->depth_cap < S + 2)) n.select_mode = 4;
+      const int asked = sm ? atoi(sm) : 0;
+      int mode = (asked == 1 || asked == 4 || asked == 5) ? asked : (A == 2 ? 5 : 1);
+      if (mode == 5 && (A != 2 || S + 2 > 64 || h->depth_cap < S + 2)) mode = 4;
+      if (mode == 4 && A != 2) mode = 1;
       pl.kind = 1;
-      pl.mode = (n.select_mode == 4 && A != 2) ? 1 : n.select_mode;
+      pl.mode = mode;
       pl.tree_in_lds = 1;
       return pl;
     }
@@ -1910,26 +1913,21 @@ int lzm_search_mlp(lzm_handle *h, int hidden, int head_hidden, int support, int 
     q.out_dist = h->step_dist; q.out_values = h->step_vals;
     const size_t lds = plan.lds;
     res_net(n, weights + round4(kernel_layout(kls, nkl, lay_w, lay_b)), A);
-    // LZM_RES_SPEC=1 (parity mode): evaluate two-way leaf ties speculatively as a second network
-    // row instead of waiting for the look-back (measured slower: every simulation pays the row)
     const char *sl = getenv("LZM_RES_LATE");
     n.late_draw = sl ? atoi(sl) : 1;
     const char *sd = getenv("LZM_RES_SPEC_DEPTH");
     n.spec_depth = sd ? atoi(sd) : 1;
-    const char *se = getenv("LZM_RES_SPEC");
-    const bool spec = !fast && se && atoi(se) == 1;
-    // production: selection mode, RNG and stamps fixed at compile time (modes 1 and 4); phase
-    // timing compiles the stamps in; the other selection modes (experiments) read it at run time
-    const int md = plan.mode;
-    void (*fn)(SearchArgs, ResNet) =
-        spec                  ? search_res_kernel<2, 1, 0, false>
-        : (md != 1 && md != 4 && md != 5) || !n.spec_depth ? search_res_kernel<1, -1, -1, true>
-        : q.phase             ? (md == 5   ? search_res_kernel<1, 5, -1, true>
-                                 : md == 4 ? search_res_kernel<1, 4, -1, true>
-                                           : search_res_kernel<1, 1, -1, true>)
-        : md == 5             ? (fast ? search_res_kernel<1, 5, 1, false> : search_res_kernel<1, 5, 0, false>)
-        : md == 4             ? (fast ? search_res_kernel<1, 4, 1, false> : search_res_kernel<1, 4, 0, false>)
-                              : (fast ? search_res_kernel<1, 1, 1, false> : search_res_kernel<1, 1, 0, false>);
+    // one instantiation per selection mode (1, 4, 5) x variant: the production kernels fix the RNG at
+    // compile time (0 glibc, 1 Philox); the stamps kernel reads the RNG and n.spec_depth at run time and
+    // serves phase timing and LZM_RES_SPEC_DEPTH=0 (then without a phase buffer: it stamps nothing)
+    typedef void (*ResKernel)(SearchArgs, ResNet);
+    static const ResKernel kernels[3][3] = {
+        {search_res_kernel<1, 0, false>, search_res_kernel<1, 1, false>, search_res_kernel<1, -1, true>},
+        {search_res_kernel<4, 0, false>, search_res_kernel<4, 1, false>, search_res_kernel<4, -1, true>},
+        {search_res_kernel<5, 0, false>, search_res_kernel<5, 1, false>, search_res_kernel<5, -1, true>}};
+    const int mi = plan.mode == 5 ? 2 : plan.mode == 4 ? 1 : 0;
+    const int vi = (q.phase || !n.spec_depth) ? 2 : fast ? 1 : 0;
+    const ResKernel fn = kernels[mi][vi];
     hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(fn, dim3(G), dim3(kRT), lds, (hipStream_t)stream, q, n);

@@ -14,19 +14,20 @@
 //   streamed:  fc_dynamics[0] (latent rows) and the two 32 -> 601 support heads, ≈0.2 MiB per
 //              simulation, each prefetched into one 80-register buffer several steps (or, for
 //              the first layer, a whole tree phase) ahead of its use.
-// Every 128 x 128 layer uses one lane mapping: lane l computes column l >> 1 over K half l & 1 and
-// the halves meet by one DPP swap. The one-hot action rows of fc_dynamics[0] are never multiplied:
-// the action's row is added after the latent rows (the exact value of the one-hot product), so the
-// layer can start before the action is known.
+// Every 128 x 128 layer uses one lane mapping (the D-block lane map below). The one-hot action rows
+// of fc_dynamics[0] are never multiplied: the action's row is added after the latent rows (the exact
+// value of the one-hot product), so the layer can start before the action is known.
 //
-// Tree phase (R = 1): wave 0 walks the tree (descend_wave, bit-exact with the reference). In
-// parity mode the reference's single rand() stream makes root i's draws start at the sum of the
+// Tree phase (R = 1): every thread computes the expanded nodes' walk-independent pUCT terms, then
+// wave 0 walks the tree over them (descend_terms / descend_a2f / descend_a2r: descend_wave's float
+// operations in the same order, so bit-exact with the reference). In parity
+// mode the reference's single rand() stream makes root i's draws start at the sum of the
 // depths of roots < i; every workgroup publishes its depth at once (lzm_search_mlp.h, decoupled
 // look-back), but only a root whose walk stopped at a tie among unexpanded children needs the
 // draw VALUE — and that tie leaves the leaf's parent (the gathered latent) known, only the action
 // open. So the look-back wait is deferred behind the first layer's latent rows and skipped
 // entirely when no draw value is needed. A tie reaching an expanded child (depth depends on the
-// draw) is resolved serially before the gather, as in search_mlp_kernel.
+// draw) is resolved by wave 0 after its look-back, which resumes the walk at the tie.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -45,51 +46,17 @@ static_assert(kRTail > 0 && 2 * kRTail <= kRT, "support tail: two lanes per colu
 // float4 slots (each kRT lanes wide) per resident block
 constexpr int kRSlotsD = 16, kRSlotsRH = 4, kRSlotsVPH = 8, kRSlotsS = 20, kRSlotsPO = 1;
 
-// D-block lane map (every 128 x 128 layer). LZM_RES_D4 = 1 (default): lane l owns the four columns
-// 4 (l >> 3) .. +3 over the K eighth 16 (l & 7) .. +15, so it reads 4 activation float4 per row (all in
-// flight at once) and uses each for 4 columns; the 8 lanes of a column group meet by a 3-step DPP
-// butterfly that leaves column 4 (l >> 3) + ((l & 7) >> 1) in lane pair (l, l ^ 1) (reduce_d4). 0: lane
-// l owns column l >> 1 over K half l & 1 (16 activation float4 per row, read through a shallow
-// software pipeline for lack of registers). Same weights per lane either way.
-#ifndef LZM_RES_D4
-#define LZM_RES_D4 1
-#endif
-// LZM_RES_EGATHER (default 1): the walking wave gathers the leaf's parent latent X0 itself, right
-// after its walk when x is final (the walk's barrier orders it), or after a status-2 root's draw
-// resolution: the gather phase's own barrier and its dependent load after it go.
-#ifndef LZM_RES_EGATHER
-#define LZM_RES_EGATHER 1
-#endif
-// LZM_RES_SEEDW1 (default 1): this simulation's glibc seed state (s_z0, read only after the walk) is
-// computed by wave 1 during wave 0's walk instead of by wave 0 before the terms pass's barrier:
-// +0.8% with random and with zero-init heads (profiles/r04/ab_rd5e_seedw1.txt).
-#ifndef LZM_RES_SEEDW1
-#define LZM_RES_SEEDW1 1
-#endif
-// Measured and removed in round 4 (DESIGN.md §9 gives each A/B): wave 0 computing the pUCT terms
-// alone with an early latent gather, wave 0's fc_dynamics[0] prefetch in quarters, a two-column
-// value / policy head hidden layer, a one-barrier support softmax, the late draw from a window of
-// draws built during the walk, fc_prediction_common[1] prefetched during the look-back.
+// D-block lane map (every 128 x 128 layer): lane l owns the four columns 4 (l >> 3) .. +3 over the K
+// eighth 16 (l & 7) .. +15, so it reads 4 activation float4 per row (all in flight at once) and uses
+// each for 4 columns; the 8 lanes of a column group meet by a 3-step DPP butterfly that leaves column
+// 4 (l >> 3) + ((l & 7) >> 1) in lane pair (l, l ^ 1) (reduce_d4).
+//
+// The draw window (parity mode, A = 2): a tie between visited children (status 2/3: the walk's
+// remaining levels need draws, the zero-init-heads regime at nearly every simulation) waits for its
+// look-back with wave 0 alone (lookback_sum_w0) while waves 1-3 compute the window of draws around the
+// previous look-back base, so the resumed walk reads its draws from LDS instead of a coefficient-row
+// round trip per lane after the wait (positions outside the window: the rows).
 constexpr int kDwinBack = 20;  // draw window [base_prev - kDwinBack, base_prev - kDwinBack + 64)
-// LZM_RES_DWIN2 (default 1, parity mode, A = 2): a tie between visited children (status 2/3: the
-// walk's remaining levels need draws, the zero-init-heads regime at nearly every simulation) waits
-// for its look-back with wave 0 alone (lookback_sum_w0) while wave 1 computes the window of draws
-// around the previous look-back base, so the resumed walk reads its draws from LDS instead of a
-// coefficient-row round trip per lane after the wait (positions outside the window: the rows).
-#ifndef LZM_RES_DWIN2
-#define LZM_RES_DWIN2 1
-#endif
-// LZM_RES_SPEC_PATH (default 1): a status-3 root (depth speculated over all draw patterns) resolves
-// its path after the look-back from the matching pattern lane's choice bits (speculate_depth_a2) —
-// a pointer chase — instead of re-walking the tie subtree with scores.
-#ifndef LZM_RES_SPEC_PATH
-#define LZM_RES_SPEC_PATH 1
-#endif
-// LZM_RES_R5_BAR2 (default 0, selection mode 5): keep the barrier between the terms pass and the walk
-// (an A/B switch: with S + 2 <= 64 the pass runs in wave 0 alone, which is also the walk's wave).
-#ifndef LZM_RES_R5_BAR2
-#define LZM_RES_R5_BAR2 0
-#endif
 
 // Part `part` (0..2: coefficient words 11 part .. 11 part + 10) of the window's 64 dot products, added
 // to win (the sums are mod 2^32, so the three waves' LDS adds may land in any order); win must be zero
@@ -126,7 +93,6 @@ __device__ __forceinline__ uint32_t window_draw(int npos, int base, int lo, int 
 // below is its definition). Every block is [slot][lane] float4, so a wave-instruction of a block
 // is one contiguous 1 KiB read.
 //   D (128 x 128, six of them): slot j, lane l: W[16 (l & 7) + 4 (j >> 2) .. +3][4 (l >> 3) + (j & 3)]
-//      (LZM_RES_D4; else W[64 (l & 1) + 4 j .. +3][l >> 1])
 //   RH (128 -> 32 reward head hidden): slot j < 4: W[16 (l & 7) + 4 j ..][l >> 3]
 //   VPH (128 -> 64: [value hidden | policy hidden]): slot j < 8: W[32 (l & 3) + 4 j ..][l >> 2]
 //   S (32 -> 601 support head): slots 0-7: column l, k = 4 j; slots 8-15: column 256 + l;
@@ -145,8 +111,7 @@ struct ResNet {
   const float *w;
   // LDS float offsets beyond SearchArgs' tree plan
   ResPlan plan;      // dynamic LDS plan (res_plan)
-  int select_mode;  // LZM_RES_SELECT (experiments): how the walk runs, see the simulation loop
-  int late_draw;    // NR = 1: two-way leaf ties run the dynamics layers for both candidates before the
+  int late_draw;    // two-way leaf ties run the dynamics layers for both candidates before the
                     // look-back wait (LZM_RES_LATE, default 1)
   int spec_depth;   // status-2 ties: publish the depth early when every draw outcome gives the same
                     // depth (speculate_depth_a2; LZM_RES_SPEC_DEPTH, default 1)
@@ -195,11 +160,7 @@ __host__ __device__ inline void res_source(int b, size_t d, int A, int *layer, i
   if (b < kRbRH) {
     const int src[6] = {0, 1, 2, 3, 6, 7};
     *layer = src[b];
-#if LZM_RES_D4
     *col = 4 * (l >> 3) + (j & 3); *k = 16 * (l & 7) + 4 * (j >> 2) + e;
-#else
-    *col = l >> 1; *k = 64 * (l & 1) + 4 * j + e;
-#endif
     return;
   }
   switch (b) {
@@ -243,24 +204,14 @@ __device__ __forceinline__ void res_fetch(const float4 *blk, float4 *dst) {
 }
 
 // Partial dot product of 4*NJ consecutive inputs x4[0..NJ) with weights w(j): four independent
-// FMA chains (k mod 4), summed as (c0 + c1) + (c2 + c3).
-// (LZM_PK_FMA: the chains in pairs, v_pk_fma_f32 — each half rounds exactly like v_fma_f32)
-#ifndef LZM_PK_FMA
-#define LZM_PK_FMA 1
-#endif
+// FMA chains (k mod 4), summed as (c0 + c1) + (c2 + c3). The chains run in pairs (v_pk_fma_f32: each
+// half rounds exactly like v_fma_f32).
 typedef float lzm_f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void fma4(float4 v, float4 q, float *a) {
-#if LZM_PK_FMA
   lzm_f2 lo = {a[0], a[1]}, hi = {a[2], a[3]};
   lo = __builtin_elementwise_fma((lzm_f2){v.x, v.y}, (lzm_f2){q.x, q.y}, lo);
   hi = __builtin_elementwise_fma((lzm_f2){v.z, v.w}, (lzm_f2){q.z, q.w}, hi);
   a[0] = lo.x; a[1] = lo.y; a[2] = hi.x; a[3] = hi.y;
-#else
-  a[0] = __fmaf_rn(v.x, q.x, a[0]);
-  a[1] = __fmaf_rn(v.y, q.y, a[1]);
-  a[2] = __fmaf_rn(v.z, q.z, a[2]);
-  a[3] = __fmaf_rn(v.w, q.w, a[3]);
-#endif
 }
 template <int NJ, typename WF>
 __device__ __forceinline__ float dot4(const float4 *x4, WF w) {
@@ -275,20 +226,13 @@ __device__ __forceinline__ float dot4(const float4 *x4, WF w) {
 // different banks (unpadded, the halves are 256 B apart: the same bank, a 2-way conflict on every
 // activation read of every dense layer). rpad(c): column c's float offset in a padded row.
 constexpr int kRRow = kRHid + 4;
-constexpr int kRHalf4 = kRHid / 8 + 1;  // float4 offset of the upper half
 __device__ __forceinline__ int rpad(int c) { return c + ((c >> 6) << 2); }
 
 // The column of a 128 x 128 layer this lane's result holds (both lanes of the pair (l, l ^ 1) hold
 // it; the even lane writes it).
-__device__ __forceinline__ int d_col() {
-#if LZM_RES_D4
-  return 4 * ((int)threadIdx.x >> 3) + (((int)threadIdx.x & 7) >> 1);
-#else
-  return (int)threadIdx.x >> 1;
-#endif
-}
+__device__ __forceinline__ int d_col() { return 4 * ((int)threadIdx.x >> 3) + (((int)threadIdx.x & 7) >> 1); }
 
-// LZM_RES_D4: the four column partials h0..h3 of the 8 lanes of a column group to full sums —
+// The four column partials h0..h3 of the 8 lanes of a column group to full sums —
 // lanes e and 7 - e (row_half_mirror) split the columns {0, 1} / {2, 3}, lanes e and e ^ 2 split the
 // pair, lanes e and e ^ 1 add: column (e >> 1) ends in lanes e, e ^ 1 (the same bits in both: the last
 // add is commutative). A fixed order, so every launch rounds the same way.
@@ -309,7 +253,6 @@ __device__ __forceinline__ float reduce_d4(float h0, float h1, float h2, float h
 // Full pre-activation of this lane's column (d_col) of a 128 x 128 layer.
 template <typename WF>
 __device__ __forceinline__ float dense128(const float *x, WF w) {
-#if LZM_RES_D4
   const int e = threadIdx.x & 7;
   const float4 *x4 = reinterpret_cast<const float4 *>(x) + 4 * e + (e >> 2);
   float4 xv[4];
@@ -324,10 +267,6 @@ __device__ __forceinline__ float dense128(const float *x, WF w) {
     for (int c = 0; c < 4; ++c) fma4(xv[j], w(4 * j + c), a[c]);
   return reduce_d4((a[0][0] + a[0][1]) + (a[0][2] + a[0][3]), (a[1][0] + a[1][1]) + (a[1][2] + a[1][3]),
                    (a[2][0] + a[2][1]) + (a[2][2] + a[2][3]), (a[3][0] + a[3][1]) + (a[3][2] + a[3][3]));
-#else
-  const float h = dot4<16>(reinterpret_cast<const float4 *>(x) + kRHalf4 * (threadIdx.x & 1), w);
-  return h + dpp_f<0xB1>(h);
-#endif
 }
 
 // Logits of one support head (input: 32 floats in LDS; weights: the 20-slot buffer P): lane l
@@ -601,78 +540,79 @@ __device__ inline Descent descend_terms(const TreeView &t, const float2 *nq, con
   return d;
 }
 
-// descend_terms for small action spaces (A <= AM <= 4): every lane of the wave evaluates the level
-// (all AM children's terms as broadcast LDS reads, the max / first index / tie list as a short
-// unrolled chain of per-lane compares), so a level is one round of LDS reads and a few dozen
-// dependent VALU operations — no DPP reduction, ballots or readlanes on the chain. The root's legal
-// actions (rleg, nleg) are passed in registers. Same float operations and tie rule as descend_terms
-// (SURVEY.md A7 closed form), so the same bits; every lane returns the same Descent.
-template <int AM, bool CLASSIFY, typename Draw>
-__device__ inline Descent descend_small(const TreeView &t, const float2 *nq, const float4 *cs, float4 mm, int vtp,
-                                        int players, const int *rleg, int nleg, Draw draw, TieInfo *tie,
-                                        WalkState *resume = nullptr, WalkState *at_tie = nullptr) {
+// descend_terms for exactly two actions, written for the shortest dependent chain per level: every
+// lane of the wave evaluates the level (both children's terms as broadcast LDS reads, per-lane
+// compares: no DPP reduction, ballots or readlanes on the chain), and the root's legal actions (rleg,
+// nleg) are passed in registers. The terms phase precomputes each node's walk-independent outcome
+// (dec[latent], a2_decision); where it is known the level takes it as it is, and only a node with an
+// unvisited child scores its children with the normalised mean-q. The normaliser's divisor is fixed
+// per walk (mm_normalize's branches become one division); same float operations as descend_terms,
+// so the same bits.
+__device__ __forceinline__ float mm_norm_fixed(bool scale, float lo, float div, float v) {
+  return scale ? (v - lo) / div : v;
+}
+
+template <bool CLASSIFY, typename Draw>
+__device__ inline Descent descend_a2(const TreeView &t, const float2 *nq, const int *dec, const float4 *cs, float4 mm,
+                                     int vtp, int players, const int *rleg, int nleg, Draw draw, TieInfo *tie,
+                                     WalkState *resume = nullptr, WalkState *at_tie = nullptr) {
   const int lane = threadIdx.x & 63;
-  const int A = t.A;
+  const float delta = mm.x - mm.y;
+  const bool scale = delta > 0;
+  const float div = (delta < mm.z) ? mm.z : delta;
+  const float lo = mm.y;
   WalkState w0 = resume ? *resume : walk_start(t, vtp);
-  int node = w0.node, is_root = w0.is_root, len = w0.len, last_action = w0.last_action, plat = w0.plat;
+  int node = w0.node, len = w0.len, last_action = w0.last_action, plat = w0.plat, lat = w0.lat;
   float parent_q = w0.parent_q;
-  int lat = w0.lat;
+  bool is_root = w0.is_root;
   vtp = w0.vtp;
   if (lane == 0 && !resume) t.path[0] = 0;
   if (CLASSIFY) tie->status = 0;
-  while (lat >= 0 && len < t.depth_cap - 1) {
-    if (CLASSIFY && at_tie) {
-      at_tie->node = node; at_tie->lat = lat; at_tie->len = len; at_tie->plat = plat;
-      at_tie->last_action = last_action; at_tie->is_root = is_root; at_tie->vtp = vtp; at_tie->parent_q = parent_q;
-    }
-    const bool root = node == 0;
-    const int n = root ? nleg : A;
-    const int base = 1 + A * lat;
-    int act[AM];
-    float4 c[AM];
-#pragma unroll
-    for (int j = 0; j < AM; ++j) {
-      act[j] = root ? rleg[j] : j;
-      c[j] = j < n ? cs[base + act[j]] : make_float4(0.0f, 0.0f, __int_as_float(-1), __int_as_float(0));
-    }
-    const float2 q = nq[lat];
+  const int dmax = t.depth_cap - 1;
+  int a0 = 0, a1 = 0, n = 2;
+  float4 c0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c1 = c0;
+  float2 q = make_float2(0.0f, 0.0f);
+  int dl = 2;
+  auto fetch = [&](int nd, int lt) {
+    const bool root = nd == 0;  // (only the first level of a walk from the root)
+    a0 = root ? rleg[0] : 0;
+    a1 = root ? rleg[1] : 1;
+    n = root ? nleg : 2;
+    const int base = 1 + 2 * lt;
+    c0 = cs[base + a0];
+    c1 = cs[base + (n > 1 ? a1 : a0)];
+    q = nq[lt];
+    dl = dec[lt];
+  };
+  while (lat >= 0 && len < dmax) {
+    fetch(node, lat);
+    const int base = 1 + 2 * lat;
     const int total_v = __float_as_int(q.y);
-    float mean_q;
-    if (is_root && total_v > 0)
-      mean_q = q.x / (float)total_v;
-    else
-      mean_q = (parent_q + q.x) / (float)(total_v + 1);
-    is_root = 0;
-    parent_q = mean_q;
-    float vu = mm_normalize(mm, mean_q);
-    if (vu < 0) vu = 0;
-    if (vu > 1) vu = 1;
-    float sc[AM];
-    float M = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < AM; ++j) {
-      sc[j] = c[j].x + (__float_as_int(c[j].w) ? c[j].y : vu);
-      if (j < n) M = fmaxf(M, sc[j]);
+    const float qx = q.x;
+    int jsel = dl;
+    bool tie2 = dl == 3;
+    const bool rootq = is_root && total_v > 0;
+    const float mean_q = rootq ? qx / (float)total_v : (parent_q + qx) / (float)(total_v + 1);
+    if (dl == 2) {
+      float vu = mm_norm_fixed(scale, lo, div, mean_q);
+      if (vu < 0) vu = 0;
+      if (vu > 1) vu = 1;
+      const float s0 = c0.x + (__float_as_int(c0.w) ? c0.y : vu);
+      const float s1 = c1.x + (__float_as_int(c1.w) ? c1.y : vu);
+      const float M = fmaxf(s0, s1);
+      jsel = (s0 == M) ? 0 : 1;
+      tie2 = jsel == 0 && s1 >= M - 0.000001f;
     }
-    int r = 0;
-#pragma unroll
-    for (int j = AM - 1; j >= 0; --j)
-      if (j < n && sc[j] == M) r = j;
-    const float thr = M - 0.000001f;
-    unsigned mask = 1u << r;
-#pragma unroll
-    for (int j = 1; j < AM; ++j)
-      if (j < n && j > r && sc[j] >= thr) mask |= 1u << j;
-    const int nl = __popc(mask);
-    if (CLASSIFY && nl > 1) {
-      bool all_leaves = true;
-#pragma unroll
-      for (int j = 0; j < AM; ++j)
-        if (((mask >> j) & 1u) && __float_as_int(c[j].z) >= 0) all_leaves = false;
+    if (CLASSIFY && tie2) {
+      if (at_tie) {
+        at_tie->node = node; at_tie->lat = lat; at_tie->len = len; at_tie->plat = plat;
+        at_tie->last_action = last_action; at_tie->is_root = is_root; at_tie->vtp = vtp; at_tie->parent_q = parent_q;
+      }
       if (players > 1) vtp = (vtp == 1) ? 2 : 1;
+      const bool all_leaves = __float_as_int(c0.z) < 0 && __float_as_int(c1.z) < 0;
       tie->status = all_leaves ? 1 : 2;
       tie->level = len;
-      tie->mask = mask;
+      tie->mask = 3ull;
       Descent d;
       d.len = len + 1;
       d.x = lat;
@@ -681,23 +621,14 @@ __device__ inline Descent descend_small(const TreeView &t, const float2 *nq, con
       d.leaf = -1;
       return d;
     }
-    int jsel = r;
-    if (!CLASSIFY) {
-      const uint32_t rr = draw(len);
-      int kk = (int)(rr % (uint32_t)nl);
-      unsigned m_ = mask;
-      for (; kk > 0; --kk) m_ &= m_ - 1;
-      jsel = __ffs(m_) - 1;
-    }
-    int action = act[0], nlat = __float_as_int(c[0].z);
-#pragma unroll
-    for (int j = 1; j < AM; ++j)
-      if (jsel == j) {
-        action = act[j];
-        nlat = __float_as_int(c[j].z);
-      }
+    if (!CLASSIFY && tie2) jsel = (int)(draw(len) % 2u);
+    const int action = jsel ? a1 : a0;
+    const int nlat = __float_as_int(jsel ? c1.z : c0.z);
+    const int nnode = base + action;
+    is_root = false;
+    parent_q = mean_q;
     if (players > 1) vtp = (vtp == 1) ? 2 : 1;
-    node = base + action;
+    node = nnode;
     last_action = action;
     if (lane == 0) {
       t.path_act[len] = action;
@@ -716,156 +647,6 @@ __device__ inline Descent descend_small(const TreeView &t, const float2 *nq, con
   return d;
 }
 
-// descend_small for exactly two actions, written for the shortest dependent chain per level. The
-// terms phase precomputes each node's walk-independent outcome (dec[latent], a2_decision); where
-// it is known the level is a pointer chase — the next node's terms are read while this level's
-// mean-q division (needed further down only) completes. Only a node with an unvisited child waits
-// for its normalised mean-q. The normaliser's divisor is fixed per walk (mm_normalize's branches
-// become one division); same float operations as descend_terms, so the same bits.
-__device__ __forceinline__ float mm_norm_fixed(bool scale, float lo, float div, float v) {
-  return scale ? (v - lo) / div : v;
-}
-
-// OPT (experiments): bit 0 collects the path in lanes (one store at the end instead of two LDS
-// stores per level), bit 1 reads the next level's node data before this level's mean-q division.
-template <bool CLASSIFY, typename Draw, int OPT = 0>
-__device__ inline Descent descend_a2(const TreeView &t, const float2 *nq, const int *dec, const float4 *cs, float4 mm,
-                                     int vtp, int players, const int *rleg, int nleg, Draw draw, TieInfo *tie,
-                                     WalkState *resume = nullptr, WalkState *at_tie = nullptr,
-                                     float2 *chain = nullptr) {
-  const int lane = threadIdx.x & 63;
-  const float delta = mm.x - mm.y;
-  const bool scale = delta > 0;
-  const float div = (delta < mm.z) ? mm.z : delta;
-  const float lo = mm.y;
-  WalkState w0 = resume ? *resume : walk_start(t, vtp);
-  int node = w0.node, len = w0.len, last_action = w0.last_action, plat = w0.plat, lat = w0.lat;
-  float parent_q = w0.parent_q;
-  bool is_root = w0.is_root;
-  vtp = w0.vtp;
-  if (lane == 0 && !resume) t.path[0] = 0;
-  if (CLASSIFY) tie->status = 0;
-  const int dmax = t.depth_cap - 1;
-  const bool lanes_path = (OPT & 1) && t.depth_cap <= 64;
-  const int len0 = len;
-  int pnode = 0, pact = 0;
-  auto flush = [&]() {
-    if (lanes_path) {
-      if (lane > len0 && lane <= len) t.path[lane] = pnode;
-      if (lane >= len0 && lane < len) t.path_act[lane] = pact;
-    }
-  };
-  int a0 = 0, a1 = 0, n = 2;
-  float4 c0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c1 = c0;
-  float2 q = make_float2(0.0f, 0.0f);
-  int dl = 2;
-  auto fetch = [&](int nd, int lt) {
-    const bool root = nd == 0;  // (only the first level of a walk from the root)
-    a0 = root ? rleg[0] : 0;
-    a1 = root ? rleg[1] : 1;
-    n = root ? nleg : 2;
-    const int base = 1 + 2 * lt;
-    c0 = cs[base + a0];
-    c1 = cs[base + (n > 1 ? a1 : a0)];
-    q = nq[lt];
-    dl = dec[lt];
-  };
-  if ((OPT & 2) && lat >= 0) fetch(node, lat);
-  // OPT & 4: the mean-q chain is evaluated lazily — a level whose outcome is known only records
-  // its (total_q, total_v) in chain[]; the divisions run (in level order, the same operations)
-  // when a level needs its normalised mean-q or a tie needs parent_q
-  const bool lazy = (OPT & 4) && chain != nullptr;
-  const bool root0 = is_root;
-  int pend = len;
-  auto settle = [&](int upto) {
-    for (int l = pend; l < upto; ++l) {
-      const float2 cq = chain[l];
-      const int tv = __float_as_int(cq.y);
-      parent_q = (l == len0 && root0 && tv > 0) ? cq.x / (float)tv : (parent_q + cq.x) / (float)(tv + 1);
-    }
-    pend = upto > pend ? upto : pend;
-  };
-  while (lat >= 0 && len < dmax) {
-    if (!(OPT & 2)) fetch(node, lat);
-    const int base = 1 + 2 * lat;
-    const int total_v = __float_as_int(q.y);
-    const float qx = q.x;
-    int jsel = dl;
-    bool tie2 = dl == 3;
-    float mean_q = 0.0f;
-    if (lazy && (dl == 2 || (CLASSIFY && dl == 3))) settle(len);
-    const bool rootq = (lazy ? (len == len0 && root0) : is_root) && total_v > 0;
-    if ((!(OPT & 2) && !lazy) || dl == 2) mean_q = rootq ? qx / (float)total_v : (parent_q + qx) / (float)(total_v + 1);
-    if (dl == 2) {
-      float vu = mm_norm_fixed(scale, lo, div, mean_q);
-      if (vu < 0) vu = 0;
-      if (vu > 1) vu = 1;
-      const float s0 = c0.x + (__float_as_int(c0.w) ? c0.y : vu);
-      const float s1 = c1.x + (__float_as_int(c1.w) ? c1.y : vu);
-      const float M = fmaxf(s0, s1);
-      jsel = (s0 == M) ? 0 : 1;
-      tie2 = jsel == 0 && s1 >= M - 0.000001f;
-    }
-    if (CLASSIFY && tie2) {
-      if (at_tie) {
-        at_tie->node = node; at_tie->lat = lat; at_tie->len = len; at_tie->plat = plat;
-        at_tie->last_action = last_action; at_tie->is_root = is_root; at_tie->vtp = vtp; at_tie->parent_q = parent_q;
-      }
-      flush();
-      if (players > 1) vtp = (vtp == 1) ? 2 : 1;
-      const bool all_leaves = __float_as_int(c0.z) < 0 && __float_as_int(c1.z) < 0;
-      tie->status = all_leaves ? 1 : 2;
-      tie->level = len;
-      tie->mask = 3ull;
-      Descent d;
-      d.len = len + 1;
-      d.x = lat;
-      d.action = -1;
-      d.vtp = vtp;
-      d.leaf = -1;
-      return d;
-    }
-    if (!CLASSIFY && tie2) jsel = (int)(draw(len) % 2u);
-    const int action = jsel ? a1 : a0;
-    const int nlat = __float_as_int(jsel ? c1.z : c0.z);
-    const int nnode = base + action;
-    if (OPT & 2) {
-      if (nlat >= 0) fetch(nnode, nlat);
-      if (dl != 2) mean_q = rootq ? qx / (float)total_v : (parent_q + qx) / (float)(total_v + 1);
-    }
-    is_root = false;
-    if (!lazy) {
-      parent_q = mean_q;
-    } else if (dl == 2) {
-      parent_q = mean_q;
-      pend = len + 1;
-    } else if (lane == 0) {
-      chain[len] = make_float2(qx, __int_as_float(total_v));
-    }
-    if (players > 1) vtp = (vtp == 1) ? 2 : 1;
-    node = nnode;
-    last_action = action;
-    if (lanes_path) {
-      pact = lane == len ? action : pact;
-      pnode = lane == len + 1 ? node : pnode;
-    } else if (lane == 0) {
-      t.path_act[len] = action;
-      t.path[len + 1] = node;
-    }
-    ++len;
-    plat = lat;
-    lat = nlat;
-  }
-  flush();
-  Descent d;
-  d.len = len;
-  d.x = plat;
-  d.action = last_action;
-  d.vtp = vtp;
-  d.leaf = node;
-  return d;
-}
-
 // Depth speculation for a classification walk stopped at a tie between children of which one is
 // expanded (status 2, A == 2): lane `pattern` continues the walk from the tie's state taking, at the
 // i-th tie on its way, the child that draw parity bit i of `pattern` selects (rr % 2 picks legal
@@ -873,16 +654,16 @@ __device__ inline Descent descend_a2(const TreeView &t, const float2 *nq, const 
 // If all 64 patterns give one depth, the root's draw count is known before any of its draw values:
 // it is published at once and the path is resolved after the look-back (same walk, same bits).
 // Same per-level operations as descend_a2.
-// (LZM_RES_SPEC_PATH: *choice gets bit l = the legal position taken at level w.len + l, *ties bit l
+// *choice gets bit l = the legal position taken at level w.len + l, *ties bit l
 // when that level was a tie decided by the pattern, *leaf_tie the offset of a final tie between two
 // unexpanded children (its draw picks the leaf; -1: none); *choice = ~0u when the walk is longer than
 // 31 levels past w.len. The path of a walk is then its choice bits: the look-back's draw parities
-// select the lane whose pattern matches, and the path is a pointer chase without the scores.)
+// select the lane whose pattern matches, and the path is a pointer chase without the scores.
 __device__ inline int speculate_depth_a2(const TreeView &t, const float2 *nq, const int *dec, const float4 *cs,
                                          float4 mm, const int *rleg, int nleg, const WalkState &w, int pattern,
-                                         uint32_t *choice = nullptr, uint32_t *ties = nullptr, int *leaf_tie = nullptr) {
+                                         uint32_t *choice, uint32_t *ties, int *leaf_tie) {
   uint32_t ch = 0u, tm = 0u;
-  if (leaf_tie) *leaf_tie = -1;
+  *leaf_tie = -1;
   const float delta = mm.x - mm.y;
   const bool scale = delta > 0;
   const float div = (delta < mm.z) ? mm.z : delta;
@@ -916,7 +697,7 @@ __device__ inline int speculate_depth_a2(const TreeView &t, const float2 *nq, co
     const int off = len - w.len;
     if (tie2) {
       if (__float_as_int(c0.z) < 0 && __float_as_int(c1.z) < 0) {  // either way a leaf
-        if (choice) { *choice = off < 31 ? ch : ~0u; *ties = tm; *leaf_tie = off; }
+        *choice = off < 31 ? ch : ~0u; *ties = tm; *leaf_tie = off;
         return len + 1;
       }
       if (used == 6) return -1;
@@ -931,7 +712,7 @@ __device__ inline int speculate_depth_a2(const TreeView &t, const float2 *nq, co
     lat = __float_as_int(jsel ? c1.z : c0.z);
     ++len;
   }
-  if (choice) { *choice = len - w.len <= 31 ? ch : ~0u; *ties = tm; }
+  *choice = len - w.len <= 31 ? ch : ~0u; *ties = tm;
   return len;
 }
 
@@ -1177,88 +958,8 @@ __device__ inline Descent descend_a2r(const TreeView &t, const A2Rec &rc, bool l
   return d;
 }
 
-// descend_terms by one lane: the reference's sequential tie-list scan (cselect_child,
-// cnode.cpp:551-596) over the precomputed terms, no cross-lane operations.
-template <bool CLASSIFY, typename Draw>
-__device__ inline Descent descend_terms_lane(const TreeView &t, const float2 *nq, const float4 *cs, float4 mm, int vtp,
-                                             int players, Draw draw, TieInfo *tie) {
-  int node = 0, is_root = 1, len = 0, last_action = -1, plat = -1;
-  float parent_q = 0.0f;
-  int lat = t.meta[0].latent;
-  t.path[0] = 0;
-  if (CLASSIFY) tie->status = 0;
-  while (lat >= 0 && len < t.depth_cap - 1) {
-    const int n = legal_n(t, 0, node);
-    const int base = 1 + t.A * lat;
-    const float2 q = nq[lat];
-    const int total_v = __float_as_int(q.y);
-    float mean_q;
-    if (is_root && total_v > 0)
-      mean_q = q.x / (float)total_v;
-    else
-      mean_q = (parent_q + q.x) / (float)(total_v + 1);
-    is_root = 0;
-    parent_q = mean_q;
-    float vu = mm_normalize(mm, mean_q);
-    if (vu < 0) vu = 0;
-    if (vu > 1) vu = 1;
-    float max_score = kFloatMin;
-    uint64_t mask = 0;
-    bool all_leaves = true;
-    for (int j = 0; j < n; ++j) {
-      const float4 c = cs[base + legal_at(t, 0, node, j)];
-      const float score = c.x + (__float_as_int(c.w) ? c.y : vu);
-      if (max_score < score) {
-        max_score = score;
-        mask = 1ull << j;
-        all_leaves = __float_as_int(c.z) < 0;
-      } else if (score >= max_score - 0.000001f) {
-        mask |= 1ull << j;
-        all_leaves = all_leaves && __float_as_int(c.z) < 0;
-      }
-    }
-    const int nl = __popcll(mask);
-    if (CLASSIFY && nl > 1) {
-      if (players > 1) vtp = (vtp == 1) ? 2 : 1;
-      tie->status = all_leaves ? 1 : 2;
-      tie->level = len;
-      tie->mask = mask;
-      Descent d;
-      d.len = len + 1;
-      d.x = lat;
-      d.action = -1;
-      d.vtp = vtp;
-      d.leaf = -1;
-      return d;
-    }
-    const uint32_t rr = CLASSIFY ? 0u : draw(len);
-    int kk = (int)(rr % (uint32_t)nl);
-    uint64_t mm_ = mask;
-    for (; kk > 0; --kk) mm_ &= mm_ - 1;
-    const int jsel = __ffsll((long long)mm_) - 1;
-    const int action = legal_at(t, 0, node, jsel);
-    if (players > 1) vtp = (vtp == 1) ? 2 : 1;
-    node = base + action;
-    last_action = action;
-    t.path_act[len] = action;
-    t.path[len + 1] = node;
-    ++len;
-    plat = lat;
-    lat = __float_as_int(cs[node].z);
-  }
-  Descent d;
-  d.len = len;
-  d.x = plat;
-  d.action = last_action;
-  d.vtp = vtp;
-  d.leaf = node;
-  return d;
-}
-
-// NR rows of a 128 x 128 layer (inputs x + r * 128): each weight read once for all rows.
-#ifndef LZM_RES_STAGE_WD1
-#define LZM_RES_STAGE_WD1 1
-#endif
+// NR rows of a 128 x 128 layer (inputs x + r * kRRow): each weight read once for all rows (NR = 2:
+// the two candidates of a late draw through fc_dynamics[1]).
 struct NoSide {
   __device__ __forceinline__ void operator()(int) const {}
 };
@@ -1267,7 +968,6 @@ struct NoSide {
 // 1 KiB wave-load per 16 cycles and four waves share it)
 template <int NR, typename WF, typename SF = NoSide>
 __device__ __forceinline__ void dense128n(const float *x, WF w, float *z, SF side = SF()) {
-#if LZM_RES_D4
   const int e = threadIdx.x & 7;
   float4 xv[NR][4];
 #pragma unroll
@@ -1294,24 +994,6 @@ __device__ __forceinline__ void dense128n(const float *x, WF w, float *z, SF sid
                      (a[r][1][0] + a[r][1][1]) + (a[r][1][2] + a[r][1][3]),
                      (a[r][2][0] + a[r][2][1]) + (a[r][2][2] + a[r][2][3]),
                      (a[r][3][0] + a[r][3][1]) + (a[r][3][2] + a[r][3][3]));
-#else
-  const int p = threadIdx.x & 1;
-  float a[NR][4];
-#pragma unroll
-  for (int r = 0; r < NR; ++r) a[r][0] = a[r][1] = a[r][2] = a[r][3] = 0.0f;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    side(j);
-    const float4 q = w(j);
-#pragma unroll
-    for (int r = 0; r < NR; ++r) fma4(reinterpret_cast<const float4 *>(x + r * kRRow)[kRHalf4 * p + j], q, a[r]);
-  }
-#pragma unroll
-  for (int r = 0; r < NR; ++r) {
-    const float h = (a[r][0] + a[r][1]) + (a[r][2] + a[r][3]);
-    z[r] = h + dpp_f<0xB1>(h);
-  }
-#endif
 }
 
 // NH supports decoded together (z[h] = this lane's logits of support h, see support_logits):
@@ -1424,16 +1106,16 @@ __device__ inline int lookback_sum_w0(const SearchArgs &p, int k, int g, int G, 
   return (int)wave_sum(sum);
 }
 
-// NR = 2 (parity mode): the network carries a second, speculative row for two-way leaf ties.
-// SMODE: the selection mode at compile time (-1: n.select_mode at run time, experiments); RNG:
-// 0 glibc, 1 Philox, -1 p.fast at run time; STAMPS: phase stamps compiled in (LZM_PHASE_TIMING).
-// Production launches fix all three, so the unused paths cost neither code nor registers.
+// SMODE: the selection mode (1, 4 or 5: see the simulation loop); RNG: 0 glibc, 1 Philox, -1 p.fast
+// at run time; STAMPS: phase stamps compiled in (LZM_PHASE_TIMING). Production launches fix all
+// three, so the unused paths cost neither code nor registers.
 // The kernel's dynamic LDS plan (float offsets from the dynamic base): the two LDS weight layers
 // first (their slot addresses become instruction immediates), then the tree slice, the selection
 // tables and the optional pUCT visit table. cap / lut_n / depth_cap: the handle's capacities;
 // S: simulations the selection tables hold. (A compile-time plan for the production handle, which
 // frees ~45 scalar registers of offsets, measured even: the scalar spills are not on the path.)
-// static LDS of the kernel: activations (two rows), biases, scalars (below 2 KiB)
+// static LDS of the kernel, an upper bound: activations (counted as two full network rows; the
+// kernel holds one plus the late draw's second T1 / NL row), biases, scalars (below 2 KiB)
 constexpr int kResStaticBytes = (kRRow + 4 * kRRow + 2 * (4 * kRRow + kRF + 2 * kRF + kRMaxA) + kResBiasFloats) * 4 + 2048;
 constexpr int kResMaxBytes = 160 * 1024 - kResStaticBytes;
 __host__ __device__ constexpr int res_round4(int x) { return (x + 3) & ~3; }
@@ -1463,12 +1145,12 @@ __host__ __device__ constexpr ResPlan res_plan(int cap, int lut_n, int depth_cap
   return q;
 }
 
-template <int NR, int SMODE, int RNG, bool STAMPS>
+template <int SMODE, int RNG, bool STAMPS>
 __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) void search_res_kernel(SearchArgs p, ResNet n) {
   if (!STAMPS) p.phase = nullptr;
   if (RNG >= 0) p.fast = RNG;
   const ResPlan L = n.plan;
-  if (SMODE >= 0) n.select_mode = SMODE;
+  static_assert(SMODE == 1 || SMODE == 4 || SMODE == 5, "selection modes: 1, 4, 5");
   if ((SMODE == 4 || SMODE == 5) && RNG == 0 && !STAMPS) n.spec_depth = 1;  // production parity kernel
   extern __shared__ float4 smem4[];
   float *smem = reinterpret_cast<float *>(smem4);
@@ -1492,8 +1174,8 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   __shared__ unsigned long long s_tmask;
   __shared__ WalkState s_walk;
   __shared__ float4 s_mm;
-  __shared__ float s_red[12 * 2 * NR];
-  __shared__ uint32_t s_dwin[64];  // LZM_RES_DWIN2: draw sums at stream positions s_dlo + 0..63
+  __shared__ float s_red[12 * 2];  // support_decode_n<2>: the reward and the value support
+  __shared__ uint32_t s_dwin[64];  // the draw window: draw sums at stream positions s_dlo + 0..63
   __shared__ int s_dlo, s_base_prev;
   if (tid == 0) { s_dlo = -1000000; s_base_prev = 0; }
   __shared__ uint64_t s_exptab[32];  // glibc_expf's table: expand reads it from LDS (no vmcnt wait
@@ -1568,13 +1250,12 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // ---- network residency: LDS layers, action rows, register layers and biases
   // activations and biases at static LDS addresses: lane-dependent addresses then share a few base
   // registers and fold the arrays' offsets into the instructions' immediates
-  // T1 / NL hold two rows even at NR = 1: the two candidates of a leaf tie run the dynamics
-  // layers side by side while the draw offset is still unknown (see the simulation loop)
-  __shared__ float4 s_acts[(kRRow + 4 * kRRow + NR * (4 * kRRow + kRF + 2 * kRF + kRMaxA)) / 4];
+  // T1 / NL hold two rows: the two candidates of a leaf tie run the dynamics layers side by side
+  // while the draw offset is still unknown (the late draw, see the simulation loop)
+  __shared__ float4 s_acts[(kRRow + 4 * kRRow + 4 * kRRow + kRF + 2 * kRF + kRMaxA) / 4];
   __shared__ float4 s_bias[kResBiasFloats / 4];
   float *X0 = reinterpret_cast<float *>(s_acts), *T1 = X0 + kRRow, *NL = T1 + 2 * kRRow, *T2 = NL + 2 * kRRow,
-        *T3 = T2 + NR * kRRow, *U2 = T3 + NR * kRRow, *U3 = U2 + NR * kRRow, *RHo = U3 + NR * kRRow,
-        *HV = RHo + NR * kRF, *LG = HV + NR * 2 * kRF;
+        *T3 = T2 + kRRow, *U2 = T3 + kRRow, *U3 = U2 + kRRow, *RHo = U3 + kRRow, *HV = RHo + kRF, *LG = HV + 2 * kRF;
   float *ACT = smem + L.act;
   const float4 *WD1 = reinterpret_cast<const float4 *>(smem + L.wd1);
   const float4 *WD2 = reinterpret_cast<const float4 *>(smem + L.wd2);
@@ -1622,7 +1303,7 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   __syncthreads();
   const int players = s_players;
   const unsigned long long epoch = (unsigned long long)(uint32_t)s_epoch;
-  // the root's legal actions in registers (descend_small)
+  // the root's legal actions in registers (the two-action walks)
   int rleg[2];
   const int nleg = t.nlegal[0];
 #pragma unroll
@@ -1632,32 +1313,31 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
   for (int k = 0; k < p.S; ++k) {
     const uint32_t seed = s_seeds[k];
-    if (!LZM_RES_SEEDW1 && !p.fast) seed_state_parallel(seed, s_pow, s_z0);
-    // ---- selection, part 1: every expanded node's walk-independent pUCT terms (all threads)
-    // 0: descend_wave; 1: terms + wave walk; 2: terms + lane walk; 3: descend_slice; 4: terms + the
-    // two-action walk (descend_a2f) when A == 2, else as 1; 5 (default for A == 2, S + 2 <= 64, chosen
-    // on the host): 4 with the walk on the terms pass's registers (descend_a2r)
-    const bool regwalk = n.select_mode == 5;
-    const int smode = regwalk ? 4 : (n.select_mode == 4 && A != 2) ? 1 : n.select_mode;
+    // ---- selection, part 1: every expanded node's walk-independent pUCT terms (all threads), then
+    // part 2, the walk over them (wave 0). SMODE, chosen on the host:
+    //   1: the wave walk, one lane per child (descend_terms), any A;
+    //   4: the two-action walk over the LDS tables (descend_a2f), A == 2 (else as 1);
+    //   5: 4 with the terms pass and the walk on wave 0's registers (descend_a2r), A == 2, S + 2 <= 64.
+    const bool regwalk = SMODE == 5;
+    const int smode = regwalk ? 4 : (SMODE == 4 && A != 2) ? 1 : SMODE;
     A2Rec rc = {0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    if (smode == 1 || smode == 2 || smode == 4) {
-      __syncthreads();  // the previous simulation's backup (wave 0) and children (wave 1) are complete
-      if (regwalk) {
-        // one node per lane, all in wave 0, which alone reads the records (registers) and, after the
-        // walk's barrier, the tables: no barrier between the pass and the walk
-        if (tid < s_nlat + k) node_terms_a2(t, tid, L2N, NQ, CS, s_mm, players, p.disc, DEC, rleg, nleg, &rc);
-        if (LZM_RES_R5_BAR2) __syncthreads();
-      } else {
-        if (smode == 4)
-          precompute_terms_a2(t, s_nlat + k, L2N, NQ, CS, s_mm, players, p.disc, DEC, rleg, nleg);
-        else
-          precompute_terms(t, s_nlat + k, L2N, NQ, CS, s_mm, players, p.disc, smode == 4 ? DEC : nullptr);
-        __syncthreads();
-      }
+    __syncthreads();  // the previous simulation's backup (wave 0) and children (wave 1) are complete
+    if (regwalk) {
+      // one node per lane, all in wave 0, which alone reads the records (registers) and, after the
+      // walk's barrier, the tables: no barrier between the pass and the walk
+      if (tid < s_nlat + k) node_terms_a2(t, tid, L2N, NQ, CS, s_mm, players, p.disc, DEC, rleg, nleg, &rc);
+    } else {
+      if (smode == 4)
+        precompute_terms_a2(t, s_nlat + k, L2N, NQ, CS, s_mm, players, p.disc, DEC, rleg, nleg);
+      else
+        precompute_terms(t, s_nlat + k, L2N, NQ, CS, s_mm, players, p.disc);
+      __syncthreads();
     }
     LZM_STAMP(12);
     if (wid != 0 && k > 0) res_fetch<kRSlotsD>(res_blk4(n, kRbD), P);  // (see the expand)
-    if (LZM_RES_SEEDW1 && !p.fast && wid == 1) {  // (the post-walk barrier orders s_z0 for its readers)
+    // this simulation's glibc seed state (s_z0, read only after the walk) by wave 1 during wave 0's
+    // walk (the post-walk barrier orders it for its readers)
+    if (!p.fast && wid == 1) {
       const uint32_t sd = seed == 0 ? 1u : seed;
       if (sd < 0x7fffffffu) {
         if (lane < 31) {
@@ -1671,8 +1351,8 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         glibc_seed_state(seed, s_z0);
       }
     }
-    if (LZM_RES_DWIN2 && RNG != 1 && wid == 1) s_dwin[lane] = 0u;  // (the status-2 window's adds follow a barrier)
-    // ---- selection, part 2: the walk (wave 0, one lane per child)
+    if (RNG != 1 && wid == 1) s_dwin[lane] = 0u;  // (the status-2 window's adds follow a barrier)
+    // ---- selection, part 2: the walk (wave 0)
     if (wid == 0) {
       const float4 mm = s_mm;
       int w_status = 0, w_x = 0;  // (mode 5) the walk's status and x, wave-uniform
@@ -1687,13 +1367,8 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           w_x = d.x;
         } else if (smode == 4) {
           d = descend_a2f<false>(t, NQ, DEC, CS, mm, s_vtp, players, rleg, nleg, draw, nullptr);
-        } else if (smode == 1) {
+        } else if (smode == 1) {  // (smode is 4 or 1)
           d = descend_terms<false>(t, NQ, CS, mm, s_vtp, players, draw, nullptr);
-        } else if (smode == 0) {
-          d = descend_wave<false, false>(t, 0, 0, 1, mm, players, s_vtp, p.disc, draw, nullptr);
-        } else if (lane == 0) {
-          d = smode == 2 ? descend_terms_lane<false>(t, NQ, CS, mm, s_vtp, players, draw, nullptr)
-                         : descend_slice<false, false>(t, 0, 0, 1, mm, players, s_vtp, p.disc, draw, nullptr);
         }
         if (lane == 0) { s_len[0] = d.len; s_x = d.x; s_act = d.action; s_status = 0; }
       } else {
@@ -1716,11 +1391,6 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           WalkState ws;
           d = descend_terms<true>(t, NQ, CS, mm, s_vtp, players, nodraw, &ti, nullptr, &ws);
           if (lane == 0 && ti.status == 2) s_walk = ws;
-        } else if (smode == 0) {
-          d = descend_wave<false, true>(t, 0, 0, 1, mm, players, s_vtp, p.disc, nodraw, &ti);
-        } else if (lane == 0) {
-          d = smode == 2 ? descend_terms_lane<true>(t, NQ, CS, mm, s_vtp, players, nodraw, &ti)
-                         : descend_slice<false, true>(t, 0, 0, 1, mm, players, s_vtp, p.disc, nodraw, &ti);
         }
         if (lane == 0) {
           s_len[0] = d.len; s_x = d.x; s_act = d.action;
@@ -1731,10 +1401,9 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                                __HIP_MEMORY_SCOPE_AGENT);
         }
       }
-#if LZM_RES_EGATHER
       // gather the leaf's parent latent now, by the walking wave, when the walk's x is final (every
-      // status but 2): the walk's barrier then also orders the gather (one barrier fewer)
-      // (mode 5: straight from the walk's registers, no LDS round trip)
+      // status but 2; a status-2 root gathers after its draw resolution below): the walk's barrier
+      // then also orders the gather (mode 5: straight from the walk's registers, no LDS round trip)
       if (!regwalk) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // lane 0's s_status / s_x to the wave
         __builtin_amdgcn_wave_barrier();
@@ -1745,12 +1414,11 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       if (stw != 2 && lane < kRHid / 4)
         reinterpret_cast<float4 *>(X0)[lane + (lane >= kRHid / 8)] =
             reinterpret_cast<const float4 *>(p.pool + ((size_t)max(x0, 0) * B + i) * kRHid)[lane];
-#endif
     }
     __syncthreads();
     LZM_STAMP(0);
     const int status = s_status;
-    if (__builtin_expect(status == 2 && (smode == 1 || smode == 4), 0)) {
+    if (__builtin_expect(status == 2, 0)) {
       // the depth depends on a draw: look back now, then resume the walk at the tie with the draws
       // (exact semantics; the draws of the forced levels above the tie are never read). First
       // (A == 2), when every draw outcome gives the same depth (speculate_depth_a2), publish it at
@@ -1760,9 +1428,7 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       int sp_leaf = -1;
       unsigned long long sub_ = p.phase ? __builtin_amdgcn_s_memtime() : 0ull;
       if (smode == 4 && n.spec_depth && wid == 0) {
-        const int de = LZM_RES_SPEC_PATH
-                           ? speculate_depth_a2(t, NQ, DEC, CS, s_mm, rleg, nleg, s_walk, lane, &sp_choice, &sp_ties, &sp_leaf)
-                           : speculate_depth_a2(t, NQ, DEC, CS, s_mm, rleg, nleg, s_walk, lane);
+        const int de = speculate_depth_a2(t, NQ, DEC, CS, s_mm, rleg, nleg, s_walk, lane, &sp_choice, &sp_ties, &sp_leaf);
         d0 = __builtin_amdgcn_readfirstlane(de);
         if (d0 >= 0 && __ballot(de != d0) == 0ull) {
           st = 3;
@@ -1772,8 +1438,8 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
       }
       LZM_SUBSTAMP(20);
-      // LZM_RES_DWIN2: wave 0 alone waits for the look-back while wave 1 fills the draw window
-      const bool win2 = LZM_RES_DWIN2 && RNG != 1 && smode == 4 && G <= kRT;
+      // the draw window: wave 0 alone waits for the look-back while waves 1-3 fill the window
+      const bool win2 = RNG != 1 && smode == 4 && G <= kRT;
       int base = 0;
       if (win2) {
         if (wid == 0) {
@@ -1814,11 +1480,12 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
         const LaneDraws draw{p.coef, s_z0, p.diag, p.coef_positions, base, ws.len, wv};
         Descent d;
-        // LZM_RES_SPEC_PATH: the lane whose pattern agrees with the draws' parities at its tie levels
-        // (lane l holds the draw of level ws.len + l); that lane's choice bits are the path
+        // a speculated depth (st 3): the lane whose pattern agrees with the draws' parities at its tie
+        // levels (lane l holds the draw of level ws.len + l); that lane's choice bits are the path, a
+        // pointer chase instead of re-walking the tie subtree with scores
         int m = -1;
         uint32_t pch = 0u;
-        if (LZM_RES_SPEC_PATH && st == 3 && smode == 4) {
+        if (st == 3 && smode == 4) {
           const unsigned long long par = __ballot((wv & 1u) != 0u);
           const bool ok = sp_choice != ~0u && ((sp_choice ^ (uint32_t)par) & sp_ties) == 0u;
           const unsigned long long okm = __ballot(ok);
@@ -1868,72 +1535,39 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             __hip_atomic_store(&p.flags[(size_t)k * G + g], (epoch << 32) | (unsigned)d.len, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
         }
-        if (LZM_RES_EGATHER) {  // X0 by this wave (the barrier below orders it)
-          const int x0 = __builtin_amdgcn_readfirstlane(d.x);
-          if (lane < kRHid / 4)
-            reinterpret_cast<float4 *>(X0)[lane + (lane >= kRHid / 8)] =
-                reinterpret_cast<const float4 *>(p.pool + ((size_t)max(x0, 0) * B + i) * kRHid)[lane];
-        }
+        // X0 by this wave (the barrier below orders it)
+        const int x0 = __builtin_amdgcn_readfirstlane(d.x);
+        if (lane < kRHid / 4)
+          reinterpret_cast<float4 *>(X0)[lane + (lane >= kRHid / 8)] =
+              reinterpret_cast<const float4 *>(p.pool + ((size_t)max(x0, 0) * B + i) * kRHid)[lane];
       }
       LZM_SUBSTAMP(22);
       __syncthreads();
       LZM_SUBSTAMP(23);
-    } else if (status == 2) {
-      // the depth depends on a draw: look back now, then walk with the draws (exact semantics)
-      const int base = lookback_sum(p, k, g, G, epoch, s_part);
-      if (tid == 0) {
-        {
-          atomicAdd(p.diag + 1, 1);
-          const uint32_t *coef = p.coef;
-          const int npos = p.coef_positions;
-          int32_t *diag = p.diag;
-          auto draw = [coef, npos, diag, base](int level) -> uint32_t {
-            return glibc_draw(coef, npos, s_z0, base + level, diag);
-          };
-          Descent d = descend_slice<false, false>(t, 0, 0, 1, s_mm, players, s_vtp, p.disc, draw, nullptr);
-          s_len[0] = d.len; s_x = d.x; s_act = d.action;  // (s_status stays: other waves may still read it)
-          __hip_atomic_store(&p.flags[(size_t)k * G + g], (epoch << 32) | (unsigned)d.len, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-      __syncthreads();
     }
+    // X0 = pool[x][i], the leaf's parent latent, is in LDS: gathered by the walking wave
     LZM_STAMP(1);
-    // ---- gather the leaf's parent latent: X0 = pool[x][i] (LZM_RES_EGATHER: already done by the
-    // walking wave)
-    const bool gathered = LZM_RES_EGATHER && (status != 2 || smode == 1 || smode == 4);
-    if (!gathered) {
-      if (tid < kRHid / 4)
-        reinterpret_cast<float4 *>(X0)[tid + (tid >= kRHid / 8)] =
-            reinterpret_cast<const float4 *>(p.pool + ((size_t)max(s_x, 0) * B + i) * kRHid)[tid];
-      __syncthreads();
-    }
-    LZM_STAMP(2);
+    LZM_STAMP(2);  // (the separate gather phase this stamp closed is gone; the stamp indices stay)
     unsigned long long sub_ = p.phase ? __builtin_amdgcn_s_memtime() : 0ull;
-    // ---- fc_dynamics[0], latent rows (streamed weights in P): shared by the speculative rows
+    // ---- fc_dynamics[0], latent rows (streamed weights in P): shared by the late draw's two rows
     const float z0 = dense128(X0, [&](int j) { return P[j]; });
-#if LZM_RES_STAGE_WD1
     // the stream buffer is free until the next pair's prefetch: stage fc_dynamics[1]'s LDS slots in
     // it now, so the layer below reads registers (its LDS reads in flight during the action rows)
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int j = 0; j < kRSlotsD; ++j) P[j] = WD1[j * kRT + tid];
-#endif
     LZM_SUBSTAMP(16);
-    // Rows: row r carries the network for action act_r. A tie between exactly two unexpanded
-    // children (status 1) is evaluated speculatively for both (NR = 2) and resolved after the
-    // network, when the predecessors' draw counts have long been published; other ties wait here.
-    // NR = 1, late draw: a two-way leaf tie runs the two dynamics layers for both candidates (two
-    // rows, shared weight reads) and only then waits for the look-back, which by then has mostly
-    // been published; the draw picks the next-latent row the rest of the network reads.
-    bool spec = false, late = false;
+    // A tie between exactly two unexpanded children (status 1) takes the late draw: the two dynamics
+    // layers run for both candidates (rows act_r[0], act_r[1] of T1 / NL, shared weight reads) and only
+    // then the look-back is waited for, which by then has mostly been published; the draw picks the
+    // next-latent row the rest of the network reads. Other leaf ties wait for their draw here.
+    bool late = false;
     int act_r[2];
     if (status == 1) {
       const unsigned long long m = s_tmask;
       const int parent = t.path[s_tlevel];
-      if (__popcll(m) == 2 && (NR == 2 || n.late_draw)) {
-        spec = NR == 2;
-        late = NR == 1;
+      if (__popcll(m) == 2 && n.late_draw) {
+        late = true;
         act_r[0] = legal_at(t, 0, parent, __ffsll((long long)m) - 1);
         act_r[1] = legal_at(t, 0, parent, __ffsll((long long)(m & (m - 1))) - 1);
       } else {
@@ -1942,46 +1576,35 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         __syncthreads();
       }
     }
-    if (!spec && !late) act_r[0] = act_r[1] = s_act;
+    if (!late) act_r[0] = act_r[1] = s_act;
     LZM_SUBSTAMP(17);
     __builtin_amdgcn_sched_barrier(0);
     // + the action's one-hot row, bias, ReLU (muzero_model_mlp.py:188-190)
     if (pD == 0) {
 #pragma unroll
       for (int r = 0; r < 2; ++r)
-        if (r < NR || late) T1[r * kRRow + rpad(cD)] = fmaxf((z0 + ACT[act_r[r] * kRHid + cD]) + BD[cD], 0.0f);
+        if (r < 1 || late) T1[r * kRRow + rpad(cD)] = fmaxf((z0 + ACT[act_r[r] * kRHid + cD]) + BD[cD], 0.0f);
     }
     __syncthreads();
     LZM_SUBSTAMP(18);
-    // ---- fc_dynamics[1] (LDS weights) + latent residual -> next latent
-    if (NR == 1 && late) {
+    // ---- fc_dynamics[1] (its weights staged in P) + latent residual -> next latent
+    if (late) {
       float z[2];
-#if LZM_RES_STAGE_WD1
       dense128n<2>(T1, [&](int j) { return P[j]; }, z);
-#else
-      dense128n<2>(T1, [&](int j) { return WD1[j * kRT + tid]; }, z);
-#endif
       LZM_SUBSTAMP(32);
       if (pD == 0) {
 #pragma unroll
         for (int r = 0; r < 2; ++r) NL[r * kRRow + rpad(cD)] = fmaxf(z[r] + BD[kRHid + cD], 0.0f) + X0[rpad(cD)];
       }
     } else {
-      float z[NR];
-#if LZM_RES_STAGE_WD1
-      dense128n<NR>(T1, [&](int j) { return P[j]; }, z);
-#else
-      dense128n<NR>(T1, [&](int j) { return WD1[j * kRT + tid]; }, z);
-#endif
-      if (pD == 0) {
-#pragma unroll
-        for (int r = 0; r < NR; ++r) NL[r * kRRow + rpad(cD)] = fmaxf(z[r] + BD[kRHid + cD], 0.0f) + X0[rpad(cD)];
-      }
+      float z;
+      dense128n<1>(T1, [&](int j) { return P[j]; }, &z);
+      if (pD == 0) NL[rpad(cD)] = fmaxf(z + BD[kRHid + cD], 0.0f) + X0[rpad(cD)];
     }
     __syncthreads();
     LZM_SUBSTAMP(33);
     int lrow = 0;  // the late draw's pick: the two-way tie's second candidate when rand() % 2 == 1
-    if (NR == 1 && late) {
+    if (late) {
       const unsigned long long w0_ = p.phase ? __builtin_amdgcn_s_memtime() : 0ull;
       if (G <= kRT) {
         // every wave looks back and draws for itself, so no barrier hands the pick over; wave 0 files it
@@ -1998,38 +1621,35 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         lrow = s_act == act_r[1] ? 1 : 0;
       }
     }
-    // the next latent row the rest of the network reads (NR = 1: the late draw's pick)
-    const float *NLb = NL + ((NR == 1 && late && lrow) ? kRRow : 0);
+    // the next latent row the rest of the network reads (the late draw's pick)
+    const float *NLb = NL + ((late && lrow) ? kRRow : 0);
     LZM_SUBSTAMP(34);
     LZM_STAMP(3);
     // The reward chain (fc_dynamics_2 -> reward head) and the prediction chain (prediction
     // common -> value / policy heads) both start from the next latent: one step per layer pair.
     // ---- [fc_dynamics_2[0] (LDS) | fc_prediction_common[0] (registers)]
     {
-      float z2[NR], z6[NR];
+      float z2, z6;
       // fc_prediction_common[1] into P (used by the next pair), one slot per slot of this layer
       const __amdgpu_buffer_rsrc_t rd5 = wave_rsrc(res_blk4(n, kRbD + 5), kRSlotsD * kRT * 16);
-      dense128n<NR>(NLb, [&](int j) { return WD2[j * kRT + tid]; }, z2, [&](int j) {
+      dense128n<1>(NLb, [&](int j) { return WD2[j * kRT + tid]; }, &z2, [&](int j) {
         const f32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rd5, tid * 16, j * kRT * 16, 0);
         P[j] = make_float4(v.x, v.y, v.z, v.w);
       });
       LZM_SUBSTAMP(35);
-      dense128n<NR>(NLb, [&](int j) { return wD4[j]; }, z6);
+      dense128n<1>(NLb, [&](int j) { return wD4[j]; }, &z6);
       LZM_SUBSTAMP(36);
       if (pD == 0) {
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-          T2[r * kRRow + rpad(cD)] = fmaxf(z2[r] + BD[2 * kRHid + cD], 0.0f);
-          U2[r * kRRow + rpad(cD)] = fmaxf(z6[r] + BD[4 * kRHid + cD], 0.0f);
-        }
+        T2[rpad(cD)] = fmaxf(z2 + BD[2 * kRHid + cD], 0.0f);
+        U2[rpad(cD)] = fmaxf(z6 + BD[4 * kRHid + cD], 0.0f);
       }
     }
     __syncthreads();
     LZM_SUBSTAMP(19);
     // ---- [fc_prediction_common[1] (streamed) | fc_dynamics_2[1] (registers)]
     {
-      float z7[NR], z3[NR];
-      dense128n<NR>(U2, [&](int j) { return P[j]; }, z7);
+      float z7, z3;
+      dense128n<1>(U2, [&](int j) { return P[j]; }, &z7);
       LZM_SUBSTAMP(37);
       // the value support head into P (two steps on): half before this layer, half after it (a
       // 20-load burst stalls the wave at issue)
@@ -2043,82 +1663,61 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
       };
       fetch_vs(0, kRSlotsS / 2);
-      dense128n<NR>(T2, [&](int j) { return wD3[j]; }, z3);
+      dense128n<1>(T2, [&](int j) { return wD3[j]; }, &z3);
       LZM_SUBSTAMP(38);
       __builtin_amdgcn_sched_barrier(0);
       fetch_vs(kRSlotsS / 2, kRSlotsS);
       if (pD == 0) {
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-          T3[r * kRRow + rpad(cD)] = fmaxf(z3[r] + BD[3 * kRHid + cD], 0.0f);
-          U3[r * kRRow + rpad(cD)] = fmaxf(z7[r] + BD[5 * kRHid + cD], 0.0f);
-        }
+        T3[rpad(cD)] = fmaxf(z3 + BD[3 * kRHid + cD], 0.0f);
+        U3[rpad(cD)] = fmaxf(z7 + BD[5 * kRHid + cD], 0.0f);
       }
     }
     __syncthreads();
     LZM_SUBSTAMP(39);
     LZM_STAMP(4);
     // ---- [reward head hidden | (value | policy) head hidden]
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-      float h = dot4<kRSlotsRH>(reinterpret_cast<const float4 *>(T3 + r * kRRow) + 4 * pRH + (pRH >= 4),
-                                [&](int j) { return wRH[j]; });
-      float u = dot4<kRSlotsVPH>(reinterpret_cast<const float4 *>(U3 + r * kRRow) + 8 * pVP + (pVP >= 2),
-                                 [&](int j) { return wVPH[j]; });
+    {
+      float h = dot4<kRSlotsRH>(reinterpret_cast<const float4 *>(T3) + 4 * pRH + (pRH >= 4), [&](int j) { return wRH[j]; });
+      float u = dot4<kRSlotsVPH>(reinterpret_cast<const float4 *>(U3) + 8 * pVP + (pVP >= 2), [&](int j) { return wVPH[j]; });
       h += dpp_f<0xB1>(h);
       u += dpp_f<0xB1>(u);
       h += dpp_f<0x4E>(h);
       u += dpp_f<0x4E>(u);
       h += dpp_f<0x141>(h);
-      if (pRH == 0) RHo[r * kRF + cRH] = fmaxf(h + BRH[cRH], 0.0f);
-      if (pVP == 0) HV[r * 2 * kRF + cVP] = fmaxf(u + BVP[cVP], 0.0f);
+      if (pRH == 0) RHo[cRH] = fmaxf(h + BRH[cRH], 0.0f);
+      if (pVP == 0) HV[cVP] = fmaxf(u + BVP[cVP], 0.0f);
     }
     __syncthreads();
     LZM_STAMP(5);
-    // ---- reward support (registers), value support (streamed), policy logits; every support
+    // ---- reward support (registers), value support (streamed), policy logits; both supports
     // decoded together
-    float dec[2 * NR];  // [row][reward, value]
+    float dec[2];  // [reward, value]
     {
-      float zz[2 * NR][3];
-#pragma unroll
-      for (int r = 0; r < NR; ++r) {
-        const float4 hp = reinterpret_cast<const float4 *>(HV + r * 2 * kRF + kRF)[tid & 7];
-        float q = __fmaf_rn(hp.x, wPO[0].x, 0.0f);
-        q = __fmaf_rn(hp.y, wPO[0].y, q);
-        q = __fmaf_rn(hp.z, wPO[0].z, q);
-        q = __fmaf_rn(hp.w, wPO[0].w, q);
-        q += dpp_f<0xB1>(q);
-        q += dpp_f<0x4E>(q);
-        q += dpp_f<0x141>(q);
-        if ((tid & 7) == 0 && cPO < A) LG[r * kRMaxA + cPO] = q + BPO[cPO];
-        support_logits(HV + r * 2 * kRF, P, BVS, zz[2 * r + 1][0], zz[2 * r + 1][1], zz[2 * r + 1][2]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int r = 0; r < NR; ++r) {
-        support_logits(RHo + r * kRF, wRS, BRS, zz[2 * r][0], zz[2 * r][1], zz[2 * r][2]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      float zz[2][3];
+      const float4 hp = reinterpret_cast<const float4 *>(HV + kRF)[tid & 7];
+      float q = __fmaf_rn(hp.x, wPO[0].x, 0.0f);
+      q = __fmaf_rn(hp.y, wPO[0].y, q);
+      q = __fmaf_rn(hp.z, wPO[0].z, q);
+      q = __fmaf_rn(hp.w, wPO[0].w, q);
+      q += dpp_f<0xB1>(q);
+      q += dpp_f<0x4E>(q);
+      q += dpp_f<0x141>(q);
+      if ((tid & 7) == 0 && cPO < A) LG[cPO] = q + BPO[cPO];
+      support_logits(HV, P, BVS, zz[1][0], zz[1][1], zz[1][2]);
+      __builtin_amdgcn_sched_barrier(0);
+      support_logits(RHo, wRS, BRS, zz[0][0], zz[0][1], zz[0][2]);
       __builtin_amdgcn_sched_barrier(0);
       LZM_STAMP(15);
-      support_decode_n<2 * NR>(zz, s_red, dec);
+      support_decode_n<2>(zz, s_red, dec);
     }
+    const float rdec = dec[0], vdec = dec[1];
     LZM_STAMP(6);
-    // ---- resolve a speculative tie: the draw picks the row (predecessors published long ago)
-    if (spec) {
-      const int base = lookback_sum(p, k, g, G, epoch, s_part);
-      if (tid == 0) resolve_tie(t, A, s_tlevel, s_tmask, glibc_draw(p.coef, p.coef_positions, s_z0, base + s_tlevel, p.diag), &s_act);
-      __syncthreads();
-    }
-    const int row = (spec && s_act == act_r[1]) ? 1 : 0;
-    const float rdec = (NR == 2 && row) ? dec[2 * NR - 2] : dec[0];  // static indices: no scratch
-    const float vdec = (NR == 2 && row) ? dec[2 * NR - 1] : dec[1];
-    LZM_STAMP(7);
+    LZM_STAMP(7);  // (the tie resolution this stamp closed is gone; the stamp indices stay)
     if (p.phase && tid == 0) sub_ = __builtin_amdgcn_s_memtime();
     // file the next latent (mcts_ctree.py:305): pool[k + 1][i], by wave 1 (wave 0 expands)
     if (tid >= 64 && tid < 64 + kRHid / 4)
       reinterpret_cast<float4 *>(p.pool + ((size_t)(k + 1) * B + i) * kRHid)[tid - 64] =
-          reinterpret_cast<const float4 *>(NLb + row * kRRow)[(tid - 64) + (tid - 64 >= kRHid / 8)];
+          reinterpret_cast<const float4 *>(NLb)[(tid - 64) + (tid - 64 >= kRHid / 8)];
     if (p.rec_x && tid == 0) {
       p.rec_x[(size_t)k * B + i] = s_x;
       p.rec_a[(size_t)k * B + i] = s_act;
@@ -2127,7 +1726,7 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     if (p.rec_dec && tid == 0) {
       p.rec_dec[((size_t)k * B + i) * 2] = rdec;
       p.rec_dec[((size_t)k * B + i) * 2 + 1] = vdec;
-      for (int a = 0; a < A; ++a) p.rec_logits[((size_t)k * B + i) * A + a] = LG[row * kRMaxA + a];
+      for (int a = 0; a < A; ++a) p.rec_logits[((size_t)k * B + i) * A + a] = LG[a];
     }
     // fc_dynamics[0] for the next simulation: wave 0 now, alone on the texture path (16 loads
     // issue in a few hundred cycles), waves 1-3 during the next walk, which only wave 0 runs
@@ -2144,12 +1743,12 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       if (players > 1)
         for (int l = 0; l < len; ++l) vtp = (vtp == 1) ? 2 : 1;
       LZM_SUBSTAMP(31);
-      expand_wave(t, 0, leaf, vtp, k + 1, rdec, LG + row * kRMaxA, -1, s_exptab, 1);
+      expand_wave(t, 0, leaf, vtp, k + 1, rdec, LG, -1, s_exptab, 1);
       LZM_STAMP(14);
       if (lane == 0) L2N[s_nlat + k] = leaf;  // the leaf now holds latent k + 1 (= s_nlat + k)
       backup_wave(t, 0, 0, 1, &s_mm, vtp, vdec, p.disc);
     } else if (wid == 1) {
-      expand_wave(t, 0, 0, 0, k + 1, 0.0f, LG + row * kRMaxA, -1, s_exptab, 2);
+      expand_wave(t, 0, 0, 0, k + 1, 0.0f, LG, -1, s_exptab, 2);
     }
     LZM_STAMP(9);
   }

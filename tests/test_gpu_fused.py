@@ -128,9 +128,10 @@ def test_fused_roots_per_workgroup(case, roots, monkeypatch):
 
 
 # the config-2 shape takes the network-resident kernel (lzm_search_res.h); the same cases through
-# the weight-streaming kernel (LZM_FUSED_RES=0) and the speculative two-row variant (LZM_RES_SPEC=1)
-@pytest.mark.parametrize("env", ["LZM_FUSED_RES=0", "LZM_RES_SPEC=1", "LZM_RES_SELECT=0", "LZM_RES_SELECT=2",
-                                 "LZM_RES_SELECT=3", "LZM_RES_SPEC_DEPTH=0"])
+# the weight-streaming kernel (LZM_FUSED_RES=0), the resident kernel's other two selection modes (the
+# default here is 5: LZM_RES_SELECT=1, 4) and its look-back resume without depth speculation
+# (LZM_RES_SPEC_DEPTH=0, which runs the stamps instantiation of mode 5)
+@pytest.mark.parametrize("env", ["LZM_FUSED_RES=0", "LZM_RES_SELECT=1", "LZM_RES_SELECT=4", "LZM_RES_SPEC_DEPTH=0"])
 @pytest.mark.parametrize("case", [CASES[0], CASES[1], CASES[4]], ids=_case_id)
 def test_fused_kernel_variants(case, env, monkeypatch):
     k, v = env.split("=")

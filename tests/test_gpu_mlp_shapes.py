@@ -162,6 +162,17 @@ def test_mode_1_at_two_actions_equals_mode_5(monkeypatch):
         assert np.array_equal(out[1][f], out[5][f]), f
 
 
+@pytest.mark.parametrize("A,mode", [(2, 5), (3, 1)])
+def test_unknown_select_mode_is_ignored(A, mode, monkeypatch):
+    """LZM_RES_SELECT takes 1, 4 and 5: a removed mode (3) and garbage (7) leave the default for A in place"""
+    B, S = 8, 12
+    for value in ("3", "7"):
+        monkeypatch.setenv("LZM_RES_SELECT", value)
+        r = fused_search(B, S, A, H, False, 1, False, seed=B + S + A, tree_sims=S)
+        assert r["plan"] == dict(RESIDENT, mode=mode), (value, r["plan"])
+        exact(r, B, S, A)
+
+
 @pytest.mark.parametrize("A,want", [(4, 30), (9, 17)])
 def test_resident_network_matches_float64(A, want):
     B = 16

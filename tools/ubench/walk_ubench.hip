@@ -1,9 +1,11 @@
 // Micro-benchmark (diagnostic, not shipped): cycles per level of the resident kernel's selection
-// walk (descend_small<2>, descend_a2, descend_a2f, and the register walk descend_a2r as variants 5 and
-// 6: without and with a final settle of the mean-q chain; lzm_search_res.h) in isolation, on a synthetic full binary tree in LDS
-// (depth D, walk ends at a two-way tie among unexpanded children like most real simulations),
+// walk (lzm_search_res.h) in isolation, on a synthetic full binary tree in LDS (depth D, walk ends at
+// a two-way tie among unexpanded children like most real simulations),
 // with NP float4 per lane held live across the walk to emulate the resident kernel's register
 // pressure (its network weights stay in registers for the whole launch).
+// Variants (the numbers of profiles/walk_regs/walk_ubench.txt; 0 and 4 measured walks since removed):
+//   1 descend_a2, 2 the floor (a bare pointer chase), 3 descend_a2f, 5 / 6 the register walk
+//   descend_a2r without / with a final settle of the mean-q chain.
 // Build: hipcc -O3 -std=c++17 -ffp-contract=off --offload-arch=gfx950 -o walk_ubench walk_ubench.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -28,7 +30,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   __shared__ int path[64], pact[64], lg[4];
   __shared__ NodeMeta meta[1];
   __shared__ int dec[NLAT + 1];
-  __shared__ float2 chain[64];
   for (int e = threadIdx.x; e < CAP; e += 256) cs[e] = gcs[e];
   for (int e = threadIdx.x; e <= NLAT; e += 256) nq[e] = gnq[e];
   __syncthreads();
@@ -75,13 +76,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         Descent d = descend_a2r<true>(t, rc, V == 5, mm, vtp, players, rleg, nleg, nodraw, &ti);
         acc += d.len + ti.status;
       } else {
-        Descent d = V == 0 ? descend_small<2, true>(t, nq, cs, mm, vtp, players, rleg, nleg, nodraw, &ti)
-                  : V == 1 ? descend_a2<true, decltype(nodraw), 0>(t, nq, dec, cs, mm, vtp, players, rleg, nleg, nodraw, &ti)
-                  : V == 3 ? descend_a2f<true>(t, nq, dec, cs, mm, vtp, players, rleg, nleg, nodraw, &ti)
-                  : V == 4 ? descend_a2<true, decltype(nodraw), 4>(t, nq, dec, cs, mm, vtp, players, rleg, nleg, nodraw, &ti,
-                                                                   nullptr, nullptr, chain)
-                           : descend_a2<true, decltype(nodraw), 5>(t, nq, dec, cs, mm, vtp, players, rleg, nleg, nodraw, &ti,
-                                                                   nullptr, nullptr, chain);
+        static_assert(V == 1 || V == 2 || V == 3 || V == 5 || V == 6, "variants: 1, 2, 3, 5, 6");
+        Descent d = V == 1 ? descend_a2<true>(t, nq, dec, cs, mm, vtp, players, rleg, nleg, nodraw, &ti)
+                           : descend_a2f<true>(t, nq, dec, cs, mm, vtp, players, rleg, nleg, nodraw, &ti);
         acc += d.len + ti.status;
       }
       __builtin_amdgcn_s_waitcnt(0);
@@ -159,7 +156,6 @@ int main() {
   (void)hipMalloc(&dgi, sizeof(hgi));
   (void)hipMemcpy(dmm, &hmm, sizeof(float4), hipMemcpyHostToDevice);
   (void)hipMemcpy(dgi, hgi, sizeof(hgi), hipMemcpyHostToDevice);
-  run<0, 0>(dcs, dnq, dc, dout, dpin, G, dmm, dgi);
   run<0, 1>(dcs, dnq, dc, dout, dpin, G, dmm, dgi);
   run<0, 2>(dcs, dnq, dc, dout, dpin, G, dmm, dgi);
   run<0, 3>(dcs, dnq, dc, dout, dpin, G, dmm, dgi);
