@@ -18,6 +18,8 @@ import copy
 import os
 import weakref
 from collections import OrderedDict
+from contextlib import contextmanager
+from types import SimpleNamespace
 from typing import Any, List, Union
 
 import numpy as np
@@ -205,8 +207,11 @@ def _native_trunk(net, buf):
     return getattr(net, "native", None) is not None and tuple(buf.pool.shape[2:]) == (64, 8, 8)
 
 
-class MuZeroMCTSCtree(object):
-    """MCTS for MuZero on the GPU (reference: mcts_ctree.py:172-321)."""
+class _MCTSCtree(object):
+    """What MuZeroMCTSCtree and EfficientZeroMCTSCtree share: the class surface, the search prologue, the
+    staging of seeds and to_play, the collect step's glue, the per-simulation loop and its graph capture.
+    The subclasses add their public signatures, the network step of one simulation and their one-launch
+    searches."""
 
     config = dict(
         root_dirichlet_alpha=0.3,
@@ -216,6 +221,15 @@ class MuZeroMCTSCtree(object):
         value_delta_max=0.01,
         env_type='not_board_games',
     )
+
+    _tree = None  # the ctree module of the roots this search takes (mz_tree / ez_tree)
+    reward_name = None  # the step output the decode reads as the reward logits
+    # MuZero keeps cfg.fuse_traverse on under search_with_reuse, EfficientZero turns it off there
+    fuse_under_reuse = True
+    # 'glibc': the reference's tie-break stream, bit-exact (default); 'philox': independent
+    # counter-based stream per root (LZM_RNG_FAST), no batch-serial dependency.
+    rng_mode = 'glibc'
+    record = False  # set on an instance: keep a _Recorder of the next searches in last_record
 
     @classmethod
     def default_config(cls: type) -> EasyDict:
@@ -232,24 +246,241 @@ class MuZeroMCTSCtree(object):
         )
         self._buf = _SearchBuffers()
         self._graphs = _GraphCache(int(self._cfg.get('graph_cache_size', 4)))
-        self._packed = PackedCache()
         self._folded = FoldedCache()
-
-    # 'glibc': the reference's tie-break stream, bit-exact (default); 'philox': independent
-    # counter-based stream per root (LZM_RNG_FAST), no batch-serial dependency.
-    rng_mode = 'glibc'
+        self.residency_fallbacks = self.timeout_fallbacks = 0  # (one-launch searches re-run on the generic path)
 
     @classmethod
-    def roots(cls: int, active_collect_env_num: int, legal_actions: List[Any]) -> "mz_tree.Roots":
-        return mz_tree.Roots(active_collect_env_num, legal_actions, fast_rng=(cls.rng_mode == 'philox'))
+    def roots(cls: int, active_collect_env_num: int, legal_actions: List[Any]) -> "Roots":
+        return cls._tree.Roots(active_collect_env_num, legal_actions, fast_rng=(cls.rng_mode == 'philox'))
+
+    def _categorical(self):
+        return bool(self._cfg.model.get('categorical_distribution', True))
+
+    def _pb_c(self):
+        return int(self._cfg.pb_c_base), float(self._cfg.pb_c_init)
+
+    def _discount(self):
+        return float(np.float32(self._cfg.discount_factor))
+
+    # ---- the pieces of search() / search_with_reuse() ---------------------------------------------------------
+    def _begin(self, what, roots, model, latent_state_roots, state_roots=()):
+        """The prologue: the prepared tree with S simulations reserved, the root latents and the root rows of
+        the extra state pools (EfficientZero's LSTM (c, h)) on the device, and their sizes."""
+        model.eval()
+        t = roots.tree
+        if t is None:
+            raise RuntimeError(f"{what}: roots must be prepared (Roots.prepare / prepare_no_noise) first")
+        if what == "search_with_reuse" and t.fast_rng:
+            raise ValueError("search_with_reuse: parity (glibc) mode only")
+        B, S = roots.num, int(self._cfg.num_simulations)
+        t.reserve(S)
+        t.set_pb_c(*self._pb_c())
+        lat0 = _latent_tensor(latent_state_roots, t.device)
+        shape = tuple(lat0.shape[1:])
+        state = [_latent_tensor(s, t.device).reshape(B, -1) for s in state_roots]
+        return SimpleNamespace(t=t, B=B, S=S, dev=t.device, lat0=lat0, shape=shape,
+                               row=int(np.prod(shape)) if len(shape) else 1, state=state,
+                               extra=tuple(s.shape[1] for s in state), in_kernel=False)
+
+    def _buffers(self, c, model, graph=False):
+        """The search's buffers — the driver's own or, for a search replayed as a graph (cfg.use_hip_graph),
+        the ones its captured graph owns (they are what its kernels point at) — with the roots' slots filled."""
+        c.graph = bool(graph)
+        c.gkey = _graph_key(c.t, model, c.B, c.S, c.shape, c.extra) if graph else None
+        c.entry = self._graphs.get(c.gkey, model, c.t) if graph else None
+        c.buf = c.entry.buf if c.entry is not None else (_SearchBuffers() if graph else self._buf).get(
+            c.B, c.S, c.shape, c.dev, extra=c.extra)
+        if c.lat0.data_ptr() != c.buf.pool[0].data_ptr():  # (the collect step writes it in place)
+            c.buf.pool[0].copy_(c.lat0.reshape((c.B,) + c.shape))
+        for pool, rows in zip(c.buf.extra, c.state):
+            pool[0].copy_(rows)
+
+    def _stage(self, c, to_play_batch, seeds, step, in_place=False):
+        """(to_play, seeds) as device int32 tensors for the search: copied into the buffers, or with in_place
+        the caller's own tensors where a kernel can read them as they are. The seeds come from the host seed
+        source, from `seeds`, or from the collect step's counter (lzm_seed_sequence); None when the one-launch
+        kernel derives them itself (c.in_kernel)."""
+        buf = c.buf
+        vt = to_play_batch if in_place and _usable_i32(to_play_batch, c.B, c.dev) else None
+        if vt is None:
+            buf.vtp_in.copy_(_to_play_tensor(to_play_batch, c.B, c.dev))
+            vt = buf.vtp_in
+        if c.in_kernel:
+            return vt, None
+        if step is not None:
+            self._step_seeds(c, step)
+            return vt, buf.seeds
+        sd = seeds if in_place and _usable_i32(seeds, c.S, c.dev) else None
+        if sd is None:
+            buf.seeds.copy_(_seeds(c.S, c.dev) if seeds is None else seeds.reshape(c.S))
+            sd = buf.seeds
+        return vt, sd
+
+    def _recorder(self, c):
+        """a fresh _Recorder holding the staged seeds when self.record is set (is_reset on EfficientZero trees)"""
+        if not self.record:
+            return None
+        rec = _Recorder(c.S, c.B, c.t.A, c.dev)
+        if c.t.ez:
+            rec.is_reset = torch.zeros((c.S, c.B), dtype=torch.int32, device=c.dev)
+        rec.seeds = c.buf.seeds.cpu().numpy().view(np.uint32)
+        return rec
+
+    # the collect step's glue (search()'s `step`) as launches around a search: the seeds
+    # (base + count * S + k) mod 10^6 before it, the root outputs and the counter increment after it
+    def _step_seeds(self, c, step):
+        _lib.call("lzm_seed_sequence", _lib.ptr(step["count"]), int(step["base"]), c.S, _lib.ptr(c.buf.seeds),
+                  _lib.stream_ptr())
+
+    def _step_outputs(self, c, step):
+        _lib.call("lzm_get_root_outputs", c.t.h, _lib.ptr(step["dist"]), _lib.ptr(step["values"]), _lib.stream_ptr())
+        if step.get("increment", True):
+            step["count"].add_(1)
+
+    @contextmanager
+    def _glue(self, c, step):
+        """Around a one-launch search: with c.in_kernel the kernel runs the collect step's glue itself
+        (lzm_search_set_step: seeds from the step counter, fresh min-max bounds, root outputs, the counter
+        increment), else fresh min-max bounds. A body that falls back to the generic path clears the mode
+        and c.in_kernel itself."""
+        if c.in_kernel:
+            c.t.set_step(step["count"], int(step["base"]), step.get("increment", True), step["dist"], step["values"],
+                         True, self._cfg.value_delta_max)
+        else:
+            new_minmax(c.B, self._cfg.value_delta_max, c.dev, out=c.buf.mm)
+        try:
+            yield
+        finally:
+            if c.in_kernel:
+                c.t.set_step()
+
+    def _generic(self, c, model, rec):
+        """the per-simulation path: the loop itself or, with the graph _buffers looked up, its capture's replay"""
+        if not c.graph:
+            return self._loop(c.t, model, c, rec)
+        if c.entry is None:
+            c.entry = self._capture(c, model)
+            self._graphs.put(c.gkey, c.entry)
+        c.entry.replay()
+
+    def _finish(self, c, roots, step, rec):
+        if step is not None and not c.in_kernel:
+            self._step_outputs(c, step)
+        c.t.searched()
+        roots._last_minmax = c.buf.mm
+        self.last_record = rec
+
+    def _search_with_reuse(self, roots, model, latent_state_roots, state_roots, to_play_batch, true_action_list,
+                           reuse_value_list, seeds):
+        if true_action_list is None or reuse_value_list is None:
+            raise TypeError("search_with_reuse needs true_action_list and reuse_value_list")
+        with torch.no_grad():
+            c = self._begin("search_with_reuse", roots, model, latent_state_roots, state_roots)
+            self._buffers(c, model)
+            self._stage(c, to_play_batch, seeds, None)
+            ta = torch.as_tensor(np.asarray(true_action_list, np.int32).reshape(c.B) if not torch.is_tensor(
+                true_action_list) else true_action_list, device=c.dev)
+            rv = torch.as_tensor(np.asarray(reuse_value_list, np.float32).reshape(c.B) if not torch.is_tensor(
+                reuse_value_list) else reuse_value_list, device=c.dev)
+            rec = self._recorder(c)
+            infer = torch.zeros(c.S, dtype=torch.int64, device=c.dev)
+            c.t.set_reuse(ta, rv)
+            try:
+                self._loop(c.t, model, c, rec, infer=infer)
+            finally:
+                c.t.set_reuse(None)
+            roots._last_minmax = c.buf.mm
+            self.last_record = rec
+            counts = infer.cpu().numpy()
+        return int(counts[-1]) if c.S else 0, float(counts.sum()) / max(c.S, 1)
+
+    def _loop(self, t, model, c, rec=None, infer=None, net=None):
+        """The S simulations (mcts_ctree.py:255-321, 756-827) on tree t over c.buf, all enqueued on the current
+        stream. infer: optional device int64 [S], per simulation the number of roots that ran inference
+        (search-with-reuse: roots whose walk stopped on an expanded node report x = -1).
+        net: the step network to run (default: _step_net(model))."""
+        cfg, buf, S = self._cfg, c.buf, c.S
+        disc, cat, pb_c = self._discount(), self._categorical(), self._pb_c()
+        new_minmax(t.B, cfg.value_delta_max, t.device, out=buf.mm)
+        net = _step_net(self, model) if net is None else net
+        native = _native_trunk(net, buf)
+        fuse = _fuse_traverse(cfg, t) and (infer is None or self.fuse_under_reuse)
+        with _HeadVerdicts(t, net, buf, native and cat and getattr(net, "heads", None) is not None):
+            for k in range(S):
+                if k == 0 or not fuse:
+                    t.traverse(buf.mm, buf.seeds[k:k + 1], buf.vtp_in, *pb_c, disc)
+                if infer is not None:
+                    infer[k] = (t.x >= 0).sum()
+                out = self._step(t, net, c, k, native)
+                logits = out.policy_logits.float().contiguous()
+                if rec is not None:
+                    rec.step(k, t, logits)
+                reward = getattr(out, self.reward_name).float().contiguous()
+                value = out.value.float().contiguous()
+                kw = dict(next_latent=None if native else out.latent_state.float().contiguous(),
+                          pool_slot=None if native else buf.pool[k + 1], row_elems=0 if native else c.row,
+                          out_decoded=None if rec is None else rec.decoded[k])
+                if t.ez:
+                    kw.update(lstm_horizon=int(cfg.lstm_horizon_len), out_is_reset=t.is_reset)
+                if fuse and k + 1 < S:  # this simulation's backup and the next one's traverse in one launch
+                    t.decode_backprop_traverse(k + 1, disc, buf.mm, reward, value, cat, logits, t.vtp,
+                                               buf.seeds[k + 1:k + 2], buf.vtp_in, *pb_c, **kw)
+                else:
+                    t.decode_backprop(k + 1, disc, buf.mm, reward, value, cat, logits, t.vtp, **kw)
+                self._after_step(t, out, c, k, native, rec)
+
+    def _after_step(self, t, out, c, k, native, rec):
+        pass  # (EfficientZero: the is_reset record and the reset mask on the LSTM state)
+
+    def _capture(self, c, model):
+        """Captures the whole S-simulation loop as one HIP graph over c.buf (the static buffers filled just
+        before) and the network _step_net picks now; the entry keeps both alive."""
+        t = c.t
+        net = _step_net(self, model)
+        # warm up every kernel and library handle on a scratch tree (must not touch `t`)
+        scratch = DeviceTree(t.B, t.A, max(c.S, t.sims_capacity), ez=t.ez, fast_rng=t.fast_rng, device=t.device)
+        scratch.copy_roots_from(t)
+        scratch.set_pb_c(*self._pb_c())
+        self._loop(scratch, model, c, net=net)
+        torch.cuda.synchronize(t.device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._loop(t, model, c, net=net)
+        scratch.close()
+        return _GraphEntry(g, c.buf, net if net is not model else None, model, t)
+
+    def _native_conv_net(self, model, t, shape):
+        """What both _fused_conv start from: the native split-precision step network of this class's family,
+        with packed heads, when cfg.fused_search (default on) and LZM_FUSED_CONV allow a one-launch search of
+        a 64 x 8 x 8 latent on tree t; None otherwise. Clears last_plan (the plan of this search, when the
+        library is asked)."""
+        self.last_plan = None
+        ez = self._tree.Roots.EZ
+        if not self._cfg.get('fused_search', True) or t.ez != ez or os.environ.get("LZM_FUSED_CONV", "1") == "0":
+            return None
+        net = _step_net(self, model)
+        hp = getattr(net, "heads", None)
+        if tuple(shape) != (64, 8, 8) or getattr(net, "native", None) is None or hp is None \
+                or getattr(net, "precision", None) != "split" or bool(getattr(net, "ez", not ez)) != ez \
+                or hp["A"] != t.A:
+            return None
+        return net
+
+
+class MuZeroMCTSCtree(_MCTSCtree):
+    """MCTS for MuZero on the GPU (reference: mcts_ctree.py:172-321)."""
+
+    _tree = mz_tree
+    reward_name = 'reward'
+
+    def __init__(self, cfg: EasyDict = None) -> None:
+        super().__init__(cfg)
+        self._packed = PackedCache()
 
     @classmethod
     def roots_from_mask(cls, action_mask: torch.Tensor) -> "mz_tree.Roots":
         """roots() with the legal lists taken from a device action mask (no host round trip)"""
         return mz_tree.Roots.from_action_mask(action_mask, fast_rng=(cls.rng_mode == 'philox'))
-
-    def _categorical(self):
-        return bool(self._cfg.model.get('categorical_distribution', True))
 
     def _fused(self, model, t, S=None):
         """(packed weights, dims) when the whole search can run as one lzm_search_mlp launch:
@@ -275,58 +506,18 @@ class MuZeroMCTSCtree(object):
         library (DeviceTree.search_conv_plan: head K multiples of 128, supports <= 1024, up to 1024 roots, the
         tree in the workgroup's LDS); None otherwise (the generic per-simulation path). cfg.fused_search
         (default on) and LZM_FUSED_CONV=0 turn it off."""
-        self.last_plan = None  # (the plan of this search, when the library is asked)
-        if not self._cfg.get('fused_search', True) or t.ez or os.environ.get("LZM_FUSED_CONV", "1") == "0":
+        net = self._native_conv_net(model, t, shape)
+        if net is None:
             return None
-        net = _step_net(self, model)
-        hp = getattr(net, "heads", None)
-        if tuple(shape) != (64, 8, 8) or getattr(net, "native", None) is None or hp is None \
-                or getattr(net, "precision", None) != "split" or getattr(net, "ez", True) or hp["A"] != t.A:
-            return None
-        plan = t.search_conv_plan(net, t.sims_capacity if S is None else S, categorical=self._categorical())
-        self.last_plan = plan
-        return net if plan["supported"] else None
+        self.last_plan = t.search_conv_plan(net, t.sims_capacity if S is None else S, categorical=self._categorical())
+        return net if self.last_plan["supported"] else None
 
-    def _loop(self, t, model, buf, mm, vtp_in, seeds, S, row, rec=None, infer=None, net=None):
-        """The S simulations (mcts_ctree.py:255-321), all enqueued on the current stream.
-        infer: optional device int64 [S], per simulation the number of roots that ran inference
-        (search-with-reuse: roots whose walk stopped on an expanded node report x = -1).
-        net: the step network to run (default: _step_net(model))."""
-        cfg = self._cfg
-        disc = float(np.float32(cfg.discount_factor))
-        cat = self._categorical()
-        new_minmax(t.B, cfg.value_delta_max, t.device, out=mm)
-        model = _step_net(self, model) if net is None else net
-        native = _native_trunk(model, buf)
-        with _HeadVerdicts(t, model, buf, native and cat and getattr(model, "heads", None) is not None):
-            self._sims(t, model, buf, mm, vtp_in, seeds, S, row, rec, infer, native, cat, disc)
-
-    def _sims(self, t, model, buf, mm, vtp_in, seeds, S, row, rec, infer, native, cat, disc):
-        cfg = self._cfg
-        fuse = _fuse_traverse(cfg, t)
-        for k in range(S):
-            if k == 0 or not fuse:
-                t.traverse(mm, seeds[k:k + 1], vtp_in, int(cfg.pb_c_base), float(cfg.pb_c_init), disc)
-            if infer is not None:
-                infer[k] = (t.x >= 0).sum()
-            if native:  # leaf latents read from the pool and the next latents filed by the trunk kernel
-                out = model.step_from_pool(buf.pool, t.x, t.action, buf.pool[k + 1], range_err=t.error_word(4))
-            else:
-                t.gather(buf.pool, row, buf.net_in)
-                out = model.recurrent_inference(buf.net_in, t.action64)
-            logits = out.policy_logits.float().contiguous()
-            if rec is not None:
-                rec.step(k, t, logits)
-            kw = dict(next_latent=None if native else out.latent_state.float().contiguous(),
-                      pool_slot=None if native else buf.pool[k + 1], row_elems=0 if native else row,
-                      out_decoded=None if rec is None else rec.decoded[k])
-            if fuse and k + 1 < S:  # this simulation's backup and the next one's traverse in one launch
-                t.decode_backprop_traverse(k + 1, disc, mm, out.reward.float().contiguous(),
-                                           out.value.float().contiguous(), cat, logits, t.vtp, seeds[k + 1:k + 2],
-                                           vtp_in, int(cfg.pb_c_base), float(cfg.pb_c_init), **kw)
-            else:
-                t.decode_backprop(k + 1, disc, mm, out.reward.float().contiguous(), out.value.float().contiguous(),
-                                  cat, logits, t.vtp, **kw)
+    def _step(self, t, net, c, k, native):
+        buf = c.buf
+        if native:  # leaf latents read from the pool and the next latents filed by the trunk kernel
+            return net.step_from_pool(buf.pool, t.x, t.action, buf.pool[k + 1], range_err=t.error_word(4))
+        t.gather(buf.pool, c.row, buf.net_in)
+        return net.recurrent_inference(buf.net_in, t.action64)
 
     def search(self, roots: Any, model: torch.nn.Module, latent_state_roots: List[Any],
                to_play_batch: Union[int, List[Any]], seeds: torch.Tensor = None, step: dict = None) -> None:
@@ -341,92 +532,32 @@ class MuZeroMCTSCtree(object):
         fresh min-max bounds. The one-launch search does all of it in its kernel
         (lzm_search_set_step); other paths run the same steps as separate launches."""
         with torch.no_grad():
-            model.eval()
-            t = roots.tree
-            if t is None:
-                raise RuntimeError("search: roots must be prepared (Roots.prepare / prepare_no_noise) first")
-            B, S = roots.num, int(self._cfg.num_simulations)
-            t.reserve(S)
-            t.set_pb_c(int(self._cfg.pb_c_base), float(self._cfg.pb_c_init))
-            dev = t.device
-            lat0 = _latent_tensor(latent_state_roots, dev)
-            shape = lat0.shape[1:]
-            row = int(np.prod(shape)) if len(shape) else 1
-            rec = _Recorder(S, B, t.A, dev) if getattr(self, "record", False) else None
+            c = self._begin("search", roots, model, latent_state_roots)
+            t, S = c.t, c.S
             fz = self._fused(model, t, S)
-            cz = self._fused_conv(model, t, shape, S) if fz is None else None
-            graph = fz is None and cz is None and rec is None and self._cfg.get('use_hip_graph', False)
-            gkey = _graph_key(t, model, B, S, shape) if graph else None
-            entry = self._graphs.get(gkey, model, t) if graph else None
-            # a captured search owns its buffers (they are what its kernels point at)
-            buf = entry.buf if entry is not None else (_SearchBuffers() if graph else self._buf).get(B, S, shape, dev)
-            if lat0.data_ptr() != buf.pool[0].data_ptr():  # (the collect step writes it in place)
-                buf.pool[0].copy_(lat0.reshape((B,) + tuple(shape)))
-            # the one-launch searches read device seeds / to_play in place (no staging copies)
-            in_place = (fz is not None or cz is not None) and rec is None
-            # the one-launch searches run the collect step's glue in their kernels (lzm_search_set_step:
-            # seeds from the step counter, fresh min-max bounds, root outputs, the counter increment)
-            step_in_kernel = step is not None and in_place
-            vt = to_play_batch if in_place and _usable_i32(to_play_batch, B, dev) else None
-            if vt is None:
-                buf.vtp_in.copy_(_to_play_tensor(to_play_batch, B, dev))
-                vt = buf.vtp_in
-            sd = None
-            if step is not None and not step_in_kernel:
-                _lib.call("lzm_seed_sequence", _lib.ptr(step["count"]), int(step["base"]), S, _lib.ptr(buf.seeds),
-                          _lib.stream_ptr())
-                sd = buf.seeds
-            elif step is None:
-                sd = seeds if in_place and _usable_i32(seeds, S, dev) else None
-                if sd is None:
-                    buf.seeds.copy_(_seeds(S, dev) if seeds is None else seeds.reshape(S))
-                    sd = buf.seeds
-            if rec is not None:
-                rec.seeds = buf.seeds.cpu().numpy().view(np.uint32)
-            if cz is not None:
-                # the conv network's whole search in one launch (lzm_search_conv)
-                cfg = self._cfg
-                if step_in_kernel:
-                    t.set_step(step["count"], int(step["base"]), step.get("increment", True), step["dist"],
-                               step["values"], True, cfg.value_delta_max)
-                else:
-                    new_minmax(B, cfg.value_delta_max, dev, out=buf.mm)
-                try:
-                    t.search_conv(cz, S, buf.mm, sd, vt, buf.pool, int(cfg.pb_c_base), float(cfg.pb_c_init),
-                                  float(np.float32(cfg.discount_factor)), self._categorical(), rec=rec)
-                finally:
-                    if step_in_kernel:
-                        t.set_step()
-            elif fz is not None:
-                packed, dims = fz
-                cfg = self._cfg
-                if step_in_kernel:
-                    t.set_step(step["count"], int(step["base"]), step.get("increment", True), step["dist"],
-                               step["values"], True, cfg.value_delta_max)
-                else:
-                    new_minmax(B, cfg.value_delta_max, dev, out=buf.mm)
-                try:
-                    t.search_mlp(dims, packed, S, buf.mm, sd, vt, buf.pool, int(cfg.pb_c_base),
-                                 float(cfg.pb_c_init), float(np.float32(cfg.discount_factor)), rec=rec)
-                finally:
-                    if step_in_kernel:
-                        t.set_step()
-            elif graph:
-                if entry is None:
-                    entry = self._capture(t, model, buf, S, row)
-                    self._graphs.put(gkey, entry)
-                entry.replay()
+            cz = self._fused_conv(model, t, c.shape, S) if fz is None else None
+            one_launch = fz is not None or cz is not None
+            self._buffers(c, model, graph=not one_launch and not self.record and self._cfg.get('use_hip_graph', False))
+            # the one-launch searches read the caller's device seeds / to_play in place (no staging copies:
+            # EfficientZero's always stages them) and run the collect step's glue in their kernels
+            in_place = one_launch and not self.record
+            c.in_kernel = step is not None and in_place
+            vt, sd = self._stage(c, to_play_batch, seeds, step, in_place)
+            rec = self._recorder(c)
+            buf = c.buf
+            if not one_launch:
+                self._generic(c, model, rec)
             else:
-                self._loop(t, model, buf, buf.mm, buf.vtp_in, buf.seeds, S, row, rec)
-            if step is not None and not step_in_kernel:
-                _lib.call("lzm_get_root_outputs", t.h, _lib.ptr(step["dist"]), _lib.ptr(step["values"]),
-                          _lib.stream_ptr())
-                if step.get("increment", True):
-                    step["count"].add_(1)
-            t.searched()
+                with self._glue(c, step):
+                    if cz is not None:  # the conv network's whole search in one launch (lzm_search_conv)
+                        t.search_conv(cz, S, buf.mm, sd, vt, buf.pool, *self._pb_c(), self._discount(),
+                                      self._categorical(), rec=rec)
+                    else:
+                        packed, dims = fz
+                        t.search_mlp(dims, packed, S, buf.mm, sd, vt, buf.pool, *self._pb_c(), self._discount(),
+                                     rec=rec)
+            self._finish(c, roots, step, rec)
             self.last_path = "fused-conv" if cz is not None else ("fused-mlp" if fz is not None else "generic")
-            roots._last_minmax = buf.mm
-            self.last_record = rec
 
     def search_with_reuse(self, roots: Any, model: torch.nn.Module, latent_state_roots: List[Any],
                           to_play_batch: Union[int, List[Any]], true_action_list=None, reuse_value_list=None,
@@ -439,95 +570,22 @@ class MuZeroMCTSCtree(object):
         (lzm_set_reuse); the network is evaluated for every root (rows of skipped roots unused).
         Returns (length, average_infer) as the reference: roots that ran inference in the last
         simulation, and inferences per simulation."""
-        if true_action_list is None or reuse_value_list is None:
-            raise TypeError("search_with_reuse needs true_action_list and reuse_value_list")
-        with torch.no_grad():
-            model.eval()
-            t = roots.tree
-            if t is None:
-                raise RuntimeError("search_with_reuse: roots must be prepared (Roots.prepare / prepare_no_noise) first")
-            if t.fast_rng:
-                raise ValueError("search_with_reuse: parity (glibc) mode only")
-            B, S = roots.num, int(self._cfg.num_simulations)
-            t.reserve(S)
-            t.set_pb_c(int(self._cfg.pb_c_base), float(self._cfg.pb_c_init))
-            dev = t.device
-            lat0 = _latent_tensor(latent_state_roots, dev)
-            shape = lat0.shape[1:]
-            row = int(np.prod(shape)) if len(shape) else 1
-            buf = self._buf.get(B, S, shape, dev)
-            buf.pool[0].copy_(lat0.reshape((B,) + tuple(shape)))
-            buf.vtp_in.copy_(_to_play_tensor(to_play_batch, B, dev))
-            buf.seeds.copy_(_seeds(S, dev) if seeds is None else seeds.reshape(S))
-            ta = torch.as_tensor(np.asarray(true_action_list, np.int32).reshape(B) if not torch.is_tensor(
-                true_action_list) else true_action_list, device=dev)
-            rv = torch.as_tensor(np.asarray(reuse_value_list, np.float32).reshape(B) if not torch.is_tensor(
-                reuse_value_list) else reuse_value_list, device=dev)
-            rec = _Recorder(S, B, t.A, dev) if getattr(self, "record", False) else None
-            if rec is not None:
-                rec.seeds = buf.seeds.cpu().numpy().view(np.uint32)
-            infer = torch.zeros(S, dtype=torch.int64, device=dev)
-            t.set_reuse(ta, rv)
-            try:
-                self._loop(t, model, buf, buf.mm, buf.vtp_in, buf.seeds, S, row, rec, infer=infer)
-            finally:
-                t.set_reuse(None)
-            roots._last_minmax = buf.mm
-            self.last_record = rec
-            counts = infer.cpu().numpy()
-        return int(counts[-1]) if S else 0, float(counts.sum()) / max(S, 1)
-
-    def _capture(self, t, model, buf, S, row):
-        """Captures the whole S-simulation loop as one HIP graph over `buf` (the static buffers
-        filled just before) and the network _step_net picks now; the entry keeps both alive."""
-        net = _step_net(self, model)
-        # warm up every kernel and library handle on a scratch tree (must not touch `t`)
-        scratch = DeviceTree(t.B, t.A, max(S, t.sims_capacity), ez=t.ez, fast_rng=t.fast_rng, device=t.device)
-        scratch.copy_roots_from(t)
-        scratch.set_pb_c(int(self._cfg.pb_c_base), float(self._cfg.pb_c_init))
-        self._loop(scratch, model, buf, buf.mm, buf.vtp_in, buf.seeds, S, row, net=net)
-        torch.cuda.synchronize(t.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._loop(t, model, buf, buf.mm, buf.vtp_in, buf.seeds, S, row, net=net)
-        scratch.close()
-        return _GraphEntry(g, buf, net if net is not model else None, model, t)
+        return self._search_with_reuse(roots, model, latent_state_roots, (), to_play_batch, true_action_list,
+                                       reuse_value_list, seeds)
 
 
-class EfficientZeroMCTSCtree(object):
+class EfficientZeroMCTSCtree(_MCTSCtree):
     """MCTS for EfficientZero on the GPU (reference: mcts_ctree.py:623-827)."""
 
-    config = dict(
-        root_dirichlet_alpha=0.3,
-        root_noise_weight=0.25,
-        pb_c_base=19652,
-        pb_c_init=1.25,
-        value_delta_max=0.01,
-        env_type='not_board_games',
-    )
+    _tree = ez_tree
+    reward_name = 'value_prefix'
+    fuse_under_reuse = False
 
-    @classmethod
-    def default_config(cls: type) -> EasyDict:
-        cfg = EasyDict(copy.deepcopy(cls.config))
-        cfg.cfg_type = cls.__name__ + 'Dict'
-        return cfg
-
-    def __init__(self, cfg: EasyDict = None) -> None:
-        default_config = self.default_config()
-        default_config.update(cfg)
-        self._cfg = default_config
-        self.inverse_scalar_transform_handle = InverseScalarTransform(
-            self._cfg.model.support_scale, self._cfg.device, self._cfg.model.categorical_distribution
-        )
-        self._buf = _SearchBuffers()
-        self._graphs = _GraphCache(int(self._cfg.get('graph_cache_size', 4)))
-        self._folded = FoldedCache()
-
-    rng_mode = 'glibc'
-
-    @classmethod
-    def roots(cls: int, active_collect_env_num: int, legal_actions: List[Any]) -> "ez_tree.Roots":
-        return ez_tree.Roots(active_collect_env_num, legal_actions, fast_rng=(cls.rng_mode == 'philox'))
+    def _horizon(self):
+        horizon = int(self._cfg.lstm_horizon_len)
+        if horizon <= 0:
+            raise ValueError("lstm_horizon_len must be > 0 (mcts_ctree.py:809, 899)")
+        return horizon
 
     def _fused_conv(self, model, t, shape, Hl, S=None):
         """The native split-precision FoldedConvNet (with the fused LSTM step packed) when the whole search of
@@ -540,209 +598,106 @@ class EfficientZeroMCTSCtree(object):
         search() launches, is refused with ResidencyError before anything runs, and counts the fallback; a
         captured one takes the generic path without launching.
         cfg.fused_search (default on) and LZM_FUSED_CONV=0 turn it off."""
-        self.last_plan = None  # (the plan of this search, when the library is asked)
-        if not self._cfg.get('fused_search', True) or not t.ez or os.environ.get("LZM_FUSED_CONV", "1") == "0":
-            return None
-        net = _step_net(self, model)
-        hp = getattr(net, "heads", None)
-        if tuple(shape) != (64, 8, 8) or getattr(net, "native", None) is None or hp is None \
-                or getattr(net, "precision", None) != "split" or not getattr(net, "ez", False) \
-                or getattr(net, "lstm_frag", None) is None or hp["A"] != t.A or hp["Kr"] != Hl:
+        net = self._native_conv_net(model, t, shape)
+        if net is None or getattr(net, "lstm_frag", None) is None or net.heads["Kr"] != Hl:
             return None
         plan = t.search_conv_plan(net, t.sims_capacity if S is None else S, H=Hl,
-                                  horizon=int(self._cfg.lstm_horizon_len),
-                                  categorical=bool(self._cfg.model.get('categorical_distribution', True)))
+                                  horizon=int(self._cfg.lstm_horizon_len), categorical=self._categorical())
         self.last_plan = plan
         return net if plan["supported"] or plan["code"] == _lib.LZM_ERR_RESIDENCY else None
 
-    def _loop(self, t, model, buf, S, row, Hl, rec=None, net=None, infer=None):
-        """The S simulations (mcts_ctree.py:756-827), all enqueued on the current stream. infer: optional
-        device int64 [S], per simulation the number of roots that ran inference (search-with-reuse)."""
-        cfg = self._cfg
-        disc = float(np.float32(cfg.discount_factor))
-        horizon = int(cfg.lstm_horizon_len)
-        cat = bool(cfg.model.get('categorical_distribution', True))
-        B = t.B
-        new_minmax(B, cfg.value_delta_max, t.device, out=buf.mm)
-        model = _step_net(self, model) if net is None else net
-        native = _native_trunk(model, buf)
-        with _HeadVerdicts(t, model, buf, native and cat and getattr(model, "heads", None) is not None):
-            self._sims(t, model, buf, S, row, Hl, rec, native, cat, disc, horizon, infer)
+    def _step(self, t, net, c, k, native):
+        buf = c.buf
+        if native:
+            # the LSTM state is gathered from / filed (reset-masked) into the state pools on the device
+            return net.step_from_pool_lstm(buf.pool, t.x, t.action, buf.pool[k + 1], buf.extra[0], buf.extra[1], k,
+                                           t.search_len, int(self._cfg.lstm_horizon_len), err=t.error_word(3),
+                                           range_err=t.error_word(4))
+        t.gather(buf.extra[0], c.extra[0], buf.extra_in[0])
+        t.gather(buf.extra[1], c.extra[1], buf.extra_in[1])
+        hidden = (buf.extra_in[0].unsqueeze(0), buf.extra_in[1].unsqueeze(0))
+        t.gather(buf.pool, c.row, buf.net_in)
+        return net.recurrent_inference(buf.net_in, hidden, t.action64)
 
-    def _sims(self, t, model, buf, S, row, Hl, rec, native, cat, disc, horizon, infer=None):
-        cfg = self._cfg
-        B = t.B
-        fuse = _fuse_traverse(cfg, t) and infer is None
-        for k in range(S):
-            if k == 0 or not fuse:
-                t.traverse(buf.mm, buf.seeds[k:k + 1], buf.vtp_in, int(cfg.pb_c_base), float(cfg.pb_c_init), disc)
-            if infer is not None:
-                infer[k] = (t.x >= 0).sum()
-            if native:
-                # the LSTM state is gathered from / filed (reset-masked) into the state pools on the device
-                out = model.step_from_pool_lstm(buf.pool, t.x, t.action, buf.pool[k + 1], buf.extra[0], buf.extra[1],
-                                                k, t.search_len, horizon, err=t.error_word(3),
-                                                range_err=t.error_word(4))
-            else:
-                t.gather(buf.extra[0], Hl, buf.extra_in[0])
-                t.gather(buf.extra[1], Hl, buf.extra_in[1])
-                hidden = (buf.extra_in[0].unsqueeze(0), buf.extra_in[1].unsqueeze(0))
-                t.gather(buf.pool, row, buf.net_in)
-                out = model.recurrent_inference(buf.net_in, hidden, t.action64)
-            logits = out.policy_logits.float().contiguous()
-            if rec is not None:
-                rec.step(k, t, logits)
-            kw = dict(lstm_horizon=horizon, out_is_reset=t.is_reset,
-                      next_latent=None if native else out.latent_state.float().contiguous(),
-                      pool_slot=None if native else buf.pool[k + 1], row_elems=0 if native else row,
-                      out_decoded=None if rec is None else rec.decoded[k])
-            if fuse and k + 1 < S:  # this simulation's backup and the next one's traverse in one launch
-                t.decode_backprop_traverse(k + 1, disc, buf.mm, out.value_prefix.float().contiguous(),
-                                           out.value.float().contiguous(), cat, logits, t.vtp, buf.seeds[k + 1:k + 2],
-                                           buf.vtp_in, int(cfg.pb_c_base), float(cfg.pb_c_init), **kw)
-            else:
-                t.decode_backprop(k + 1, disc, buf.mm, out.value_prefix.float().contiguous(),
-                                  out.value.float().contiguous(), cat, logits, t.vtp, **kw)
-            if rec is not None:
-                rec.is_reset[k].copy_(t.is_reset)
-            if native:
-                continue  # lzm_ez_lstm_cell already filed the masked state
-            # reset the LSTM state of roots whose search_len % horizon == 0 (mcts_ctree.py:810-816)
-            keep = (1 - t.is_reset).to(torch.float32).unsqueeze(1)
-            hc, hh = out.reward_hidden_state
-            torch.mul(hc.reshape(B, Hl).float(), keep, out=buf.extra[0][k + 1])
-            torch.mul(hh.reshape(B, Hl).float(), keep, out=buf.extra[1][k + 1])
+    def _after_step(self, t, out, c, k, native, rec):
+        if rec is not None:
+            rec.is_reset[k].copy_(t.is_reset)
+        if native:
+            return  # lzm_ez_lstm_cell already filed the masked state
+        # reset the LSTM state of roots whose search_len % horizon == 0 (mcts_ctree.py:810-816)
+        keep = (1 - t.is_reset).to(torch.float32).unsqueeze(1)
+        for pool, s in zip(c.buf.extra, out.reward_hidden_state):
+            torch.mul(s.reshape(t.B, -1).float(), keep, out=pool[k + 1])
 
     def search(self, roots: Any, model: torch.nn.Module, latent_state_roots: List[Any],
                reward_hidden_state_roots: List[Any], to_play_batch: Union[int, List[Any]],
                seeds: torch.Tensor = None, step: dict = None) -> None:
         """seeds: optional device int32 [num_simulations] traverse seeds; step: the collect step's glue
         (lightzero_amd.collect: device seeds from a step counter, root outputs into device tensors, the
-        counter advanced) — both as in MuZeroMCTSCtree.search, here as small launches around the search."""
+        counter advanced) — both as in MuZeroMCTSCtree.search."""
         with torch.no_grad():
-            model.eval()
-            t = roots.tree
-            if t is None:
-                raise RuntimeError("search: roots must be prepared (Roots.prepare / prepare_no_noise) first")
-            B, S = roots.num, int(self._cfg.num_simulations)
-            t.reserve(S)
-            t.set_pb_c(int(self._cfg.pb_c_base), float(self._cfg.pb_c_init))
-            dev = t.device
-            if int(self._cfg.lstm_horizon_len) <= 0:
-                raise ValueError("lstm_horizon_len must be > 0 (mcts_ctree.py:809)")
-            lat0 = _latent_tensor(latent_state_roots, dev)
-            shape = lat0.shape[1:]
-            row = int(np.prod(shape)) if len(shape) else 1
-            hc0 = _latent_tensor(reward_hidden_state_roots[0], dev).reshape(B, -1)
-            hh0 = _latent_tensor(reward_hidden_state_roots[1], dev).reshape(B, -1)
-            Hl = hc0.shape[1]
-            rec = None
-            cz = self._fused_conv(model, t, shape, Hl, S)
+            self._horizon()
+            c = self._begin("search", roots, model, latent_state_roots, reward_hidden_state_roots[:2])
+            cz = self._fused_conv(model, c.t, c.shape, c.extra[0], c.S)
             # A grid the plan refuses for co-residency is not launched where a fallback after the refusal is
             # not possible: when this search captures the generic path itself (use_hip_graph), and inside a
             # caller's stream capture (collect.py's graph), which then captures the generic path instead of
             # raising. (The plan is a host query; eagerly the launch is tried, refused and counted.)
             refused = cz is not None and not self.last_plan["supported"]
-            graph = self._cfg.get('use_hip_graph', False) and not getattr(self, "record", False) \
-                and (cz is None or refused)
+            graph = self._cfg.get('use_hip_graph', False) and not self.record and (cz is None or refused)
             if graph or (refused and torch.cuda.is_current_stream_capturing()):
                 cz = None
-            gkey = _graph_key(t, model, B, S, shape, (Hl, Hl)) if graph else None
-            entry = self._graphs.get(gkey, model, t) if graph else None
-            buf = entry.buf if entry is not None else (_SearchBuffers() if graph else self._buf).get(
-                B, S, shape, dev, extra=(Hl, Hl))
-            if lat0.data_ptr() != buf.pool[0].data_ptr():  # (the collect step writes it in place)
-                buf.pool[0].copy_(lat0.reshape((B,) + tuple(shape)))
-            buf.extra[0][0].copy_(hc0)
-            buf.extra[1][0].copy_(hh0)
-            buf.vtp_in.copy_(_to_play_tensor(to_play_batch, B, dev))
-            recording = getattr(self, "record", False)
-            # the one-launch search runs the collect step's glue in its kernel (lzm_search_set_step: seeds
-            # from the step counter, fresh min-max bounds, root outputs, the counter increment)
-            step_in_kernel = step is not None and cz is not None and not recording
-
-            def step_seeds():  # seeds (base + count * S + k) mod 10^6 on the device
-                _lib.call("lzm_seed_sequence", _lib.ptr(step["count"]), int(step["base"]), S, _lib.ptr(buf.seeds),
-                          _lib.stream_ptr())
-
-            if step is None:
-                buf.seeds.copy_(_seeds(S, dev) if seeds is None else seeds.reshape(S))
-            elif not step_in_kernel:
-                step_seeds()
-            if recording:
-                rec = _Recorder(S, B, t.A, dev)
-                rec.is_reset = torch.zeros((S, B), dtype=torch.int32, device=dev)
-                rec.seeds = buf.seeds.cpu().numpy().view(np.uint32)
-            if cz is not None:
-                # the conv network's whole search, reward LSTM included, in one launch (lzm_search_conv_ez);
-                # the launch needs its whole grid co-resident: when the occupancy bound refuses it, nothing
-                # ran and the generic per-simulation path runs instead — eagerly only: inside a stream
-                # capture a plan-refused grid never gets here (cz was dropped above), and a refusal the plan
-                # did not foresee is raised (no fallback inside a capture)
-                cfg = self._cfg
-                if step_in_kernel:
-                    t.set_step(step["count"], int(step["base"]), step.get("increment", True), step["dist"],
-                               step["values"], True, cfg.value_delta_max)
-                else:
-                    new_minmax(B, cfg.value_delta_max, dev, out=buf.mm)
-                # eager launches are checked for hand-off timeouts (ADVICE r05: another stream's kernel can hold
-                # CUs the static occupancy bound counted on): the tree (and the step counter) are kept, and a
-                # search whose waits timed out is discarded and re-run on the generic path
-                guard = bool(cfg.get('guard_handoffs', True)) and not torch.cuda.is_current_stream_capturing()
-                if guard:
-                    snap = self._snapshot(t)
-                    count0 = step["count"].clone() if step_in_kernel else None
-                try:
-                    t.search_conv_ez(cz, S, buf.mm, None if step_in_kernel else buf.seeds, buf.vtp_in, buf.pool,
-                                     buf.extra[0], buf.extra[1], int(cfg.lstm_horizon_len), int(cfg.pb_c_base),
-                                     float(cfg.pb_c_init), float(np.float32(cfg.discount_factor)),
-                                     bool(cfg.model.get('categorical_distribution', True)), rec=rec)
-                    self.last_path = "fused"
-                    if guard and t.peek_errors()[0]:
-                        t.copy_roots_from(snap)
-                        t.reset_errors()
-                        if step_in_kernel:
-                            step["count"].copy_(count0)
-                            t.set_step()
-                            step_in_kernel = False
-                            step_seeds()
-                        if rec is not None:
-                            rec = _Recorder(S, B, t.A, dev)
-                            rec.is_reset = torch.zeros((S, B), dtype=torch.int32, device=dev)
-                            rec.seeds = buf.seeds.cpu().numpy().view(np.uint32)
-                        self.timeout_fallbacks = getattr(self, "timeout_fallbacks", 0) + 1
-                        self.last_path = "generic (hand-off timeout)"
-                        self._loop(t, model, buf, S, row, Hl, rec)
-                except _lib.ResidencyError:
-                    if torch.cuda.is_current_stream_capturing():
-                        raise
-                    if step_in_kernel:  # nothing ran: the glue as launches around the generic path
-                        t.set_step()
-                        step_in_kernel = False
-                        step_seeds()
-                    self.residency_fallbacks = getattr(self, "residency_fallbacks", 0) + 1
-                    self.last_path = "generic (co-residency refused)"
-                    self._loop(t, model, buf, S, row, Hl, rec)
-                finally:
-                    if step_in_kernel:
-                        t.set_step()
-            elif graph:
+            self._buffers(c, model, graph)
+            c.in_kernel = step is not None and cz is not None and not self.record
+            self._stage(c, to_play_batch, seeds, step)  # (always into the buffers, unlike MuZero's)
+            rec = self._recorder(c)
+            if cz is None:
                 self.last_path = "generic"
-                if entry is None:
-                    entry = self._capture(t, model, buf, S, row, Hl)
-                    self._graphs.put(gkey, entry)
-                entry.replay()
+                self._generic(c, model, rec)
             else:
-                self.last_path = "generic"
-                self._loop(t, model, buf, S, row, Hl, rec)
-            if step is not None and not step_in_kernel:
-                _lib.call("lzm_get_root_outputs", t.h, _lib.ptr(step["dist"]), _lib.ptr(step["values"]),
-                          _lib.stream_ptr())
-                if step.get("increment", True):
-                    step["count"].add_(1)
-            t.searched()
-            roots._last_minmax = buf.mm
-            self.last_record = rec
+                rec = self._search_conv_ez(c, model, cz, step, rec)
+            self._finish(c, roots, step, rec)
+
+    def _search_conv_ez(self, c, model, cz, step, rec):
+        """The conv network's whole search, reward LSTM included, in one launch (lzm_search_conv_ez). The launch
+        needs its whole grid co-resident: when the occupancy bound refuses it, nothing ran and the generic
+        per-simulation path runs instead — eagerly only: inside a stream capture a plan-refused grid never gets
+        here (search() dropped cz), and a refusal the plan did not foresee is raised (no fallback inside a
+        capture). Eager launches are also checked for hand-off timeouts (another stream's kernel can
+        hold CUs the static occupancy bound counted on): the tree (and the step counter) are kept, and a search
+        whose waits timed out is discarded and re-run on the generic path. Returns the record that counts."""
+        cfg, t, buf = self._cfg, c.t, c.buf
+        capturing = torch.cuda.is_current_stream_capturing()
+        guard = bool(cfg.get('guard_handoffs', True)) and not capturing
+        with self._glue(c, step):
+            if guard:
+                snap = self._snapshot(t)
+                count0 = step["count"].clone() if c.in_kernel else None
+            try:
+                t.search_conv_ez(cz, c.S, buf.mm, None if c.in_kernel else buf.seeds, buf.vtp_in, buf.pool,
+                                 buf.extra[0], buf.extra[1], int(cfg.lstm_horizon_len), *self._pb_c(),
+                                 self._discount(), self._categorical(), rec=rec)
+                self.last_path = "fused"
+                if not (guard and t.peek_errors()[0]):
+                    return rec
+                t.copy_roots_from(snap)
+                t.reset_errors()
+                if c.in_kernel:
+                    step["count"].copy_(count0)
+                self.timeout_fallbacks += 1
+                self.last_path = "generic (hand-off timeout)"
+            except _lib.ResidencyError:
+                if capturing:
+                    raise
+                self.residency_fallbacks += 1
+                self.last_path = "generic (co-residency refused)"
+            if c.in_kernel:  # the glue as launches around the generic path
+                t.set_step()
+                c.in_kernel = False
+                self._step_seeds(c, step)
+            rec = self._recorder(c)
+            self._loop(t, model, c, rec)
+        return rec
 
     def _snapshot(self, t):
         """a copy of tree t (lzm_copy_tree) in a handle kept for the purpose"""
@@ -767,63 +722,6 @@ class EfficientZeroMCTSCtree(object):
         reuse value, a walk stopping on it ends there (no inference when it is expanded, its reuse
         value backed up), the device loop runs every env's network row (skipped rows unused). Returns
         (length, average_infer) as the reference."""
-        if true_action_list is None or reuse_value_list is None:
-            raise TypeError("search_with_reuse needs true_action_list and reuse_value_list")
-        with torch.no_grad():
-            model.eval()
-            t = roots.tree
-            if t is None:
-                raise RuntimeError("search_with_reuse: roots must be prepared (Roots.prepare / prepare_no_noise) first")
-            if t.fast_rng:
-                raise ValueError("search_with_reuse: parity (glibc) mode only")
-            if int(self._cfg.lstm_horizon_len) <= 0:
-                raise ValueError("lstm_horizon_len must be > 0 (mcts_ctree.py:899)")
-            B, S = roots.num, int(self._cfg.num_simulations)
-            t.reserve(S)
-            t.set_pb_c(int(self._cfg.pb_c_base), float(self._cfg.pb_c_init))
-            dev = t.device
-            lat0 = _latent_tensor(latent_state_roots, dev)
-            shape = lat0.shape[1:]
-            row = int(np.prod(shape)) if len(shape) else 1
-            hc0 = _latent_tensor(reward_hidden_state_roots[0], dev).reshape(B, -1)
-            hh0 = _latent_tensor(reward_hidden_state_roots[1], dev).reshape(B, -1)
-            Hl = hc0.shape[1]
-            buf = self._buf.get(B, S, shape, dev, extra=(Hl, Hl))
-            buf.pool[0].copy_(lat0.reshape((B,) + tuple(shape)))
-            buf.extra[0][0].copy_(hc0)
-            buf.extra[1][0].copy_(hh0)
-            buf.vtp_in.copy_(_to_play_tensor(to_play_batch, B, dev))
-            buf.seeds.copy_(_seeds(S, dev) if seeds is None else seeds.reshape(S))
-            ta = torch.as_tensor(np.asarray(true_action_list, np.int32).reshape(B) if not torch.is_tensor(
-                true_action_list) else true_action_list, device=dev)
-            rv = torch.as_tensor(np.asarray(reuse_value_list, np.float32).reshape(B) if not torch.is_tensor(
-                reuse_value_list) else reuse_value_list, device=dev)
-            rec = None
-            if getattr(self, "record", False):
-                rec = _Recorder(S, B, t.A, dev)
-                rec.is_reset = torch.zeros((S, B), dtype=torch.int32, device=dev)
-                rec.seeds = buf.seeds.cpu().numpy().view(np.uint32)
-            infer = torch.zeros(S, dtype=torch.int64, device=dev)
-            t.set_reuse(ta, rv)
-            try:
-                self._loop(t, model, buf, S, row, Hl, rec, infer=infer)
-            finally:
-                t.set_reuse(None)
-            roots._last_minmax = buf.mm
-            self.last_record = rec
-            counts = infer.cpu().numpy()
-        return int(counts[-1]) if S else 0, float(counts.sum()) / max(S, 1)
-
-    def _capture(self, t, model, buf, S, row, Hl):
-        """The S-simulation loop captured as one HIP graph (see MuZeroMCTSCtree._capture)."""
-        net = _step_net(self, model)
-        scratch = DeviceTree(t.B, t.A, max(S, t.sims_capacity), ez=t.ez, fast_rng=t.fast_rng, device=t.device)
-        scratch.copy_roots_from(t)
-        scratch.set_pb_c(int(self._cfg.pb_c_base), float(self._cfg.pb_c_init))
-        self._loop(scratch, model, buf, S, row, Hl, net=net)
-        torch.cuda.synchronize(t.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._loop(t, model, buf, S, row, Hl, net=net)
-        scratch.close()
-        return _GraphEntry(g, buf, net if net is not model else None, model, t)
+        self._horizon()
+        return self._search_with_reuse(roots, model, latent_state_roots, reward_hidden_state_roots[:2], to_play_batch,
+                                       true_action_list, reuse_value_list, seeds)

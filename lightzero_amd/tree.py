@@ -54,6 +54,12 @@ class SequentialSeeds:
 _uids = itertools.count(1)
 
 
+def _rec_ptrs(rec, names=("x", "action", "search_len", "decoded", "policy_logits")):
+    """the one-launch searches' record outputs: device pointers of a _Recorder-like object's buffers, NULL
+    without one (or without that buffer)"""
+    return [None if rec is None else ptr(getattr(rec, n, None)) for n in names]
+
+
 class DeviceTree:
     def __init__(self, num_roots, action_space, max_sims=64, ez=False, fast_rng=False, device=None):
         _lib.require_gpu()
@@ -202,12 +208,10 @@ class DeviceTree:
     def search_mlp(self, dims, weights, S, minmax, seeds, vtp_in, pool, pb_c_base=19652, pb_c_init=1.25,
                    discount=0.997, rec=None, stream=None):
         """One launch for the whole search (lzm_search_mlp); rec: optional _Recorder-like object."""
-        r = (lambda n: None) if rec is None else (lambda n: ptr(getattr(rec, n)))
         self._unchecked = True
         call("lzm_search_mlp", self.h, dims["hidden"], dims["head_hidden"], dims["support"], int(dims["res"]),
              ptr(weights), int(S), int(pb_c_base), float(pb_c_init), float(discount), ptr(minmax), ptr(seeds),
-             ptr(vtp_in), ptr(pool), r("x"), r("action"), r("search_len"), r("decoded"), r("policy_logits"),
-             stream_ptr(stream))
+             ptr(vtp_in), ptr(pool), *_rec_ptrs(rec), stream_ptr(stream))
 
     def search_mlp_plan(self, dims, S):
         """What search_mlp(dims, ..., S) launches on this handle as it stands (lzm_search_mlp_plan; host
@@ -244,14 +248,13 @@ class DeviceTree:
                     categorical=True, rec=None, stream=None):
         """One launch for the whole search of a conv MuZeroModel (lzm_search_conv; net: a native
         split-precision conv_infer.FoldedConvNet); rec: optional _Recorder-like object."""
-        r = (lambda n: None) if rec is None else (lambda n: ptr(getattr(rec, n)))
         hp = net.heads
         self._unchecked = True
         call("lzm_search_conv", self.h, int(S), int(pb_c_base), float(pb_c_init), float(discount), ptr(minmax),
              ptr(seeds), ptr(vtp_in), ptr(pool), ptr(net.native), ptr(net.actmap), int(net.n_dres), int(net.n_pres),
              int(net.r_ch), int(net.h_ch), ptr(hp["w1t"]), ptr(hp["b1"]), ptr(hp["w2q"]), ptr(hp["b2"]), int(hp["Kr"]),
-             int(hp["Khd"]), int(hp["off_policy"]), int(hp["Vr"]), int(hp["Vv"]), int(bool(categorical)), r("x"),
-             r("action"), r("search_len"), r("decoded"), r("policy_logits"), stream_ptr(stream))
+             int(hp["Khd"]), int(hp["off_policy"]), int(hp["Vr"]), int(hp["Vv"]), int(bool(categorical)),
+             *_rec_ptrs(rec), stream_ptr(stream))
 
     def search_conv_ez(self, net, S, minmax, seeds, vtp_in, pool, hpool, cpool, horizon, pb_c_base=19652,
                        pb_c_init=1.25, discount=0.997, categorical=True, rec=None, stream=None):
@@ -259,7 +262,6 @@ class DeviceTree:
         split-precision conv_infer.FoldedConvNet with the fused LSTM step packed); hpool / cpool: the LSTM
         state pools [S + 1, B, H] with slot 0 = the roots' state; rec: optional _Recorder-like object
         (with is_reset)."""
-        r = (lambda n: None) if rec is None else (lambda n: ptr(getattr(rec, n, None)))
         hp, t = net.heads, net.t
         self._unchecked = True
         call("lzm_search_conv_ez", self.h, int(S), int(pb_c_base), float(pb_c_init), float(discount), ptr(minmax),
@@ -267,8 +269,7 @@ class DeviceTree:
              ptr(net.native), ptr(net.actmap), int(net.n_dres), int(net.n_pres), int(net.r_ch), int(net.h_ch),
              ptr(net.lstm_frag), ptr(t["lstm_b"]), ptr(t["vp_s"]), ptr(t["vp_t"]), ptr(hp["w1t"]), ptr(hp["b1"]),
              ptr(hp["w2q"]), ptr(hp["b2"]), int(hp["Khd"]), int(hp["off_policy"]), int(hp["Vr"]), int(hp["Vv"]),
-             int(bool(categorical)), r("x"), r("action"), r("search_len"), r("decoded"), r("policy_logits"),
-             r("is_reset"), stream_ptr(stream))
+             int(bool(categorical)), *_rec_ptrs(rec), *_rec_ptrs(rec, ("is_reset",)), stream_ptr(stream))
 
     def set_step(self, count=None, base=0, increment=True, dist=None, values=None, fresh_minmax=False,
                  value_delta_max=0.0):

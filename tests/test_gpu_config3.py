@@ -69,6 +69,83 @@ def test_ez_collect_step_equals_plain_search(B, S):
             roots.clear()
 
 
+# the collect step's glue as launches around the per-simulation path: asked for (cfg.fused_search off), after the
+# one-launch search was refused for co-residency eagerly (set_step cleared again, the fallback counted), and
+# where a captured step's plan says it would be (nothing launched, the per-simulation path captured)
+@pytest.mark.parametrize("mode", ["fused_search_off", "refused_eager", "refused_captured"])
+def test_ez_collect_step_glue_as_launches_equals_plain_search(mode, monkeypatch):
+    from lightzero_amd.collect import DeviceSearchStep
+    from lightzero_amd.mcts_ctree import EfficientZeroMCTSCtree
+    from lightzero_amd.utils import EasyDict
+    B, S, seed = 5, 6, 6
+    model = _ez_model(3)
+    obs, noises = _inputs(B, seed)
+    refused = mode != "fused_search_off"
+    if refused:
+        monkeypatch.setenv("LZM_RESIDENCY_CUS", "1")
+    step = DeviceSearchStep(model, B, S, [list(range(6))] * B, (4, 64, 64), DEV, seed=seed, support_scale=50,
+                            graph=mode == "refused_captured", cfg_extra={} if refused else dict(fused_search=False))
+    step.set_inputs(obs=obs, noises=noises)
+    outs = []
+    for n in range(2):
+        o = step.step()
+        outs.append((o["distributions"].clone(), o["values"].clone()))
+        assert step.mcts.last_path == ("generic (co-residency refused)" if mode == "refused_eager" else "generic")
+        assert int(step.step_counter.item()) == n + 1
+    # (a captured step is run twice eagerly before its capture, which itself counts nothing)
+    assert getattr(step.mcts, "residency_fallbacks", 0) == (2 if refused else 0)
+    monkeypatch.delenv("LZM_RESIDENCY_CUS", raising=False)
+    cfg = EasyDict(dict(num_simulations=S, discount_factor=0.997, device=DEV, lstm_horizon_len=5,
+                        model=dict(support_scale=50, categorical_distribution=True)))
+    mcts = EfficientZeroMCTSCtree(cfg)
+    base = (1000003 * seed) % 1000000
+    to_play = torch.full((B,), -1, dtype=torch.int32, device=DEV)
+    with torch.no_grad():
+        for n, (dist, vals) in enumerate(outs):
+            out = step.initial.initial_inference(obs)
+            roots = EfficientZeroMCTSCtree.roots(B, [list(range(6))] * B)
+            roots.prepare_device(0.25, noises, torch.zeros(B, device=DEV), out.policy_logits, to_play)
+            seeds = torch.tensor([(base + n * S + k) % 1000000 for k in range(S)], dtype=torch.int32, device=DEV)
+            mcts.search(roots, model, out.latent_state, out.reward_hidden_state, to_play, seeds=seeds)
+            assert mcts.last_path == "fused"
+            assert torch.equal(roots.tree.distributions(), dist), n
+            assert torch.equal(roots.tree.values(), vals), n
+            roots.clear()
+
+
+@pytest.mark.parametrize("refused", [False, True])
+def test_ez_use_hip_graph_captures_only_without_the_one_launch_search(refused, monkeypatch):
+    """cfg.use_hip_graph: the one-launch search runs as it is (nothing captured); where its plan is refused for
+    co-residency the per-simulation path is captured and replayed without a launch being tried — the same tree"""
+    from lightzero_amd.mcts_ctree import EfficientZeroMCTSCtree
+    from lightzero_amd.utils import EasyDict
+    B, S = 5, 6
+    model = _ez_model(3)
+    obs, noises = _inputs(B, 4)
+    to_play = torch.full((B,), -1, dtype=torch.int32, device=DEV)
+    seeds = torch.arange(50, 50 + S, dtype=torch.int32, device=DEV)
+    res = []
+    for graph in (False, True):
+        if graph and refused:
+            monkeypatch.setenv("LZM_RESIDENCY_CUS", "1")
+        mcts = EfficientZeroMCTSCtree(EasyDict(dict(num_simulations=S, discount_factor=0.997, device=DEV,
+                                                    lstm_horizon_len=5, use_hip_graph=graph,
+                                                    model=dict(support_scale=50, categorical_distribution=True))))
+        for _ in range(2 if graph else 1):  # (the capture's own replay, then the cached graph's)
+            with torch.no_grad():
+                out = model.initial_inference(obs)
+                roots = EfficientZeroMCTSCtree.roots(B, [list(range(6))] * B)
+                roots.prepare_device(0.25, noises, torch.zeros(B, device=DEV), out.policy_logits, to_play)
+                mcts.search(roots, model, out.latent_state, out.reward_hidden_state, to_play, seeds=seeds)
+            res.append((roots.tree.distributions().clone(), roots.tree.values().clone()))
+            roots.clear()
+        captured = graph and refused
+        assert mcts.last_path == ("generic" if captured else "fused")
+        assert len(mcts._graphs) == int(captured) and getattr(mcts, "residency_fallbacks", 0) == 0
+    for d, v in res[1:]:
+        assert torch.equal(d, res[0][0]) and torch.equal(v, res[0][1])
+
+
 def test_ez_collect_step_graph_equals_eager():
     from lightzero_amd.collect import DeviceSearchStep
     B, S = 48, 16

@@ -147,6 +147,98 @@ def test_search_with_reuse_matches_module_api(quant, players):
         assert np.array_equal(got[key], dev_out[key]), key
 
 
+def test_search_with_reuse_fused_traverse_equals_separate_launches():
+    """cfg.fuse_traverse stays on under MuZero's search_with_reuse (the backup of simulation k and the traverse
+    of k + 1 in one launch): the same requests, tree and (length, average_infer) as with the two launches"""
+    from lightzero_amd.mcts_ctree import MuZeroMCTSCtree
+    from lightzero_amd.tree import SequentialSeeds, set_seed_source
+    from lightzero_amd.utils import EasyDict
+    from tests.helpers import NOISE_W, VDM, ScriptedTables, make_scripted_model
+    B, S, A, seed = 48, 20, 3, 9
+    tab = ScriptedTables(B, S, A, seed, players=1, quant=False)
+    rng = np.random.default_rng(seed)
+    ta = rng.integers(0, A, size=B).astype(np.int32)
+    rv = rng.normal(0, 1, size=B).astype(np.float32)
+    runs = []
+    # the third run also takes search_with_reuse's other inputs: no record, device seeds (the first run's), the
+    # true actions and reuse values as tensors
+    for fuse, record in ((False, True), (True, True), (False, False)):
+        cfg = EasyDict(dict(num_simulations=S, discount_factor=0.997, device=DEV, value_delta_max=float(VDM),
+                            fuse_traverse=fuse, model=dict(support_scale=300, categorical_distribution=False)))
+        mcts = MuZeroMCTSCtree(cfg)
+        mcts.record = record
+        roots = MuZeroMCTSCtree.roots(B, [list(range(A))] * B)
+        roots.prepare(float(NOISE_W), [row.tolist() for row in tab.noises], [0.0] * B, tab.root_logits.tolist(),
+                      tab.to_play.tolist())
+        kw = {} if record else dict(seeds=torch.from_numpy(runs[0]["seeds"].view(np.int32)).to(DEV))
+        tav, rvv = (ta.tolist(), rv.tolist()) if record else (torch.from_numpy(ta), torch.from_numpy(rv))
+        set_seed_source(SequentialSeeds(seed))
+        try:
+            ret = mcts.search_with_reuse(roots, make_scripted_model(tab, DEV), tab.lat0, tab.to_play.tolist(),
+                                         tav, rvv, **kw)
+        finally:
+            set_seed_source(None)
+        assert (mcts.last_record is not None) == record
+        rec = mcts.last_record.numpy() if record else {}
+        roots.tree.check_errors()
+        runs.append(dict(rec, ret=ret, dist=roots.tree.distributions().cpu().numpy(),
+                         values=roots.tree.values().cpu().numpy()))
+        roots.clear()
+    a, b, c = runs
+    assert (a["x"] == -1).any(), "the case exercises no skipped inference"
+    for key in ("x", "action", "search_len", "vtp"):
+        assert np.array_equal(a[key], b[key]), key
+    for other in (b, c):
+        assert a["ret"] == other["ret"]
+        for key in ("dist", "values"):
+            assert np.array_equal(a[key], other[key]), key
+
+
+@pytest.mark.parametrize("kind", ["mz", "ez"])
+def test_search_refuses_unusable_arguments(kind):
+    """roots that were never prepared, search_with_reuse without its lists or on Philox roots, and (EfficientZero)
+    a non-positive lstm_horizon_len raise before anything runs"""
+    from lightzero_amd.mcts_ctree import EfficientZeroMCTSCtree, MuZeroMCTSCtree
+    from lightzero_amd.utils import EasyDict
+    cls = EfficientZeroMCTSCtree if kind == "ez" else MuZeroMCTSCtree
+    B, A = 4, 2
+    cfg = dict(num_simulations=3, discount_factor=0.997, device=DEV, lstm_horizon_len=5,
+               model=dict(support_scale=300, categorical_distribution=False))
+    mcts, model = cls(EasyDict(cfg)), torch.nn.Identity()
+    lat0 = torch.zeros(B, 2, device=DEV)
+    state = ((torch.zeros(1, B, 4, device=DEV),) * 2,) if kind == "ez" else ()
+    lists = ([0] * B, [0.5] * B)
+
+    def prepared(mode):
+        old, cls.rng_mode = cls.rng_mode, mode
+        try:
+            roots = cls.roots(B, [[0, 1]] * B)
+        finally:
+            cls.rng_mode = old
+        roots.prepare(0.25, [[0.5, 0.5]] * B, [0.0] * B, [[1.0, 0.0]] * B, [-1] * B)
+        return roots
+
+    fresh = cls.roots(B, [[0, 1]] * B)
+    with pytest.raises(RuntimeError, match="must be prepared"):
+        mcts.search(fresh, model, lat0, *state, [-1] * B)
+    with pytest.raises(RuntimeError, match="must be prepared"):
+        mcts.search_with_reuse(fresh, model, lat0, *state, [-1] * B, *lists)
+    roots = prepared("glibc")
+    with pytest.raises(TypeError, match="true_action_list"):
+        mcts.search_with_reuse(roots, model, lat0, *state, [-1] * B)
+    if kind == "ez":
+        bad = cls(EasyDict(dict(cfg, lstm_horizon_len=0)))
+        with pytest.raises(ValueError, match="lstm_horizon_len must be > 0"):
+            bad.search(roots, model, lat0, *state, [-1] * B)
+        with pytest.raises(ValueError, match="lstm_horizon_len must be > 0"):
+            bad.search_with_reuse(roots, model, lat0, *state, [-1] * B, *lists)
+    roots.clear()
+    roots = prepared("philox")
+    with pytest.raises(ValueError, match="parity"):
+        mcts.search_with_reuse(roots, model, lat0, *state, [-1] * B, *lists)
+    roots.clear()
+
+
 def make_scripted_ez_model(tab, device, Hl=4):
     """ScriptedTables behind the EfficientZero recurrent_inference surface (value prefix, LSTM state)."""
     class Out:
