@@ -538,6 +538,55 @@ int lzm_search_conv_plan(const lzm_handle *h, int num_simulations, int ez, int H
                          int r_ch, int h_ch, int Kr, int Khd, int off_policy, int Vr, int Vv, int categorical,
                          int32_t *out);
 
+/* Root slices of the one-launch conv searches, for the batch sizes reanalyze searches with: the reference
+ * reanalyzes with the search it collects with (lzero/mcts/buffer/game_buffer_muzero.py:519-604; EfficientZero,
+ * with reward_hidden_state_roots: game_buffer_efficientzero.py:322-391), batch_size x (num_unroll_steps + 1) =
+ * 1,536 roots at the Atari defaults. batch_traverse reseeds rand() in every call (cnode.cpp:783-796), so in one
+ * simulation a root's draws depend only on the lower roots' depths: the batch is cut into consecutive slices of
+ * roots, one launch each, enqueued lowest roots first on one stream; every look-back lands on the same launch or
+ * a finished one, and the results equal the single launch's and the generic path's bit for bit.
+ *
+ * lzm_conv_slice_roots: roots per slice for B roots (host arithmetic only; no handle, no HIP call).
+ * max_roots: a cap on the slice, 0 = none. ez = 0 (H, resident_workgroups unused): min(B, 1024, cap).
+ * ez = 1, with R = resident_workgroups (what lzm_search_conv_ez measures its grid against: occupancy per CU x
+ * CUs) and T = ceil(B / 64) * H / 16: B when B <= 256, max(B, 2 T) <= R and B <= cap (the single launch);
+ * else 64 m for the largest integer m >= 1 with 64 m <= min(256, cap) and max(64 m, 2 m H / 16) <= R
+ * (slices start at whole LSTM row blocks); LZM_ERR_RESIDENCY when no m fits; LZM_ERR_ARG when the batch
+ * needs slices and cap < 64, or for B <= 0, max_roots < 0, H not a positive multiple of 16. */
+int lzm_conv_slice_roots(int ez, int B, int H, int resident_workgroups, int max_roots);
+
+/* lzm_search_conv_plan for the sliced launches below with the same max_roots (the plan and the launches ask
+ * lzm_conv_slice_roots; EfficientZero's R as lzm_search_conv_ez computes it, LZM_RESIDENCY_CUS honoured).
+ * out int32 [11]: [0 .. 7] as lzm_search_conv_plan, for the largest (the first) slice — for a batch that fits
+ * one slice exactly lzm_search_conv_plan's answer; [8] slices, [9] roots per slice, [10] roots in the last
+ * slice ([8 .. 10] are 0 when [0] is not LZM_OK). Returns LZM_ERR_ARG for a null handle or output,
+ * num_simulations <= 0 or max_roots < 0, before any HIP call; launches nothing. */
+int lzm_search_conv_sliced_plan(const lzm_handle *h, int num_simulations, int ez, int H, int horizon, int n_dres,
+                                int n_pres, int r_ch, int h_ch, int Kr, int Khd, int off_policy, int Vr, int Vv,
+                                int categorical, int max_roots, int32_t *out);
+
+/* lzm_search_conv / lzm_search_conv_ez over root slices: the same arguments, then max_roots (0 = no cap).
+ * Every slice is enqueued on `stream` by the call itself (plain launches, eager or captured). All slices run
+ * under one look-back epoch and read the collect step's counter before the last slice's last workgroup
+ * advances both; trees, pools, records and outputs keep the whole batch's layout. EfficientZero: every slice
+ * is a co-resident grid of its own (LZM_ERR_RESIDENCY, nothing launched, when not even 64 roots fit); a
+ * hand-off timeout in one slice sets the abort word, the later slices fall through, and lzm_check_errors
+ * reports it as for the single launch. A batch that fits one slice is exactly the single launch. */
+int lzm_search_conv_sliced(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init, float discount,
+                           float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
+                           const float *trunk_w, const float *actmap, int n_dres, int n_pres, int r_ch, int h_ch,
+                           const float *w1t, const float *b1, const float *w2q, const float *b2, int Kr, int Khd,
+                           int off_policy, int Vr, int Vv, int categorical, int32_t *rec_x, int32_t *rec_a,
+                           int32_t *rec_len, float *rec_decoded, float *rec_logits, int max_roots, void *stream);
+int lzm_search_conv_ez_sliced(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init, float discount,
+                              float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
+                              float *hpool, float *cpool, int H, int horizon, const float *trunk_w,
+                              const float *actmap, int n_dres, int n_pres, int r_ch, int h_ch, const float *lstm_frag,
+                              const float *lstm_bias, const float *vp_s, const float *vp_t, const float *w1t,
+                              const float *b1, const float *w2q, const float *b2, int Khd, int off_policy, int Vr,
+                              int Vv, int categorical, int32_t *rec_x, int32_t *rec_a, int32_t *rec_len,
+                              float *rec_decoded, float *rec_logits, int32_t *rec_reset, int max_roots, void *stream);
+
 /* lzm_decode_backprop of simulation `cur` fused with lzm_traverse of the next simulation (parity /
  * glibc mode only): one launch in which the wave that backs up root i then walks root i again
  * (same requests, draws and outputs as the two separate calls). Replaces the pair

@@ -89,6 +89,13 @@ SIGNATURES = {
     "lzm_conv_heads_supported": [_i, _i, _i, _i, _i, _i],
     "lzm_set_value_support": [_vp, _i],
     "lzm_search_conv_plan": [_vp] + [_i] * 14 + [_vp],
+    "lzm_conv_slice_roots": [_i] * 5,
+    "lzm_search_conv_sliced_plan": [_vp] + [_i] * 15 + [_vp],
+    "lzm_search_conv_sliced": [_vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
+                               _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
+    "lzm_search_conv_ez_sliced": [_vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i,
+                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                  _vp, _i, _vp],
     "lzm_seed_sequence": [_vp, _i64, _i, _vp, _vp],
     "lzm_get_root_outputs": [_vp, _vp, _vp, _vp],
     "lzm_mlp_prepare": [_i, _i, _i, _i, _i, _vp, _vp, _vp],

@@ -2973,7 +2973,40 @@ extern "C" int lzm_conv_heads_prepare(lzm_handle *h, int B, int Khd, int off_pol
 struct ConvPlan {
   int rc, G, T, npin, pbt_rows, out_rounds, r_one_round;
   size_t lds;
+  int roots;  // roots per launch (the whole batch, or the slice rule's answer: G, T, npin are the largest slice's)
 };
+
+// The slice rule of the one-launch conv searches (lzm_search_conv.h "Root slices"): roots per launch for a
+// batch of B roots. resident_workgroups: the co-resident bound R of the EfficientZero grid (occupancy x CUs);
+// max_roots: the caller's cap, 0 = none. MuZero: min(kScMaxRoots, cap) (at most B). EfficientZero: the whole
+// batch when it passes the single launch's check (B <= 256, max(B, 2 T) <= R, B <= cap), else 64 m roots with
+// m the largest integer >= 1 such that 64 m <= min(256, cap) and max(64 m, 2 m H / 16) <= R;
+// LZM_ERR_RESIDENCY when no m fits, LZM_ERR_ARG for a cap below 64 on a batch that needs slicing. Host
+// arithmetic only.
+extern "C" int lzm_conv_slice_roots(int ez, int B, int H, int resident_workgroups, int max_roots) {
+  if (B <= 0 || max_roots < 0 || (ez && (H <= 0 || H % kLsUnits || resident_workgroups < 0))) {
+    set_err("lzm_conv_slice_roots: B > 0, max_roots >= 0 (0: no cap), EfficientZero: H a multiple of 16, "
+            "resident_workgroups >= 0");
+    return LZM_ERR_ARG;
+  }
+  if (!ez) return std::min(B, max_roots ? std::min(kScMaxRoots, max_roots) : kScMaxRoots);
+  const int R = resident_workgroups, nb = H / kLsUnits;
+  const long long T = (long long)((B + kLsRows - 1) / kLsRows) * nb;
+  if (B <= 256 && std::max<long long>(B, 2 * T) <= R && (!max_roots || B <= max_roots)) return B;
+  if (max_roots && max_roots < kLsRows) {
+    snprintf(g_err, sizeof(g_err), "lzm_conv_slice_roots: max_roots %d < %d (EfficientZero slices are whole row "
+             "blocks of %d roots)", max_roots, kLsRows, kLsRows);
+    return LZM_ERR_ARG;
+  }
+  int m = std::min(256, max_roots ? max_roots : 256) / kLsRows;
+  while (m >= 1 && std::max(kLsRows * m, 2 * m * nb) > R) --m;
+  if (m < 1) {
+    snprintf(g_err, sizeof(g_err), "lzm_conv_slice_roots: a slice of %d roots needs %d workgroups (%d LSTM tiles x "
+             "2) > %d resident", kLsRows, std::max(kLsRows, 2 * nb), nb, R);
+    return LZM_ERR_RESIDENCY;
+  }
+  return kLsRows * m;
+}
 // lower bits shared by both kinds: tree, walk and head buffers after the activation buffers (float offsets)
 static size_t conv_plan_lds(const lzm_handle *h, int S, int Kr, int Khd, int Vr, int Vv, size_t o, ConvSearchArgs &p) {
   p.off_stat = (int)o; o += (size_t)h->cap * 4;
@@ -3000,9 +3033,10 @@ static bool conv_shape_ok(int n_dres, int n_pres, int r_ch, int h_ch, int Khd, i
          Khd - off_policy <= kHdKMax && !(off_policy % 128) && !(Khd % 128) && Vr > 0 && Vv > 0 && Vr <= 1024 &&
          Vv <= 1024 && (categorical || (Vr == 1 && Vv == 1));
 }
+// max_roots < 0: the whole batch in one launch (lzm_search_conv); >= 0: root slices by lzm_conv_slice_roots.
 static ConvPlan conv_plan_mz(const lzm_handle *h, int S, int n_dres, int n_pres, int r_ch, int h_ch, int Kr, int Khd,
-                             int off_policy, int Vr, int Vv, int categorical, ConvSearchArgs &p) {
-  ConvPlan pl{LZM_ERR_ARG, 0, 0, 0, 0, 0, 0, 0};
+                             int off_policy, int Vr, int Vv, int categorical, ConvSearchArgs &p, int max_roots = -1) {
+  ConvPlan pl{LZM_ERR_ARG, 0, 0, 0, 0, 0, 0, 0, 0};
   if (h->flags & LZM_TREE_EZ) {
     set_err("lzm_search_conv: MuZero trees only");
     return pl;
@@ -3020,8 +3054,13 @@ static ConvPlan conv_plan_mz(const lzm_handle *h, int S, int n_dres, int n_pres,
   }
   // one workgroup per root; roots beyond the CUs queue behind the first ones (their look-back waits only on
   // lower roots: lzm_search_conv.h sc_lookback)
-  if (h->B > kScMaxRoots) {
-    snprintf(g_err, sizeof(g_err), "lzm_search_conv: %d roots > %d", h->B, kScMaxRoots);
+  const int roots = max_roots < 0 ? h->B : lzm_conv_slice_roots(0, h->B, 0, 0, max_roots);
+  if (roots < 0) {
+    pl.rc = roots;
+    return pl;
+  }
+  if (roots > kScMaxRoots) {
+    snprintf(g_err, sizeof(g_err), "lzm_search_conv: %d roots > %d", roots, kScMaxRoots);
     return pl;
   }
   // dynamic LDS plan (float offsets, 16-B aligned): the two split-fp16 activation buffers first
@@ -3032,19 +3071,19 @@ static ConvPlan conv_plan_mz(const lzm_handle *h, int S, int n_dres, int n_pres,
              o * sizeof(float));
     return pl;
   }
-  // the head hidden layers' first half-head resident in LDS when it fits and every root has a CU of its own
-  // (more roots than CUs: the smaller footprint lets two workgroups share one)
+  // the head hidden layers' first half-head resident in LDS when it fits and every root of the launch (the
+  // slice) has a CU of its own (more roots than CUs: the smaller footprint lets two workgroups share one)
   constexpr size_t kPinFloats = (size_t)kHdParts * 16 * 32 * 4;
   const char *pin_env = getenv("LZM_CONV_PIN");
   const int pin_max = pin_env ? atoi(pin_env) : 1;
   p.off_wpin = (int)o;
   p.npin = 0;
-  while (p.npin < pin_max && p.npin < 6 && h->B <= device_cus() && (o + kPinFloats) * sizeof(float) <= kMaxLds) {
+  while (p.npin < pin_max && p.npin < 6 && roots <= device_cus() && (o + kPinFloats) * sizeof(float) <= kMaxLds) {
     o += kPinFloats;
     ++p.npin;
   }
   pl.rc = LZM_OK;
-  pl.G = h->B;
+  pl.G = pl.roots = roots;
   pl.npin = p.npin;
   pl.out_rounds = sc_out_rounds(Vr + Vv + h->A);
   pl.r_one_round = 0;
@@ -3055,12 +3094,14 @@ static ConvPlan conv_plan_mz(const lzm_handle *h, int S, int n_dres, int n_pres,
 // Whole-search launch for the conv MuZero networks (lzm_search_conv.h): one workgroup per root,
 // every simulation inside the kernel. The grid must be co-resident (one workgroup per CU, B <= CUs):
 // parity-mode roots wait on their predecessors' depth flags.
-extern "C" int lzm_search_conv(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init, float discount,
-                               float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
-                               const float *trunk_w, const float *actmap, int n_dres, int n_pres, int r_ch, int h_ch,
-                               const float *w1t, const float *b1, const float *w2q, const float *b2, int Kr, int Khd,
-                               int off_policy, int Vr, int Vv, int categorical, int32_t *rec_x, int32_t *rec_a,
-                               int32_t *rec_len, float *rec_decoded, float *rec_logits, void *stream) {
+// max_roots < 0: lzm_search_conv (the whole batch, one launch); >= 0: lzm_search_conv_sliced (every root slice
+// enqueued on the stream, lowest roots first).
+static int search_conv_launch(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init, float discount,
+                              float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
+                              const float *trunk_w, const float *actmap, int n_dres, int n_pres, int r_ch, int h_ch,
+                              const float *w1t, const float *b1, const float *w2q, const float *b2, int Kr, int Khd,
+                              int off_policy, int Vr, int Vv, int categorical, int32_t *rec_x, int32_t *rec_a,
+                              int32_t *rec_len, float *rec_decoded, float *rec_logits, void *stream, int max_roots) {
   const int S = num_simulations;
   if (!h || !minmax || (!seeds && !h->step_count) || !vtp_in || !latent_pool || !trunk_w || !actmap || !w1t || !b1 ||
       !w2q || !b2 ||
@@ -3074,7 +3115,8 @@ extern "C" int lzm_search_conv(lzm_handle *h, int num_simulations, int pb_c_base
   }
   ConvSearchArgs p;
   memset(&p, 0, sizeof(p));
-  const ConvPlan plan = conv_plan_mz(h, S, n_dres, n_pres, r_ch, h_ch, Kr, Khd, off_policy, Vr, Vv, categorical, p);
+  const ConvPlan plan = conv_plan_mz(h, S, n_dres, n_pres, r_ch, h_ch, Kr, Khd, off_policy, Vr, Vv, categorical, p,
+                                     max_roots);
   if (plan.rc != LZM_OK) return plan.rc;
   int rc = fill_lut(h, pb_c_base, pb_c_init);
   if (rc != LZM_OK) return rc;
@@ -3107,12 +3149,44 @@ extern "C" int lzm_search_conv(lzm_handle *h, int num_simulations, int pb_c_base
   auto fn = stamps ? (fast ? search_conv_kernel<kBxAhead, true, true> : search_conv_kernel<kBxAhead, false, true>)
                    : (fast ? search_conv_kernel<kBxAhead, true> : search_conv_kernel<kBxAhead, false>);
   hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(fn, dim3(h->B), dim3(kScThreads), lds, (hipStream_t)stream, p);
+  for (int root0 = 0; e == hipSuccess && root0 < h->B; root0 += plan.roots) {
+    p.root0 = root0;
+    p.nroots = std::min(plan.roots, h->B - root0);
+    p.last_slice = root0 + p.nroots >= h->B;
+    hipLaunchKernelGGL(fn, dim3(p.nroots), dim3(kScThreads), lds, (hipStream_t)stream, p);
     e = hipGetLastError();
   }
   LZM_HIP(e);
   return LZM_OK;
+}
+
+extern "C" int lzm_search_conv(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init, float discount,
+                               float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
+                               const float *trunk_w, const float *actmap, int n_dres, int n_pres, int r_ch, int h_ch,
+                               const float *w1t, const float *b1, const float *w2q, const float *b2, int Kr, int Khd,
+                               int off_policy, int Vr, int Vv, int categorical, int32_t *rec_x, int32_t *rec_a,
+                               int32_t *rec_len, float *rec_decoded, float *rec_logits, void *stream) {
+  return search_conv_launch(h, num_simulations, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in, latent_pool,
+                            trunk_w, actmap, n_dres, n_pres, r_ch, h_ch, w1t, b1, w2q, b2, Kr, Khd, off_policy, Vr, Vv,
+                            categorical, rec_x, rec_a, rec_len, rec_decoded, rec_logits, stream, -1);
+}
+
+// lzm_search_conv over root slices (lzm_conv_slice_roots; max_roots: the caller's cap on a slice, 0 = none): any
+// number of roots, the slices enqueued one after another on `stream` (plain launches, capturable).
+extern "C" int lzm_search_conv_sliced(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init,
+                                      float discount, float *minmax, const uint32_t *seeds, const int32_t *vtp_in,
+                                      float *latent_pool, const float *trunk_w, const float *actmap, int n_dres,
+                                      int n_pres, int r_ch, int h_ch, const float *w1t, const float *b1,
+                                      const float *w2q, const float *b2, int Kr, int Khd, int off_policy, int Vr,
+                                      int Vv, int categorical, int32_t *rec_x, int32_t *rec_a, int32_t *rec_len,
+                                      float *rec_decoded, float *rec_logits, int max_roots, void *stream) {
+  if (max_roots < 0) {
+    set_err("lzm_search_conv_sliced: max_roots >= 0 (0: no cap)");
+    return LZM_ERR_ARG;
+  }
+  return search_conv_launch(h, num_simulations, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in, latent_pool,
+                            trunk_w, actmap, n_dres, n_pres, r_ch, h_ch, w1t, b1, w2q, b2, Kr, Khd, off_policy, Vr, Vv,
+                            categorical, rec_x, rec_a, rec_len, rec_decoded, rec_logits, stream, max_roots);
 }
 
 using ConvEzFn = decltype(&search_conv_ez_kernel<kBxAheadEz, false, false>);
@@ -3124,9 +3198,13 @@ static bool conv_stamps() { return getenv("LZM_PHASE_TIMING") && atoi(getenv("LZ
 
 // conv_plan_mz's EfficientZero twin. The shape, capacity and grid checks touch no HIP state; a request that
 // passes them is then measured against the occupancy of the kernel it would launch (residency = true).
+// max_roots < 0: the whole batch in one launch (lzm_search_conv_ez); >= 0: root slices by lzm_conv_slice_roots,
+// asked first with the CU count for R (host only: a refusal comes before any HIP call, as the single launch's)
+// and again with the occupancy bound once the kernel's LDS need is known.
 static ConvPlan conv_plan_ez(const lzm_handle *h, int S, int H, int horizon, int n_dres, int n_pres, int r_ch, int h_ch,
-                             int Khd, int off_policy, int Vr, int Vv, int categorical, ConvSearchArgs &p) {
-  ConvPlan pl{LZM_ERR_ARG, 0, 0, 0, 0, 0, 0, 0};
+                             int Khd, int off_policy, int Vr, int Vv, int categorical, ConvSearchArgs &p,
+                             int max_roots = -1) {
+  ConvPlan pl{LZM_ERR_ARG, 0, 0, 0, 0, 0, 0, 0, 0};
   if (!(h->flags & LZM_TREE_EZ)) {
     set_err("lzm_search_conv_ez: EfficientZero trees only");
     return pl;
@@ -3148,10 +3226,20 @@ static ConvPlan conv_plan_ez(const lzm_handle *h, int S, int H, int horizon, int
   int cus = device_cus();
   if (const char *ov = getenv("LZM_RESIDENCY_CUS"))
     if (atoi(ov) > 0) cus = std::min(cus, atoi(ov));
-  const int B = h->B, nmb = (B + kLsRows - 1) / kLsRows, T = nmb * (H / kLsUnits), G = std::max(B, 2 * T);
+  int B = h->B;  // roots per launch
+  if (max_roots >= 0) {
+    B = lzm_conv_slice_roots(1, h->B, H, cus, max_roots);
+    if (B < 0) {
+      pl.rc = B;
+      return pl;
+    }
+  }
+  int nmb = (B + kLsRows - 1) / kLsRows, T = nmb * (H / kLsUnits), G = std::max(B, 2 * T);
   pl.G = G;
   pl.T = T;
-  p.nmb = nmb; p.T = T;
+  pl.roots = B;
+  p.nmb = (h->B + kLsRows - 1) / kLsRows; p.T = p.nmb * (H / kLsUnits);  // (the whole batch's: hand-off words)
+  p.nmb_s = nmb; p.T_s = T;
   if (B > 256 || G > cus) {
     snprintf(g_err, sizeof(g_err),
              "lzm_search_conv_ez: %d workgroups (%d roots, %d LSTM tiles x 2) > min(%d CUs) or B > 256 (the grid is "
@@ -3189,6 +3277,16 @@ static ConvPlan conv_plan_ez(const lzm_handle *h, int S, int H, int horizon, int
     pl.rc = LZM_ERR_HIP;
     return pl;
   }
+  if (max_roots >= 0) {  // the slice rule again, with the occupancy bound (the CU cap above still holds)
+    B = lzm_conv_slice_roots(1, h->B, H, (int)std::min<long long>((long long)per_cu * cus, cus), max_roots);
+    if (B < 0) {
+      pl.rc = B;
+      return pl;
+    }
+    nmb = (B + kLsRows - 1) / kLsRows; T = nmb * (H / kLsUnits); G = std::max(B, 2 * T);
+    pl.G = G; pl.T = T; pl.roots = B;
+    p.nmb_s = nmb; p.T_s = T;
+  }
   if ((long long)per_cu * cus < G) {
     snprintf(g_err, sizeof(g_err), "lzm_search_conv_ez: %d workgroups > %d resident (%d per CU x %d CUs)", G,
              per_cu * cus, per_cu, cus);
@@ -3222,19 +3320,45 @@ extern "C" int lzm_search_conv_plan(const lzm_handle *h, int num_simulations, in
   return LZM_OK;
 }
 
+// lzm_search_conv_plan for lzm_search_conv_sliced / lzm_search_conv_ez_sliced with the same max_roots: out[0 .. 7]
+// as above for the largest slice (the first), then out[8 .. 10] = {slices, roots per slice, roots in the last
+// slice} (zeros when refused). Launches nothing.
+extern "C" int lzm_search_conv_sliced_plan(const lzm_handle *h, int num_simulations, int ez, int H, int horizon,
+                                           int n_dres, int n_pres, int r_ch, int h_ch, int Kr, int Khd,
+                                           int off_policy, int Vr, int Vv, int categorical, int max_roots,
+                                           int32_t *out) {
+  if (!h || !out || num_simulations <= 0 || max_roots < 0) {
+    set_err("lzm_search_conv_sliced_plan: null argument, no simulations or max_roots < 0");
+    return LZM_ERR_ARG;
+  }
+  ConvSearchArgs p;
+  memset(&p, 0, sizeof(p));
+  const ConvPlan pl = ez ? conv_plan_ez(h, num_simulations, H, horizon, n_dres, n_pres, r_ch, h_ch, Khd, off_policy,
+                                        Vr, Vv, categorical, p, max_roots)
+                         : conv_plan_mz(h, num_simulations, n_dres, n_pres, r_ch, h_ch, Kr, Khd, off_policy, Vr, Vv,
+                                        categorical, p, max_roots);
+  out[0] = pl.rc; out[1] = pl.G; out[2] = pl.T; out[3] = (int32_t)pl.lds; out[4] = pl.npin; out[5] = pl.pbt_rows;
+  out[6] = pl.out_rounds; out[7] = pl.r_one_round;
+  const int n = pl.rc == LZM_OK && pl.roots > 0 ? (h->B + pl.roots - 1) / pl.roots : 0;
+  out[8] = n; out[9] = n ? pl.roots : 0; out[10] = n ? h->B - (n - 1) * pl.roots : 0;
+  return LZM_OK;
+}
+
 // Whole-search launch for the conv EfficientZero networks (lzm_search_conv.h, EZ instantiation): the
 // MuZero launch's flow plus the reward LSTM as split-K tiles spread over the grid (G = max(B, 2 T)
 // workgroups, one per CU, co-resident: the tiles wait on the roots' LSTM input rows and the roots on
 // their rows' tiles inside the launch).
-extern "C" int lzm_search_conv_ez(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init, float discount,
-                                  float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
-                                  float *hpool, float *cpool, int H, int horizon, const float *trunk_w,
-                                  const float *actmap, int n_dres, int n_pres, int r_ch, int h_ch,
-                                  const float *lstm_frag, const float *lstm_bias, const float *vp_s, const float *vp_t,
-                                  const float *w1t, const float *b1, const float *w2q, const float *b2, int Khd,
-                                  int off_policy, int Vr, int Vv, int categorical, int32_t *rec_x, int32_t *rec_a,
-                                  int32_t *rec_len, float *rec_decoded, float *rec_logits, int32_t *rec_reset,
-                                  void *stream) {
+// max_roots < 0: lzm_search_conv_ez (the whole batch, one launch); >= 0: lzm_search_conv_ez_sliced (every root
+// slice, each a co-resident grid of its own, enqueued on the stream, lowest roots first).
+static int search_conv_ez_launch(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init, float discount,
+                                 float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
+                                 float *hpool, float *cpool, int H, int horizon, const float *trunk_w,
+                                 const float *actmap, int n_dres, int n_pres, int r_ch, int h_ch,
+                                 const float *lstm_frag, const float *lstm_bias, const float *vp_s, const float *vp_t,
+                                 const float *w1t, const float *b1, const float *w2q, const float *b2, int Khd,
+                                 int off_policy, int Vr, int Vv, int categorical, int32_t *rec_x, int32_t *rec_a,
+                                 int32_t *rec_len, float *rec_decoded, float *rec_logits, int32_t *rec_reset,
+                                 void *stream, int max_roots) {
   const int S = num_simulations;
   if (!h || !minmax || (!seeds && !h->step_count) || !vtp_in || !latent_pool || !hpool || !cpool || !trunk_w ||
       !actmap || !lstm_frag ||
@@ -3250,9 +3374,10 @@ extern "C" int lzm_search_conv_ez(lzm_handle *h, int num_simulations, int pb_c_b
   ConvSearchArgs p;
   memset(&p, 0, sizeof(p));
   const ConvPlan plan = conv_plan_ez(h, S, H, horizon, n_dres, n_pres, r_ch, h_ch, Khd, off_policy, Vr, Vv,
-                                     categorical, p);
+                                     categorical, p, max_roots);
   if (plan.rc != LZM_OK) return plan.rc;
-  const int Kx = r_ch * 64 + H, B = h->B, T = plan.T, G = plan.G;
+  // (T: the whole batch's tile grid — the hand-off words and partials are filed by the global tile index)
+  const int Kx = r_ch * 64 + H, B = h->B, T = p.T;
   int rc = fill_lut(h, pb_c_base, pb_c_init);
   if (rc != LZM_OK) return rc;
   const bool fast = (h->flags & LZM_RNG_FAST) != 0;
@@ -3301,9 +3426,55 @@ extern "C" int lzm_search_conv_ez(lzm_handle *h, int num_simulations, int pb_c_b
     LZM_HIP(hipMemset(h->phase, 0, (64 + 1024) * sizeof(unsigned long long)));
   }
   p.stamps = stamps ? h->phase : nullptr;
-  hipLaunchKernelGGL(conv_ez_kernel_fn(fast, stamps), dim3(G), dim3(kScThreads), lds, (hipStream_t)stream, p);
-  LZM_CHECK_LAUNCH();
+  for (int root0 = 0; root0 < B; root0 += plan.roots) {  // (slices start at multiples of 64 roots)
+    p.root0 = root0;
+    p.nroots = std::min(plan.roots, B - root0);
+    p.last_slice = root0 + p.nroots >= B;
+    p.nmb_s = (p.nroots + kLsRows - 1) / kLsRows;
+    p.T_s = p.nmb_s * (H / kLsUnits);
+    hipLaunchKernelGGL(conv_ez_kernel_fn(fast, stamps), dim3(std::max(p.nroots, 2 * p.T_s)), dim3(kScThreads), lds,
+                       (hipStream_t)stream, p);
+    LZM_CHECK_LAUNCH();
+  }
   return LZM_OK;
+}
+
+extern "C" int lzm_search_conv_ez(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init, float discount,
+                                  float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
+                                  float *hpool, float *cpool, int H, int horizon, const float *trunk_w,
+                                  const float *actmap, int n_dres, int n_pres, int r_ch, int h_ch,
+                                  const float *lstm_frag, const float *lstm_bias, const float *vp_s, const float *vp_t,
+                                  const float *w1t, const float *b1, const float *w2q, const float *b2, int Khd,
+                                  int off_policy, int Vr, int Vv, int categorical, int32_t *rec_x, int32_t *rec_a,
+                                  int32_t *rec_len, float *rec_decoded, float *rec_logits, int32_t *rec_reset,
+                                  void *stream) {
+  return search_conv_ez_launch(h, num_simulations, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in, latent_pool,
+                               hpool, cpool, H, horizon, trunk_w, actmap, n_dres, n_pres, r_ch, h_ch, lstm_frag,
+                               lstm_bias, vp_s, vp_t, w1t, b1, w2q, b2, Khd, off_policy, Vr, Vv, categorical, rec_x,
+                               rec_a, rec_len, rec_decoded, rec_logits, rec_reset, stream, -1);
+}
+
+// lzm_search_conv_ez over root slices (lzm_conv_slice_roots with the launch's own residency bound; max_roots: the
+// caller's cap on a slice, 0 = none): batches past 256 roots or past the co-resident grid, the slices enqueued
+// one after another on `stream` (plain launches, capturable). LZM_ERR_RESIDENCY, with nothing launched, when
+// not even a 64-root slice is co-resident.
+extern "C" int lzm_search_conv_ez_sliced(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init,
+                                         float discount, float *minmax, const uint32_t *seeds, const int32_t *vtp_in,
+                                         float *latent_pool, float *hpool, float *cpool, int H, int horizon,
+                                         const float *trunk_w, const float *actmap, int n_dres, int n_pres, int r_ch,
+                                         int h_ch, const float *lstm_frag, const float *lstm_bias, const float *vp_s,
+                                         const float *vp_t, const float *w1t, const float *b1, const float *w2q,
+                                         const float *b2, int Khd, int off_policy, int Vr, int Vv, int categorical,
+                                         int32_t *rec_x, int32_t *rec_a, int32_t *rec_len, float *rec_decoded,
+                                         float *rec_logits, int32_t *rec_reset, int max_roots, void *stream) {
+  if (max_roots < 0) {
+    set_err("lzm_search_conv_ez_sliced: max_roots >= 0 (0: no cap)");
+    return LZM_ERR_ARG;
+  }
+  return search_conv_ez_launch(h, num_simulations, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in, latent_pool,
+                               hpool, cpool, H, horizon, trunk_w, actmap, n_dres, n_pres, r_ch, h_ch, lstm_frag,
+                               lstm_bias, vp_s, vp_t, w1t, b1, w2q, b2, Khd, off_policy, Vr, Vv, categorical, rec_x,
+                               rec_a, rec_len, rec_decoded, rec_logits, rec_reset, stream, max_roots);
 }
 
 // Test support: n workgroups that each occupy a CU (the whole LDS) for `usec` microseconds of the 100 MHz real-time

@@ -26,6 +26,20 @@
 // verdict (softmax); one whose own row passes cannot decide alone and counts an integrity error
 // (sdiag[0], raised by lzm_check_errors) instead of waiting on the whole grid — a network whose
 // raw support logits sum to 1 within 1e-5 does not occur in practice.
+//
+// Root slices. A search over more roots than one launch takes (kScMaxRoots; EfficientZero: what the GPU holds
+// co-resident) is cut into consecutive slices of roots, launched one after another on one stream
+// (lzm_search_conv_sliced / lzm_search_conv_ez_sliced; the slice rule is lzm_conv_slice_roots). The reference
+// reseeds rand() in every batch_traverse call, so in simulation k a root's draw offset depends only on the
+// depth flags of the lower roots in the same simulation: every look-back lands on roots of the same launch or
+// of a finished one, and no launch waits on a later one. All slices of a search run under one epoch: only the
+// last slice's last workgroup advances it (and the collect step's counter, which every slice reads before).
+// The tree, the pools, the records, the outputs and the look-back flags stay indexed by the global root with
+// the batch's stride B. EfficientZero slices start at multiples of 64 roots, so a slice's LSTM tiles cover
+// its own row blocks; the hand-off words are INDEXED GLOBALLY — xflags by the global root row, tflags / pflags
+// (and the split-K partials) by the tile's index in the whole batch's tile grid (n-block * nmb + global row
+// block) — so no slice ever reads a word an earlier slice of the same epoch published, and nothing is cleared
+// between launches. A batch that fits one slice is exactly the single launch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -107,6 +121,11 @@ struct ConvSearchArgs {
   int off_stat, off_meta, off_val, off_lut, off_legal, off_path, off_pact, off_pbt, off_r, off_hd, off_hid, off_part,
       off_lg, off_seed, off_lmax;
   int off_wpin, npin;  // LDS copy of the first npin half-heads of w1t (sc_heads_hidden_rs), 64 KiB each
+  // root slice of this launch (see "Root slices" above): workgroup g owns root root0 + g, g < nroots; every
+  // array above keeps the whole batch's stride B and is indexed by the global root. last_slice: this launch
+  // ends the search (its last workgroup advances the epoch and the collect step's counter).
+  int root0, nroots, last_slice;
+  int nmb_s, T_s;  // EfficientZero: the slice's own row blocks and LSTM tiles (nmb, T: the whole batch's)
 };
 
 // Bounded waits of the one-launch conv searches (their grid must be co-resident; the host checks the static
@@ -438,7 +457,7 @@ __global__ __launch_bounds__(kScThreads) __attribute__((amdgpu_waves_per_eu(1, 1
   uint16_t *act = reinterpret_cast<uint16_t *>(sc_lds4);
   float *smem = reinterpret_cast<float *>(sc_lds4);
   auto buf = [&](int i) { return act + i * kBxBuf; };
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int b = p.root0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int c = 16 * wv + (lane & 15);
   const int B = p.B, A = p.A, S = p.S;
   __shared__ uint32_t s_z0[31];
@@ -782,8 +801,10 @@ __global__ __launch_bounds__(kScThreads) __attribute__((amdgpu_waves_per_eu(1, 1
     const uint32_t done = atomicAdd(p.epoch + 1, 1u);
     if (done == (uint32_t)gridDim.x - 1) {
       p.epoch[1] = 0;
-      __hip_atomic_store(p.epoch, (uint32_t)(epoch + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (p.step_count && p.step_inc) *p.step_count += 1;
+      if (p.last_slice) {  // (the slices of one search share the epoch and the counter's value)
+        __hip_atomic_store(p.epoch, (uint32_t)(epoch + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (p.step_count && p.step_inc) *p.step_count += 1;
+      }
     }
   }
 }
@@ -793,7 +814,8 @@ __global__ __launch_bounds__(kScThreads) __attribute__((amdgpu_waves_per_eu(1, 1
 #define LZM_EZ_POOL_AUX 16  // cache policy of the latent pool stores (16: sc1)
 #endif
 // The EfficientZero one-launch search (lzm_search_conv_ez). The grid is G = max(B, 2 T)
-// workgroups; workgroup g owns root g (g < B) and K half (g & 1 or the XCD map below) of LSTM tile
+// workgroups (a root slice: its own roots and tiles, root0 + g and T_s for g and T below);
+// workgroup g owns root g (g < B) and K half (g & 1 or the XCD map below) of LSTM tile
 // q(g) (g < 2 T). Per simulation, on top of the MuZero flow:
 //   - the trunk writes root b's LSTM input row xin[b] = [reward planes | hpool[x][b]] with sc1 stores
 //     and publishes {epoch, x, search_len} in xflags[k][b] (every storing wave's vmcnt(0), a barrier,
@@ -817,10 +839,10 @@ __global__ __launch_bounds__(kScThreads) __attribute__((amdgpu_waves_per_eu(1, 1
   uint16_t *act = reinterpret_cast<uint16_t *>(sc_lds4);
   float *smem = reinterpret_cast<float *>(sc_lds4);
   auto buf = [&](int i) { return act + i * kBxBuf; };
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int g = blockIdx.x, b = p.root0 + g, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int c = 16 * wv + (lane & 15);
   const int B = p.B, A = p.A, S = p.S;
-  const bool has_root = b < B;
+  const bool has_root = g < p.nroots;
   __shared__ uint32_t s_z0[31];
   __shared__ int s_players, s_epoch, s_x, s_act, s_vtp0, s_leafvtp, s_late, s_tlevel;
   __shared__ unsigned long long s_tmask;
@@ -898,23 +920,27 @@ __global__ __launch_bounds__(kScThreads) __attribute__((amdgpu_waves_per_eu(1, 1
 
   // EfficientZero: this workgroup's LSTM tile (fixed for the launch)
   __shared__ int s_rx[64], s_rlen[64], s_rexp[64];
+  // (the slice's own tiles T_s map onto its workgroups; q becomes the tile's index in the whole batch's grid
+  // of T tiles, which the hand-off words and the split-K partials are filed under)
   const int T = p.T, NB = p.H / kLsUnits;
-  const bool has_tile = b < 2 * T;
+  const bool has_tile = g < 2 * p.T_s;
   int q = 0;
   LpTile tile{0, 0, 0};
   {
-    int kh = b & 1;
-    q = b >> 1;
-    if ((T & 3) == 0) {
+    const int Ts = p.T_s;
+    int kh = g & 1;
+    q = g >> 1;
+    if ((Ts & 3) == 0) {
       // XCD map (block % 8 = XCD): one K half per XCD (XCD & 1) and consecutive tiles — whole
       // n-blocks, every row block — so an XCD's L2 holds its W slice (K / 2 x 64 columns per n-block)
       // and only its K half of the LSTM input rows; the split-K partner sits on the next XCD
-      const int xcd = b & 7, j = b >> 3;
-      q = (xcd >> 1) * (T >> 2) + j;
+      const int xcd = g & 7, j = g >> 3;
+      q = (xcd >> 1) * (Ts >> 2) + j;
       kh = xcd & 1;
     }
-    const int nb = q / p.nmb, mb = q - nb * p.nmb;
-    tile = LpTile{kLsRows * mb, nb, kh};
+    const int nb = q / p.nmb_s, mb = q - nb * p.nmb_s;
+    tile = LpTile{p.root0 + kLsRows * mb, nb, kh};
+    q = nb * p.nmb + p.root0 / kLsRows + mb;
   }
   const int Kx = p.Kx, H = p.H;
   typedef unsigned sc_u4 __attribute__((ext_vector_type(4)));
@@ -1317,8 +1343,10 @@ __global__ __launch_bounds__(kScThreads) __attribute__((amdgpu_waves_per_eu(1, 1
     const uint32_t done = atomicAdd(p.epoch + 1, 1u);
     if (done == (uint32_t)gridDim.x - 1) {
       p.epoch[1] = 0;
-      __hip_atomic_store(p.epoch, (uint32_t)(epoch + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (p.step_count && p.step_inc) *p.step_count += 1;
+      if (p.last_slice) {  // (the slices of one search share the epoch and the counter's value)
+        __hip_atomic_store(p.epoch, (uint32_t)(epoch + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (p.step_count && p.step_inc) *p.step_count += 1;
+      }
     }
   }
 }

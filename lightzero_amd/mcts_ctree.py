@@ -220,6 +220,11 @@ class _MCTSCtree(object):
         pb_c_init=1.25,
         value_delta_max=0.01,
         env_type='not_board_games',
+        # the one-launch conv searches over root slices (lzm_search_conv_sliced / lzm_search_conv_ez_sliced):
+        # batches past 1,024 roots (EfficientZero: past 256 roots or the co-resident grid) stay on the
+        # hand-written kernels, one launch per slice; sliced_search_max_roots caps a slice (0: the library's rule)
+        sliced_search=False,
+        sliced_search_max_roots=0,
     )
 
     _tree = None  # the ctree module of the roots this search takes (mz_tree / ez_tree)
@@ -449,6 +454,28 @@ class _MCTSCtree(object):
         scratch.close()
         return _GraphEntry(g, c.buf, net if net is not model else None, model, t)
 
+    def _sliced(self):
+        return bool(self._cfg.get('sliced_search', False))
+
+    def _conv_plan(self, t, net, S, **kw):
+        """the library's plan of this search's conv launch: the sliced launches' with cfg.sliced_search (the slice
+        fields in last_plan), the single launch's otherwise"""
+        if self._sliced():
+            return t.search_conv_sliced_plan(net, S, max_roots=int(self._cfg.get('sliced_search_max_roots', 0) or 0),
+                                             **kw)
+        return t.search_conv_plan(net, S, **kw)
+
+    def _conv_call(self, t, name, *args, **kw):
+        """DeviceTree.<name> or, with cfg.sliced_search, DeviceTree.<name>_sliced with the configured cap"""
+        if self._sliced():
+            return getattr(t, name + "_sliced")(*args, max_roots=int(self._cfg.get('sliced_search_max_roots', 0) or 0),
+                                                **kw)
+        return getattr(t, name)(*args, **kw)
+
+    def _conv_path(self, name):
+        n = (self.last_plan or {}).get("slices", 1)
+        return name if n <= 1 else f"{name} ({n} slices)"
+
     def _native_conv_net(self, model, t, shape):
         """What both _fused_conv start from: the native split-precision step network of this class's family,
         with packed heads, when cfg.fused_search (default on) and LZM_FUSED_CONV allow a one-launch search of
@@ -505,11 +532,12 @@ class MuZeroMCTSCtree(_MCTSCtree):
         whose trunk and heads are packed, of a shape and tree size the launch itself accepts — asked of the
         library (DeviceTree.search_conv_plan: head K multiples of 128, supports <= 1024, up to 1024 roots, the
         tree in the workgroup's LDS); None otherwise (the generic per-simulation path). cfg.fused_search
-        (default on) and LZM_FUSED_CONV=0 turn it off."""
+        (default on) and LZM_FUSED_CONV=0 turn it off. With cfg.sliced_search the sliced launches' plan is asked
+        (DeviceTree.search_conv_sliced_plan: any number of roots, in slices of up to 1,024)."""
         net = self._native_conv_net(model, t, shape)
         if net is None:
             return None
-        self.last_plan = t.search_conv_plan(net, t.sims_capacity if S is None else S, categorical=self._categorical())
+        self.last_plan = self._conv_plan(t, net, t.sims_capacity if S is None else S, categorical=self._categorical())
         return net if self.last_plan["supported"] else None
 
     def _step(self, t, net, c, k, native):
@@ -550,14 +578,15 @@ class MuZeroMCTSCtree(_MCTSCtree):
             else:
                 with self._glue(c, step):
                     if cz is not None:  # the conv network's whole search in one launch (lzm_search_conv)
-                        t.search_conv(cz, S, buf.mm, sd, vt, buf.pool, *self._pb_c(), self._discount(),
-                                      self._categorical(), rec=rec)
+                        self._conv_call(t, "search_conv", cz, S, buf.mm, sd, vt, buf.pool, *self._pb_c(),
+                                        self._discount(), self._categorical(), rec=rec)
                     else:
                         packed, dims = fz
                         t.search_mlp(dims, packed, S, buf.mm, sd, vt, buf.pool, *self._pb_c(), self._discount(),
                                      rec=rec)
             self._finish(c, roots, step, rec)
-            self.last_path = "fused-conv" if cz is not None else ("fused-mlp" if fz is not None else "generic")
+            self.last_path = self._conv_path("fused-conv") if cz is not None else (
+                "fused-mlp" if fz is not None else "generic")
 
     def search_with_reuse(self, roots: Any, model: torch.nn.Module, latent_state_roots: List[Any],
                           to_play_batch: Union[int, List[Any]], true_action_list=None, reuse_value_list=None,
@@ -597,12 +626,15 @@ class EfficientZeroMCTSCtree(_MCTSCtree):
         H / 16 LSTM tiles, against the CUs and the kernel's occupancy) still returns the network: an eager
         search() launches, is refused with ResidencyError before anything runs, and counts the fallback; a
         captured one takes the generic path without launching.
-        cfg.fused_search (default on) and LZM_FUSED_CONV=0 turn it off."""
+        cfg.fused_search (default on) and LZM_FUSED_CONV=0 turn it off. With cfg.sliced_search the sliced
+        launches' plan is asked (DeviceTree.search_conv_sliced_plan): a batch past 256 roots or past the
+        co-resident grid runs as slices of whole 64-root blocks, and the co-residency refusal is left only
+        when not even one block fits."""
         net = self._native_conv_net(model, t, shape)
         if net is None or getattr(net, "lstm_frag", None) is None or net.heads["Kr"] != Hl:
             return None
-        plan = t.search_conv_plan(net, t.sims_capacity if S is None else S, H=Hl,
-                                  horizon=int(self._cfg.lstm_horizon_len), categorical=self._categorical())
+        plan = self._conv_plan(t, net, t.sims_capacity if S is None else S, H=Hl,
+                               horizon=int(self._cfg.lstm_horizon_len), categorical=self._categorical())
         self.last_plan = plan
         return net if plan["supported"] or plan["code"] == _lib.LZM_ERR_RESIDENCY else None
 
@@ -674,10 +706,10 @@ class EfficientZeroMCTSCtree(_MCTSCtree):
                 snap = self._snapshot(t)
                 count0 = step["count"].clone() if c.in_kernel else None
             try:
-                t.search_conv_ez(cz, c.S, buf.mm, None if c.in_kernel else buf.seeds, buf.vtp_in, buf.pool,
-                                 buf.extra[0], buf.extra[1], int(cfg.lstm_horizon_len), *self._pb_c(),
-                                 self._discount(), self._categorical(), rec=rec)
-                self.last_path = "fused"
+                self._conv_call(t, "search_conv_ez", cz, c.S, buf.mm, None if c.in_kernel else buf.seeds, buf.vtp_in,
+                                buf.pool, buf.extra[0], buf.extra[1], int(cfg.lstm_horizon_len), *self._pb_c(),
+                                self._discount(), self._categorical(), rec=rec)
+                self.last_path = self._conv_path("fused")
                 if not (guard and t.peek_errors()[0]):
                     return rec
                 t.copy_roots_from(snap)

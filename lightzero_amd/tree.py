@@ -244,6 +244,49 @@ class DeviceTree:
                     out_one_round=bool(self.ez and out[6] == 0),
                     reward_one_round=bool(out[7]))
 
+    def search_conv_sliced_plan(self, net, S, H=0, horizon=1, categorical=True, max_roots=0):
+        """search_conv_plan for search_conv_sliced / search_conv_ez_sliced with the same max_roots
+        (lzm_search_conv_sliced_plan; host only, nothing is launched): search_conv_plan's fields for the largest
+        slice, plus slices, slice_roots (roots per slice) and last_slice_roots (all 0 when refused). A batch that
+        fits one slice gets search_conv_plan's own answer with slices = 1."""
+        hp = net.heads
+        out = (ctypes.c_int32 * 11)()
+        call("lzm_search_conv_sliced_plan", self.h, int(S), int(self.ez), int(H), int(horizon), int(net.n_dres),
+             int(net.n_pres), int(net.r_ch), int(net.h_ch), int(hp["Kr"]), int(hp["Khd"]), int(hp["off_policy"]),
+             int(hp["Vr"]), int(hp["Vv"]), int(bool(categorical)), int(max_roots), out)
+        reason = None if out[0] == 0 else _lib.load().lzm_last_error().decode()
+        return dict(supported=out[0] == 0, code=out[0], reason=reason, workgroups=out[1], lstm_tiles=out[2],
+                    lds_bytes=out[3], pinned=out[4], pbt_rows=out[5], out_rounds=out[6],
+                    out_one_round=bool(self.ez and out[6] == 0), reward_one_round=bool(out[7]),
+                    slices=out[8], slice_roots=out[9], last_slice_roots=out[10])
+
+    def search_conv_sliced(self, net, S, minmax, seeds, vtp_in, pool, pb_c_base=19652, pb_c_init=1.25,
+                           discount=0.997, categorical=True, rec=None, max_roots=0, stream=None):
+        """search_conv over root slices (lzm_search_conv_sliced): any number of roots, one launch per slice of
+        up to min(1024, max_roots or 1024) roots, enqueued here one after another; the same results."""
+        hp = net.heads
+        self._unchecked = True
+        call("lzm_search_conv_sliced", self.h, int(S), int(pb_c_base), float(pb_c_init), float(discount),
+             ptr(minmax), ptr(seeds), ptr(vtp_in), ptr(pool), ptr(net.native), ptr(net.actmap), int(net.n_dres),
+             int(net.n_pres), int(net.r_ch), int(net.h_ch), ptr(hp["w1t"]), ptr(hp["b1"]), ptr(hp["w2q"]),
+             ptr(hp["b2"]), int(hp["Kr"]), int(hp["Khd"]), int(hp["off_policy"]), int(hp["Vr"]), int(hp["Vv"]),
+             int(bool(categorical)), *_rec_ptrs(rec), int(max_roots), stream_ptr(stream))
+
+    def search_conv_ez_sliced(self, net, S, minmax, seeds, vtp_in, pool, hpool, cpool, horizon, pb_c_base=19652,
+                              pb_c_init=1.25, discount=0.997, categorical=True, rec=None, max_roots=0, stream=None):
+        """search_conv_ez over root slices (lzm_search_conv_ez_sliced): batches past 256 roots or past the
+        co-resident grid, one launch per slice (whole blocks of 64 roots, each grid co-resident on its own),
+        enqueued here one after another; the same results. ResidencyError when not even 64 roots fit."""
+        hp, t = net.heads, net.t
+        self._unchecked = True
+        call("lzm_search_conv_ez_sliced", self.h, int(S), int(pb_c_base), float(pb_c_init), float(discount),
+             ptr(minmax), ptr(seeds), ptr(vtp_in), ptr(pool), ptr(hpool), ptr(cpool), int(hpool.shape[2]),
+             int(horizon), ptr(net.native), ptr(net.actmap), int(net.n_dres), int(net.n_pres), int(net.r_ch),
+             int(net.h_ch), ptr(net.lstm_frag), ptr(t["lstm_b"]), ptr(t["vp_s"]), ptr(t["vp_t"]), ptr(hp["w1t"]),
+             ptr(hp["b1"]), ptr(hp["w2q"]), ptr(hp["b2"]), int(hp["Khd"]), int(hp["off_policy"]), int(hp["Vr"]),
+             int(hp["Vv"]), int(bool(categorical)), *_rec_ptrs(rec), *_rec_ptrs(rec, ("is_reset",)), int(max_roots),
+             stream_ptr(stream))
+
     def search_conv(self, net, S, minmax, seeds, vtp_in, pool, pb_c_base=19652, pb_c_init=1.25, discount=0.997,
                     categorical=True, rec=None, stream=None):
         """One launch for the whole search of a conv MuZeroModel (lzm_search_conv; net: a native
