@@ -209,6 +209,13 @@ int lzm_last_traverse_passes(lzm_handle *h, int32_t *out, void *stream);
 /* Device-side numerics helpers exposed for exhaustive checks. */
 int lzm_debug_expf(const float *x, float *out, int64_t n, void *stream);
 int lzm_debug_glibc_rand(uint32_t seed, int n, int32_t *out, void *stream);
+/* div_small (lzm_numerics.h): out[e] = x[e] / (float)d[e] for d[e] in {1, 2, 3} (device arrays, n elements). */
+int lzm_debug_div_small(const float *x, const int32_t *d, float *out, int64_t n, void *stream);
+/* The register walk's mean-q chain (lzm_search_res.h settle_chain) on a synthetic path of n_levels <= 64
+ * levels, one wave: level l has total_q tq[l] and total_v tv[l] in {0, 1, 2}; out_q[l] = the chain's value
+ * through level l, settled in two calls ([0, l / 2), then [l / 2, l]) as a walk that stops on the way does.
+ * Device arrays of n_levels elements. */
+int lzm_debug_settle_chain(const float *tq, const int32_t *tv, int n_levels, float *out_q, void *stream);
 /* Shader-clock cycles per phase of the fused search, summed over workgroups, when the process
  * runs with LZM_PHASE_TIMING=1 (synchronous; reset != 0 clears the counters). Phases: 0 select,
  * 1 draw offsets + look-back, 2 leaf gather, 3 dynamics, 4 reward head + decode, 5 prediction

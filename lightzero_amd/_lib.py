@@ -106,6 +106,8 @@ SIGNATURES = {
     "lzm_check_errors": [_vp, _vp, _i, _vp],
     "lzm_debug_expf": [_vp, _vp, _i64, _vp],
     "lzm_debug_glibc_rand": [_u32, _i, _vp, _vp],
+    "lzm_debug_div_small": [_vp, _vp, _vp, _i64, _vp],
+    "lzm_debug_settle_chain": [_vp, _vp, _i, _vp, _vp],
     "lzm_debug_philox": [_vp, _vp, _i, _vp],
     "lzm_debug_xor": [_vp, _vp, _vp],
     "lzm_debug_az_rules": [_i, _vp, _vp, _vp, _vp],

@@ -610,6 +610,27 @@ __global__ void debug_expf_kernel(const float *x, float *out, long long n) {
     out[e] = glibc_expf(x[e]);
 }
 
+__global__ void debug_div_small_kernel(const float *x, const int32_t *d, float *out, long long n) {
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x)
+    out[e] = div_small(x[e], d[e]);
+}
+
+// lzm_debug_settle_chain: one wave, level l's latent is n - 1 - l (so the gather is no identity): lane L holds
+// the record of latent L, lane l the latent of level l, as in descend_a2r
+__global__ void __launch_bounds__(64) debug_settle_chain_kernel(const float *tq, const int32_t *tv, int n, float *out) {
+  const int lane = threadIdx.x;
+  const int lev = n - 1 - lane;  // the level whose latent is this lane
+  const float rtq = lane < n ? tq[lev] : 0.0f;
+  const int rpk = lane < n ? (tv[lev] & 3) << 5 : 0;
+  const int plev = lane < n ? n - 1 - lane : 0;
+  const bool fin = __ballot(lane < n && (__float_as_int(rtq) & 0x7f800000) == 0x7f800000) == 0ull;  // terms_finite_a2r
+  for (int l = 0; l < n; ++l) {
+    const float q = settle_chain(rtq, rpk, plev, fin, 0, l / 2, 0.0f);
+    const float r = settle_chain(rtq, rpk, plev, fin, l / 2, l + 1, q);
+    if (lane == 0) out[l] = r;
+  }
+}
+
 // lzm_debug_xor: the DPP / permlane butterfly helpers (lzm_tree.h xor_partner / xor_sum / xor_max) beside
 // the ds_bpermute __shfl_xor they replace, one 64-lane wave; rows of out [16][64]:
 //   0-5 xor_partner<1..32>, 6-11 __shfl_xor(v, 1..32), 12 xor_sum, 13 the __shfl_xor butterfly sum,
@@ -1337,6 +1358,23 @@ int lzm_debug_expf(const float *x, float *out, int64_t n, void *stream) {
   long long grid = (n + 255) / 256;
   if (grid > 65536) grid = 65536;
   hipLaunchKernelGGL(debug_expf_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, out, (long long)n);
+  LZM_CHECK_LAUNCH();
+  return LZM_OK;
+}
+
+int lzm_debug_div_small(const float *x, const int32_t *d, float *out, int64_t n, void *stream) {
+  if (!x || !d || !out || n <= 0) return LZM_ERR_ARG;
+  long long grid = (n + 255) / 256;
+  if (grid > 65536) grid = 65536;
+  hipLaunchKernelGGL(debug_div_small_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, d, out,
+                     (long long)n);
+  LZM_CHECK_LAUNCH();
+  return LZM_OK;
+}
+
+int lzm_debug_settle_chain(const float *tq, const int32_t *tv, int n_levels, float *out_q, void *stream) {
+  if (!tq || !tv || !out_q || n_levels <= 0 || n_levels > 64) return LZM_ERR_ARG;
+  hipLaunchKernelGGL(debug_settle_chain_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, tq, tv, n_levels, out_q);
   LZM_CHECK_LAUNCH();
   return LZM_OK;
 }

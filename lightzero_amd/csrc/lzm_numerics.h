@@ -57,6 +57,41 @@ __device__ inline float glibc_expf(float x, const uint64_t *tab = kExp2fTab) {
   return (float)y;
 }
 
+// x / (float)d for d in {1, 2, 3} (the divisors of the two-action mean-q chain) without the IEEE
+// division sequence: with y = RN(1/d), q0 = x * y, r = fma(-d, q0, x), q = fma(r, y, q0) is the
+// correctly rounded quotient for every finite x but -0, subnormals included (f32 denormals are on in
+// these kernels); +-inf give NaN (r is inf - inf) and -0 gives +0. For those and for a NaN, q0 itself
+// is the quotient: +-inf, +-0, and a NaN stays a NaN. Same bits as the division for every non-NaN x
+// (exhaustive check on the host: tools/div_small_check.c, tests/test_div_small.py). Explicit fmaf:
+// the library is built -ffp-contract=off.
+// A 32-bit literal in a scalar register at its point of use. The compiler otherwise materialises such a
+// constant once in a vector register and keeps it there across the whole simulation loop, and the
+// resident search kernel has no vector register to spare.
+template <int C>
+__device__ __forceinline__ int sgpr_literal() {
+  int r;
+  asm volatile("s_mov_b32 %0, %1" : "=s"(r) : "i"(C));
+  return r;
+}
+__device__ __forceinline__ float div_small_y(int d) {
+  // (selected as integers: scalar selects where d is uniform)
+  return __uint_as_float(d == 1 ? 0x3F800000u : (d == 2 ? 0x3F000000u : 0x3EAAAAABu));
+}
+// the three operations alone (nd = -(float)d): for callers that check their operands themselves
+__device__ __forceinline__ float div_small_core(float x, float y, float nd) {
+  const float q0 = x * y;
+  const float r = __fmaf_rn(nd, q0, x);
+  return __fmaf_rn(r, y, q0);
+}
+__device__ __forceinline__ float div_small(float x, int d) {
+  const float y = div_small_y(d);
+  const float q0 = x * y;
+  const float r = __fmaf_rn(-(float)d, q0, x);
+  const float q = __fmaf_rn(r, y, q0);
+  // +-0, +-inf, NaN (v_cmp_class_f32: sNaN 1, qNaN 2, -inf 4, -0 0x20, +0 0x40, +inf 0x200)
+  return __builtin_amdgcn_classf(x, sgpr_literal<0x267>()) ? q0 : q;
+}
+
 // glibc srandom_r initial state (31 words) for `seed` (0 -> 1), Schrage's method.
 __device__ inline void glibc_seed_state(uint32_t seed, uint32_t *z0) {
   if (seed == 0) seed = 1;

@@ -798,14 +798,75 @@ __device__ __forceinline__ bool terms_finite_a2r(const A2Rec &rc, float4 mm) {
   return __ballot(!fin(rc.tq)) == 0ull && fin(mm.x) && fin(mm.y) && fin(mm.z);
 }
 
+// The register walk's mean-q chain over the path levels [pend, upto) (wave 0; lane l holds level l's
+// latent plev, lane L the record (rtq = total_q, rpk = A2Rec::pk) of latent L; parent_q: the chain's
+// value through level pend - 1, 0.0f at pend == 0). Returns the value through level upto - 1:
+//   q_0 = tv_0 > 0 ? tq_0 / tv_0 : (0.0f + tq_0) / 1,   q_l = (q_{l-1} + tq_l) / (tv_l + 1)
+// with descend_a2's operations in level order, so the same bits. With two actions the divisors are
+// 1, 2 or 3 (div_small). Two forms:
+//  - serial: three v_readlane, the add and div_small per level;
+//  - in lanes (kSettleLanesMin levels or more): one ds_bpermute pair gives every path lane its own
+//    tq_l and divisor, then a systolic pass of upto - pend steps in which every lane takes its left
+//    neighbour's value (DPP wave_shr:1; lane 0 reads 0.0f, the root's parent_q), adds its tq and
+//    divides by its own divisor. Lane l's value is final from step l - pend + 1 on, and recomputing
+//    it from final inputs gives the same bits; lanes below pend hold parent_q and stay. Five
+//    vector instructions a step, no readlane, no scalar select: it pays from three levels on
+//    (walk_ubench variant 8, profiles/settle_lanes/). The pass uses div_small's three
+//    operations unguarded and 0.0f + tq for the root's tq, which is exact unless a tq is -0 or a
+//    value of the chain is not finite (an overflowing sum: the terms are finite under leaf_ok): one
+//    ballot after the pass then hands the levels to the serial form, as does !leaf_ok.
+constexpr int kSettleLanesMin = 3;
+__device__ __forceinline__ float settle_chain(float rtq, int rpk, int plev, bool leaf_ok, int pend, int upto,
+                                              float parent_q) {
+  if (upto <= pend) return parent_q;  // (the level above was scored: nothing pending)
+  if (upto - pend >= kSettleLanesMin && leaf_ok) {
+    const int lane = threadIdx.x & 63;
+    const float tq = __int_as_float(__builtin_amdgcn_ds_bpermute(plev << 2, __float_as_int(rtq)));
+    const int tv = (__builtin_amdgcn_ds_bpermute(plev << 2, rpk) >> 5) & 3;
+    const int d = (lane == 0 && tv > 0) ? tv : tv + 1;
+    const float y = div_small_y(d), nd = -(float)d;
+    const bool below = lane < pend;
+    float qv = parent_q;  // (lane pend - 1 is the one that is read)
+    for (int i = pend; i < upto; ++i) {
+      const float in = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(qv), 0x138, 0xF, 0xF, true));
+      const float q = div_small_core(in + tq, y, nd);
+      qv = below ? qv : q;
+    }
+    // lanes [pend, upto): a tq of -0, a value that is inf or NaN (v_cmp_class masks)
+    const unsigned long long range = (~0ull >> (64 - (upto - pend))) << pend;
+    const unsigned long long bad = __builtin_amdgcn_ballot_w64(__builtin_amdgcn_classf(tq, 0x020) ||
+                                                               __builtin_amdgcn_classf(qv, sgpr_literal<0x207>()));
+    if ((bad & range) == 0ull) return readlane_f(qv, upto - 1);
+    parent_q = pend > 0 ? readlane_f(qv, pend - 1) : 0.0f;  // (as it came: it need not stay live over the pass)
+  }
+  const auto level = [&](int l, float &tq) {
+    const int Ls = __builtin_amdgcn_readlane(plev, l);
+    tq = readlane_f(rtq, Ls);
+    return (__builtin_amdgcn_readlane(rpk, Ls) >> 5) & 3;
+  };
+  int l = pend;
+  if (l == 0) {  // the root's rule
+    float tq;
+    const int tv = level(0, tq);
+    parent_q = div_small(tv > 0 ? tq : parent_q + tq, tv > 0 ? tv : 1);
+    l = 1;
+  }
+  for (; l < upto; ++l) {
+    float tq;
+    const int tv = level(l, tq);
+    parent_q = div_small(parent_q + tq, tv + 1);
+  }
+  return parent_q;
+}
+
 // The walk on the terms pass's registers (selection mode 5; S + 2 <= 64, so lane L of wave 0 holds
 // the record of the node with latent L): a chase of v_readlane reads with the current latent in a
 // scalar register, no LDS read per level. A decided level (code 0 / 1) only moves the pointer; a
 // leaf tie (code 4, when leaf_ok: terms_finite_a2r) ends the walk with no floating-point work. The
 // mean-q chain is evaluated only where its value is read — a node with an unvisited child (code
-// 2), a tie between visited children (code 3: the resume needs WalkState::parent_q) — by settle():
-// the same divisions, in level order, over the (total_q, total_v) of the path's levels, so the same
-// bits as descend_a2's level-by-level chain. The path is collected in lanes (lane l: level l's
+// 2), a tie between visited children (code 3: the resume needs WalkState::parent_q) — by settle()
+// (settle_chain above): the same quotients, in level order, over the (total_q, total_v) of the path's
+// levels, so the same bits as descend_a2's level-by-level chain. The path is collected in lanes (lane l: level l's
 // latent and action) and stored once. Same outputs as descend_a2f (Descent, TieInfo, at_tie, path,
 // path_act), every lane returns the same values. With !leaf_ok a leaf tie is scored like code 2:
 // the walk then does what descend_a2 does at every level.
@@ -833,12 +894,7 @@ __device__ inline Descent descend_a2r(const TreeView &t, const A2Rec &rc, bool l
   const auto plat_of = [&]() { return len > 0 ? rl(plev, len - 1) : -1; };
   const auto act_of = [&]() { return len > 0 ? rl(pact, len - 1) : -1; };
   auto settle = [&](int upto) {
-    for (int l = pend; l < upto; ++l) {
-      const int Ls = rl(plev, l);
-      const float tq = rlf(rc.tq, Ls);
-      const int tv = (rl(rc.pk, Ls) >> 5) & 3;
-      parent_q = (l == 0 && tv > 0) ? tq / (float)tv : (parent_q + tq) / (float)(tv + 1);
-    }
+    parent_q = settle_chain(rc.tq, rc.pk, plev, leaf_ok, pend, upto, parent_q);
     pend = upto > pend ? upto : pend;
   };
   auto flush = [&]() {
@@ -908,7 +964,8 @@ __device__ inline Descent descend_a2r(const TreeView &t, const A2Rec &rc, bool l
         const float div = (delta < mm.z) ? mm.z : delta;
         const float tq = rlf(rc.tq, lat);
         const int tv = (pk >> 5) & 3;
-        mean_q = (root && tv > 0) ? tq / (float)tv : (parent_q + tq) / (float)(tv + 1);
+        const bool rootq = root && tv > 0;
+        mean_q = div_small(rootq ? tq : parent_q + tq, rootq ? tv : tv + 1);
         float vu = mm_norm_fixed(scale, mm.y, div, mean_q);
         if (vu < 0) vu = 0;
         if (vu > 1) vu = 1;

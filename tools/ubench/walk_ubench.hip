@@ -5,7 +5,11 @@
 // pressure (its network weights stay in registers for the whole launch).
 // Variants (the numbers of profiles/walk_regs/walk_ubench.txt; 0 and 4 measured walks since removed):
 //   1 descend_a2, 2 the floor (a bare pointer chase), 3 descend_a2f, 5 / 6 the register walk
-//   descend_a2r without / with a final settle of the mean-q chain.
+//   descend_a2r without / with a final settle of the mean-q chain (6: leaf_ok = false, the serial
+//   settle), 7 / 8 the register walk with leaf_ok = true on trees that make it settle: 7 the last node
+//   is scored (its unvisited children have unequal prior scores: the whole chain settles there, in
+//   lanes), 8 a node at depth K (K = 1, 2, 3) has one unvisited child, is scored and the walk goes on to a
+//   leaf tie (a mid-walk stop settling K levels).
 // Build: hipcc -O3 -std=c++17 -ffp-contract=off --offload-arch=gfx950 -o walk_ubench walk_ubench.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -69,14 +73,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           ++len;
         }
         acc += len + 1;
-      } else if (V == 5 || V == 6) {
+      } else if (V >= 5) {
         // descend_a2r: the chase on registers; 5 ends at the leaf tie without the mean-q, 6 scores the
         // last node with it (leaf_ok = false: the whole chain settles there, then the two scores)
         asm volatile("" : "+v"(rc.pk));
-        Descent d = descend_a2r<true>(t, rc, V == 5, mm, vtp, players, rleg, nleg, nodraw, &ti);
+        // (7 / 8: as 5, on main()'s settling trees)
+        Descent d = descend_a2r<true>(t, rc, V != 6, mm, vtp, players, rleg, nleg, nodraw, &ti);
         acc += d.len + ti.status;
       } else {
-        static_assert(V == 1 || V == 2 || V == 3 || V == 5 || V == 6, "variants: 1, 2, 3, 5, 6");
+        static_assert(V == 1 || V == 2 || V == 3 || (V >= 5 && V <= 8), "variants: 1, 2, 3, 5, 6, 7, 8");
         Descent d = V == 1 ? descend_a2<true>(t, nq, dec, cs, mm, vtp, players, rleg, nleg, nodraw, &ti)
                            : descend_a2f<true>(t, nq, dec, cs, mm, vtp, players, rleg, nleg, nodraw, &ti);
         acc += d.len + ti.status;
@@ -119,22 +124,38 @@ static float i2f(int v) {
   return f;
 }
 
-int main() {
-  std::vector<float4> cs(CAP);
-  std::vector<float2> nq(NLAT + 1);
+// kind 0: the full tree (leaves tie); 1: leaves with unequal prior scores (the last node is scored);
+// 2: as 0, but every node at depth `stop` has child 1 unvisited and child 0 the clear winner
+static void make_tree(int kind, int stop, std::vector<float4> &cs, std::vector<float2> &nq) {
   srand(1);
   auto rnd = []() { return (float)rand() / 2147483648.0f; };
   // latent L's children are nodes 1 + 2L + j; expanded children get BFS latents
   int next = 1;
-  for (int L = 0; L < NLAT; ++L)
+  std::vector<int> depth(NLAT + 1, 0);
+  for (int L = 0; L <= NLAT; ++L) nq[L] = make_float2(rnd(), i2f(0));
+  for (int L = 0; L < NLAT; ++L) {
+    int tv = 0;
     for (int j = 0; j < 2; ++j) {
       const int c = 1 + 2 * L + j;
-      const bool exp = next < NLAT;
+      const bool cut = kind == 2 && depth[L] == stop && j == 1;
+      const bool exp = next < NLAT && depth[L] < D - 1 && !cut && L < next;
       const int cl = exp ? next++ : -1;
+      if (exp) depth[cl] = depth[L] + 1;
+      tv += exp ? 1 : 0;
       // expanded children: visited, distinct scores; leaves: unvisited, equal prior scores (tie)
-      cs[c] = make_float4(exp ? rnd() : 0.0f, exp ? rnd() : 0.0f, i2f(cl), i2f(exp ? 1 : 0));
+      float x = exp ? rnd() : 0.0f;
+      if (!exp && kind == 1) x = j ? 0.25f : 0.5f;
+      if (kind == 2 && depth[L] == stop && j == 0) x += 4.0f;
+      cs[c] = make_float4(x, exp ? rnd() : 0.0f, i2f(cl), i2f(exp ? 1 : 0));
     }
-  for (int L = 0; L <= NLAT; ++L) nq[L] = make_float2(rnd(), i2f(L < NLAT / 2 ? 2 : 0));
+    nq[L].y = i2f(tv);
+  }
+}
+
+int main() {
+  std::vector<float4> cs(CAP);
+  std::vector<float2> nq(NLAT + 1);
+  make_tree(0, 0, cs, nq);
   float4 *dcs, *dpin;
   float2 *dnq;
   unsigned long long *dc;
@@ -146,8 +167,11 @@ int main() {
   (void)hipMalloc(&dout, 4 * G);
   (void)hipMalloc(&dpin, sizeof(float4) * 256 * 120);
   (void)hipMemset(dpin, 0, sizeof(float4) * 256 * 120);
-  (void)hipMemcpy(dcs, cs.data(), sizeof(float4) * CAP, hipMemcpyHostToDevice);
-  (void)hipMemcpy(dnq, nq.data(), sizeof(float2) * (NLAT + 1), hipMemcpyHostToDevice);
+  auto upload = [&]() {
+    (void)hipMemcpy(dcs, cs.data(), sizeof(float4) * CAP, hipMemcpyHostToDevice);
+    (void)hipMemcpy(dnq, nq.data(), sizeof(float2) * (NLAT + 1), hipMemcpyHostToDevice);
+  };
+  upload();
   const float4 hmm = make_float4(1.0f, 0.0f, 0.01f, 0.0f);
   const int hgi[8] = {2, 64, 0, 1, 2, 1, -1, 0};
   float4 *dmm;
@@ -161,6 +185,14 @@ int main() {
   run<0, 3>(dcs, dnq, dc, dout, dpin, G, dmm, dgi);
   run<0, 5>(dcs, dnq, dc, dout, dpin, G, dmm, dgi);
   run<0, 6>(dcs, dnq, dc, dout, dpin, G, dmm, dgi);
-
+  make_tree(1, 0, cs, nq);
+  upload();
+  run<0, 7>(dcs, dnq, dc, dout, dpin, G, dmm, dgi);
+  for (int stop = 1; stop <= 3; ++stop) {
+    make_tree(2, stop, cs, nq);
+    upload();
+    printf("stop at depth %d: ", stop);
+    run<0, 8>(dcs, dnq, dc, dout, dpin, G, dmm, dgi);
+  }
   return 0;
 }
