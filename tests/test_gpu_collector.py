@@ -1,8 +1,10 @@
 """GPU: the device collect loop (lzm_cartpole_* kernels, lightzero_amd.collector.DeviceCollector).
 
 Env parity is unpinned (gymnasium is absent): the device CartPole is checked against the numpy
-restatement of the same published equations (oracle/cartpole.py) to float64 round-off; action
-sampling and Dirichlet noise (Philox streams, not numpy's) are checked statistically.
+restatement of the same published equations (oracle/cartpole.py) to float64 round-off. Action
+sampling, Dirichlet noise and the reset draws (Philox streams, not numpy's) are pinned draw for draw to a
+host restatement in tests/test_gpu_collect_rng.py, and that restatement to the sampling laws in
+tests/test_collect_rng.py; the frequency check here is a coarse end-to-end one.
 """
 import numpy as np
 import pytest
