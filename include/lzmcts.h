@@ -184,6 +184,44 @@ int lzm_search_mlp_supported(int actions, int hidden, int head_hidden, int suppo
  * tree slice in LDS}. Reads the same environment overrides as the launch. Host-only, no GPU work. */
 int lzm_search_mlp_plan(const lzm_handle *h, int num_simulations, int hidden, int head_hidden, int support,
                         int res_dynamics, int32_t *out);
+/* ---- One-launch search for EfficientZeroModelMLP, the reward LSTM in the kernel ----
+ * Replaces the per-simulation loop of EfficientZeroMCTSCtree.search (mcts_ctree.py:756-827) over
+ * EfficientZeroModelMLP.recurrent_inference (efficientzero_model_mlp.py:186-216, :252-308) and
+ * DynamicsNetworkMLP.forward (:439-468): the hidden-state gathers (:775-790), the dynamics layers, nn.LSTM's one
+ * step, the value-prefix head, the prediction network, the support decodes, the reset of the hidden state every
+ * lstm_horizon_len levels (:810-816) and cbatch_backpropagate (ctree_efficientzero/lib/cnode.cpp:482-575).
+ * Packed network (lightzero_amd/fused.py pack_efficientzero_mlp), per layer W[K][N] then bias[N], BatchNorm
+ * folded: fc_dynamics(_1)[0], [1], (fc_dynamics_2[0], [1] with res_dynamics), the LSTM gate layer (K = hidden +
+ * lstm_hidden, rows [x ; h_prev], N = 4 lstm_hidden in nn.LSTM order i, f, g, o: [weight_ih_l0 | weight_hh_l0],
+ * bias_ih_l0 + bias_hh_l0), fc_reward_head[0], [1], then the prediction layers as for lzm_mlp_packed_floats. */
+int64_t lzm_mlp_ez_packed_floats(int hidden, int lstm_hidden, int actions, int head_hidden, int support,
+                                 int res_dynamics);
+/* The kernel layout's size and the re-layout itself, as lzm_mlp_kernel_floats / lzm_mlp_prepare
+ * (efficientzero_model_mlp.py:341-475's parameters in the order the kernel's lanes stream them). */
+int64_t lzm_mlp_ez_kernel_floats(int hidden, int lstm_hidden, int actions, int head_hidden, int support,
+                                 int res_dynamics);
+int lzm_mlp_ez_prepare(int hidden, int lstm_hidden, int actions, int head_hidden, int support, int res_dynamics,
+                       const float *packed, float *out, void *stream);
+/* The whole search of an EfficientZero tree in one launch (mcts_ctree.py:756-827). h_pool / c_pool:
+ * float[S+1][B][lstm_hidden] with slot 0 = the roots' reward hidden state; slot k + 1 receives simulation k's
+ * (h1, c1), zeroed for roots whose search_len % lstm_horizon_len == 0 (:810-813). rec_reset (nullable,
+ * int32[S][B]): is_reset per simulation; the other arguments as lzm_search_mlp (rec_decoded: {value prefix,
+ * value}). lzm_search_set_step applies as to the weight-streaming kernel: one launch before and one after.
+ * LZM_ERR_ARG on a MuZero handle, lstm_horizon_len <= 0 or a refused shape (lzm_search_mlp_ez_plan). */
+int lzm_search_mlp_ez(lzm_handle *h, int hidden, int lstm_hidden, int head_hidden, int support, int res_dynamics,
+                      const float *weights, int num_simulations, int lstm_horizon_len, int pb_c_base, float pb_c_init,
+                      float discount, float *minmax, const uint32_t *seeds, const int32_t *virtual_to_play,
+                      float *latent_pool, float *h_pool, float *c_pool, int32_t *rec_x, int32_t *rec_a,
+                      int32_t *rec_len, int32_t *rec_reset, float *rec_decoded, float *rec_logits, void *stream);
+/* 1 when lzm_mlp_ez_prepare / lzm_search_mlp_ez take this network shape (efficientzero_model_mlp.py:16-41's
+ * widths): lzm_search_mlp_supported's rules, and lstm_hidden a multiple of 16 up to 512. Host-only. */
+int lzm_search_mlp_ez_supported(int actions, int hidden, int lstm_hidden, int head_hidden, int support);
+/* What lzm_search_mlp_ez launches for this handle as it stands (the function the launch decides with; reads
+ * LZM_ROOTS_PER_WG as the launch does; the dispatch mcts_ctree.py:756 has no counterpart of). out int32[4]:
+ * {roots per workgroup (1, 2 or 4); kernel: 0 weight-streaming, -1 none (a MuZero handle, a refused shape or LDS
+ * need); 0; tree slice in LDS}. Host-only, no GPU work. */
+int lzm_search_mlp_ez_plan(const lzm_handle *h, int num_simulations, int hidden, int lstm_hidden, int head_hidden,
+                           int support, int res_dynamics, int32_t *out);
 /* int32[4]: {integrity errors: look-back spin timeouts and speculation mismatches (must stay 0),
  * slices resolved serially (ties that reached an expanded child, depth unknown until the draw),
  * such ties whose depth was published early (every draw outcome gives the same depth),

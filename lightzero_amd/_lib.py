@@ -100,6 +100,13 @@ SIGNATURES = {
     "lzm_get_root_outputs": [_vp, _vp, _vp, _vp],
     "lzm_mlp_prepare": [_i, _i, _i, _i, _i, _vp, _vp, _vp],
     "lzm_search_mlp": [_vp, _i, _i, _i, _i, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "lzm_mlp_ez_packed_floats": [_i, _i, _i, _i, _i, _i],
+    "lzm_mlp_ez_kernel_floats": [_i, _i, _i, _i, _i, _i],
+    "lzm_mlp_ez_prepare": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    "lzm_search_mlp_ez": [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                          _vp, _vp, _vp, _vp, _vp],
+    "lzm_search_mlp_ez_supported": [_i, _i, _i, _i, _i],
+    "lzm_search_mlp_ez_plan": [_vp, _i, _i, _i, _i, _i, _i, _vp],
     "lzm_search_diagnostics": [_vp, _vp, _vp],
     "lzm_debug_root_wait_cycles": [_vp, _vp, _i, _i],
     "lzm_search_set_step": [_vp, _vp, _i64, _i, _vp, _vp, _i, _f],
@@ -155,7 +162,8 @@ SIGNATURES = {
                              _vp],
 }
 _RESTYPE = {"lzm_last_error": ctypes.c_char_p, "lzm_mlp_packed_floats": ctypes.c_int64,
-            "lzm_mlp_kernel_floats": ctypes.c_int64, "lzm_az_net_floats": ctypes.c_int64,
+            "lzm_mlp_kernel_floats": ctypes.c_int64, "lzm_mlp_ez_packed_floats": ctypes.c_int64,
+            "lzm_mlp_ez_kernel_floats": ctypes.c_int64, "lzm_az_net_floats": ctypes.c_int64,
             "lzm_conv_trunk_floats": ctypes.c_int64, "lzm_conv_trunk_floats_p": ctypes.c_int64,
             "lzm_ez_lstm_frag_floats": ctypes.c_int64, "lzm_ez_lstm_workspace_bytes": ctypes.c_int64,
             "lzm_error_word": ctypes.c_void_p, "lzm_repr_floats": ctypes.c_int64,

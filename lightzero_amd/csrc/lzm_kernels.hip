@@ -2026,6 +2026,332 @@ int lzm_search_set_step(lzm_handle *h, int64_t *count, int64_t base, int increme
   return LZM_OK;
 }
 
+}  // extern "C"
+
+// ------------------------------------------- fused whole-search (EfficientZeroModelMLP, reward LSTM in-kernel)
+namespace {
+
+// Packed layers of the EfficientZeroModelMLP recurrent network (lightzero_amd/fused.py
+// pack_efficientzero_mlp): the dynamics layers, the LSTM gate layer as one dense layer over [x ; h_prev]
+// (columns in nn.LSTM order i, f, g, o), the value-prefix head, the prediction layers.
+constexpr int kEzLayers = 13;
+void ez_shapes(int H, int Hl, int A, int F, int V, LayerShape *s) {
+  s[0] = {H + A, (H + A + kKC - 1) / kKC * kKC, H};  // fc_dynamics(_1)[0]: [latent; one-hot action]
+  s[1] = {H, H, H};
+  s[2] = {H, H, H};                // fc_dynamics_2 (res_connection_in_dynamics)
+  s[3] = {H, H, H};
+  s[4] = {H + Hl, H + Hl, 4 * Hl};  // [weight_ih_l0 | weight_hh_l0], bias_ih_l0 + bias_hh_l0
+  s[5] = {Hl, Hl, F};              // fc_reward_head (reads h1)
+  s[6] = {F, F, V};
+  s[7] = {H, H, H};                // fc_prediction_common
+  s[8] = {H, H, H};
+  s[9] = {H, H, F};                // fc_value_head
+  s[10] = {F, F, V};
+  s[11] = {H, H, F};               // fc_policy_head
+  s[12] = {F, F, A};
+}
+int ez_kernel_layers(const LayerShape *s, int res, KLayer *kl) {
+  int n = 0;
+  auto one = [&](int l) { kl[n++] = KLayer{l, -1, s[l].K, s[l].N, s[l].N}; };
+  auto two = [&](int a, int b) { kl[n++] = KLayer{a, b, s[a].K, s[a].N + s[b].N, s[a].N}; };
+  one(0);
+  one(1);
+  if (res) {
+    one(2);
+    one(3);
+  }
+  for (int l = 4; l <= 8; ++l) one(l);
+  two(9, 11);
+  two(10, 12);
+  return n;
+}
+void ez_packed_offsets(const LayerShape *s, int res, size_t *w, size_t *b) {
+  size_t off = 0;
+  for (int l = 0; l < kEzLayers; ++l) {
+    w[l] = b[l] = off;
+    if (!layer_used(l, res)) continue;
+    off += (size_t)s[l].krows * s[l].N;
+    b[l] = off;
+    off += s[l].N;
+  }
+}
+// the EfficientZero kernel's own limits on top of the dense steps': the cell's lane map and the h1 rows
+// (the value-prefix head's K) need Hl % kKC == 0, the gate layer at most four column rounds.
+// Widths routed: see DESIGN.md 10 (every width the one-launch path was measured to win at).
+bool ez_shape_ok(int H, int Hl, int A, int F, int V) {
+  return mlp_shape_ok(H, A, F, V) && Hl > 0 && Hl % kKC == 0 && 4 * Hl <= 4 * kThreads;
+}
+// roots per workgroup of the EfficientZero kernel: 1, 2 or 4 (the gate rows of 8 would not leave the tree
+// its LDS), by roots_per_wg's rule
+int ez_roots_per_wg(int B) { return std::min(roots_per_wg(B), 4); }
+// LDS plan: the streaming kernel's, then the gate layer's input [x ; h_prev], the gates, h1 and c_prev
+size_t plan_stream_ez(SearchArgs &p, const lzm_handle *h, int R, int S, int H, int Hl, int A, int F, int V, int res) {
+  size_t o = plan_stream(p, h, R, S, H, A, F, V) / sizeof(float);
+  auto tfl = [R](int K) { return (size_t)((K + kKC - 1) / kKC) * (kKC * R + 4); };
+  p.off_g = o; o += round4(tfl(H + Hl));
+  p.off_gates = o; o += round4(tfl(4 * Hl));
+  p.off_hh = o; o += round4(tfl(Hl));
+  p.off_cp = o; o += round4((size_t)Hl * R);
+  if (!res) p.off_n = p.off_g;  // the next latent is the LSTM's input: the front rows of [x ; h_prev]
+  return o * sizeof(float);
+}
+struct EzPlan {
+  int R, kind, tree_in_lds;
+  size_t lds;
+};
+// What lzm_search_mlp_ez launches (kind 0: the weight-streaming kernel; -1: refused shape or LDS need)
+EzPlan ez_plan(const lzm_handle *h, int H, int Hl, int F, int V, int res, int S, SearchArgs &p) {
+  EzPlan pl{ez_roots_per_wg(h->B), -1, 0, 0};
+  if (!ez_shape_ok(H, Hl, h->A, F, V)) return pl;
+  pl.lds = plan_stream_ez(p, h, pl.R, S, H, Hl, h->A, F, V, res);
+  pl.tree_in_lds = p.tree_in_lds;
+  pl.kind = pl.lds <= kMaxLds ? 0 : -1;
+  return pl;
+}
+// The schedule (efficientzero_model_mlp.py:186-216, :452-468): fc_dynamics(_1) on [latent; one-hot]
+// (+ latent), fc_dynamics_2, the gate layer on [x ; h_prev] (the cell follows it in the kernel), the
+// value-prefix head on h1 (decoded), fc_prediction_common, the merged value | policy head. Padded to an
+// even length with an empty step (the two weight-prefetch buffers alternate).
+void build_schedule_ez(SearchArgs &p, const KLayer *kl, const size_t *w_off, const size_t *b_off, const float *weights,
+                       int res, int A, int V, int F, int R) {
+  const int x0 = (int)p.off_x0, x1 = (int)p.off_x1, x2 = (int)p.off_x2, nl = (int)p.off_n, hd = (int)p.off_h,
+            lg = (int)p.off_logit, gx = (int)p.off_g, gt = (int)p.off_gates, hh = (int)p.off_hh;
+  int n = 0, l = 0;
+  auto add = [&](int in, int out, int relu, int resid, int rowmajor, int ldout, int dec) -> StepRec & {
+    const KLayer &k = kl[l];
+    StepRec &q = p.sched[n++];
+    q.w = weights + w_off[l];
+    q.b = weights + b_off[l];
+    q.K = k.K;
+    q.N = k.N;
+    q.wbytes = (int)(swz_floats(k.K, k.N) * sizeof(float));
+    q.in = in; q.out = out; q.relu = relu; q.resid = resid; q.rowmajor = rowmajor; q.ldout = ldout; q.decode = dec;
+    q.ncol1 = k.N;
+    q.in2 = in; q.out2 = out; q.rowmajor2 = rowmajor; q.ldout2 = ldout;
+    const Split sp = layer_split(k.K, k.N);
+    q.Np = sp.Np; q.splits = sp.splits; q.cpl = sp.cpl; q.log2s = sp.log2s;
+    ++l;
+    return q;
+  };
+  add(x0, x1, 1, -1, 0, 0, 0);                    // fc_dynamics(_1)[0]
+  add(x1, nl, 1, res ? x0 : -1, 0, 0, 0);         // [1] (+ latent); without the residual nl == gx
+  if (res) {
+    add(nl, x1, 1, -1, 0, 0, 0);                  // fc_dynamics_2 -> the LSTM's input rows
+    add(x1, gx, 1, -1, 0, 0, 0);
+  }
+  add(gx, gt, 0, -1, 0, 0, 0);                    // gates = [x ; h_prev] . [W_ih | W_hh] + (b_ih + b_hh)
+  p.cell_after = n - 1;
+  add(hh, hd, 1, -1, 0, 0, 0);                    // fc_reward_head on the unmasked h1
+  add(hd, lg, 0, -1, 1, V + 1, 1);
+  add(nl, x1, 1, -1, 0, 0, 0);                    // fc_prediction_common
+  add(x1, x2, 1, -1, 0, 0, 0);
+  add(x2, hd, 1, -1, 0, 0, 0);                    // [fc_value_head[0] | fc_policy_head[0]]
+  StepRec &o = add(hd, lg, 0, -1, 1, V + 1, 2);   // [fc_value_head[1] | fc_policy_head[1]]
+  o.ncol1 = V;
+  o.in2 = hd + F / kKC * (kKC * R + 4);
+  o.out2 = x1; o.rowmajor2 = 1; o.ldout2 = A;
+  if (n & 1) {  // the empty step: no columns, no weights (every load out of range), one barrier
+    StepRec &q = p.sched[n++];
+    memset(&q, 0, sizeof(q));
+    q.w = weights; q.b = weights;
+    q.resid = -1;
+    const Split sp = layer_split(0, 0);
+    q.Np = sp.Np; q.splits = sp.splits; q.cpl = sp.cpl; q.log2s = sp.log2s;
+  }
+  for (int i = 0; i < 4; ++i) p.stamp_at[i] = -1;
+  p.nsteps = n;
+}
+
+template <int R>
+hipError_t launch_search_ez(const SearchArgs &p, int G, size_t lds, hipStream_t stream) {
+  const void *fn = p.tree_in_lds ? (const void *)search_mlp_kernel<R, true, true>
+                                 : (const void *)search_mlp_kernel<R, false, true>;
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  if (p.tree_in_lds)
+    hipLaunchKernelGGL((search_mlp_kernel<R, true, true>), dim3(G), dim3(kThreads), lds, stream, p);
+  else
+    hipLaunchKernelGGL((search_mlp_kernel<R, false, true>), dim3(G), dim3(kThreads), lds, stream, p);
+  return hipGetLastError();
+}
+}  // namespace
+
+extern "C" {
+
+int64_t lzm_mlp_ez_packed_floats(int hidden, int lstm_hidden, int actions, int head_hidden, int support,
+                                 int res_dynamics) {
+  if (hidden <= 0 || lstm_hidden <= 0 || actions <= 0 || head_hidden <= 0 || support <= 0) return -1;
+  LayerShape s[kEzLayers];
+  ez_shapes(hidden, lstm_hidden, actions, head_hidden, support, s);
+  int64_t n = 0;
+  for (int l = 0; l < kEzLayers; ++l)
+    if (layer_used(l, res_dynamics)) n += (int64_t)s[l].krows * s[l].N + s[l].N;
+  return n;
+}
+
+int64_t lzm_mlp_ez_kernel_floats(int hidden, int lstm_hidden, int actions, int head_hidden, int support,
+                                 int res_dynamics) {
+  if (hidden <= 0 || lstm_hidden <= 0 || actions <= 0 || head_hidden <= 0 || support <= 0) return -1;
+  LayerShape s[kEzLayers];
+  ez_shapes(hidden, lstm_hidden, actions, head_hidden, support, s);
+  KLayer kl[kEzLayers];
+  const int nk = ez_kernel_layers(s, res_dynamics, kl);
+  size_t w_off[kEzLayers], b_off[kEzLayers];
+  return (int64_t)kernel_layout(kl, nk, w_off, b_off);
+}
+
+int lzm_mlp_ez_prepare(int hidden, int lstm_hidden, int actions, int head_hidden, int support, int res_dynamics,
+                       const float *packed, float *out, void *stream) {
+  if (!packed || !out || hidden <= 0 || lstm_hidden <= 0 || actions <= 0 || head_hidden <= 0 || support <= 0 ||
+      hidden % kKC != 0 || head_hidden % kKC != 0 || lstm_hidden % kKC != 0) {
+    set_err("lzm_mlp_ez_prepare: bad arguments (hidden, LSTM and head widths must be multiples of 16)");
+    return LZM_ERR_ARG;
+  }
+  LayerShape s[kEzLayers];
+  ez_shapes(hidden, lstm_hidden, actions, head_hidden, support, s);
+  size_t pw[kEzLayers], pb[kEzLayers];
+  ez_packed_offsets(s, res_dynamics, pw, pb);
+  KLayer kl[kEzLayers];
+  const int nk = ez_kernel_layers(s, res_dynamics, kl);
+  size_t w_off[kEzLayers], b_off[kEzLayers];
+  kernel_layout(kl, nk, w_off, b_off);
+  for (int l = 0; l < nk; ++l) {
+    const KLayer &q = kl[l];
+    const size_t n = swz_floats(q.K, q.N);
+    const int s1 = q.src1 >= 0 ? q.src1 : q.src0;
+    hipLaunchKernelGGL(mlp_swizzle_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       packed + pw[q.src0], s[q.src0].krows, packed + pw[s1], s[s1].krows, q.K, q.N, q.N0,
+                       out + w_off[l], n);
+    LZM_CHECK_LAUNCH();
+    LZM_HIP(hipMemcpyAsync(out + b_off[l], packed + pb[q.src0], (size_t)q.N0 * sizeof(float),
+                           hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (q.src1 >= 0)
+      LZM_HIP(hipMemcpyAsync(out + b_off[l] + q.N0, packed + pb[q.src1], (size_t)(q.N - q.N0) * sizeof(float),
+                             hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  }
+  return LZM_OK;
+}
+
+int lzm_search_mlp_ez_supported(int actions, int hidden, int lstm_hidden, int head_hidden, int support) {
+  return ez_shape_ok(hidden, lstm_hidden, actions, head_hidden, support) ? 1 : 0;
+}
+
+int lzm_search_mlp_ez_plan(const lzm_handle *h, int num_simulations, int hidden, int lstm_hidden, int head_hidden,
+                           int support, int res_dynamics, int32_t *out) {
+  if (!h || !out || num_simulations <= 0) {
+    set_err("lzm_search_mlp_ez_plan: null argument or no simulations");
+    return LZM_ERR_ARG;
+  }
+  if (num_simulations > h->sims_cap) {
+    snprintf(g_err, sizeof(g_err), "lzm_search_mlp_ez_plan: %d simulations > reserved %d (lzm_reserve)",
+             num_simulations, h->sims_cap);
+    return LZM_ERR_CAPACITY;
+  }
+  SearchArgs p;
+  memset(&p, 0, sizeof(p));
+  const EzPlan pl = ez_plan(h, hidden, lstm_hidden, head_hidden, support, res_dynamics, num_simulations, p);
+  out[0] = pl.R;
+  out[1] = (h->flags & LZM_TREE_EZ) ? pl.kind : -1;
+  out[2] = 0;
+  out[3] = pl.tree_in_lds;
+  return LZM_OK;
+}
+
+int lzm_search_mlp_ez(lzm_handle *h, int hidden, int lstm_hidden, int head_hidden, int support, int res_dynamics,
+                      const float *weights, int num_simulations, int lstm_horizon_len, int pb_c_base, float pb_c_init,
+                      float discount, float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
+                      float *h_pool, float *c_pool, int32_t *rec_x, int32_t *rec_a, int32_t *rec_len,
+                      int32_t *rec_reset, float *rec_decoded, float *rec_logits, void *stream) {
+  if (!h || !weights || !minmax || (!seeds && !h->step_count) || !vtp_in || !latent_pool || !h_pool || !c_pool ||
+      num_simulations <= 0) {
+    set_err("lzm_search_mlp_ez: null argument or no simulations");
+    return LZM_ERR_ARG;
+  }
+  if ((uintptr_t)weights & 15) {
+    set_err("lzm_search_mlp_ez: weights must be 16-byte aligned (lzm_mlp_ez_prepare output)");
+    return LZM_ERR_ARG;
+  }
+  if (!(h->flags & LZM_TREE_EZ)) {
+    set_err("lzm_search_mlp_ez: EfficientZero trees only");
+    return LZM_ERR_ARG;
+  }
+  if (lstm_horizon_len <= 0) {
+    set_err("lzm_search_mlp_ez: lstm_horizon_len must be > 0");
+    return LZM_ERR_ARG;
+  }
+  const int H = hidden, Hl = lstm_hidden, F = head_hidden, V = support, A = h->A, S = num_simulations;
+  if (!ez_shape_ok(H, Hl, A, F, V)) {
+    set_err("lzm_search_mlp_ez: unsupported network shape (lzm_search_mlp_ez_supported)");
+    return LZM_ERR_ARG;
+  }
+  if (S > h->sims_cap) {
+    snprintf(g_err, sizeof(g_err), "lzm_search_mlp_ez: %d simulations > reserved %d (lzm_reserve)", S, h->sims_cap);
+    return LZM_ERR_CAPACITY;
+  }
+  int rc = fill_lut(h, pb_c_base, pb_c_init);
+  if (rc != LZM_OK) return rc;
+  SearchArgs p;
+  memset(&p, 0, sizeof(p));
+  const EzPlan plan = ez_plan(h, H, Hl, F, V, res_dynamics, S, p);
+  if (plan.kind != 0) {
+    snprintf(g_err, sizeof(g_err), "lzm_search_mlp_ez: %zu B of LDS needed (network or tree too large)", plan.lds);
+    return LZM_ERR_ARG;
+  }
+  const int R = plan.R;
+  const int G = (h->B + R - 1) / R;
+  const bool fast = (h->flags & LZM_RNG_FAST) != 0;
+  if (!fast) {
+    rc = ensure_coef(h, h->B * (S + 1) + 64);
+    if (rc != LZM_OK) return rc;
+  }
+  rc = ensure_flags(h, S, G);
+  if (rc != LZM_OK) return rc;
+  p.stat = h->stat; p.meta = h->meta; p.legal = h->legal; p.nlegal = h->nlegal;
+  p.path = h->path; p.path_act = h->path_act; p.pathlen = h->pathlen; p.lut = h->lut;
+  p.B = h->B; p.A = A; p.cap = h->cap; p.lut_n = h->lut_n; p.depth_cap = h->depth_cap;
+  p.S = S; p.disc = discount; p.seeds = seeds; p.vtp_in = vtp_in; p.minmax = (float4 *)minmax; p.pool = latent_pool;
+  p.H = H; p.F = F; p.V = V; p.res = res_dynamics ? 1 : 0;
+  p.hpool = h_pool; p.cpool = c_pool; p.Hl = Hl; p.horizon = lstm_horizon_len; p.rec_reset = rec_reset;
+  p.coef = h->coef; p.coef_positions = h->coef_positions; p.pow16807 = h->pow16807;
+  p.flags = h->lb_flags; p.epoch = h->epoch; p.diag = h->search_diag; p.fast = fast ? 1 : 0;
+  p.rec_x = rec_x; p.rec_a = rec_a; p.rec_len = rec_len; p.rec_dec = rec_decoded; p.rec_logits = rec_logits;
+  {
+    LayerShape s[kEzLayers];
+    ez_shapes(H, Hl, A, F, V, s);
+    KLayer kls[kEzLayers];
+    const int nkl = ez_kernel_layers(s, res_dynamics, kls);
+    size_t lay_w[kEzLayers], lay_b[kEzLayers];
+    kernel_layout(kls, nkl, lay_w, lay_b);
+    build_schedule_ez(p, kls, lay_w, lay_b, weights, res_dynamics ? 1 : 0, A, V, F, R);
+  }
+  // collect-step mode: the prologue and epilogue launches of lzm_search_mlp's streaming kernel
+  if (h->step_count || h->step_fresh) {
+    if (h->step_count && h->step_seeds_n < S) {
+      set_err("lzm_search_mlp_ez: step seeds buffer smaller than num_simulations (reserve first)");
+      return LZM_ERR_STATE;
+    }
+    const int n = std::max(S, h->B);
+    hipLaunchKernelGGL(step_prologue_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->step_count,
+                       h->step_base, S, h->step_seeds, (float4 *)minmax, h->B, h->step_fresh, h->step_delta);
+    LZM_CHECK_LAUNCH();
+    if (h->step_count) p.seeds = reinterpret_cast<const uint32_t *>(h->step_seeds);
+  }
+  hipError_t e;
+  switch (R) {
+    case 1: e = launch_search_ez<1>(p, G, plan.lds, (hipStream_t)stream); break;
+    case 2: e = launch_search_ez<2>(p, G, plan.lds, (hipStream_t)stream); break;
+    default: e = launch_search_ez<4>(p, G, plan.lds, (hipStream_t)stream); break;
+  }
+  LZM_HIP(e);
+  LZM_CHECK_LAUNCH();
+  if ((h->step_count && h->step_inc) || h->step_dist || h->step_vals) {
+    hipLaunchKernelGGL(step_epilogue_kernel, dim3((h->B + 255) / 256), dim3(256), 0, (hipStream_t)stream, view(h),
+                       h->step_dist, h->step_vals, h->step_inc ? h->step_count : nullptr);
+    LZM_CHECK_LAUNCH();
+  }
+  return LZM_OK;
+}
+
 int lzm_debug_phase_cycles(lzm_handle *h, uint64_t *out_host, int reset) {
   if (!h || !out_host) return LZM_ERR_ARG;
   if (!h->phase) {

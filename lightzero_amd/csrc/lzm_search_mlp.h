@@ -20,10 +20,17 @@
 // (random_r is linear over Z/2^32). Roots whose depth does depend on a draw are resolved after
 // the predecessors' counts are known (exact serial semantics, slower). Fast mode uses Philox
 // per (seed, root, level) and skips the look-back.
+//
+// search_mlp_kernel<R, TL, true> is the same launch for the EfficientZeroModelMLP family
+// (lzero/model/efficientzero_model_mlp.py:14-475; EfficientZeroMCTSCtree.search, mcts_ctree.py:756-827): the
+// EfficientZero walk, expansion and backup, the reward LSTM's state gathered and filed beside the latents, its
+// gate layer as one more schedule step and its cell after it (ez_cell below). The MuZero instantiations are
+// untouched by it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lzm_lstm.h"
 #include "lzm_numerics.h"
 #include "lzm_tree.h"
 
@@ -101,6 +108,14 @@ struct SearchArgs {
   float mm_delta;
   int32_t *out_dist;
   float *out_values;
+  // EfficientZero (search_mlp_kernel<R, TL, true>; unused otherwise): the reward LSTM's state pools
+  // [S + 1][B][Hl] (slot 0 = the roots' state), its width, lstm_horizon_len, the schedule step whose
+  // output is the gate pre-activations (the cell runs after it), and the LDS float offsets of the gate
+  // layer's input rows [x ; h_prev], the gates [4 Hl][r], h1 [Hl][r] and c_prev [r][Hl]
+  float *hpool, *cpool;
+  int Hl, horizon, cell_after;
+  int32_t *rec_reset;  // nullable: is_reset [S][B]
+  size_t off_g, off_gates, off_hh, off_cp;
 };
 
 // ------------------------------------------------------------------------------ LDS helpers
@@ -396,7 +411,7 @@ __device__ __forceinline__ void store_col(const StepRec &s, float *smem_f, const
 // expectation (scaling_transform.py:118-121: softmax, then sum p_j * (j - (V-1)/2)) is reduced
 // across the workgroup from registers and h^-1 applied (InverseScalarTransform), into dec_out[r].
 // `red`: 3 * kWaves * R floats of LDS. The caller's barrier follows.
-template <int R, int P>
+template <int R, int P, bool XR = false>
 __device__ __forceinline__ void dense_step(const StepRec &s, float *smem_f, float *w, float &bias, float *red,
                                           float *dec_out, int nr, const StepRec &sn, int diag = 0) {
   const int tid = threadIdx.x;
@@ -439,6 +454,21 @@ __device__ __forceinline__ void dense_step(const StepRec &s, float *smem_f, floa
           } else {
             store_col<R>(s, smem_f, residT, c, a2);
           }
+        }
+      }
+    }
+    if constexpr (XR) {
+      // column rounds past the decode's (the EfficientZero gate layer: up to 4 Hl = 2048 columns), stored
+      for (int u = kMaxRounds; u * kThreads < N; ++u) {
+        const int c = u * kThreads + tid;
+        const int nu = N - u * kThreads < kThreads ? N - u * kThreads : kThreads;
+        if (c < N) {
+          float a2[R];
+          const float b = ((gfloat_p)s.b)[c];
+#pragma unroll
+          for (int r = 0; r < R; ++r) a2[r] = b;
+          dot_stream<R>((gfloat4_p)(s.w + (size_t)u * kThreads * s.K), nu, tid, 0, s.cpl, 0, in_of(c), a2);
+          store_col<R>(s, smem_f, residT, c, a2);
         }
       }
     }
@@ -640,7 +670,37 @@ __device__ inline void build_pbt(const float2 *lut, int rows, float *lpbt, int t
   }
 }
 
-template <int R, bool TL>
+// The reward LSTM's cell for the workgroup's rows (efficientzero_model_mlp.py:464-465, nn.LSTM gate
+// order i, f, g, o), one lane per (row, unit), lzm_lstm.h's arithmetic (ez_lstm_cell_kernel): the gate
+// pre-activations are the gate step's output in LDS, c_prev was staged with the gather. The unmasked h1
+// goes to LDS for the value-prefix head; slot k + 1 of both state pools gets h1 / c1, zeroed for rows
+// whose search_len % lstm_horizon_len == 0 (mcts_ctree.py:810-816). The caller's barrier follows.
+template <int R>
+__device__ __forceinline__ void ez_cell(const SearchArgs &p, float *smem, int k, int i0, int nr, const int *s_len) {
+  const int Hl = p.Hl, B = p.B;
+  const float *GT = smem + p.off_gates, *CP = smem + p.off_cp;
+  float *HH = smem + p.off_hh;
+  for (int e = threadIdx.x; e < Hl * R; e += kThreads) {
+    const int r = e / Hl, u = e % Hl;
+    const float gi = GT[tpos<R>(u, r)], gf = GT[tpos<R>(Hl + u, r)], gg = GT[tpos<R>(2 * Hl + u, r)],
+                go = GT[tpos<R>(3 * Hl + u, r)];
+    const float c0 = CP[e];
+    const float cc = lstm_sigmoid(gf) * c0 + lstm_sigmoid(gi) * tanhf(gg);
+    const float hh = lstm_sigmoid(go) * tanhf(cc);
+    HH[tpos<R>(u, r)] = hh;
+    if (r < nr) {
+      const bool reset = (s_len[r] % p.horizon) == 0;
+      const size_t o = ((size_t)(k + 1) * B + i0 + r) * Hl + u;
+      p.hpool[o] = reset ? 0.0f : hh;
+      p.cpool[o] = reset ? 0.0f : cc;
+    }
+  }
+}
+
+// EZ: the EfficientZero search over EfficientZeroModelMLP (mcts_ctree.py:756-827): the EfficientZero
+// walk, expansion (is_reset) and backup, the reward LSTM's state gathered from / filed into the state
+// pools beside the latents, its gate layer as a schedule step and its cell after it (ez_cell).
+template <int R, bool TL, bool EZ = false>
 __global__ __launch_bounds__(kThreads) void search_mlp_kernel(SearchArgs p) {
   extern __shared__ float4 smem4[];
   float *smem = reinterpret_cast<float *>(smem4);
@@ -756,13 +816,13 @@ __global__ __launch_bounds__(kThreads) void search_mlp_kernel(SearchArgs p) {
           uint4 o = philox4x32_10(make_uint4((uint32_t)level, (uint32_t)i, 0u, 0u), make_uint2(seed, 0x4c5a4d43u));
           return o.x >> 1;
         };
-        Descent d = descend_wave<false, false>(tv, ti, li, R, s_mm[li], players, s_vtp[li], p.disc, draw, nullptr);
+        Descent d = descend_wave<EZ, false>(tv, ti, li, R, s_mm[li], players, s_vtp[li], p.disc, draw, nullptr);
         if (lead) { s_len[li] = d.len; s_x[li] = d.x; s_act[li] = d.action; s_status[li] = 0; }
       } else {
         // classification pass: no draw values needed unless a tie involves an expanded child
         TieInfo ti_info;
         auto nodraw = [](int) -> uint32_t { return 0u; };
-        Descent d = descend_wave<false, true>(tv, ti, li, R, s_mm[li], players, s_vtp[li], p.disc, nodraw, &ti_info);
+        Descent d = descend_wave<EZ, true>(tv, ti, li, R, s_mm[li], players, s_vtp[li], p.disc, nodraw, &ti_info);
         if (lead) {
           s_len[li] = d.len; s_x[li] = d.x; s_act[li] = d.action;
           s_status[li] = ti_info.status;
@@ -826,7 +886,7 @@ __global__ __launch_bounds__(kThreads) void search_mlp_kernel(SearchArgs p) {
             auto draw = [coef, npos, diag, off](int level) -> uint32_t {
               return glibc_draw(coef, npos, s_z0, off + level, diag);
             };
-            Descent d = descend_slice<false, false>(tv, ti, li, R, s_mm[li], players, s_vtp[li], p.disc, draw, nullptr);
+            Descent d = descend_slice<EZ, false>(tv, ti, li, R, s_mm[li], players, s_vtp[li], p.disc, draw, nullptr);
             s_len[li] = d.len; s_x[li] = d.x; s_act[li] = d.action; s_status[li] = 0;
             total += d.len;
           }
@@ -860,6 +920,9 @@ __global__ __launch_bounds__(kThreads) void search_mlp_kernel(SearchArgs p) {
       p.rec_x[(size_t)k * B + i0 + tid] = s_x[tid];
       p.rec_a[(size_t)k * B + i0 + tid] = s_act[tid];
       p.rec_len[(size_t)k * B + i0 + tid] = s_len[tid];
+      if constexpr (EZ) {
+        if (p.rec_reset) p.rec_reset[(size_t)k * B + i0 + tid] = (s_len[tid] % p.horizon) == 0 ? 1 : 0;
+      }
     }
     LZM_STAMP(1);
     // ---- gather leaf latents: X0[h][r] = pool[x_r][i0+r][h]
@@ -873,6 +936,22 @@ __global__ __launch_bounds__(kThreads) void search_mlp_kernel(SearchArgs p) {
     for (int e = tid; e < (p.sched[0].K - H) * R; e += kThreads) {
       const int a = e / R, r = e % R;
       X0[tpos<R>(H + a, r)] = (r < nr && s_act[r] == a) ? 1.0f : 0.0f;
+    }
+    if constexpr (EZ) {
+      // the leaf's LSTM state (mcts_ctree.py:775-790): h_prev = hpool[x_r][i0+r] as rows H .. H + Hl of the
+      // gate layer's input, c_prev = cpool[x_r][i0+r] for the cell
+      float *GH = smem + p.off_g, *CP = smem + p.off_cp;
+      for (int e = tid; e < p.Hl * R; e += kThreads) {
+        const int r = e / p.Hl, u = e % p.Hl;
+        float hv = 0.0f, cv = 0.0f;
+        if (r < nr) {
+          const size_t o = ((size_t)max(s_x[r], 0) * B + i0 + r) * p.Hl + u;
+          hv = p.hpool[o];
+          cv = p.cpool[o];
+        }
+        GH[tpos<R>(H + u, r)] = hv;
+        CP[e] = cv;
+      }
     }
     __syncthreads();
     LZM_STAMP(2);
@@ -890,7 +969,7 @@ __global__ __launch_bounds__(kThreads) void search_mlp_kernel(SearchArgs p) {
     unsigned long long sub_ = p.phase ? __builtin_amdgcn_s_memtime() : 0ull;                         \
     const int nx = st_ + kPrefetchAhead < p.nsteps ? st_ + kPrefetchAhead : st_ + kPrefetchAhead - p.nsteps; \
     float *dec = q.decode == 1 ? s_r : s_v;                                                          \
-    dense_step<R, P>(q, smem, W, BIAS, s_red, dec, nr, p.sched[nx], p.diag_mode);                    \
+    dense_step<R, P, EZ>(q, smem, W, BIAS, s_red, dec, nr, p.sched[nx], p.diag_mode);                \
     LZM_SUBSTAMP(16 + 4 * st_);                                                                      \
     if (p.diag_mode != 5) __syncthreads();                                                           \
     LZM_SUBSTAMP(17 + 4 * st_);                                                                      \
@@ -900,6 +979,12 @@ __global__ __launch_bounds__(kThreads) void search_mlp_kernel(SearchArgs p) {
         if ((tid & 63) == 0) dec[r] = h_inverse(e);                                                  \
       }                                                                                              \
       __syncthreads();                                                                               \
+    }                                                                                                \
+    if constexpr (EZ) {                                                                              \
+      if (st_ == p.cell_after) { /* the gates are in LDS: the cell, h1 for the value-prefix head */  \
+        ez_cell<R>(p, smem, k, i0, nr, s_len);                                                       \
+        __syncthreads();                                                                             \
+      }                                                                                              \
     }                                                                                                \
     if (st_ == p.stamp_at[0]) LZM_STAMP(3);                                                          \
     if (st_ == p.stamp_at[1]) LZM_STAMP(4);                                                          \
@@ -937,8 +1022,17 @@ __global__ __launch_bounds__(kThreads) void search_mlp_kernel(SearchArgs p) {
       int vtp = s_vtp[li];
       if (players > 1)
         for (int l = 0; l < len; ++l) vtp = (vtp == 1) ? 2 : 1;
-      expand_wave(tv, ti, leaf, vtp, k + 1, s_r[li], X1 + li * A);
-      backup_wave(tv, ti, li, R, &s_mm[li], vtp, s_v[li], p.disc);
+      if constexpr (EZ) {
+        // is_reset of every leaf (mcts_ctree.py:810-816), the EfficientZero backup, best_action along the
+        // path (ctree_efficientzero/lib/cnode.cpp:482-575, :806)
+        expand_wave(tv, ti, leaf, vtp, k + 1, s_r[li], X1 + li * A, (len % p.horizon) == 0 ? 1 : 0);
+        for (int l = tid & 63; l < len; l += 64)
+          tv.meta[nidx(tv, tv.path[(size_t)l * R + li], ti)].best = tv.path_act[(size_t)l * R + li];
+        backup_wave_ez(tv, ti, li, R, &s_mm[li], vtp, s_v[li], p.disc);
+      } else {
+        expand_wave(tv, ti, leaf, vtp, k + 1, s_r[li], X1 + li * A);
+        backup_wave(tv, ti, li, R, &s_mm[li], vtp, s_v[li], p.disc);
+      }
     }
     __syncthreads();
     LZM_STAMP(9);

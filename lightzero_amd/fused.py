@@ -1,4 +1,5 @@
-"""Fused whole-search path for MuZeroModelMLP-shaped networks (lzm_search_mlp, include/lzmcts.h).
+"""Fused whole-search path for MuZeroModelMLP-shaped networks (lzm_search_mlp, include/lzmcts.h) and, with
+the reward LSTM, EfficientZeroModelMLP-shaped ones (lzm_search_mlp_ez; describe_ez / pack_efficientzero_mlp).
 
 ``pack_muzero_mlp(model)`` folds every eval-mode BatchNorm1d into the Linear in front of it
 (W' = W * gamma/sqrt(var+eps), b' = (b - mean) * gamma/sqrt(var+eps) + beta) and lays the
@@ -60,7 +61,7 @@ def _linear_bn_pairs(seq):
     return out
 
 
-def _fold(lin, bn):
+def _fold(lin, bn, dtype=torch.float32):
     W = lin.weight.detach().to(torch.float64)
     b = lin.bias.detach().to(torch.float64) if lin.bias is not None else torch.zeros(W.shape[0], dtype=torch.float64,
                                                                                       device=W.device)
@@ -70,11 +71,12 @@ def _fold(lin, bn):
         s = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
         W = W * s[:, None]
         b = (b - bn.running_mean.detach().double()) * s + bn.bias.detach().double()
-    return W.float(), b.float()
+    return W.to(dtype), b.to(dtype)
 
 
-def describe(model):
-    """Returns (layers [(W, b, relu)], dims dict) or raises NotPackable."""
+def describe(model, dtype=torch.float32):
+    """Returns (layers [((W, b), relu)], dims dict) or raises NotPackable. dtype: of the folded layers (the
+    folding itself runs in float64; the packers take float32)."""
     dyn = getattr(model, "dynamics_network", None)
     pred = getattr(model, "prediction_network", None)
     if dyn is None or pred is None:
@@ -96,7 +98,7 @@ def describe(model):
     for g, e in zip(groups, expect_relu):
         if [r for _, _, r in g] != e:
             raise NotPackable("unexpected activation placement")
-    layers = [(_fold(l, bn), relu) for g in groups for (l, bn, relu) in g]
+    layers = [(_fold(l, bn, dtype), relu) for g in groups for (l, bn, relu) in g]
     H = layers[0][0][0].shape[0]
     A = layers[0][0][0].shape[1] - H
     off = 4 if res else 2
@@ -124,14 +126,64 @@ def pack_muzero_mlp(model, device):
     return flat, dims
 
 
+def _ez_args(dims):
+    return (dims["hidden"], dims["lstm_hidden"], dims["actions"], dims["head_hidden"], dims["support"],
+            int(dims["res"]))
+
+
+def describe_ez(model, dtype=torch.float32):
+    """describe() for EfficientZeroModelMLP (efficientzero_model_mlp.py:14-338, :341-475): returns (layers
+    [((W, b), relu)], dims dict with lstm_hidden) in the packed order — the dynamics layers, the LSTM's gate
+    layer as one dense layer over [x ; h_prev] (W = [weight_ih_l0 | weight_hh_l0], nn.LSTM's gate order i, f, g, o;
+    bias = bias_ih_l0 + bias_hh_l0 summed in float64), the value-prefix head, the prediction layers — or raises
+    NotPackable: everything describe() refuses, a model without the reward LSTM (MuZero), and an LSTM with
+    more than one layer, two directions, a projection or no biases."""
+    dyn = getattr(model, "dynamics_network", None)
+    lstm = getattr(dyn, "lstm", None)
+    if not isinstance(lstm, nn.LSTM):
+        raise NotPackable("not an EfficientZeroModelMLP (no dynamics_network.lstm)")
+    if lstm.num_layers != 1 or lstm.bidirectional or not lstm.bias or getattr(lstm, "proj_size", 0):
+        raise NotPackable("reward LSTM must be one unidirectional layer with biases")
+    layers, dims = describe(model, dtype)  # (the same attribute names; fc_reward_head reads the LSTM's output)
+    H, Hl = dims["hidden"], lstm.hidden_size
+    nd = 4 if dims["res"] else 2
+    if lstm.input_size != H or layers[nd][0][0].shape[1] != Hl:
+        raise NotPackable("LSTM input / value-prefix head widths do not match the dynamics network")
+    W = torch.cat((lstm.weight_ih_l0.detach().double(), lstm.weight_hh_l0.detach().double()), dim=1)
+    b = lstm.bias_ih_l0.detach().double() + lstm.bias_hh_l0.detach().double()
+    layers = layers[:nd] + [((W.to(dtype), b.to(dtype)), False)] + layers[nd:]
+    return layers, dict(dims, lstm_hidden=Hl)
+
+
+def pack_efficientzero_mlp(model, device):
+    layers, dims = describe_ez(model)
+    L = _lib.load()
+    if not L.lzm_search_mlp_ez_supported(dims["actions"], dims["hidden"], dims["lstm_hidden"], dims["head_hidden"],
+                                         dims["support"]):
+        raise NotPackable("network shape outside the search kernel's range: {}".format(dims))
+    parts = []
+    for (W, b), _ in layers:
+        parts.append(W.t().contiguous().reshape(-1))
+        parts.append(b.reshape(-1))
+    flat = torch.cat(parts).to(device=device, dtype=torch.float32).contiguous()
+    n = L.lzm_mlp_ez_packed_floats(*_ez_args(dims))
+    if n != flat.numel():
+        raise NotPackable(f"packed size {flat.numel()} != expected {n}")
+    return flat, dims
+
+
 def prepare_kernel_weights(flat, dims, out=None):
-    """Packed network -> the search kernel's lane-order layout (lzm_mlp_prepare, on the current stream);
-    out: optional existing buffer of the right size to refill in place."""
-    args = (dims["hidden"], dims["actions"], dims["head_hidden"], dims["support"], int(dims["res"]))
-    n = _lib.load().lzm_mlp_kernel_floats(*args)
+    """Packed network -> the search kernel's lane-order layout (lzm_mlp_prepare, or lzm_mlp_ez_prepare for
+    dims with lstm_hidden, on the current stream); out: optional existing buffer of the right size to refill
+    in place."""
+    ez = "lstm_hidden" in dims
+    args = _ez_args(dims) if ez else (dims["hidden"], dims["actions"], dims["head_hidden"], dims["support"],
+                                      int(dims["res"]))
+    n = getattr(_lib.load(), "lzm_mlp_ez_kernel_floats" if ez else "lzm_mlp_kernel_floats")(*args)
     if out is None or out.numel() != n or out.device != flat.device:
         out = torch.empty(n, dtype=torch.float32, device=flat.device)
-    _lib.call("lzm_mlp_prepare", *args, _lib.ptr(flat), _lib.ptr(out), _lib.stream_ptr())
+    _lib.call("lzm_mlp_ez_prepare" if ez else "lzm_mlp_prepare", *args, _lib.ptr(flat), _lib.ptr(out),
+              _lib.stream_ptr())
     return out
 
 
@@ -140,8 +192,9 @@ class PackedCache:
     when the model's parameters or buffers change (tensor version counters), and then IN PLACE, so a
     HIP graph that captured a search over these weights keeps reading the current ones."""
 
-    def __init__(self, cap=4):
+    def __init__(self, cap=4, pack=pack_muzero_mlp):
         self.cap = int(cap)
+        self.pack = pack  # pack_muzero_mlp or pack_efficientzero_mlp
         self._d = OrderedDict()  # (id(model), device) -> [model weakref, version, weights, dims]
 
     @staticmethod
@@ -156,13 +209,13 @@ class PackedCache:
             e = None
         ver = self._version(model)
         if e is None:
-            flat, dims = pack_muzero_mlp(model, device)
+            flat, dims = self.pack(model, device)
             e = [weakref.ref(model), ver, prepare_kernel_weights(flat, dims), dims]
             self._d[key] = e
             while len(self._d) > self.cap:
                 self._d.popitem(last=False)
         elif e[1] != ver:
-            flat, dims = pack_muzero_mlp(model, device)
+            flat, dims = self.pack(model, device)
             e[2] = prepare_kernel_weights(flat, dims, out=e[2] if dims == e[3] else None)
             e[1], e[3] = ver, dims
         self._d.move_to_end(key)

@@ -112,6 +112,13 @@ class FusedInitialInference:
                       float(prepare["noise_weight"]), _lib.ptr(prepare["rewards"].to(**f32).contiguous()),
                       _lib.ptr(prepare["to_play"].to(device=x.device, dtype=torch.int32).contiguous()),
                       _lib.stream_ptr())
+        lstm = getattr(getattr(self.model, "dynamics_network", None), "lstm", None)
+        if lstm is not None:
+            # EfficientZeroModelMLP (efficientzero_model_mlp.py:149-184): the same two networks, and the
+            # zero reward hidden state (h, c) of shape [1, B, lstm_hidden_size]
+            from .model_conv import EZNetworkOutput
+            hidden = (torch.zeros((1, B, lstm.hidden_size), **kw), torch.zeros((1, B, lstm.hidden_size), **kw))
+            return EZNetworkOutput(value, [0. for _ in range(B)], policy, latent, hidden)
         return MZNetworkOutput(value, [0. for _ in range(B)], policy, latent)
 
 

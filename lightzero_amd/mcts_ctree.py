@@ -28,7 +28,7 @@ import torch
 from . import _lib
 from .ctree import ez_tree, mz_tree
 from .conv_infer import FoldedCache
-from .fused import NotPackable, PackedCache
+from .fused import NotPackable, PackedCache, pack_efficientzero_mlp
 from .scaling_transform import InverseScalarTransform
 from .tree import DeviceTree, new_minmax, next_seed
 from .utils import EasyDict
@@ -610,6 +610,31 @@ class EfficientZeroMCTSCtree(_MCTSCtree):
     reward_name = 'value_prefix'
     fuse_under_reuse = False
 
+    def __init__(self, cfg: EasyDict = None) -> None:
+        super().__init__(cfg)
+        self._packed = PackedCache(pack=pack_efficientzero_mlp)
+
+    def _fused(self, model, t, Hl=None, S=None):
+        """(packed weights, dims) when the whole search can run as one lzm_search_mlp_ez launch, by
+        MuZeroMCTSCtree._fused's rules: cfg.fused_search, categorical heads, an EfficientZero tree, an
+        EfficientZeroModelMLP-shaped network (eval-mode BatchNorm, ReLU, a one-layer reward LSTM) whose action
+        and support sizes are the tree's and the config's and whose LSTM width is the root state's (Hl; None:
+        not checked), of a shape the kernel takes on this tree for S simulations (default: the tree's reserved
+        capacity) by the library's own launch plan (lzm_search_mlp_ez_supported, lzm_search_mlp_ez_plan)."""
+        if not self._cfg.get('fused_search', True) or not self._categorical() or not t.ez:
+            return None
+        try:
+            packed, dims = self._packed.get(model, t.device)
+        except NotPackable:
+            return None
+        if dims["actions"] != t.A or dims["support"] != 2 * int(self._cfg.model.support_scale) + 1:
+            return None
+        if Hl is not None and dims["lstm_hidden"] != Hl:
+            return None
+        if t.search_mlp_ez_plan(dims, t.sims_capacity if S is None else S)["kernel"] is None:
+            return None
+        return packed, dims
+
     def _horizon(self):
         horizon = int(self._cfg.lstm_horizon_len)
         if horizon <= 0:
@@ -670,6 +695,23 @@ class EfficientZeroMCTSCtree(_MCTSCtree):
         with torch.no_grad():
             self._horizon()
             c = self._begin("search", roots, model, latent_state_roots, reward_hidden_state_roots[:2])
+            fz = self._fused(model, c.t, c.extra[0], c.S) if len(c.shape) == 1 else None
+            if fz is not None:
+                # the MLP network's whole search, reward LSTM included, in one launch (lzm_search_mlp_ez): every
+                # root's LSTM is its own workgroup's work, nothing is co-resident (no hand-off guard, no snapshot)
+                self.last_plan = None
+                self._buffers(c, model)
+                c.in_kernel = step is not None and not self.record
+                self._stage(c, to_play_batch, seeds, step)
+                rec = self._recorder(c)
+                buf = c.buf
+                with self._glue(c, step):
+                    c.t.search_mlp_ez(fz[1], fz[0], c.S, buf.mm, None if c.in_kernel else buf.seeds, buf.vtp_in,
+                                      buf.pool, buf.extra[0], buf.extra[1], self._horizon(), *self._pb_c(),
+                                      self._discount(), rec=rec)
+                self.last_path = "fused-mlp"
+                self._finish(c, roots, step, rec)
+                return
             cz = self._fused_conv(model, c.t, c.shape, c.extra[0], c.S)
             # A grid the plan refuses for co-residency is not launched where a fallback after the refusal is
             # not possible: when this search captures the generic path itself (use_hip_graph), and inside a

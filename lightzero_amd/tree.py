@@ -223,6 +223,28 @@ class DeviceTree:
         return dict(roots_per_wg=out[0], kernel={1: "resident", 0: "streaming"}.get(out[1]), mode=out[2],
                     tree_in_lds=bool(out[3]))
 
+    def search_mlp_ez(self, dims, weights, S, minmax, seeds, vtp_in, pool, hpool, cpool, horizon, pb_c_base=19652,
+                      pb_c_init=1.25, discount=0.997, rec=None, stream=None):
+        """One launch for the whole search of an EfficientZeroModelMLP (lzm_search_mlp_ez; dims / weights:
+        fused.pack_efficientzero_mlp's, in the kernel layout); hpool / cpool: the LSTM state pools
+        [S + 1, B, lstm_hidden] with slot 0 = the roots' state; rec: optional _Recorder-like object (with
+        is_reset)."""
+        self._unchecked = True
+        rx, ra, rl, rd, rg = _rec_ptrs(rec)
+        call("lzm_search_mlp_ez", self.h, dims["hidden"], dims["lstm_hidden"], dims["head_hidden"], dims["support"],
+             int(dims["res"]), ptr(weights), int(S), int(horizon), int(pb_c_base), float(pb_c_init), float(discount),
+             ptr(minmax), ptr(seeds), ptr(vtp_in), ptr(pool), ptr(hpool), ptr(cpool), rx, ra, rl,
+             *_rec_ptrs(rec, ("is_reset",)), rd, rg, stream_ptr(stream))
+
+    def search_mlp_ez_plan(self, dims, S):
+        """What search_mlp_ez(dims, ..., S) launches on this handle as it stands (lzm_search_mlp_ez_plan; host
+        only): dict(roots_per_wg, kernel 'streaming' / None when the kernel refuses the shape, its LDS need or
+        a MuZero tree, mode 0, tree_in_lds)."""
+        out = (ctypes.c_int32 * 4)()
+        call("lzm_search_mlp_ez_plan", self.h, int(S), dims["hidden"], dims["lstm_hidden"], dims["head_hidden"],
+             dims["support"], int(dims["res"]), out)
+        return dict(roots_per_wg=out[0], kernel={0: "streaming"}.get(out[1]), mode=out[2], tree_in_lds=bool(out[3]))
+
     def search_conv_plan(self, net, S, H=0, horizon=1, categorical=True):
         """What search_conv (MuZero trees) / search_conv_ez (EfficientZero trees; H: the LSTM width, horizon:
         lstm_horizon_len) launches for the native FoldedConvNet `net` and S simulations on this handle as the
