@@ -1435,16 +1435,14 @@ int lzm_debug_glibc_rand(uint32_t seed, int n, int32_t *out, void *stream) {
 
 }  // extern "C"
 
-// ---------------------------------------------------------------- fused whole-search (MLP)
+// ------------------------- fused whole-search (MuZeroModelMLP and EfficientZeroModelMLP, reward LSTM in-kernel)
 namespace {
 
-// Layer shapes of the packed MuZeroModelMLP recurrent network (lzm_search_mlp.h order): krows
-// input rows in the packed (torch-transposed) layout, K = krows rounded up to kKC in the kernel's.
+// One packed layer (lightzero_amd/fused.py pack_muzero_mlp / pack_efficientzero_mlp): krows input rows in
+// the packed (torch-transposed) layout, K = krows rounded up to kKC in the kernel's.
 struct LayerShape {
   int krows, K, N;
 };
-bool layer_used(int l, int res_dynamics) { return res_dynamics || (l != 2 && l != 3); }
-
 // Kernel layers: the packed layers as the search kernel runs them. Two pairs are merged, each
 // into one layer with columns [src0 | src1] over the same K: the value and policy head hiddens
 // (fc_value_head[0] | fc_policy_head[0], same input) and the value and policy head outputs
@@ -1454,45 +1452,64 @@ struct KLayer {
   int src0, src1;  // packed layer indices (src1 < 0: single source)
   int K, N, N0;    // N0: columns taken from src0
 };
-int kernel_layers(const LayerShape *s, int res, KLayer *kl) {
-  int n = 0;
-  auto one = [&](int l) { kl[n++] = KLayer{l, -1, s[l].K, s[l].N, s[l].N}; };
-  auto two = [&](int a, int b) { kl[n++] = KLayer{a, b, s[a].K, s[a].N + s[b].N, s[a].N}; };
-  one(0);
-  one(1);
-  if (res) {
-    one(2);
-    one(3);
-  }
-  one(4);
-  one(5);
-  one(6);
-  one(7);
-  two(8, 10);
-  two(9, 11);
-  return n;
-}
-// float offsets of each packed layer (weights [krows][N], then bias [N]) in the packed buffer
-void packed_offsets(const LayerShape *s, int res, size_t *w, size_t *b) {
+// The packed MLP recurrent network of MuZeroModelMLP (Hl == 0) and EfficientZeroModelMLP (Hl > 0: the
+// reward LSTM's width), the one description behind the packed sizes, the weight preparation, the plans and
+// the schedule. Layers in packed order; the two fc_dynamics_2 layers are present with
+// res_connection_in_dynamics, the LSTM gate layer — one dense layer over [x ; h_prev], columns in nn.LSTM
+// order i, f, g, o — for EfficientZero, whose value-prefix head reads h1 (K = Hl) where MuZero's reward
+// head reads the next latent (K = H).
+constexpr int kMlpLayers = 13, kGateLayer = 4;
+struct MlpNet {
+  int H, Hl, A, F, V, res;
+  LayerShape s[kMlpLayers];
+  bool used[kMlpLayers];
+  size_t pw[kMlpLayers], pb[kMlpLayers], packed_floats;  // float offsets (weights [krows][N], then bias [N])
+  KLayer kl[kMlpLayers];
+  int nk;
+  size_t w_off[kMlpLayers], b_off[kMlpLayers], kernel_floats;  // kernel layout (16-B aligned) and its total
+};
+MlpNet mlp_net(int H, int Hl, int A, int F, int V, int res) {
+  MlpNet n;
+  n.H = H; n.Hl = Hl; n.A = A; n.F = F; n.V = V; n.res = res ? 1 : 0;
+  const int Kr = Hl > 0 ? Hl : H;
+  LayerShape *s = n.s;
+  s[0] = {H + A, (H + A + kKC - 1) / kKC * kKC, H};  // fc_dynamics(_1)[0]: [latent; one-hot action]
+  s[1] = {H, H, H};
+  s[2] = {H, H, H};                 // fc_dynamics_2 (res_connection_in_dynamics)
+  s[3] = {H, H, H};
+  s[4] = {H + Hl, H + Hl, 4 * Hl};  // [weight_ih_l0 | weight_hh_l0], bias_ih_l0 + bias_hh_l0
+  s[5] = {Kr, Kr, F};               // fc_reward_head
+  s[6] = {F, F, V};
+  s[7] = {H, H, H};                 // fc_prediction_common
+  s[8] = {H, H, H};
+  s[9] = {H, H, F};                 // fc_value_head
+  s[10] = {F, F, V};
+  s[11] = {H, H, F};                // fc_policy_head
+  s[12] = {F, F, A};
   size_t off = 0;
-  for (int l = 0; l < 12; ++l) {
-    w[l] = b[l] = off;
-    if (!layer_used(l, res)) continue;
+  for (int l = 0; l < kMlpLayers; ++l) {
+    n.used[l] = (l == 2 || l == 3) ? n.res != 0 : (l == kGateLayer ? Hl > 0 : true);
+    n.pw[l] = n.pb[l] = off;
+    if (!n.used[l]) continue;
     off += (size_t)s[l].krows * s[l].N;
-    b[l] = off;
+    n.pb[l] = off;
     off += s[l].N;
   }
-}
-// float offset of each kernel layer's weights / bias in the kernel layout (16-B aligned), total
-size_t kernel_layout(const KLayer *kl, int nk, size_t *w_off, size_t *b_off) {
-  size_t off = 0;
-  for (int l = 0; l < nk; ++l) {
-    w_off[l] = off;
-    off += swz_floats(kl[l].K, kl[l].N);
-    b_off[l] = off;
-    off = (off + kl[l].N + 3) & ~(size_t)3;
+  n.packed_floats = off;
+  n.nk = 0;
+  for (int l = 0; l <= 8; ++l)
+    if (n.used[l]) n.kl[n.nk++] = KLayer{l, -1, s[l].K, s[l].N, s[l].N};
+  n.kl[n.nk++] = KLayer{9, 11, s[9].K, s[9].N + s[11].N, s[9].N};
+  n.kl[n.nk++] = KLayer{10, 12, s[10].K, s[10].N + s[12].N, s[10].N};
+  off = 0;
+  for (int l = 0; l < n.nk; ++l) {
+    n.w_off[l] = off;
+    off += swz_floats(n.kl[l].K, n.kl[l].N);
+    n.b_off[l] = off;
+    off = (off + n.kl[l].N + 3) & ~(size_t)3;
   }
-  return off;
+  n.kernel_floats = off;
+  return n;
 }
 
 // kernel-layout float d <- packed (k, col): col < N0 from src0 [krows0][N0], else src1 [krows1][N - N0]
@@ -1509,20 +1526,6 @@ __global__ void mlp_swizzle_kernel(const float *src0, int krows0, const float *s
     if (k < krows1) v = src1[(size_t)k * (N - N0) + (col - N0)];
   }
   dst[d] = v;
-}
-void mlp_shapes(int H, int A, int F, int V, LayerShape *s) {
-  s[0] = {H + A, (H + A + kKC - 1) / kKC * kKC, H};  // fc_dynamics(_1)[0]: [latent; one-hot action]
-  s[1] = {H, H, H};
-  s[2] = {H, H, H};      // fc_dynamics_2 (res_connection_in_dynamics)
-  s[3] = {H, H, H};
-  s[4] = {H, H, F};      // fc_reward_head
-  s[5] = {F, F, V};
-  s[6] = {H, H, H};      // fc_prediction_common
-  s[7] = {H, H, H};
-  s[8] = {H, H, F};      // fc_value_head
-  s[9] = {F, F, V};
-  s[10] = {H, H, F};     // fc_policy_head
-  s[11] = {F, F, A};
 }
 
 // Coefficients of z[344 + p] (the p-th rand() output before >> 1) over the 31 seeded words.
@@ -1596,38 +1599,66 @@ int roots_per_wg(int B) {
   return 8;
 }
 
-template <int R, bool TL>
-hipError_t launch_search(const SearchArgs &p, int G, size_t lds, hipStream_t stream) {
-  hipError_t e = hipFuncSetAttribute((const void *)search_mlp_kernel<R, TL>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((search_mlp_kernel<R, TL>), dim3(G), dim3(kThreads), lds, stream, p);
-  return hipGetLastError();
-}
-
-template <int R>
-hipError_t launch_search_r(const SearchArgs &p, int G, size_t lds, hipStream_t stream) {
-  return p.tree_in_lds ? launch_search<R, true>(p, G, lds, stream) : launch_search<R, false>(p, G, lds, stream);
-}
 constexpr size_t kMaxLds = 160 * 1024 - 1024;
 
 size_t round4(size_t x) { return (x + 3) & ~(size_t)3; }
 
+// ---- shared by the four one-launch search families (MLP and conv, MuZero and EfficientZero)
+// LZM_PHASE_TIMING > 0: the searches stamp their phases into the handle's phase buffer (diagnostics)
+bool phase_timing() {
+  const char *e = getenv("LZM_PHASE_TIMING");
+  return e && atoi(e) > 0;
+}
+int ensure_phase(lzm_handle *h) {
+  if (h->phase) return LZM_OK;
+  LZM_HIP(hipMalloc(&h->phase, (64 + 1024) * sizeof(unsigned long long)));
+  LZM_HIP(hipMemset(h->phase, 0, (64 + 1024) * sizeof(unsigned long long)));
+  return LZM_OK;
+}
+// Before any one-launch search: the pb_c table, the parity-mode draw table, the look-back words (G: the
+// launch's workgroups)
+int search_preamble(lzm_handle *h, int pb_c_base, float pb_c_init, int S, int G) {
+  int rc = fill_lut(h, pb_c_base, pb_c_init);
+  if (rc != LZM_OK) return rc;
+  if (!(h->flags & LZM_RNG_FAST)) {
+    rc = ensure_coef(h, h->B * (S + 1) + 64);
+    if (rc != LZM_OK) return rc;
+  }
+  return ensure_flags(h, S, G);
+}
+// The kernel arguments that SearchArgs and ConvSearchArgs name alike: the tree, the search, the draw tables,
+// the look-back words and the record pointers
+template <class Args>
+void fill_common(Args &p, const lzm_handle *h, int S, float discount, const uint32_t *seeds, const int32_t *vtp_in,
+                 float *minmax, float *pool, int32_t *rec_x, int32_t *rec_a, int32_t *rec_len, float *rec_decoded,
+                 float *rec_logits) {
+  p.stat = h->stat; p.meta = h->meta; p.legal = h->legal; p.nlegal = h->nlegal;
+  p.path = h->path; p.path_act = h->path_act; p.pathlen = h->pathlen; p.lut = h->lut;
+  p.B = h->B; p.A = h->A; p.cap = h->cap; p.lut_n = h->lut_n; p.depth_cap = h->depth_cap;
+  p.S = S; p.disc = discount; p.seeds = seeds; p.vtp_in = vtp_in; p.minmax = (float4 *)minmax; p.pool = pool;
+  p.coef = h->coef; p.coef_positions = h->coef_positions; p.pow16807 = h->pow16807;
+  p.flags = h->lb_flags; p.epoch = h->epoch; p.fast = (h->flags & LZM_RNG_FAST) ? 1 : 0;
+  p.rec_x = rec_x; p.rec_a = rec_a; p.rec_len = rec_len; p.rec_dec = rec_decoded; p.rec_logits = rec_logits;
+}
+
 // The recurrent network as a schedule of dense steps over the kernel layers (LDS activation
 // buffers by float offset): fc_dynamics(_1) on [latent; one-hot] (+ latent residual),
-// fc_dynamics_2, reward head (decoded), fc_prediction_common, [value | policy] head hidden,
-// [value | policy] head output: value decoded, policy logits [r][A] into X1
-// (muzero_model_mlp.py:179-204, :420-440). Even length (two weight-prefetch buffers alternate).
-void build_schedule(SearchArgs &p, const KLayer *kl, int nk, const size_t *w_off, const size_t *b_off,
-                    const float *weights, int res, int A, int V, int F, int R) {
+// fc_dynamics_2, [EfficientZero: the gate layer on [x ; h_prev], the cell follows it in the kernel,]
+// the reward head (decoded) on the next latent (EfficientZero: the value-prefix head on h1),
+// fc_prediction_common, [value | policy] head hidden, [value | policy] head output: value decoded,
+// policy logits [r][A] into X1 (muzero_model_mlp.py:179-204, :420-440; efficientzero_model_mlp.py:186-216,
+// :452-468). Padded to an even length with an empty step (two weight-prefetch buffers alternate).
+void build_schedule(SearchArgs &p, const MlpNet &net, const float *weights, int R) {
   const int x0 = (int)p.off_x0, x1 = (int)p.off_x1, x2 = (int)p.off_x2, nl = (int)p.off_n, hd = (int)p.off_h,
-            lg = (int)p.off_logit;
+            lg = (int)p.off_logit, gx = (int)p.off_g, gt = (int)p.off_gates, hh = (int)p.off_hh;
+  const int A = net.A, V = net.V, F = net.F, res = net.res;
+  const bool gate = net.used[kGateLayer];
   int n = 0, l = 0;
   auto add = [&](int in, int out, int relu, int resid, int rowmajor, int ldout, int dec) -> StepRec & {
-    const KLayer &k = kl[l];
+    const KLayer &k = net.kl[l];
     StepRec &q = p.sched[n++];
-    q.w = weights + w_off[l];
-    q.b = weights + b_off[l];
+    q.w = weights + net.w_off[l];
+    q.b = weights + net.b_off[l];
     q.K = k.K;
     q.N = k.N;
     q.wbytes = (int)(swz_floats(k.K, k.N) * sizeof(float));
@@ -1639,30 +1670,45 @@ void build_schedule(SearchArgs &p, const KLayer *kl, int nk, const size_t *w_off
     ++l;
     return q;
   };
+  // phase stamps after the dynamics, the reward head, fc_prediction_common and the heads: MuZero's only
+  auto stamp = [&](int i) { p.stamp_at[i] = gate ? -1 : n - 1; };
   add(x0, x1, 1, -1, 0, 0, 0);                  // fc_dynamics(_1)[0]
   add(x1, nl, 1, res ? x0 : -1, 0, 0, 0);       // [1] (+ latent: res_connection_in_dynamics)
-  int enc = nl;
+  int enc = nl;                                 // the dynamics' output (with a gate layer and no residual nl == gx)
   if (res) {
+    enc = gate ? gx : x2;                       // (the gate layer's input rows)
     add(nl, x1, 1, -1, 0, 0, 0);                // fc_dynamics_2
-    add(x1, x2, 1, -1, 0, 0, 0);
-    enc = x2;
+    add(x1, enc, 1, -1, 0, 0, 0);
   }
-  p.stamp_at[0] = n - 1;
+  stamp(0);
+  if (gate) {
+    add(enc, gt, 0, -1, 0, 0, 0);               // gates = [x ; h_prev] . [W_ih | W_hh] + (b_ih + b_hh)
+    p.cell_after = n - 1;
+    enc = hh;                                   // the value-prefix head reads the unmasked h1
+  }
   add(enc, hd, 1, -1, 0, 0, 0);                 // fc_reward_head
   add(hd, lg, 0, -1, 1, V + 1, 1);
-  p.stamp_at[1] = n - 1;
+  stamp(1);
   add(nl, x1, 1, -1, 0, 0, 0);                  // fc_prediction_common
   add(x1, x2, 1, -1, 0, 0, 0);
-  p.stamp_at[2] = n - 1;
+  stamp(2);
   add(x2, hd, 1, -1, 0, 0, 0);                  // [fc_value_head[0] | fc_policy_head[0]]: 2F rows of hd
   StepRec &o = add(hd, lg, 0, -1, 1, V + 1, 2);  // [fc_value_head[1] | fc_policy_head[1]]
   o.ncol1 = V;                                  // value support columns, decoded
   o.in2 = hd + F / kKC * (kKC * R + 4);         // policy columns read the policy half of hd
   o.out2 = x1; o.rowmajor2 = 1; o.ldout2 = A;   // logits [r][A]
-  p.stamp_at[3] = n - 1;
+  stamp(3);
+  if (n & 1) {  // the empty step: no columns, no weights (every load out of range), one barrier
+    StepRec &q = p.sched[n++];
+    memset(&q, 0, sizeof(q));
+    q.w = weights; q.b = weights;
+    q.resid = -1;
+    const Split sp = layer_split(0, 0);
+    q.Np = sp.Np; q.splits = sp.splits; q.cpl = sp.cpl; q.log2s = sp.log2s;
+  }
   p.nsteps = n;
-  (void)nk;
 }
+
 // ---- network-resident search (lzm_search_res.h): the config-2 shape, one root per workgroup
 bool res_shape_ok(int H, int A, int F, int V, int res) {
   return H == kRHid && F == kRF && V == kRV && res && A >= 1 && A <= kRMaxA;
@@ -1698,18 +1744,21 @@ size_t plan_res(SearchArgs &p, ResNet &n, const lzm_handle *h, int S, int A) {
   p.pbt_rows = q.pbt_rows;
   return (size_t)q.floats * sizeof(float) <= (size_t)kResMaxBytes ? (size_t)q.floats * sizeof(float) : 0;
 }
-void res_net(ResNet &n, const float *wres, int A) {
-  (void)A;
-  n.w = wres;
-}
-// network shapes the search kernels take (lzm_mlp_prepare's K padding, the dense steps' lane maps and
+// network shapes the search kernels take (the weight preparation's K padding, the dense steps' lane maps and
 // the decode's rounds over the support); everything else is refused before any launch
 bool mlp_shape_ok(int H, int A, int F, int V) {
   return H > 0 && H <= 1024 && F > 0 && F <= 1024 && V > 0 && A > 0 && V + A <= kMaxRounds * kThreads && A <= H &&
          H % kKC == 0 && F % kKC == 0;
 }
-// LDS plan of search_mlp_kernel with R roots per workgroup (float offsets, 16-B aligned); returns bytes
-size_t plan_stream(SearchArgs &p, const lzm_handle *h, int R, int S, int H, int A, int F, int V) {
+// the EfficientZero kernel's own limits on top of the dense steps': the cell's lane map and the h1 rows
+// (the value-prefix head's K) need Hl % kKC == 0, the gate layer at most four column rounds.
+// Widths routed: see DESIGN.md 10 (every width the one-launch path was measured to win at).
+bool ez_shape_ok(int H, int Hl, int A, int F, int V) {
+  return mlp_shape_ok(H, A, F, V) && Hl > 0 && Hl % kKC == 0 && 4 * Hl <= 4 * kThreads;
+}
+// LDS plan of search_mlp_kernel with R roots per workgroup (float offsets, 16-B aligned); returns bytes.
+// Hl > 0 (EfficientZero): then the gate layer's input [x ; h_prev], the gates, h1 and c_prev
+size_t plan_stream(SearchArgs &p, const lzm_handle *h, int R, int S, int H, int Hl, int A, int F, int V, int res) {
   size_t o = 0;
   const size_t tree_floats = (size_t)h->cap * R * 4;
   p.tree_in_lds = (2 * tree_floats * sizeof(float) <= 96 * 1024) ? 1 : 0;
@@ -1733,22 +1782,31 @@ size_t plan_stream(SearchArgs &p, const lzm_handle *h, int R, int S, int H, int 
   p.off_logit = o; if (V < kThreads) o += round4((size_t)(V + 1) * R);  // wide supports decode from registers
   p.off_part = o;  // (unused: split-K partials meet through DPP)
   p.off_misc = o; o += round4((size_t)S + 32);  // staged seeds[S] + 16807^i table
+  if (Hl > 0) {
+    p.off_g = o; o += round4(tfl(H + Hl));
+    p.off_gates = o; o += round4(tfl(4 * Hl));
+    p.off_hh = o; o += round4(tfl(Hl));
+    p.off_cp = o; o += round4((size_t)Hl * R);
+    if (!res) p.off_n = p.off_g;  // the next latent is the LSTM's input: the front rows of [x ; h_prev]
+  }
   return o * sizeof(float);
 }
-// What lzm_search_mlp launches for this handle, network shape and search length: the one decision
-// behind the launch and lzm_search_mlp_plan. kind: 1 network-resident, 0 weight-streaming, -1 none
-// (the shape, or the LDS the streaming kernel would need for it, is refused). mode: the resident
-// kernel's selection mode after its downgrades (0 for the streaming kernel). The LDS offsets of the
-// chosen kernel are left in p (and n.plan).
+// What lzm_search_mlp (ez false) or lzm_search_mlp_ez (ez true) launches for this handle, network shape and
+// search length: the one decision behind the launch and the plan queries. kind: 1 network-resident (MuZero
+// only), 0 weight-streaming, -1 none (the shape, or the LDS the streaming kernel would need for it, is
+// refused). mode: the resident kernel's selection mode after its downgrades (0 for the streaming kernel).
+// R: roots per workgroup by roots_per_wg's rule; the EfficientZero kernel takes 1, 2 or 4 (the gate rows
+// of 8 would not leave the tree its LDS). The LDS offsets of the chosen kernel are left in p (and n.plan).
 struct MlpPlan {
   int R, kind, mode, tree_in_lds;
   size_t lds;
 };
-MlpPlan mlp_plan(const lzm_handle *h, int H, int F, int V, int res_dynamics, int S, SearchArgs &p, ResNet &n) {
+MlpPlan mlp_plan(const lzm_handle *h, bool ez, int H, int Hl, int F, int V, int res_dynamics, int S, SearchArgs &p,
+                 ResNet &n) {
   const int A = h->A;
-  MlpPlan pl{roots_per_wg(h->B), -1, 0, 0, 0};
-  if (!mlp_shape_ok(H, A, F, V)) return pl;
-  if (pl.R == 1 && res_enabled() && res_shape_ok(H, A, F, V, res_dynamics)) {
+  MlpPlan pl{ez ? std::min(roots_per_wg(h->B), 4) : roots_per_wg(h->B), -1, 0, 0, 0};
+  if (!(ez ? ez_shape_ok(H, Hl, A, F, V) : mlp_shape_ok(H, A, F, V))) return pl;
+  if (!ez && pl.R == 1 && res_enabled() && res_shape_ok(H, A, F, V, res_dynamics)) {
     pl.lds = plan_res(p, n, h, S, A);
     if (pl.lds) {
       // the selection mode (lzm_search_res.h, the simulation loop): 1 the wave walk; 4 the two-action
@@ -1766,38 +1824,212 @@ MlpPlan mlp_plan(const lzm_handle *h, int H, int F, int V, int res_dynamics, int
       return pl;
     }
   }
-  pl.lds = plan_stream(p, h, pl.R, S, H, A, F, V);
+  pl.lds = plan_stream(p, h, pl.R, S, H, ez ? Hl : 0, A, F, V, res_dynamics);
   pl.tree_in_lds = p.tree_in_lds;
   pl.kind = pl.lds <= kMaxLds ? 0 : -1;
   return pl;
 }
+// The plan queries' body (ez: lzm_search_mlp_ez_plan); a handle of the other kind answers kind -1
+int mlp_plan_query(const char *name, const lzm_handle *h, bool ez, int S, int H, int Hl, int F, int V, int res_dynamics,
+                   int32_t *out) {
+  if (!h || !out || S <= 0) {
+    snprintf(g_err, sizeof(g_err), "%s: null argument or no simulations", name);
+    return LZM_ERR_ARG;
+  }
+  if (S > h->sims_cap) {
+    snprintf(g_err, sizeof(g_err), "%s: %d simulations > reserved %d (lzm_reserve)", name, S, h->sims_cap);
+    return LZM_ERR_CAPACITY;
+  }
+  SearchArgs p;
+  memset(&p, 0, sizeof(p));
+  ResNet n;
+  memset(&n, 0, sizeof(n));
+  const MlpPlan pl = mlp_plan(h, ez, H, Hl, F, V, res_dynamics, S, p, n);
+  out[0] = pl.R;
+  out[1] = ((h->flags & LZM_TREE_EZ) != 0) == ez ? pl.kind : -1;
+  out[2] = pl.mode;
+  out[3] = pl.tree_in_lds;
+  return LZM_OK;
+}
+
+// The network-resident layout (lzm_search_res.h) follows the kernel layout, for the MuZero shape it serves
+bool net_resident(const MlpNet &n) { return n.Hl == 0 && res_shape_ok(n.H, n.A, n.F, n.V, n.res); }
+// packed -> kernel layout: each kernel layer's weights in lane order (swz_source), then its bias
+int mlp_prepare(const MlpNet &net, const float *packed, float *out, hipStream_t stream) {
+  for (int l = 0; l < net.nk; ++l) {
+    const KLayer &q = net.kl[l];
+    const size_t n = swz_floats(q.K, q.N);
+    const int s1 = q.src1 >= 0 ? q.src1 : q.src0;
+    hipLaunchKernelGGL(mlp_swizzle_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                       packed + net.pw[q.src0], net.s[q.src0].krows, packed + net.pw[s1], net.s[s1].krows, q.K, q.N,
+                       q.N0, out + net.w_off[l], n);
+    LZM_CHECK_LAUNCH();
+    LZM_HIP(hipMemcpyAsync(out + net.b_off[l], packed + net.pb[q.src0], (size_t)q.N0 * sizeof(float),
+                           hipMemcpyDeviceToDevice, stream));
+    if (q.src1 >= 0)
+      LZM_HIP(hipMemcpyAsync(out + net.b_off[l] + q.N0, packed + net.pb[q.src1], (size_t)(q.N - q.N0) * sizeof(float),
+                             hipMemcpyDeviceToDevice, stream));
+  }
+  if (net_resident(net)) {
+    ResSrc src;  // res_source numbers the layers in MuZero's packed order: the gate layer's slot skipped
+    for (int l = 0; l < 12; ++l) {
+      const int u = l < kGateLayer ? l : l + 1;
+      src.pw[l] = net.pw[u];
+      src.pb[l] = net.pb[u];
+      src.N[l] = net.s[u].N;
+    }
+    const size_t n = res_block_offset(kRbN, net.A);
+    hipLaunchKernelGGL(mlp_res_swizzle_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, packed, src,
+                       net.A, out + round4(net.kernel_floats), n);
+    LZM_CHECK_LAUNCH();
+  }
+  return LZM_OK;
+}
+
+// The network-resident launch (search_res_kernel): one root per workgroup, collect-step mode in-kernel
+int launch_resident(lzm_handle *h, SearchArgs &p, ResNet &n, const MlpNet &net, const float *weights,
+                    const MlpPlan &plan, hipStream_t stream) {
+  p.step_count = h->step_count; p.step_inc = h->step_inc; p.step_base = h->step_base;
+  p.mm_fresh = h->step_fresh; p.mm_delta = h->step_delta;
+  p.out_dist = h->step_dist; p.out_values = h->step_vals;
+  n.w = weights + round4(net.kernel_floats);  // its weights follow the generic layout
+  const char *sl = getenv("LZM_RES_LATE");
+  n.late_draw = sl ? atoi(sl) : 1;
+  const char *sd = getenv("LZM_RES_SPEC_DEPTH");
+  n.spec_depth = sd ? atoi(sd) : 1;
+  // one instantiation per selection mode (1, 4, 5) x variant: the production kernels fix the RNG at
+  // compile time (0 glibc, 1 Philox); the stamps kernel reads the RNG and n.spec_depth at run time and
+  // serves phase timing and LZM_RES_SPEC_DEPTH=0 (then without a phase buffer: it stamps nothing)
+  typedef void (*ResKernel)(SearchArgs, ResNet);
+  static const ResKernel kernels[3][3] = {
+      {search_res_kernel<1, 0, false>, search_res_kernel<1, 1, false>, search_res_kernel<1, -1, true>},
+      {search_res_kernel<4, 0, false>, search_res_kernel<4, 1, false>, search_res_kernel<4, -1, true>},
+      {search_res_kernel<5, 0, false>, search_res_kernel<5, 1, false>, search_res_kernel<5, -1, true>}};
+  const int mi = plan.mode == 5 ? 2 : plan.mode == 4 ? 1 : 0;
+  const int vi = (p.phase || !n.spec_depth) ? 2 : p.fast ? 1 : 0;
+  const ResKernel fn = kernels[mi][vi];
+  LZM_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+  hipLaunchKernelGGL(fn, dim3(h->B), dim3(kRT), plan.lds, stream, p, n);
+  LZM_CHECK_LAUNCH();
+  return LZM_OK;
+}
+
+// The weight-streaming launch (search_mlp_kernel<R, tree in LDS, EZ>; the EfficientZero kernel serves
+// R <= 4), with the collect-step mode's prologue (seeds, fresh min-max) and epilogue (root outputs,
+// counter) as one launch each around the search. name: the entry point, for the messages.
+int launch_stream(const char *name, lzm_handle *h, SearchArgs &p, int R, size_t lds, float *minmax, hipStream_t stream) {
+  typedef void (*StreamKernel)(SearchArgs);
+  static const StreamKernel kernels[2][4][2] = {  // [EZ][R = 1, 2, 4, 8][tree in LDS, tree in HBM]
+      {{search_mlp_kernel<1, true>, search_mlp_kernel<1, false>},
+       {search_mlp_kernel<2, true>, search_mlp_kernel<2, false>},
+       {search_mlp_kernel<4, true>, search_mlp_kernel<4, false>},
+       {search_mlp_kernel<8, true>, search_mlp_kernel<8, false>}},
+      {{search_mlp_kernel<1, true, true>, search_mlp_kernel<1, false, true>},
+       {search_mlp_kernel<2, true, true>, search_mlp_kernel<2, false, true>},
+       {search_mlp_kernel<4, true, true>, search_mlp_kernel<4, false, true>},
+       {nullptr, nullptr}}};
+  const StreamKernel fn = kernels[p.Hl > 0][R == 1 ? 0 : R == 2 ? 1 : R == 4 ? 2 : 3][p.tree_in_lds ? 0 : 1];
+  if (!fn) {
+    snprintf(g_err, sizeof(g_err), "%s: no kernel for %d roots per workgroup", name, R);
+    return LZM_ERR_STATE;
+  }
+  const int S = p.S;
+  if (h->step_count || h->step_fresh) {
+    if (h->step_count && h->step_seeds_n < S) {  // (allocated with the tree: S <= sims_cap)
+      snprintf(g_err, sizeof(g_err), "%s: step seeds buffer smaller than num_simulations (reserve first)", name);
+      return LZM_ERR_STATE;
+    }
+    const int n = std::max(S, h->B);
+    hipLaunchKernelGGL(step_prologue_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, h->step_count,
+                       h->step_base, S, h->step_seeds, (float4 *)minmax, h->B, h->step_fresh, h->step_delta);
+    LZM_CHECK_LAUNCH();
+    if (h->step_count) p.seeds = reinterpret_cast<const uint32_t *>(h->step_seeds);
+  }
+  LZM_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(fn, dim3((h->B + R - 1) / R), dim3(kThreads), lds, stream, p);
+  LZM_CHECK_LAUNCH();
+  if ((h->step_count && h->step_inc) || h->step_dist || h->step_vals) {
+    hipLaunchKernelGGL(step_epilogue_kernel, dim3((h->B + 255) / 256), dim3(256), 0, stream, view(h),
+                       h->step_dist, h->step_vals, h->step_inc ? h->step_count : nullptr);
+    LZM_CHECK_LAUNCH();
+  }
+  return LZM_OK;
+}
+
+// lzm_search_mlp (ez false: Hl, horizon and the LSTM pools unused) and lzm_search_mlp_ez. name: the entry
+// point, for the messages.
+int search_mlp(const char *name, bool ez, lzm_handle *h, int H, int Hl, int F, int V, int res_dynamics,
+               const float *weights, int S, int horizon, int pb_c_base, float pb_c_init, float discount, float *minmax,
+               const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool, float *h_pool, float *c_pool,
+               int32_t *rec_x, int32_t *rec_a, int32_t *rec_len, int32_t *rec_reset, float *rec_decoded,
+               float *rec_logits, hipStream_t stream) {
+  if (!h || !weights || !minmax || (!seeds && !h->step_count) || !vtp_in || !latent_pool ||
+      (ez && (!h_pool || !c_pool)) || S <= 0) {
+    snprintf(g_err, sizeof(g_err), "%s: null argument or no simulations", name);
+    return LZM_ERR_ARG;
+  }
+  if ((uintptr_t)weights & 15) {
+    snprintf(g_err, sizeof(g_err), "%s: weights must be 16-byte aligned (%s output)", name,
+             ez ? "lzm_mlp_ez_prepare" : "lzm_mlp_prepare");
+    return LZM_ERR_ARG;
+  }
+  if (((h->flags & LZM_TREE_EZ) != 0) != ez) {
+    snprintf(g_err, sizeof(g_err), "%s: %s trees only", name, ez ? "EfficientZero" : "MuZero");
+    return LZM_ERR_ARG;
+  }
+  if (ez && horizon <= 0) {
+    snprintf(g_err, sizeof(g_err), "%s: lstm_horizon_len must be > 0", name);
+    return LZM_ERR_ARG;
+  }
+  const int A = h->A;
+  if (!(ez ? ez_shape_ok(H, Hl, A, F, V) : mlp_shape_ok(H, A, F, V))) {
+    snprintf(g_err, sizeof(g_err), "%s: unsupported network shape (%s)", name,
+             ez ? "lzm_search_mlp_ez_supported" : "hidden and head widths must be multiples of 16");
+    return LZM_ERR_ARG;
+  }
+  if (S > h->sims_cap) {
+    snprintf(g_err, sizeof(g_err), "%s: %d simulations > reserved %d (lzm_reserve)", name, S, h->sims_cap);
+    return LZM_ERR_CAPACITY;
+  }
+  SearchArgs p;
+  memset(&p, 0, sizeof(p));
+  ResNet n;
+  memset(&n, 0, sizeof(n));
+  const MlpPlan plan = mlp_plan(h, ez, H, Hl, F, V, res_dynamics, S, p, n);
+  if (plan.kind < 0) {
+    snprintf(g_err, sizeof(g_err), "%s: %zu B of LDS needed (network or tree too large)", name, plan.lds);
+    return LZM_ERR_ARG;
+  }
+  int rc = search_preamble(h, pb_c_base, pb_c_init, S, (h->B + plan.R - 1) / plan.R);
+  if (rc != LZM_OK) return rc;
+  const MlpNet net = mlp_net(H, ez ? Hl : 0, A, F, V, res_dynamics);
+  fill_common(p, h, S, discount, seeds, vtp_in, minmax, latent_pool, rec_x, rec_a, rec_len, rec_decoded, rec_logits);
+  p.H = H; p.F = F; p.V = V; p.res = net.res;
+  p.diag = h->search_diag;
+  p.hpool = h_pool; p.cpool = c_pool; p.Hl = net.Hl; p.horizon = horizon; p.rec_reset = rec_reset;
+  if (!ez) {  // the phase stamps and the timing experiments are the MuZero kernels'
+    if (phase_timing() && (rc = ensure_phase(h)) != LZM_OK) return rc;
+    p.phase = h->phase;
+    p.diag_mode = getenv("LZM_DIAG_MODE") ? atoi(getenv("LZM_DIAG_MODE")) : 0;  // timing experiments only
+  }
+  if (plan.kind == 1) return launch_resident(h, p, n, net, weights, plan, stream);
+  build_schedule(p, net, weights, plan.R);
+  return launch_stream(name, h, p, plan.R, plan.lds, minmax, stream);
+}
+
 }  // namespace
 
 extern "C" {
 
 int64_t lzm_mlp_packed_floats(int hidden, int actions, int head_hidden, int support, int res_dynamics) {
   if (hidden <= 0 || actions <= 0 || head_hidden <= 0 || support <= 0) return -1;
-  LayerShape s[12];
-  mlp_shapes(hidden, actions, head_hidden, support, s);
-  int64_t n = 0;
-  for (int l = 0; l < 12; ++l) {
-    if (!res_dynamics && (l == 2 || l == 3)) continue;
-    n += (int64_t)s[l].krows * s[l].N + s[l].N;
-  }
-  return n;
+  return (int64_t)mlp_net(hidden, 0, actions, head_hidden, support, res_dynamics).packed_floats;
 }
 
 int64_t lzm_mlp_kernel_floats(int hidden, int actions, int head_hidden, int support, int res_dynamics) {
   if (hidden <= 0 || actions <= 0 || head_hidden <= 0 || support <= 0) return -1;
-  LayerShape s[12];
-  mlp_shapes(hidden, actions, head_hidden, support, s);
-  KLayer kl[12];
-  const int nk = kernel_layers(s, res_dynamics, kl);
-  size_t w_off[12], b_off[12];
-  size_t total = kernel_layout(kl, nk, w_off, b_off);
-  // the network-resident kernel's layout follows (lzm_search_res.h), for the shape it serves
-  if (res_shape_ok(hidden, actions, head_hidden, support, res_dynamics)) total = round4(total) + res_block_offset(kRbN, actions);
-  return (int64_t)total;
+  const MlpNet net = mlp_net(hidden, 0, actions, head_hidden, support, res_dynamics);
+  return (int64_t)(net_resident(net) ? round4(net.kernel_floats) + res_block_offset(kRbN, actions) : net.kernel_floats);
 }
 
 int lzm_mlp_prepare(int hidden, int actions, int head_hidden, int support, int res_dynamics, const float *packed,
@@ -1807,42 +2039,7 @@ int lzm_mlp_prepare(int hidden, int actions, int head_hidden, int support, int r
     set_err("lzm_mlp_prepare: bad arguments (hidden and head widths must be multiples of 16)");
     return LZM_ERR_ARG;
   }
-  LayerShape s[12];
-  mlp_shapes(hidden, actions, head_hidden, support, s);
-  size_t pw[12], pb[12];
-  packed_offsets(s, res_dynamics, pw, pb);
-  KLayer kl[12];
-  const int nk = kernel_layers(s, res_dynamics, kl);
-  size_t w_off[12], b_off[12];
-  kernel_layout(kl, nk, w_off, b_off);
-  for (int l = 0; l < nk; ++l) {
-    const KLayer &q = kl[l];
-    const size_t n = swz_floats(q.K, q.N);
-    const int s1 = q.src1 >= 0 ? q.src1 : q.src0;
-    hipLaunchKernelGGL(mlp_swizzle_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       packed + pw[q.src0], s[q.src0].krows, packed + pw[s1], s[s1].krows, q.K, q.N, q.N0,
-                       out + w_off[l], n);
-    LZM_CHECK_LAUNCH();
-    LZM_HIP(hipMemcpyAsync(out + b_off[l], packed + pb[q.src0], (size_t)q.N0 * sizeof(float),
-                           hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (q.src1 >= 0)
-      LZM_HIP(hipMemcpyAsync(out + b_off[l] + q.N0, packed + pb[q.src1], (size_t)(q.N - q.N0) * sizeof(float),
-                             hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  }
-  if (res_shape_ok(hidden, actions, head_hidden, support, res_dynamics)) {
-    ResSrc src;
-    for (int l = 0; l < 12; ++l) {
-      src.pw[l] = pw[l];
-      src.pb[l] = pb[l];
-      src.N[l] = s[l].N;
-    }
-    const size_t base = round4(kernel_layout(kl, nk, w_off, b_off));
-    const size_t n = res_block_offset(kRbN, actions);
-    hipLaunchKernelGGL(mlp_res_swizzle_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       packed, src, actions, out + base, n);
-    LZM_CHECK_LAUNCH();
-  }
-  return LZM_OK;
+  return mlp_prepare(mlp_net(hidden, 0, actions, head_hidden, support, res_dynamics), packed, out, (hipStream_t)stream);
 }
 
 int lzm_search_mlp_kind(int B, int actions, int hidden, int head_hidden, int support, int res_dynamics) {
@@ -1858,157 +2055,62 @@ int lzm_search_mlp_supported(int actions, int hidden, int head_hidden, int suppo
 
 int lzm_search_mlp_plan(const lzm_handle *h, int num_simulations, int hidden, int head_hidden, int support,
                         int res_dynamics, int32_t *out) {
-  if (!h || !out || num_simulations <= 0) {
-    set_err("lzm_search_mlp_plan: null argument or no simulations");
-    return LZM_ERR_ARG;
-  }
-  if (num_simulations > h->sims_cap) {
-    snprintf(g_err, sizeof(g_err), "lzm_search_mlp_plan: %d simulations > reserved %d (lzm_reserve)", num_simulations,
-             h->sims_cap);
-    return LZM_ERR_CAPACITY;
-  }
-  SearchArgs p;
-  memset(&p, 0, sizeof(p));
-  ResNet n;
-  memset(&n, 0, sizeof(n));
-  const MlpPlan pl = mlp_plan(h, hidden, head_hidden, support, res_dynamics, num_simulations, p, n);
-  out[0] = pl.R;
-  out[1] = (h->flags & LZM_TREE_EZ) ? -1 : pl.kind;
-  out[2] = pl.mode;
-  out[3] = pl.tree_in_lds;
-  return LZM_OK;
+  return mlp_plan_query("lzm_search_mlp_plan", h, false, num_simulations, hidden, 0, head_hidden, support,
+                        res_dynamics, out);
 }
 
 int lzm_search_mlp(lzm_handle *h, int hidden, int head_hidden, int support, int res_dynamics, const float *weights,
                    int num_simulations, int pb_c_base, float pb_c_init, float discount, float *minmax,
                    const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool, int32_t *rec_x, int32_t *rec_a,
                    int32_t *rec_len, float *rec_decoded, float *rec_logits, void *stream) {
-  if (!h || !weights || !minmax || (!seeds && !h->step_count) || !vtp_in || !latent_pool || num_simulations <= 0) {
-    set_err("lzm_search_mlp: null argument or no simulations");
-    return LZM_ERR_ARG;
-  }
-  if ((uintptr_t)weights & 15) {
-    set_err("lzm_search_mlp: weights must be 16-byte aligned (lzm_mlp_prepare output)");
-    return LZM_ERR_ARG;
-  }
-  if (h->flags & LZM_TREE_EZ) {
-    set_err("lzm_search_mlp: MuZero trees only");
-    return LZM_ERR_ARG;
-  }
-  const int H = hidden, F = head_hidden, V = support, A = h->A, S = num_simulations;
-  if (!mlp_shape_ok(H, A, F, V)) {
-    set_err("lzm_search_mlp: unsupported network shape (hidden and head widths must be multiples of 16)");
-    return LZM_ERR_ARG;
-  }
-  if (S > h->sims_cap) {
-    snprintf(g_err, sizeof(g_err), "lzm_search_mlp: %d simulations > reserved %d (lzm_reserve)", S, h->sims_cap);
-    return LZM_ERR_CAPACITY;
-  }
-  int rc = fill_lut(h, pb_c_base, pb_c_init);
-  if (rc != LZM_OK) return rc;
-  SearchArgs p;
-  memset(&p, 0, sizeof(p));
-  ResNet n;
-  memset(&n, 0, sizeof(n));
-  const MlpPlan plan = mlp_plan(h, H, F, V, res_dynamics, S, p, n);
-  const int R = plan.R;
-  const int G = (h->B + R - 1) / R;
-  const bool fast = (h->flags & LZM_RNG_FAST) != 0;
-  if (!fast) {
-    rc = ensure_coef(h, h->B * (S + 1) + 64);
-    if (rc != LZM_OK) return rc;
-  }
-  rc = ensure_flags(h, S, G);
-  if (rc != LZM_OK) return rc;
+  return search_mlp("lzm_search_mlp", false, h, hidden, 0, head_hidden, support, res_dynamics, weights,
+                    num_simulations, 0, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in, latent_pool, nullptr,
+                    nullptr, rec_x, rec_a, rec_len, nullptr, rec_decoded, rec_logits, (hipStream_t)stream);
+}
 
-  KLayer kls[12];
-  int nkl = 0;
-  size_t lay_w[12], lay_b[12];
-  p.stat = h->stat; p.meta = h->meta; p.legal = h->legal; p.nlegal = h->nlegal;
-  p.path = h->path; p.path_act = h->path_act; p.pathlen = h->pathlen; p.lut = h->lut;
-  p.B = h->B; p.A = A; p.cap = h->cap; p.lut_n = h->lut_n; p.depth_cap = h->depth_cap;
-  p.S = S; p.disc = discount; p.seeds = seeds; p.vtp_in = vtp_in; p.minmax = (float4 *)minmax; p.pool = latent_pool;
-  p.H = H; p.F = F; p.V = V; p.res = res_dynamics ? 1 : 0;
-  {
-    LayerShape s[12];
-    mlp_shapes(H, A, F, V, s);
-    nkl = kernel_layers(s, res_dynamics, kls);
-    kernel_layout(kls, nkl, lay_w, lay_b);
-  }
-  p.coef = h->coef; p.coef_positions = h->coef_positions; p.pow16807 = h->pow16807;
-  p.flags = h->lb_flags; p.epoch = h->epoch; p.diag = h->search_diag; p.fast = fast ? 1 : 0;
-  if (!h->phase && getenv("LZM_PHASE_TIMING") && atoi(getenv("LZM_PHASE_TIMING")) > 0) {
-    LZM_HIP(hipMalloc(&h->phase, (64 + 1024) * sizeof(unsigned long long)));
-    LZM_HIP(hipMemset(h->phase, 0, (64 + 1024) * sizeof(unsigned long long)));
-  }
-  p.phase = h->phase;
-  p.diag_mode = getenv("LZM_DIAG_MODE") ? atoi(getenv("LZM_DIAG_MODE")) : 0;  // timing experiments only
-  p.rec_x = rec_x; p.rec_a = rec_a; p.rec_len = rec_len; p.rec_dec = rec_decoded; p.rec_logits = rec_logits;
-  if (plan.kind == 1) {
-    // the network-resident kernel (lzm_search_res.h); its weights follow the generic layout
-    SearchArgs q = p;
-    q.step_count = h->step_count; q.step_inc = h->step_inc; q.step_base = h->step_base; q.mm_fresh = h->step_fresh; q.mm_delta = h->step_delta;
-    q.out_dist = h->step_dist; q.out_values = h->step_vals;
-    const size_t lds = plan.lds;
-    res_net(n, weights + round4(kernel_layout(kls, nkl, lay_w, lay_b)), A);
-    const char *sl = getenv("LZM_RES_LATE");
-    n.late_draw = sl ? atoi(sl) : 1;
-    const char *sd = getenv("LZM_RES_SPEC_DEPTH");
-    n.spec_depth = sd ? atoi(sd) : 1;
-    // one instantiation per selection mode (1, 4, 5) x variant: the production kernels fix the RNG at
-    // compile time (0 glibc, 1 Philox); the stamps kernel reads the RNG and n.spec_depth at run time and
-    // serves phase timing and LZM_RES_SPEC_DEPTH=0 (then without a phase buffer: it stamps nothing)
-    typedef void (*ResKernel)(SearchArgs, ResNet);
-    static const ResKernel kernels[3][3] = {
-        {search_res_kernel<1, 0, false>, search_res_kernel<1, 1, false>, search_res_kernel<1, -1, true>},
-        {search_res_kernel<4, 0, false>, search_res_kernel<4, 1, false>, search_res_kernel<4, -1, true>},
-        {search_res_kernel<5, 0, false>, search_res_kernel<5, 1, false>, search_res_kernel<5, -1, true>}};
-    const int mi = plan.mode == 5 ? 2 : plan.mode == 4 ? 1 : 0;
-    const int vi = (q.phase || !n.spec_depth) ? 2 : fast ? 1 : 0;
-    const ResKernel fn = kernels[mi][vi];
-    hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(fn, dim3(G), dim3(kRT), lds, (hipStream_t)stream, q, n);
-      e = hipGetLastError();
-    }
-    LZM_HIP(e);
-    LZM_CHECK_LAUNCH();
-    return LZM_OK;
-  }
-  const size_t lds = plan.lds;  // (plan_stream left the streaming kernel's LDS offsets in p)
-  build_schedule(p, kls, nkl, lay_w, lay_b, weights, res_dynamics, A, V, F, R);
-  if (lds > kMaxLds) {
-    snprintf(g_err, sizeof(g_err), "lzm_search_mlp: %zu B of LDS needed (network too wide)", lds);
+// The EfficientZeroModelMLP twins: the same network with the reward LSTM's gate layer (lstm_hidden wide)
+int64_t lzm_mlp_ez_packed_floats(int hidden, int lstm_hidden, int actions, int head_hidden, int support,
+                                 int res_dynamics) {
+  if (hidden <= 0 || lstm_hidden <= 0 || actions <= 0 || head_hidden <= 0 || support <= 0) return -1;
+  return (int64_t)mlp_net(hidden, lstm_hidden, actions, head_hidden, support, res_dynamics).packed_floats;
+}
+
+int64_t lzm_mlp_ez_kernel_floats(int hidden, int lstm_hidden, int actions, int head_hidden, int support,
+                                 int res_dynamics) {
+  if (hidden <= 0 || lstm_hidden <= 0 || actions <= 0 || head_hidden <= 0 || support <= 0) return -1;
+  return (int64_t)mlp_net(hidden, lstm_hidden, actions, head_hidden, support, res_dynamics).kernel_floats;
+}
+
+int lzm_mlp_ez_prepare(int hidden, int lstm_hidden, int actions, int head_hidden, int support, int res_dynamics,
+                       const float *packed, float *out, void *stream) {
+  if (!packed || !out || hidden <= 0 || lstm_hidden <= 0 || actions <= 0 || head_hidden <= 0 || support <= 0 ||
+      hidden % kKC != 0 || head_hidden % kKC != 0 || lstm_hidden % kKC != 0) {
+    set_err("lzm_mlp_ez_prepare: bad arguments (hidden, LSTM and head widths must be multiples of 16)");
     return LZM_ERR_ARG;
   }
-  // collect-step mode: the prologue (seeds, fresh min-max) and epilogue (root outputs, counter)
-  // as one launch each around the search
-  if (h->step_count || h->step_fresh) {
-    if (h->step_count && h->step_seeds_n < S) {  // (allocated with the tree: S <= sims_cap)
-      set_err("lzm_search_mlp: step seeds buffer smaller than num_simulations (reserve first)");
-      return LZM_ERR_STATE;
-    }
-    const int n = std::max(S, h->B);
-    hipLaunchKernelGGL(step_prologue_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->step_count,
-                       h->step_base, S, h->step_seeds, (float4 *)minmax, h->B, h->step_fresh, h->step_delta);
-    LZM_CHECK_LAUNCH();
-    if (h->step_count) p.seeds = reinterpret_cast<const uint32_t *>(h->step_seeds);
-  }
-  hipError_t e;
-  switch (R) {
-    case 1: e = launch_search_r<1>(p, G, lds, (hipStream_t)stream); break;
-    case 2: e = launch_search_r<2>(p, G, lds, (hipStream_t)stream); break;
-    case 4: e = launch_search_r<4>(p, G, lds, (hipStream_t)stream); break;
-    default: e = launch_search_r<8>(p, G, lds, (hipStream_t)stream); break;
-  }
-  LZM_HIP(e);
-  LZM_CHECK_LAUNCH();
-  if ((h->step_count && h->step_inc) || h->step_dist || h->step_vals) {
-    hipLaunchKernelGGL(step_epilogue_kernel, dim3((h->B + 255) / 256), dim3(256), 0, (hipStream_t)stream, view(h),
-                       h->step_dist, h->step_vals, h->step_inc ? h->step_count : nullptr);
-    LZM_CHECK_LAUNCH();
-  }
-  return LZM_OK;
+  return mlp_prepare(mlp_net(hidden, lstm_hidden, actions, head_hidden, support, res_dynamics), packed, out,
+                     (hipStream_t)stream);
+}
+
+int lzm_search_mlp_ez_supported(int actions, int hidden, int lstm_hidden, int head_hidden, int support) {
+  return ez_shape_ok(hidden, lstm_hidden, actions, head_hidden, support) ? 1 : 0;
+}
+
+int lzm_search_mlp_ez_plan(const lzm_handle *h, int num_simulations, int hidden, int lstm_hidden, int head_hidden,
+                           int support, int res_dynamics, int32_t *out) {
+  return mlp_plan_query("lzm_search_mlp_ez_plan", h, true, num_simulations, hidden, lstm_hidden, head_hidden, support,
+                        res_dynamics, out);
+}
+
+int lzm_search_mlp_ez(lzm_handle *h, int hidden, int lstm_hidden, int head_hidden, int support, int res_dynamics,
+                      const float *weights, int num_simulations, int lstm_horizon_len, int pb_c_base, float pb_c_init,
+                      float discount, float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
+                      float *h_pool, float *c_pool, int32_t *rec_x, int32_t *rec_a, int32_t *rec_len,
+                      int32_t *rec_reset, float *rec_decoded, float *rec_logits, void *stream) {
+  return search_mlp("lzm_search_mlp_ez", true, h, hidden, lstm_hidden, head_hidden, support, res_dynamics, weights,
+                    num_simulations, lstm_horizon_len, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in,
+                    latent_pool, h_pool, c_pool, rec_x, rec_a, rec_len, rec_reset, rec_decoded, rec_logits,
+                    (hipStream_t)stream);
 }
 
 // Collect-step mode of lzm_search_mlp (sticky on the handle, host state only: a captured launch
@@ -2023,332 +2125,6 @@ int lzm_search_set_step(lzm_handle *h, int64_t *count, int64_t base, int increme
   h->step_vals = root_values;
   h->step_fresh = fresh_minmax ? 1 : 0;
   h->step_delta = value_delta_max;
-  return LZM_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------- fused whole-search (EfficientZeroModelMLP, reward LSTM in-kernel)
-namespace {
-
-// Packed layers of the EfficientZeroModelMLP recurrent network (lightzero_amd/fused.py
-// pack_efficientzero_mlp): the dynamics layers, the LSTM gate layer as one dense layer over [x ; h_prev]
-// (columns in nn.LSTM order i, f, g, o), the value-prefix head, the prediction layers.
-constexpr int kEzLayers = 13;
-void ez_shapes(int H, int Hl, int A, int F, int V, LayerShape *s) {
-  s[0] = {H + A, (H + A + kKC - 1) / kKC * kKC, H};  // fc_dynamics(_1)[0]: [latent; one-hot action]
-  s[1] = {H, H, H};
-  s[2] = {H, H, H};                // fc_dynamics_2 (res_connection_in_dynamics)
-  s[3] = {H, H, H};
-  s[4] = {H + Hl, H + Hl, 4 * Hl};  // [weight_ih_l0 | weight_hh_l0], bias_ih_l0 + bias_hh_l0
-  s[5] = {Hl, Hl, F};              // fc_reward_head (reads h1)
-  s[6] = {F, F, V};
-  s[7] = {H, H, H};                // fc_prediction_common
-  s[8] = {H, H, H};
-  s[9] = {H, H, F};                // fc_value_head
-  s[10] = {F, F, V};
-  s[11] = {H, H, F};               // fc_policy_head
-  s[12] = {F, F, A};
-}
-int ez_kernel_layers(const LayerShape *s, int res, KLayer *kl) {
-  int n = 0;
-  auto one = [&](int l) { kl[n++] = KLayer{l, -1, s[l].K, s[l].N, s[l].N}; };
-  auto two = [&](int a, int b) { kl[n++] = KLayer{a, b, s[a].K, s[a].N + s[b].N, s[a].N}; };
-  one(0);
-  one(1);
-  if (res) {
-    one(2);
-    one(3);
-  }
-  for (int l = 4; l <= 8; ++l) one(l);
-  two(9, 11);
-  two(10, 12);
-  return n;
-}
-void ez_packed_offsets(const LayerShape *s, int res, size_t *w, size_t *b) {
-  size_t off = 0;
-  for (int l = 0; l < kEzLayers; ++l) {
-    w[l] = b[l] = off;
-    if (!layer_used(l, res)) continue;
-    off += (size_t)s[l].krows * s[l].N;
-    b[l] = off;
-    off += s[l].N;
-  }
-}
-// the EfficientZero kernel's own limits on top of the dense steps': the cell's lane map and the h1 rows
-// (the value-prefix head's K) need Hl % kKC == 0, the gate layer at most four column rounds.
-// Widths routed: see DESIGN.md 10 (every width the one-launch path was measured to win at).
-bool ez_shape_ok(int H, int Hl, int A, int F, int V) {
-  return mlp_shape_ok(H, A, F, V) && Hl > 0 && Hl % kKC == 0 && 4 * Hl <= 4 * kThreads;
-}
-// roots per workgroup of the EfficientZero kernel: 1, 2 or 4 (the gate rows of 8 would not leave the tree
-// its LDS), by roots_per_wg's rule
-int ez_roots_per_wg(int B) { return std::min(roots_per_wg(B), 4); }
-// LDS plan: the streaming kernel's, then the gate layer's input [x ; h_prev], the gates, h1 and c_prev
-size_t plan_stream_ez(SearchArgs &p, const lzm_handle *h, int R, int S, int H, int Hl, int A, int F, int V, int res) {
-  size_t o = plan_stream(p, h, R, S, H, A, F, V) / sizeof(float);
-  auto tfl = [R](int K) { return (size_t)((K + kKC - 1) / kKC) * (kKC * R + 4); };
-  p.off_g = o; o += round4(tfl(H + Hl));
-  p.off_gates = o; o += round4(tfl(4 * Hl));
-  p.off_hh = o; o += round4(tfl(Hl));
-  p.off_cp = o; o += round4((size_t)Hl * R);
-  if (!res) p.off_n = p.off_g;  // the next latent is the LSTM's input: the front rows of [x ; h_prev]
-  return o * sizeof(float);
-}
-struct EzPlan {
-  int R, kind, tree_in_lds;
-  size_t lds;
-};
-// What lzm_search_mlp_ez launches (kind 0: the weight-streaming kernel; -1: refused shape or LDS need)
-EzPlan ez_plan(const lzm_handle *h, int H, int Hl, int F, int V, int res, int S, SearchArgs &p) {
-  EzPlan pl{ez_roots_per_wg(h->B), -1, 0, 0};
-  if (!ez_shape_ok(H, Hl, h->A, F, V)) return pl;
-  pl.lds = plan_stream_ez(p, h, pl.R, S, H, Hl, h->A, F, V, res);
-  pl.tree_in_lds = p.tree_in_lds;
-  pl.kind = pl.lds <= kMaxLds ? 0 : -1;
-  return pl;
-}
-// The schedule (efficientzero_model_mlp.py:186-216, :452-468): fc_dynamics(_1) on [latent; one-hot]
-// (+ latent), fc_dynamics_2, the gate layer on [x ; h_prev] (the cell follows it in the kernel), the
-// value-prefix head on h1 (decoded), fc_prediction_common, the merged value | policy head. Padded to an
-// even length with an empty step (the two weight-prefetch buffers alternate).
-void build_schedule_ez(SearchArgs &p, const KLayer *kl, const size_t *w_off, const size_t *b_off, const float *weights,
-                       int res, int A, int V, int F, int R) {
-  const int x0 = (int)p.off_x0, x1 = (int)p.off_x1, x2 = (int)p.off_x2, nl = (int)p.off_n, hd = (int)p.off_h,
-            lg = (int)p.off_logit, gx = (int)p.off_g, gt = (int)p.off_gates, hh = (int)p.off_hh;
-  int n = 0, l = 0;
-  auto add = [&](int in, int out, int relu, int resid, int rowmajor, int ldout, int dec) -> StepRec & {
-    const KLayer &k = kl[l];
-    StepRec &q = p.sched[n++];
-    q.w = weights + w_off[l];
-    q.b = weights + b_off[l];
-    q.K = k.K;
-    q.N = k.N;
-    q.wbytes = (int)(swz_floats(k.K, k.N) * sizeof(float));
-    q.in = in; q.out = out; q.relu = relu; q.resid = resid; q.rowmajor = rowmajor; q.ldout = ldout; q.decode = dec;
-    q.ncol1 = k.N;
-    q.in2 = in; q.out2 = out; q.rowmajor2 = rowmajor; q.ldout2 = ldout;
-    const Split sp = layer_split(k.K, k.N);
-    q.Np = sp.Np; q.splits = sp.splits; q.cpl = sp.cpl; q.log2s = sp.log2s;
-    ++l;
-    return q;
-  };
-  add(x0, x1, 1, -1, 0, 0, 0);                    // fc_dynamics(_1)[0]
-  add(x1, nl, 1, res ? x0 : -1, 0, 0, 0);         // [1] (+ latent); without the residual nl == gx
-  if (res) {
-    add(nl, x1, 1, -1, 0, 0, 0);                  // fc_dynamics_2 -> the LSTM's input rows
-    add(x1, gx, 1, -1, 0, 0, 0);
-  }
-  add(gx, gt, 0, -1, 0, 0, 0);                    // gates = [x ; h_prev] . [W_ih | W_hh] + (b_ih + b_hh)
-  p.cell_after = n - 1;
-  add(hh, hd, 1, -1, 0, 0, 0);                    // fc_reward_head on the unmasked h1
-  add(hd, lg, 0, -1, 1, V + 1, 1);
-  add(nl, x1, 1, -1, 0, 0, 0);                    // fc_prediction_common
-  add(x1, x2, 1, -1, 0, 0, 0);
-  add(x2, hd, 1, -1, 0, 0, 0);                    // [fc_value_head[0] | fc_policy_head[0]]
-  StepRec &o = add(hd, lg, 0, -1, 1, V + 1, 2);   // [fc_value_head[1] | fc_policy_head[1]]
-  o.ncol1 = V;
-  o.in2 = hd + F / kKC * (kKC * R + 4);
-  o.out2 = x1; o.rowmajor2 = 1; o.ldout2 = A;
-  if (n & 1) {  // the empty step: no columns, no weights (every load out of range), one barrier
-    StepRec &q = p.sched[n++];
-    memset(&q, 0, sizeof(q));
-    q.w = weights; q.b = weights;
-    q.resid = -1;
-    const Split sp = layer_split(0, 0);
-    q.Np = sp.Np; q.splits = sp.splits; q.cpl = sp.cpl; q.log2s = sp.log2s;
-  }
-  for (int i = 0; i < 4; ++i) p.stamp_at[i] = -1;
-  p.nsteps = n;
-}
-
-template <int R>
-hipError_t launch_search_ez(const SearchArgs &p, int G, size_t lds, hipStream_t stream) {
-  const void *fn = p.tree_in_lds ? (const void *)search_mlp_kernel<R, true, true>
-                                 : (const void *)search_mlp_kernel<R, false, true>;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  if (p.tree_in_lds)
-    hipLaunchKernelGGL((search_mlp_kernel<R, true, true>), dim3(G), dim3(kThreads), lds, stream, p);
-  else
-    hipLaunchKernelGGL((search_mlp_kernel<R, false, true>), dim3(G), dim3(kThreads), lds, stream, p);
-  return hipGetLastError();
-}
-}  // namespace
-
-extern "C" {
-
-int64_t lzm_mlp_ez_packed_floats(int hidden, int lstm_hidden, int actions, int head_hidden, int support,
-                                 int res_dynamics) {
-  if (hidden <= 0 || lstm_hidden <= 0 || actions <= 0 || head_hidden <= 0 || support <= 0) return -1;
-  LayerShape s[kEzLayers];
-  ez_shapes(hidden, lstm_hidden, actions, head_hidden, support, s);
-  int64_t n = 0;
-  for (int l = 0; l < kEzLayers; ++l)
-    if (layer_used(l, res_dynamics)) n += (int64_t)s[l].krows * s[l].N + s[l].N;
-  return n;
-}
-
-int64_t lzm_mlp_ez_kernel_floats(int hidden, int lstm_hidden, int actions, int head_hidden, int support,
-                                 int res_dynamics) {
-  if (hidden <= 0 || lstm_hidden <= 0 || actions <= 0 || head_hidden <= 0 || support <= 0) return -1;
-  LayerShape s[kEzLayers];
-  ez_shapes(hidden, lstm_hidden, actions, head_hidden, support, s);
-  KLayer kl[kEzLayers];
-  const int nk = ez_kernel_layers(s, res_dynamics, kl);
-  size_t w_off[kEzLayers], b_off[kEzLayers];
-  return (int64_t)kernel_layout(kl, nk, w_off, b_off);
-}
-
-int lzm_mlp_ez_prepare(int hidden, int lstm_hidden, int actions, int head_hidden, int support, int res_dynamics,
-                       const float *packed, float *out, void *stream) {
-  if (!packed || !out || hidden <= 0 || lstm_hidden <= 0 || actions <= 0 || head_hidden <= 0 || support <= 0 ||
-      hidden % kKC != 0 || head_hidden % kKC != 0 || lstm_hidden % kKC != 0) {
-    set_err("lzm_mlp_ez_prepare: bad arguments (hidden, LSTM and head widths must be multiples of 16)");
-    return LZM_ERR_ARG;
-  }
-  LayerShape s[kEzLayers];
-  ez_shapes(hidden, lstm_hidden, actions, head_hidden, support, s);
-  size_t pw[kEzLayers], pb[kEzLayers];
-  ez_packed_offsets(s, res_dynamics, pw, pb);
-  KLayer kl[kEzLayers];
-  const int nk = ez_kernel_layers(s, res_dynamics, kl);
-  size_t w_off[kEzLayers], b_off[kEzLayers];
-  kernel_layout(kl, nk, w_off, b_off);
-  for (int l = 0; l < nk; ++l) {
-    const KLayer &q = kl[l];
-    const size_t n = swz_floats(q.K, q.N);
-    const int s1 = q.src1 >= 0 ? q.src1 : q.src0;
-    hipLaunchKernelGGL(mlp_swizzle_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       packed + pw[q.src0], s[q.src0].krows, packed + pw[s1], s[s1].krows, q.K, q.N, q.N0,
-                       out + w_off[l], n);
-    LZM_CHECK_LAUNCH();
-    LZM_HIP(hipMemcpyAsync(out + b_off[l], packed + pb[q.src0], (size_t)q.N0 * sizeof(float),
-                           hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (q.src1 >= 0)
-      LZM_HIP(hipMemcpyAsync(out + b_off[l] + q.N0, packed + pb[q.src1], (size_t)(q.N - q.N0) * sizeof(float),
-                             hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  }
-  return LZM_OK;
-}
-
-int lzm_search_mlp_ez_supported(int actions, int hidden, int lstm_hidden, int head_hidden, int support) {
-  return ez_shape_ok(hidden, lstm_hidden, actions, head_hidden, support) ? 1 : 0;
-}
-
-int lzm_search_mlp_ez_plan(const lzm_handle *h, int num_simulations, int hidden, int lstm_hidden, int head_hidden,
-                           int support, int res_dynamics, int32_t *out) {
-  if (!h || !out || num_simulations <= 0) {
-    set_err("lzm_search_mlp_ez_plan: null argument or no simulations");
-    return LZM_ERR_ARG;
-  }
-  if (num_simulations > h->sims_cap) {
-    snprintf(g_err, sizeof(g_err), "lzm_search_mlp_ez_plan: %d simulations > reserved %d (lzm_reserve)",
-             num_simulations, h->sims_cap);
-    return LZM_ERR_CAPACITY;
-  }
-  SearchArgs p;
-  memset(&p, 0, sizeof(p));
-  const EzPlan pl = ez_plan(h, hidden, lstm_hidden, head_hidden, support, res_dynamics, num_simulations, p);
-  out[0] = pl.R;
-  out[1] = (h->flags & LZM_TREE_EZ) ? pl.kind : -1;
-  out[2] = 0;
-  out[3] = pl.tree_in_lds;
-  return LZM_OK;
-}
-
-int lzm_search_mlp_ez(lzm_handle *h, int hidden, int lstm_hidden, int head_hidden, int support, int res_dynamics,
-                      const float *weights, int num_simulations, int lstm_horizon_len, int pb_c_base, float pb_c_init,
-                      float discount, float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
-                      float *h_pool, float *c_pool, int32_t *rec_x, int32_t *rec_a, int32_t *rec_len,
-                      int32_t *rec_reset, float *rec_decoded, float *rec_logits, void *stream) {
-  if (!h || !weights || !minmax || (!seeds && !h->step_count) || !vtp_in || !latent_pool || !h_pool || !c_pool ||
-      num_simulations <= 0) {
-    set_err("lzm_search_mlp_ez: null argument or no simulations");
-    return LZM_ERR_ARG;
-  }
-  if ((uintptr_t)weights & 15) {
-    set_err("lzm_search_mlp_ez: weights must be 16-byte aligned (lzm_mlp_ez_prepare output)");
-    return LZM_ERR_ARG;
-  }
-  if (!(h->flags & LZM_TREE_EZ)) {
-    set_err("lzm_search_mlp_ez: EfficientZero trees only");
-    return LZM_ERR_ARG;
-  }
-  if (lstm_horizon_len <= 0) {
-    set_err("lzm_search_mlp_ez: lstm_horizon_len must be > 0");
-    return LZM_ERR_ARG;
-  }
-  const int H = hidden, Hl = lstm_hidden, F = head_hidden, V = support, A = h->A, S = num_simulations;
-  if (!ez_shape_ok(H, Hl, A, F, V)) {
-    set_err("lzm_search_mlp_ez: unsupported network shape (lzm_search_mlp_ez_supported)");
-    return LZM_ERR_ARG;
-  }
-  if (S > h->sims_cap) {
-    snprintf(g_err, sizeof(g_err), "lzm_search_mlp_ez: %d simulations > reserved %d (lzm_reserve)", S, h->sims_cap);
-    return LZM_ERR_CAPACITY;
-  }
-  int rc = fill_lut(h, pb_c_base, pb_c_init);
-  if (rc != LZM_OK) return rc;
-  SearchArgs p;
-  memset(&p, 0, sizeof(p));
-  const EzPlan plan = ez_plan(h, H, Hl, F, V, res_dynamics, S, p);
-  if (plan.kind != 0) {
-    snprintf(g_err, sizeof(g_err), "lzm_search_mlp_ez: %zu B of LDS needed (network or tree too large)", plan.lds);
-    return LZM_ERR_ARG;
-  }
-  const int R = plan.R;
-  const int G = (h->B + R - 1) / R;
-  const bool fast = (h->flags & LZM_RNG_FAST) != 0;
-  if (!fast) {
-    rc = ensure_coef(h, h->B * (S + 1) + 64);
-    if (rc != LZM_OK) return rc;
-  }
-  rc = ensure_flags(h, S, G);
-  if (rc != LZM_OK) return rc;
-  p.stat = h->stat; p.meta = h->meta; p.legal = h->legal; p.nlegal = h->nlegal;
-  p.path = h->path; p.path_act = h->path_act; p.pathlen = h->pathlen; p.lut = h->lut;
-  p.B = h->B; p.A = A; p.cap = h->cap; p.lut_n = h->lut_n; p.depth_cap = h->depth_cap;
-  p.S = S; p.disc = discount; p.seeds = seeds; p.vtp_in = vtp_in; p.minmax = (float4 *)minmax; p.pool = latent_pool;
-  p.H = H; p.F = F; p.V = V; p.res = res_dynamics ? 1 : 0;
-  p.hpool = h_pool; p.cpool = c_pool; p.Hl = Hl; p.horizon = lstm_horizon_len; p.rec_reset = rec_reset;
-  p.coef = h->coef; p.coef_positions = h->coef_positions; p.pow16807 = h->pow16807;
-  p.flags = h->lb_flags; p.epoch = h->epoch; p.diag = h->search_diag; p.fast = fast ? 1 : 0;
-  p.rec_x = rec_x; p.rec_a = rec_a; p.rec_len = rec_len; p.rec_dec = rec_decoded; p.rec_logits = rec_logits;
-  {
-    LayerShape s[kEzLayers];
-    ez_shapes(H, Hl, A, F, V, s);
-    KLayer kls[kEzLayers];
-    const int nkl = ez_kernel_layers(s, res_dynamics, kls);
-    size_t lay_w[kEzLayers], lay_b[kEzLayers];
-    kernel_layout(kls, nkl, lay_w, lay_b);
-    build_schedule_ez(p, kls, lay_w, lay_b, weights, res_dynamics ? 1 : 0, A, V, F, R);
-  }
-  // collect-step mode: the prologue and epilogue launches of lzm_search_mlp's streaming kernel
-  if (h->step_count || h->step_fresh) {
-    if (h->step_count && h->step_seeds_n < S) {
-      set_err("lzm_search_mlp_ez: step seeds buffer smaller than num_simulations (reserve first)");
-      return LZM_ERR_STATE;
-    }
-    const int n = std::max(S, h->B);
-    hipLaunchKernelGGL(step_prologue_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->step_count,
-                       h->step_base, S, h->step_seeds, (float4 *)minmax, h->B, h->step_fresh, h->step_delta);
-    LZM_CHECK_LAUNCH();
-    if (h->step_count) p.seeds = reinterpret_cast<const uint32_t *>(h->step_seeds);
-  }
-  hipError_t e;
-  switch (R) {
-    case 1: e = launch_search_ez<1>(p, G, plan.lds, (hipStream_t)stream); break;
-    case 2: e = launch_search_ez<2>(p, G, plan.lds, (hipStream_t)stream); break;
-    default: e = launch_search_ez<4>(p, G, plan.lds, (hipStream_t)stream); break;
-  }
-  LZM_HIP(e);
-  LZM_CHECK_LAUNCH();
-  if ((h->step_count && h->step_inc) || h->step_dist || h->step_vals) {
-    hipLaunchKernelGGL(step_epilogue_kernel, dim3((h->B + 255) / 256), dim3(256), 0, (hipStream_t)stream, view(h),
-                       h->step_dist, h->step_vals, h->step_inc ? h->step_count : nullptr);
-    LZM_CHECK_LAUNCH();
-  }
   return LZM_OK;
 }
 
@@ -3455,110 +3231,16 @@ static ConvPlan conv_plan_mz(const lzm_handle *h, int S, int n_dres, int n_pres,
   return pl;
 }
 
-// Whole-search launch for the conv MuZero networks (lzm_search_conv.h): one workgroup per root,
-// every simulation inside the kernel. The grid must be co-resident (one workgroup per CU, B <= CUs):
-// parity-mode roots wait on their predecessors' depth flags.
-// max_roots < 0: lzm_search_conv (the whole batch, one launch); >= 0: lzm_search_conv_sliced (every root slice
-// enqueued on the stream, lowest roots first).
-static int search_conv_launch(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init, float discount,
-                              float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
-                              const float *trunk_w, const float *actmap, int n_dres, int n_pres, int r_ch, int h_ch,
-                              const float *w1t, const float *b1, const float *w2q, const float *b2, int Kr, int Khd,
-                              int off_policy, int Vr, int Vv, int categorical, int32_t *rec_x, int32_t *rec_a,
-                              int32_t *rec_len, float *rec_decoded, float *rec_logits, void *stream, int max_roots) {
-  const int S = num_simulations;
-  if (!h || !minmax || (!seeds && !h->step_count) || !vtp_in || !latent_pool || !trunk_w || !actmap || !w1t || !b1 ||
-      !w2q || !b2 ||
-      S <= 0) {
-    set_err("lzm_search_conv: null argument or no simulations");
-    return LZM_ERR_ARG;
-  }
-  if (((uintptr_t)trunk_w | (uintptr_t)actmap | (uintptr_t)w1t | (uintptr_t)w2q | (uintptr_t)latent_pool) & 15) {
-    set_err("lzm_search_conv: weights and pool must be 16-byte aligned");
-    return LZM_ERR_ARG;
-  }
-  ConvSearchArgs p;
-  memset(&p, 0, sizeof(p));
-  const ConvPlan plan = conv_plan_mz(h, S, n_dres, n_pres, r_ch, h_ch, Kr, Khd, off_policy, Vr, Vv, categorical, p,
-                                     max_roots);
-  if (plan.rc != LZM_OK) return plan.rc;
-  int rc = fill_lut(h, pb_c_base, pb_c_init);
-  if (rc != LZM_OK) return rc;
-  const bool fast = (h->flags & LZM_RNG_FAST) != 0;
-  if (!fast) {
-    rc = ensure_coef(h, h->B * (S + 1) + 64);
-    if (rc != LZM_OK) return rc;
-  }
-  rc = ensure_flags(h, S, h->B);
-  if (rc != LZM_OK) return rc;
-  p.stat = h->stat; p.meta = h->meta; p.legal = h->legal; p.nlegal = h->nlegal;
-  p.path = h->path; p.path_act = h->path_act; p.pathlen = h->pathlen; p.lut = h->lut;
-  p.B = h->B; p.A = h->A; p.cap = h->cap; p.lut_n = h->lut_n; p.depth_cap = h->depth_cap;
-  p.S = S; p.disc = discount; p.seeds = seeds; p.vtp_in = vtp_in; p.minmax = (float4 *)minmax; p.pool = latent_pool;
-  p.w = trunk_w; p.actmap = actmap; p.n_dres = n_dres; p.n_pres = n_pres; p.r_ch = r_ch; p.h_ch = h_ch;
-  p.w1t = w1t; p.b1 = b1; p.w2q = w2q; p.b2 = b2; p.Kr = Kr; p.Khd = Khd; p.off_policy = off_policy;
-  p.Vr = Vr; p.Vv = Vv; p.categorical = categorical ? 1 : 0;
-  p.coef = h->coef; p.coef_positions = h->coef_positions; p.pow16807 = h->pow16807;
-  p.flags = h->lb_flags; p.epoch = h->epoch; p.err = h->err; p.sdiag = h->search_diag; p.fast = fast ? 1 : 0;
-  p.rec_x = rec_x; p.rec_a = rec_a; p.rec_len = rec_len; p.rec_dec = rec_decoded; p.rec_logits = rec_logits;
-  p.step_count = h->step_count; p.step_base = h->step_base; p.step_inc = h->step_inc; p.step_fresh = h->step_fresh;
-  p.step_delta = h->step_delta; p.out_dist = h->step_dist; p.out_values = h->step_vals;
-  const size_t lds = plan.lds;
-  const bool stamps = getenv("LZM_PHASE_TIMING") && atoi(getenv("LZM_PHASE_TIMING")) > 0;
-  if (stamps && !h->phase) {
-    LZM_HIP(hipMalloc(&h->phase, (64 + 1024) * sizeof(unsigned long long)));
-    LZM_HIP(hipMemset(h->phase, 0, (64 + 1024) * sizeof(unsigned long long)));
-  }
-  p.stamps = stamps ? h->phase : nullptr;
-  auto fn = stamps ? (fast ? search_conv_kernel<kBxAhead, true, true> : search_conv_kernel<kBxAhead, false, true>)
-                   : (fast ? search_conv_kernel<kBxAhead, true> : search_conv_kernel<kBxAhead, false>);
-  hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  for (int root0 = 0; e == hipSuccess && root0 < h->B; root0 += plan.roots) {
-    p.root0 = root0;
-    p.nroots = std::min(plan.roots, h->B - root0);
-    p.last_slice = root0 + p.nroots >= h->B;
-    hipLaunchKernelGGL(fn, dim3(p.nroots), dim3(kScThreads), lds, (hipStream_t)stream, p);
-    e = hipGetLastError();
-  }
-  LZM_HIP(e);
-  return LZM_OK;
+// the conv search kernel for a tree kind, an RNG and phase stamps
+typedef void (*ConvKernel)(ConvSearchArgs);
+static ConvKernel conv_kernel_fn(bool ez, bool fast, bool stamps) {
+  static const ConvKernel kernels[2][2][2] = {  // [EZ][stamps, none][Philox, glibc]
+      {{search_conv_kernel<kBxAhead, true, true>, search_conv_kernel<kBxAhead, false, true>},
+       {search_conv_kernel<kBxAhead, true>, search_conv_kernel<kBxAhead, false>}},
+      {{search_conv_ez_kernel<kBxAheadEz, true, true>, search_conv_ez_kernel<kBxAheadEz, false, true>},
+       {search_conv_ez_kernel<kBxAheadEz, true>, search_conv_ez_kernel<kBxAheadEz, false>}}};
+  return kernels[ez][stamps ? 0 : 1][fast ? 0 : 1];
 }
-
-extern "C" int lzm_search_conv(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init, float discount,
-                               float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
-                               const float *trunk_w, const float *actmap, int n_dres, int n_pres, int r_ch, int h_ch,
-                               const float *w1t, const float *b1, const float *w2q, const float *b2, int Kr, int Khd,
-                               int off_policy, int Vr, int Vv, int categorical, int32_t *rec_x, int32_t *rec_a,
-                               int32_t *rec_len, float *rec_decoded, float *rec_logits, void *stream) {
-  return search_conv_launch(h, num_simulations, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in, latent_pool,
-                            trunk_w, actmap, n_dres, n_pres, r_ch, h_ch, w1t, b1, w2q, b2, Kr, Khd, off_policy, Vr, Vv,
-                            categorical, rec_x, rec_a, rec_len, rec_decoded, rec_logits, stream, -1);
-}
-
-// lzm_search_conv over root slices (lzm_conv_slice_roots; max_roots: the caller's cap on a slice, 0 = none): any
-// number of roots, the slices enqueued one after another on `stream` (plain launches, capturable).
-extern "C" int lzm_search_conv_sliced(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init,
-                                      float discount, float *minmax, const uint32_t *seeds, const int32_t *vtp_in,
-                                      float *latent_pool, const float *trunk_w, const float *actmap, int n_dres,
-                                      int n_pres, int r_ch, int h_ch, const float *w1t, const float *b1,
-                                      const float *w2q, const float *b2, int Kr, int Khd, int off_policy, int Vr,
-                                      int Vv, int categorical, int32_t *rec_x, int32_t *rec_a, int32_t *rec_len,
-                                      float *rec_decoded, float *rec_logits, int max_roots, void *stream) {
-  if (max_roots < 0) {
-    set_err("lzm_search_conv_sliced: max_roots >= 0 (0: no cap)");
-    return LZM_ERR_ARG;
-  }
-  return search_conv_launch(h, num_simulations, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in, latent_pool,
-                            trunk_w, actmap, n_dres, n_pres, r_ch, h_ch, w1t, b1, w2q, b2, Kr, Khd, off_policy, Vr, Vv,
-                            categorical, rec_x, rec_a, rec_len, rec_decoded, rec_logits, stream, max_roots);
-}
-
-using ConvEzFn = decltype(&search_conv_ez_kernel<kBxAheadEz, false, false>);
-static ConvEzFn conv_ez_kernel_fn(bool fast, bool stamps) {
-  return stamps ? (fast ? search_conv_ez_kernel<kBxAheadEz, true, true> : search_conv_ez_kernel<kBxAheadEz, false, true>)
-                : (fast ? search_conv_ez_kernel<kBxAheadEz, true> : search_conv_ez_kernel<kBxAheadEz, false>);
-}
-static bool conv_stamps() { return getenv("LZM_PHASE_TIMING") && atoi(getenv("LZM_PHASE_TIMING")) > 0; }
 
 // conv_plan_mz's EfficientZero twin. The shape, capacity and grid checks touch no HIP state; a request that
 // passes them is then measured against the occupancy of the kernel it would launch (residency = true).
@@ -3633,7 +3315,7 @@ static ConvPlan conv_plan_ez(const lzm_handle *h, int S, int H, int horizon, int
   // not a residency guarantee against other streams), cannot be captured into a HIP graph, and its
   // runtime state was the one difference from the MuZero conv search in the EZ trace that faulted in
   // exit() after rocprofv3 finalised (profiles/r05/README.md).
-  const void *fn = (const void *)conv_ez_kernel_fn((h->flags & LZM_RNG_FAST) != 0, conv_stamps());
+  const void *fn = (const void *)conv_kernel_fn(true, (h->flags & LZM_RNG_FAST) != 0, phase_timing());
   int per_cu = 0;
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds) != hipSuccess ||
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kScThreads, pl.lds) != hipSuccess) {
@@ -3661,9 +3343,28 @@ static ConvPlan conv_plan_ez(const lzm_handle *h, int S, int H, int horizon, int
   return pl;
 }
 
+// The plan queries' body: what the launch would do for this request as the process stands, by the launches'
+// own decision (conv_plan_mz / conv_plan_ez); launches nothing. max_roots < 0: the single launch, out[0 .. 7];
+// >= 0: the sliced launch with that cap, out[8 .. 10] as well.
+static int conv_plan_query(const lzm_handle *h, int S, int ez, int H, int horizon, int n_dres, int n_pres, int r_ch,
+                           int h_ch, int Kr, int Khd, int off_policy, int Vr, int Vv, int categorical, int max_roots,
+                           int32_t *out) {
+  ConvSearchArgs p;
+  memset(&p, 0, sizeof(p));
+  const ConvPlan pl = ez ? conv_plan_ez(h, S, H, horizon, n_dres, n_pres, r_ch, h_ch, Khd, off_policy, Vr, Vv,
+                                        categorical, p, max_roots)
+                         : conv_plan_mz(h, S, n_dres, n_pres, r_ch, h_ch, Kr, Khd, off_policy, Vr, Vv, categorical, p,
+                                        max_roots);
+  out[0] = pl.rc; out[1] = pl.G; out[2] = pl.T; out[3] = (int32_t)pl.lds; out[4] = pl.npin; out[5] = pl.pbt_rows;
+  out[6] = pl.out_rounds; out[7] = pl.r_one_round;
+  if (max_roots < 0) return LZM_OK;
+  const int n = pl.rc == LZM_OK && pl.roots > 0 ? (h->B + pl.roots - 1) / pl.roots : 0;
+  out[8] = n; out[9] = n ? pl.roots : 0; out[10] = n ? h->B - (n - 1) * pl.roots : 0;
+  return LZM_OK;
+}
+
 // What lzm_search_conv (ez = 0: H and horizon ignored, Kr = r_ch * 64) or lzm_search_conv_ez (ez = 1: Kr ignored)
-// would do for this request as the process stands, by the launches' own decision (conv_plan_mz / conv_plan_ez);
-// launches nothing. out[8]: {rc the launch would return (LZM_OK: it runs), workgroups, LSTM tiles, dynamic LDS
+// would do. out[8]: {rc the launch would return (LZM_OK: it runs), workgroups, LSTM tiles, dynamic LDS
 // bytes, pinned head half-heads, pb_c table rows, rounds of the value | policy (MuZero: whole) output loop
 // (0 = EfficientZero's single-round form), 1 if the EfficientZero reward output takes the single-round form}.
 extern "C" int lzm_search_conv_plan(const lzm_handle *h, int num_simulations, int ez, int H, int horizon, int n_dres,
@@ -3673,15 +3374,8 @@ extern "C" int lzm_search_conv_plan(const lzm_handle *h, int num_simulations, in
     set_err("lzm_search_conv_plan: null argument or no simulations");
     return LZM_ERR_ARG;
   }
-  ConvSearchArgs p;
-  memset(&p, 0, sizeof(p));
-  const ConvPlan pl = ez ? conv_plan_ez(h, num_simulations, H, horizon, n_dres, n_pres, r_ch, h_ch, Khd, off_policy,
-                                        Vr, Vv, categorical, p)
-                         : conv_plan_mz(h, num_simulations, n_dres, n_pres, r_ch, h_ch, Kr, Khd, off_policy, Vr, Vv,
-                                        categorical, p);
-  out[0] = pl.rc; out[1] = pl.G; out[2] = pl.T; out[3] = (int32_t)pl.lds; out[4] = pl.npin; out[5] = pl.pbt_rows;
-  out[6] = pl.out_rounds; out[7] = pl.r_one_round;
-  return LZM_OK;
+  return conv_plan_query(h, num_simulations, ez, H, horizon, n_dres, n_pres, r_ch, h_ch, Kr, Khd, off_policy, Vr, Vv,
+                         categorical, -1, out);
 }
 
 // lzm_search_conv_plan for lzm_search_conv_sliced / lzm_search_conv_ez_sliced with the same max_roots: out[0 .. 7]
@@ -3695,63 +3389,23 @@ extern "C" int lzm_search_conv_sliced_plan(const lzm_handle *h, int num_simulati
     set_err("lzm_search_conv_sliced_plan: null argument, no simulations or max_roots < 0");
     return LZM_ERR_ARG;
   }
-  ConvSearchArgs p;
-  memset(&p, 0, sizeof(p));
-  const ConvPlan pl = ez ? conv_plan_ez(h, num_simulations, H, horizon, n_dres, n_pres, r_ch, h_ch, Khd, off_policy,
-                                        Vr, Vv, categorical, p, max_roots)
-                         : conv_plan_mz(h, num_simulations, n_dres, n_pres, r_ch, h_ch, Kr, Khd, off_policy, Vr, Vv,
-                                        categorical, p, max_roots);
-  out[0] = pl.rc; out[1] = pl.G; out[2] = pl.T; out[3] = (int32_t)pl.lds; out[4] = pl.npin; out[5] = pl.pbt_rows;
-  out[6] = pl.out_rounds; out[7] = pl.r_one_round;
-  const int n = pl.rc == LZM_OK && pl.roots > 0 ? (h->B + pl.roots - 1) / pl.roots : 0;
-  out[8] = n; out[9] = n ? pl.roots : 0; out[10] = n ? h->B - (n - 1) * pl.roots : 0;
-  return LZM_OK;
+  return conv_plan_query(h, num_simulations, ez, H, horizon, n_dres, n_pres, r_ch, h_ch, Kr, Khd, off_policy, Vr, Vv,
+                         categorical, max_roots, out);
 }
 
-// Whole-search launch for the conv EfficientZero networks (lzm_search_conv.h, EZ instantiation): the
-// MuZero launch's flow plus the reward LSTM as split-K tiles spread over the grid (G = max(B, 2 T)
-// workgroups, one per CU, co-resident: the tiles wait on the roots' LSTM input rows and the roots on
-// their rows' tiles inside the launch).
-// max_roots < 0: lzm_search_conv_ez (the whole batch, one launch); >= 0: lzm_search_conv_ez_sliced (every root
-// slice, each a co-resident grid of its own, enqueued on the stream, lowest roots first).
-static int search_conv_ez_launch(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init, float discount,
-                                 float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
-                                 float *hpool, float *cpool, int H, int horizon, const float *trunk_w,
-                                 const float *actmap, int n_dres, int n_pres, int r_ch, int h_ch,
-                                 const float *lstm_frag, const float *lstm_bias, const float *vp_s, const float *vp_t,
-                                 const float *w1t, const float *b1, const float *w2q, const float *b2, int Khd,
-                                 int off_policy, int Vr, int Vv, int categorical, int32_t *rec_x, int32_t *rec_a,
-                                 int32_t *rec_len, float *rec_decoded, float *rec_logits, int32_t *rec_reset,
-                                 void *stream, int max_roots) {
-  const int S = num_simulations;
-  if (!h || !minmax || (!seeds && !h->step_count) || !vtp_in || !latent_pool || !hpool || !cpool || !trunk_w ||
-      !actmap || !lstm_frag ||
-      !lstm_bias || !vp_s || !vp_t || !w1t || !b1 || !w2q || !b2 || S <= 0) {
-    set_err("lzm_search_conv_ez: null argument or no simulations");
-    return LZM_ERR_ARG;
-  }
-  if (((uintptr_t)trunk_w | (uintptr_t)actmap | (uintptr_t)w1t | (uintptr_t)w2q | (uintptr_t)latent_pool |
-       (uintptr_t)hpool | (uintptr_t)cpool | (uintptr_t)lstm_frag | (uintptr_t)vp_s | (uintptr_t)vp_t) & 15) {
-    set_err("lzm_search_conv_ez: weights and pools must be 16-byte aligned");
-    return LZM_ERR_ARG;
-  }
-  ConvSearchArgs p;
-  memset(&p, 0, sizeof(p));
-  const ConvPlan plan = conv_plan_ez(h, S, H, horizon, n_dres, n_pres, r_ch, h_ch, Khd, off_policy, Vr, Vv,
-                                     categorical, p, max_roots);
-  if (plan.rc != LZM_OK) return plan.rc;
-  // (T: the whole batch's tile grid — the hand-off words and partials are filed by the global tile index)
-  const int Kx = r_ch * 64 + H, B = h->B, T = p.T;
-  int rc = fill_lut(h, pb_c_base, pb_c_init);
-  if (rc != LZM_OK) return rc;
-  const bool fast = (h->flags & LZM_RNG_FAST) != 0;
-  if (!fast) {
-    rc = ensure_coef(h, B * (S + 1) + 64);
-    if (rc != LZM_OK) return rc;
-  }
-  rc = ensure_flags(h, S, B);
-  if (rc != LZM_OK) return rc;
-  // hand-off workspace, grown on demand (flags zeroed: epoch 0 never matches)
+// The EfficientZero inputs of the conv search beside MuZero's: the reward LSTM's state pools, width and
+// horizon, its prepared gate weights and bias, the value-prefix BatchNorm map, the is_reset record
+struct ConvEzIn {
+  float *hpool, *cpool;
+  int H, horizon;
+  const float *lstm_frag, *lstm_bias, *vp_s, *vp_t;
+  int32_t *rec_reset;
+};
+// The EfficientZero step of the launch: the hand-off workspace (LSTM input rows, outputs, split-K partials,
+// flags), grown on demand (flags zeroed: epoch 0 never matches), and the LSTM and value-prefix pointers.
+// (p.T: the whole batch's tile grid — the hand-off words and partials are filed by the global tile index)
+static int conv_ez_attach(lzm_handle *h, ConvSearchArgs &p, const ConvEzIn &z, int S, int r_ch) {
+  const int H = z.H, Kx = r_ch * 64 + H, B = h->B, T = p.T;
   const size_t f_xin = round4((size_t)B * Kx), f_h1 = round4((size_t)B * H), f_part = (size_t)T * kLpThreads * 16;
   const size_t flag_words = (size_t)S * B + 2 * (size_t)S * T;
   const size_t need = (f_xin + f_h1 + f_part) * sizeof(float) + flag_words * sizeof(unsigned long long);
@@ -3765,42 +3419,110 @@ static int search_conv_ez_launch(lzm_handle *h, int num_simulations, int pb_c_ba
   }
   float *wsf = reinterpret_cast<float *>(h->ez_ws);
   unsigned long long *wsl = reinterpret_cast<unsigned long long *>(wsf + f_xin + f_h1 + f_part);
-  p.stat = h->stat; p.meta = h->meta; p.legal = h->legal; p.nlegal = h->nlegal;
-  p.path = h->path; p.path_act = h->path_act; p.pathlen = h->pathlen; p.lut = h->lut;
-  p.B = B; p.A = h->A; p.cap = h->cap; p.lut_n = h->lut_n; p.depth_cap = h->depth_cap;
-  p.S = S; p.disc = discount; p.seeds = seeds; p.vtp_in = vtp_in; p.minmax = (float4 *)minmax; p.pool = latent_pool;
-  p.w = trunk_w; p.actmap = actmap; p.n_dres = n_dres; p.n_pres = n_pres; p.r_ch = r_ch; p.h_ch = h_ch;
-  p.w1t = w1t; p.b1 = b1; p.w2q = w2q; p.b2 = b2; p.Kr = H; p.Khd = Khd; p.off_policy = off_policy;
-  p.Vr = Vr; p.Vv = Vv; p.categorical = categorical ? 1 : 0;
-  p.coef = h->coef; p.coef_positions = h->coef_positions; p.pow16807 = h->pow16807;
-  p.flags = h->lb_flags; p.epoch = h->epoch; p.err = h->err; p.sdiag = h->search_diag; p.fast = fast ? 1 : 0;
-  p.rec_x = rec_x; p.rec_a = rec_a; p.rec_len = rec_len; p.rec_dec = rec_decoded; p.rec_logits = rec_logits;
-  p.step_count = h->step_count; p.step_base = h->step_base; p.step_inc = h->step_inc; p.step_fresh = h->step_fresh;
-  p.step_delta = h->step_delta; p.out_dist = h->step_dist; p.out_values = h->step_vals;
-  p.rec_reset = rec_reset;
+  p.rec_reset = z.rec_reset;
   p.xin = wsf; p.h1g = wsf + f_xin; p.kpart = wsf + f_xin + f_h1;
   p.xflags = wsl; p.tflags = wsl + (size_t)S * B; p.pflags = wsl + (size_t)S * B + (size_t)S * T;
-  p.Kx = Kx; p.H = H; p.horizon = horizon; p.hpool = hpool; p.cpool = cpool;
-  p.lwfrag = reinterpret_cast<const uint16_t *>(lstm_frag); p.lwinv = lstm_frag + ls_frag_floats(Kx, H);
-  p.lbias = lstm_bias; p.vp_s = vp_s; p.vp_t = vp_t;
-  const size_t lds = plan.lds;
-  const bool stamps = conv_stamps();
-  if (stamps && !h->phase) {
-    LZM_HIP(hipMalloc(&h->phase, (64 + 1024) * sizeof(unsigned long long)));
-    LZM_HIP(hipMemset(h->phase, 0, (64 + 1024) * sizeof(unsigned long long)));
+  p.Kx = Kx; p.H = H; p.horizon = z.horizon; p.hpool = z.hpool; p.cpool = z.cpool;
+  p.lwfrag = reinterpret_cast<const uint16_t *>(z.lstm_frag); p.lwinv = z.lstm_frag + ls_frag_floats(Kx, H);
+  p.lbias = z.lstm_bias; p.vp_s = z.vp_s; p.vp_t = z.vp_t;
+  return LZM_OK;
+}
+
+// Whole-search launch for the conv networks (lzm_search_conv.h): one workgroup per root, every simulation
+// inside the kernel; parity-mode roots wait on their predecessors' depth flags. ez != null: the EfficientZero
+// instantiation, the same flow plus the reward LSTM as split-K tiles spread over the grid (max(roots, 2 T)
+// workgroups, co-resident: the tiles wait on the roots' LSTM input rows and the roots on their rows' tiles
+// inside the launch; Kr is then the LSTM's width).
+// max_roots < 0: the whole batch in one launch; >= 0: the sliced entry points (every root slice, EfficientZero's
+// each a co-resident grid of its own, enqueued on the stream, lowest roots first).
+static int search_conv_launch(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init, float discount,
+                              float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
+                              const float *trunk_w, const float *actmap, int n_dres, int n_pres, int r_ch, int h_ch,
+                              const float *w1t, const float *b1, const float *w2q, const float *b2, int Kr, int Khd,
+                              int off_policy, int Vr, int Vv, int categorical, int32_t *rec_x, int32_t *rec_a,
+                              int32_t *rec_len, float *rec_decoded, float *rec_logits, void *stream, int max_roots,
+                              const ConvEzIn *ez) {
+  const char *name = ez ? "lzm_search_conv_ez" : "lzm_search_conv";
+  const int S = num_simulations;
+  if (!h || !minmax || (!seeds && !h->step_count) || !vtp_in || !latent_pool || !trunk_w || !actmap || !w1t || !b1 ||
+      !w2q || !b2 || S <= 0 ||
+      (ez && (!ez->hpool || !ez->cpool || !ez->lstm_frag || !ez->lstm_bias || !ez->vp_s || !ez->vp_t))) {
+    snprintf(g_err, sizeof(g_err), "%s: null argument or no simulations", name);
+    return LZM_ERR_ARG;
   }
+  uintptr_t bits = (uintptr_t)trunk_w | (uintptr_t)actmap | (uintptr_t)w1t | (uintptr_t)w2q | (uintptr_t)latent_pool;
+  if (ez)
+    bits |= (uintptr_t)ez->hpool | (uintptr_t)ez->cpool | (uintptr_t)ez->lstm_frag | (uintptr_t)ez->vp_s |
+            (uintptr_t)ez->vp_t;
+  if (bits & 15) {
+    snprintf(g_err, sizeof(g_err), "%s: weights and pool%s must be 16-byte aligned", name, ez ? "s" : "");
+    return LZM_ERR_ARG;
+  }
+  ConvSearchArgs p;
+  memset(&p, 0, sizeof(p));
+  const ConvPlan plan = ez ? conv_plan_ez(h, S, ez->H, ez->horizon, n_dres, n_pres, r_ch, h_ch, Khd, off_policy, Vr,
+                                          Vv, categorical, p, max_roots)
+                           : conv_plan_mz(h, S, n_dres, n_pres, r_ch, h_ch, Kr, Khd, off_policy, Vr, Vv, categorical,
+                                          p, max_roots);
+  if (plan.rc != LZM_OK) return plan.rc;
+  int rc = search_preamble(h, pb_c_base, pb_c_init, S, h->B);
+  if (rc != LZM_OK) return rc;
+  if (ez && (rc = conv_ez_attach(h, p, *ez, S, r_ch)) != LZM_OK) return rc;
+  fill_common(p, h, S, discount, seeds, vtp_in, minmax, latent_pool, rec_x, rec_a, rec_len, rec_decoded, rec_logits);
+  p.w = trunk_w; p.actmap = actmap; p.n_dres = n_dres; p.n_pres = n_pres; p.r_ch = r_ch; p.h_ch = h_ch;
+  p.w1t = w1t; p.b1 = b1; p.w2q = w2q; p.b2 = b2; p.Kr = ez ? ez->H : Kr; p.Khd = Khd; p.off_policy = off_policy;
+  p.Vr = Vr; p.Vv = Vv; p.categorical = categorical ? 1 : 0;
+  p.err = h->err; p.sdiag = h->search_diag;
+  p.step_count = h->step_count; p.step_base = h->step_base; p.step_inc = h->step_inc; p.step_fresh = h->step_fresh;
+  p.step_delta = h->step_delta; p.out_dist = h->step_dist; p.out_values = h->step_vals;
+  const bool stamps = phase_timing();
+  if (stamps && (rc = ensure_phase(h)) != LZM_OK) return rc;
   p.stamps = stamps ? h->phase : nullptr;
-  for (int root0 = 0; root0 < B; root0 += plan.roots) {  // (slices start at multiples of 64 roots)
+  const ConvKernel fn = conv_kernel_fn(ez != nullptr, p.fast != 0, stamps);
+  LZM_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+  for (int root0 = 0; root0 < h->B; root0 += plan.roots) {  // (EfficientZero slices start at multiples of 64 roots)
     p.root0 = root0;
-    p.nroots = std::min(plan.roots, B - root0);
-    p.last_slice = root0 + p.nroots >= B;
-    p.nmb_s = (p.nroots + kLsRows - 1) / kLsRows;
-    p.T_s = p.nmb_s * (H / kLsUnits);
-    hipLaunchKernelGGL(conv_ez_kernel_fn(fast, stamps), dim3(std::max(p.nroots, 2 * p.T_s)), dim3(kScThreads), lds,
-                       (hipStream_t)stream, p);
+    p.nroots = std::min(plan.roots, h->B - root0);
+    p.last_slice = root0 + p.nroots >= h->B;
+    int grid = p.nroots;
+    if (ez) {  // the slice's own row blocks and LSTM tiles
+      p.nmb_s = (p.nroots + kLsRows - 1) / kLsRows;
+      p.T_s = p.nmb_s * (ez->H / kLsUnits);
+      grid = std::max(p.nroots, 2 * p.T_s);
+    }
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(kScThreads), plan.lds, (hipStream_t)stream, p);
     LZM_CHECK_LAUNCH();
   }
   return LZM_OK;
+}
+
+extern "C" int lzm_search_conv(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init, float discount,
+                               float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
+                               const float *trunk_w, const float *actmap, int n_dres, int n_pres, int r_ch, int h_ch,
+                               const float *w1t, const float *b1, const float *w2q, const float *b2, int Kr, int Khd,
+                               int off_policy, int Vr, int Vv, int categorical, int32_t *rec_x, int32_t *rec_a,
+                               int32_t *rec_len, float *rec_decoded, float *rec_logits, void *stream) {
+  return search_conv_launch(h, num_simulations, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in, latent_pool,
+                            trunk_w, actmap, n_dres, n_pres, r_ch, h_ch, w1t, b1, w2q, b2, Kr, Khd, off_policy, Vr, Vv,
+                            categorical, rec_x, rec_a, rec_len, rec_decoded, rec_logits, stream, -1, nullptr);
+}
+
+// lzm_search_conv over root slices (lzm_conv_slice_roots; max_roots: the caller's cap on a slice, 0 = none): any
+// number of roots, the slices enqueued one after another on `stream` (plain launches, capturable).
+extern "C" int lzm_search_conv_sliced(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init,
+                                      float discount, float *minmax, const uint32_t *seeds, const int32_t *vtp_in,
+                                      float *latent_pool, const float *trunk_w, const float *actmap, int n_dres,
+                                      int n_pres, int r_ch, int h_ch, const float *w1t, const float *b1,
+                                      const float *w2q, const float *b2, int Kr, int Khd, int off_policy, int Vr,
+                                      int Vv, int categorical, int32_t *rec_x, int32_t *rec_a, int32_t *rec_len,
+                                      float *rec_decoded, float *rec_logits, int max_roots, void *stream) {
+  if (max_roots < 0) {
+    set_err("lzm_search_conv_sliced: max_roots >= 0 (0: no cap)");
+    return LZM_ERR_ARG;
+  }
+  return search_conv_launch(h, num_simulations, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in, latent_pool,
+                            trunk_w, actmap, n_dres, n_pres, r_ch, h_ch, w1t, b1, w2q, b2, Kr, Khd, off_policy, Vr, Vv,
+                            categorical, rec_x, rec_a, rec_len, rec_decoded, rec_logits, stream, max_roots, nullptr);
 }
 
 extern "C" int lzm_search_conv_ez(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init, float discount,
@@ -3812,10 +3534,10 @@ extern "C" int lzm_search_conv_ez(lzm_handle *h, int num_simulations, int pb_c_b
                                   int off_policy, int Vr, int Vv, int categorical, int32_t *rec_x, int32_t *rec_a,
                                   int32_t *rec_len, float *rec_decoded, float *rec_logits, int32_t *rec_reset,
                                   void *stream) {
-  return search_conv_ez_launch(h, num_simulations, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in, latent_pool,
-                               hpool, cpool, H, horizon, trunk_w, actmap, n_dres, n_pres, r_ch, h_ch, lstm_frag,
-                               lstm_bias, vp_s, vp_t, w1t, b1, w2q, b2, Khd, off_policy, Vr, Vv, categorical, rec_x,
-                               rec_a, rec_len, rec_decoded, rec_logits, rec_reset, stream, -1);
+  const ConvEzIn ez{hpool, cpool, H, horizon, lstm_frag, lstm_bias, vp_s, vp_t, rec_reset};
+  return search_conv_launch(h, num_simulations, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in, latent_pool,
+                            trunk_w, actmap, n_dres, n_pres, r_ch, h_ch, w1t, b1, w2q, b2, 0, Khd, off_policy, Vr, Vv,
+                            categorical, rec_x, rec_a, rec_len, rec_decoded, rec_logits, stream, -1, &ez);
 }
 
 // lzm_search_conv_ez over root slices (lzm_conv_slice_roots with the launch's own residency bound; max_roots: the
@@ -3835,10 +3557,10 @@ extern "C" int lzm_search_conv_ez_sliced(lzm_handle *h, int num_simulations, int
     set_err("lzm_search_conv_ez_sliced: max_roots >= 0 (0: no cap)");
     return LZM_ERR_ARG;
   }
-  return search_conv_ez_launch(h, num_simulations, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in, latent_pool,
-                               hpool, cpool, H, horizon, trunk_w, actmap, n_dres, n_pres, r_ch, h_ch, lstm_frag,
-                               lstm_bias, vp_s, vp_t, w1t, b1, w2q, b2, Khd, off_policy, Vr, Vv, categorical, rec_x,
-                               rec_a, rec_len, rec_decoded, rec_logits, rec_reset, stream, max_roots);
+  const ConvEzIn ez{hpool, cpool, H, horizon, lstm_frag, lstm_bias, vp_s, vp_t, rec_reset};
+  return search_conv_launch(h, num_simulations, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in, latent_pool,
+                            trunk_w, actmap, n_dres, n_pres, r_ch, h_ch, w1t, b1, w2q, b2, 0, Khd, off_policy, Vr, Vv,
+                            categorical, rec_x, rec_a, rec_len, rec_decoded, rec_logits, stream, max_roots, &ez);
 }
 
 // Test support: n workgroups that each occupy a CU (the whole LDS) for `usec` microseconds of the 100 MHz real-time

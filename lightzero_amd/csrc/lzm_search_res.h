@@ -150,7 +150,7 @@ __device__ __forceinline__ const float4 *res_blk4(const ResNet &n, int b) {
 __device__ __forceinline__ const float *res_blk(const ResNet &n, int b, int A) { return n.w + res_block_offset(b, A); }
 
 // Packed-network source of resident float d of block b: packed layer index (lzm_kernels.hip
-// mlp_shapes order: 0,1 fc_dynamics, 2,3 fc_dynamics_2, 4,5 reward head, 6,7 prediction common,
+// mlp_net order without the gate layer's slot: 0,1 fc_dynamics, 2,3 fc_dynamics_2, 4,5 reward head, 6,7 prediction common,
 // 8,9 value head, 10,11 policy head), row k (k < 0: the bias) and column; layer < 0: zero padding.
 __host__ __device__ inline void res_source(int b, size_t d, int A, int *layer, int *k, int *col) {
   *layer = -1; *k = 0; *col = 0;

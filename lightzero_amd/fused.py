@@ -109,26 +109,38 @@ def describe(model, dtype=torch.float32):
     return layers, dict(hidden=H, actions=A, head_hidden=F, support=V, res=res)
 
 
-def pack_muzero_mlp(model, device):
-    layers, dims = describe(model)
+def _net_args(dims):
+    """(prefix of the library's functions for this network, their shape arguments): lzm_mlp_ez_ for dims with
+    lstm_hidden (describe_ez's), lzm_mlp_ otherwise"""
+    if "lstm_hidden" in dims:
+        return "lzm_mlp_ez_", (dims["hidden"], dims["lstm_hidden"], dims["actions"], dims["head_hidden"],
+                               dims["support"], int(dims["res"]))
+    return "lzm_mlp_", (dims["hidden"], dims["actions"], dims["head_hidden"], dims["support"], int(dims["res"]))
+
+
+def _pack(layers, dims, device):
+    """describe()'s / describe_ez()'s layers as one flat tensor (each layer's transposed weights, then its
+    bias), checked against the library's shape limits and packed size"""
+    L = _lib.load()
+    ez = "lstm_hidden" in dims
+    widths = [dims[k] for k in (("hidden", "lstm_hidden") if ez else ("hidden",)) + ("head_hidden", "support")]
     # the kernels' own limits (widths, support + actions, actions <= hidden), asked of the library
-    if not _lib.load().lzm_search_mlp_supported(dims["actions"], dims["hidden"], dims["head_hidden"], dims["support"]):
+    if not getattr(L, "lzm_search_mlp_ez_supported" if ez else "lzm_search_mlp_supported")(dims["actions"], *widths):
         raise NotPackable("network shape outside the search kernels' range: {}".format(dims))
     parts = []
     for (W, b), _ in layers:
         parts.append(W.t().contiguous().reshape(-1))
         parts.append(b.reshape(-1))
     flat = torch.cat(parts).to(device=device, dtype=torch.float32).contiguous()
-    n = _lib.load().lzm_mlp_packed_floats(dims["hidden"], dims["actions"], dims["head_hidden"], dims["support"],
-                                          int(dims["res"]))
+    prefix, args = _net_args(dims)
+    n = getattr(L, prefix + "packed_floats")(*args)
     if n != flat.numel():
         raise NotPackable(f"packed size {flat.numel()} != expected {n}")
     return flat, dims
 
 
-def _ez_args(dims):
-    return (dims["hidden"], dims["lstm_hidden"], dims["actions"], dims["head_hidden"], dims["support"],
-            int(dims["res"]))
+def pack_muzero_mlp(model, device):
+    return _pack(*describe(model), device)
 
 
 def describe_ez(model, dtype=torch.float32):
@@ -156,34 +168,18 @@ def describe_ez(model, dtype=torch.float32):
 
 
 def pack_efficientzero_mlp(model, device):
-    layers, dims = describe_ez(model)
-    L = _lib.load()
-    if not L.lzm_search_mlp_ez_supported(dims["actions"], dims["hidden"], dims["lstm_hidden"], dims["head_hidden"],
-                                         dims["support"]):
-        raise NotPackable("network shape outside the search kernel's range: {}".format(dims))
-    parts = []
-    for (W, b), _ in layers:
-        parts.append(W.t().contiguous().reshape(-1))
-        parts.append(b.reshape(-1))
-    flat = torch.cat(parts).to(device=device, dtype=torch.float32).contiguous()
-    n = L.lzm_mlp_ez_packed_floats(*_ez_args(dims))
-    if n != flat.numel():
-        raise NotPackable(f"packed size {flat.numel()} != expected {n}")
-    return flat, dims
+    return _pack(*describe_ez(model), device)
 
 
 def prepare_kernel_weights(flat, dims, out=None):
     """Packed network -> the search kernel's lane-order layout (lzm_mlp_prepare, or lzm_mlp_ez_prepare for
     dims with lstm_hidden, on the current stream); out: optional existing buffer of the right size to refill
     in place."""
-    ez = "lstm_hidden" in dims
-    args = _ez_args(dims) if ez else (dims["hidden"], dims["actions"], dims["head_hidden"], dims["support"],
-                                      int(dims["res"]))
-    n = getattr(_lib.load(), "lzm_mlp_ez_kernel_floats" if ez else "lzm_mlp_kernel_floats")(*args)
+    prefix, args = _net_args(dims)
+    n = getattr(_lib.load(), prefix + "kernel_floats")(*args)
     if out is None or out.numel() != n or out.device != flat.device:
         out = torch.empty(n, dtype=torch.float32, device=flat.device)
-    _lib.call("lzm_mlp_ez_prepare" if ez else "lzm_mlp_prepare", *args, _lib.ptr(flat), _lib.ptr(out),
-              _lib.stream_ptr())
+    _lib.call(prefix + "prepare", *args, _lib.ptr(flat), _lib.ptr(out), _lib.stream_ptr())
     return out
 
 

@@ -245,6 +245,18 @@ class DeviceTree:
              dims["support"], int(dims["res"]), out)
         return dict(roots_per_wg=out[0], kernel={0: "streaming"}.get(out[1]), mode=out[2], tree_in_lds=bool(out[3]))
 
+    def _conv_plan(self, name, n_out, net, S, H, horizon, categorical, *cap):
+        """the two conv plan queries' call (cap: the sliced query's max_roots) and their dict"""
+        hp = net.heads
+        out = (ctypes.c_int32 * n_out)()
+        call(name, self.h, int(S), int(self.ez), int(H), int(horizon), int(net.n_dres), int(net.n_pres),
+             int(net.r_ch), int(net.h_ch), int(hp["Kr"]), int(hp["Khd"]), int(hp["off_policy"]), int(hp["Vr"]),
+             int(hp["Vv"]), int(bool(categorical)), *cap, out)
+        reason = None if out[0] == 0 else _lib.load().lzm_last_error().decode()
+        return out, dict(supported=out[0] == 0, code=out[0], reason=reason, workgroups=out[1], lstm_tiles=out[2],
+                         lds_bytes=out[3], pinned=out[4], pbt_rows=out[5], out_rounds=out[6],
+                         out_one_round=bool(self.ez and out[6] == 0), reward_one_round=bool(out[7]))
+
     def search_conv_plan(self, net, S, H=0, horizon=1, categorical=True):
         """What search_conv (MuZero trees) / search_conv_ez (EfficientZero trees; H: the LSTM width, horizon:
         lstm_horizon_len) launches for the native FoldedConvNet `net` and S simulations on this handle as the
@@ -255,71 +267,57 @@ class DeviceTree:
         out_rounds: rounds of 768 output columns (MuZero: Vr + Vv + A; EfficientZero: Vv + A, 0 when
         out_one_round), out_one_round / reward_one_round: EfficientZero's one-column-per-thread forms of the
         value | policy and the reward output (up to 256 columns))."""
-        hp = net.heads
-        out = (ctypes.c_int32 * 8)()
-        call("lzm_search_conv_plan", self.h, int(S), int(self.ez), int(H), int(horizon), int(net.n_dres),
-             int(net.n_pres), int(net.r_ch), int(net.h_ch), int(hp["Kr"]), int(hp["Khd"]), int(hp["off_policy"]),
-             int(hp["Vr"]), int(hp["Vv"]), int(bool(categorical)), out)
-        reason = None if out[0] == 0 else _lib.load().lzm_last_error().decode()
-        return dict(supported=out[0] == 0, code=out[0], reason=reason, workgroups=out[1], lstm_tiles=out[2],
-                    lds_bytes=out[3], pinned=out[4], pbt_rows=out[5], out_rounds=out[6],
-                    out_one_round=bool(self.ez and out[6] == 0),
-                    reward_one_round=bool(out[7]))
+        return self._conv_plan("lzm_search_conv_plan", 8, net, S, H, horizon, categorical)[1]
 
     def search_conv_sliced_plan(self, net, S, H=0, horizon=1, categorical=True, max_roots=0):
         """search_conv_plan for search_conv_sliced / search_conv_ez_sliced with the same max_roots
         (lzm_search_conv_sliced_plan; host only, nothing is launched): search_conv_plan's fields for the largest
         slice, plus slices, slice_roots (roots per slice) and last_slice_roots (all 0 when refused). A batch that
         fits one slice gets search_conv_plan's own answer with slices = 1."""
+        out, plan = self._conv_plan("lzm_search_conv_sliced_plan", 11, net, S, H, horizon, categorical, int(max_roots))
+        return dict(plan, slices=out[8], slice_roots=out[9], last_slice_roots=out[10])
+
+    def _search_conv(self, name, net, S, minmax, seeds, vtp_in, pool, pb_c_base, pb_c_init, discount, categorical, rec,
+                     stream, lstm=None, max_roots=None):
+        """the four one-launch conv searches' call. lstm: (hpool, cpool, horizon) for the EfficientZero entry
+        points, which take the LSTM state and weights and the is_reset record and no Kr; max_roots: the sliced
+        entry points' cap"""
         hp = net.heads
-        out = (ctypes.c_int32 * 11)()
-        call("lzm_search_conv_sliced_plan", self.h, int(S), int(self.ez), int(H), int(horizon), int(net.n_dres),
-             int(net.n_pres), int(net.r_ch), int(net.h_ch), int(hp["Kr"]), int(hp["Khd"]), int(hp["off_policy"]),
-             int(hp["Vr"]), int(hp["Vv"]), int(bool(categorical)), int(max_roots), out)
-        reason = None if out[0] == 0 else _lib.load().lzm_last_error().decode()
-        return dict(supported=out[0] == 0, code=out[0], reason=reason, workgroups=out[1], lstm_tiles=out[2],
-                    lds_bytes=out[3], pinned=out[4], pbt_rows=out[5], out_rounds=out[6],
-                    out_one_round=bool(self.ez and out[6] == 0), reward_one_round=bool(out[7]),
-                    slices=out[8], slice_roots=out[9], last_slice_roots=out[10])
+        state, gates, kr, reset = [], [], [int(hp["Kr"])], []
+        if lstm is not None:
+            hpool, cpool, horizon = lstm
+            state = [ptr(hpool), ptr(cpool), int(hpool.shape[2]), int(horizon)]
+            gates = [ptr(net.lstm_frag), ptr(net.t["lstm_b"]), ptr(net.t["vp_s"]), ptr(net.t["vp_t"])]
+            kr, reset = [], _rec_ptrs(rec, ("is_reset",))
+        cap = [] if max_roots is None else [int(max_roots)]
+        self._unchecked = True
+        call(name, self.h, int(S), int(pb_c_base), float(pb_c_init), float(discount), ptr(minmax), ptr(seeds),
+             ptr(vtp_in), ptr(pool), *state, ptr(net.native), ptr(net.actmap), int(net.n_dres), int(net.n_pres),
+             int(net.r_ch), int(net.h_ch), *gates, ptr(hp["w1t"]), ptr(hp["b1"]), ptr(hp["w2q"]), ptr(hp["b2"]), *kr,
+             int(hp["Khd"]), int(hp["off_policy"]), int(hp["Vr"]), int(hp["Vv"]), int(bool(categorical)),
+             *_rec_ptrs(rec), *reset, *cap, stream_ptr(stream))
 
     def search_conv_sliced(self, net, S, minmax, seeds, vtp_in, pool, pb_c_base=19652, pb_c_init=1.25,
                            discount=0.997, categorical=True, rec=None, max_roots=0, stream=None):
         """search_conv over root slices (lzm_search_conv_sliced): any number of roots, one launch per slice of
         up to min(1024, max_roots or 1024) roots, enqueued here one after another; the same results."""
-        hp = net.heads
-        self._unchecked = True
-        call("lzm_search_conv_sliced", self.h, int(S), int(pb_c_base), float(pb_c_init), float(discount),
-             ptr(minmax), ptr(seeds), ptr(vtp_in), ptr(pool), ptr(net.native), ptr(net.actmap), int(net.n_dres),
-             int(net.n_pres), int(net.r_ch), int(net.h_ch), ptr(hp["w1t"]), ptr(hp["b1"]), ptr(hp["w2q"]),
-             ptr(hp["b2"]), int(hp["Kr"]), int(hp["Khd"]), int(hp["off_policy"]), int(hp["Vr"]), int(hp["Vv"]),
-             int(bool(categorical)), *_rec_ptrs(rec), int(max_roots), stream_ptr(stream))
+        self._search_conv("lzm_search_conv_sliced", net, S, minmax, seeds, vtp_in, pool, pb_c_base, pb_c_init,
+                          discount, categorical, rec, stream, max_roots=max_roots)
 
     def search_conv_ez_sliced(self, net, S, minmax, seeds, vtp_in, pool, hpool, cpool, horizon, pb_c_base=19652,
                               pb_c_init=1.25, discount=0.997, categorical=True, rec=None, max_roots=0, stream=None):
         """search_conv_ez over root slices (lzm_search_conv_ez_sliced): batches past 256 roots or past the
         co-resident grid, one launch per slice (whole blocks of 64 roots, each grid co-resident on its own),
         enqueued here one after another; the same results. ResidencyError when not even 64 roots fit."""
-        hp, t = net.heads, net.t
-        self._unchecked = True
-        call("lzm_search_conv_ez_sliced", self.h, int(S), int(pb_c_base), float(pb_c_init), float(discount),
-             ptr(minmax), ptr(seeds), ptr(vtp_in), ptr(pool), ptr(hpool), ptr(cpool), int(hpool.shape[2]),
-             int(horizon), ptr(net.native), ptr(net.actmap), int(net.n_dres), int(net.n_pres), int(net.r_ch),
-             int(net.h_ch), ptr(net.lstm_frag), ptr(t["lstm_b"]), ptr(t["vp_s"]), ptr(t["vp_t"]), ptr(hp["w1t"]),
-             ptr(hp["b1"]), ptr(hp["w2q"]), ptr(hp["b2"]), int(hp["Khd"]), int(hp["off_policy"]), int(hp["Vr"]),
-             int(hp["Vv"]), int(bool(categorical)), *_rec_ptrs(rec), *_rec_ptrs(rec, ("is_reset",)), int(max_roots),
-             stream_ptr(stream))
+        self._search_conv("lzm_search_conv_ez_sliced", net, S, minmax, seeds, vtp_in, pool, pb_c_base, pb_c_init,
+                          discount, categorical, rec, stream, lstm=(hpool, cpool, horizon), max_roots=max_roots)
 
     def search_conv(self, net, S, minmax, seeds, vtp_in, pool, pb_c_base=19652, pb_c_init=1.25, discount=0.997,
                     categorical=True, rec=None, stream=None):
         """One launch for the whole search of a conv MuZeroModel (lzm_search_conv; net: a native
         split-precision conv_infer.FoldedConvNet); rec: optional _Recorder-like object."""
-        hp = net.heads
-        self._unchecked = True
-        call("lzm_search_conv", self.h, int(S), int(pb_c_base), float(pb_c_init), float(discount), ptr(minmax),
-             ptr(seeds), ptr(vtp_in), ptr(pool), ptr(net.native), ptr(net.actmap), int(net.n_dres), int(net.n_pres),
-             int(net.r_ch), int(net.h_ch), ptr(hp["w1t"]), ptr(hp["b1"]), ptr(hp["w2q"]), ptr(hp["b2"]), int(hp["Kr"]),
-             int(hp["Khd"]), int(hp["off_policy"]), int(hp["Vr"]), int(hp["Vv"]), int(bool(categorical)),
-             *_rec_ptrs(rec), stream_ptr(stream))
+        self._search_conv("lzm_search_conv", net, S, minmax, seeds, vtp_in, pool, pb_c_base, pb_c_init, discount,
+                          categorical, rec, stream)
 
     def search_conv_ez(self, net, S, minmax, seeds, vtp_in, pool, hpool, cpool, horizon, pb_c_base=19652,
                        pb_c_init=1.25, discount=0.997, categorical=True, rec=None, stream=None):
@@ -327,14 +325,8 @@ class DeviceTree:
         split-precision conv_infer.FoldedConvNet with the fused LSTM step packed); hpool / cpool: the LSTM
         state pools [S + 1, B, H] with slot 0 = the roots' state; rec: optional _Recorder-like object
         (with is_reset)."""
-        hp, t = net.heads, net.t
-        self._unchecked = True
-        call("lzm_search_conv_ez", self.h, int(S), int(pb_c_base), float(pb_c_init), float(discount), ptr(minmax),
-             ptr(seeds), ptr(vtp_in), ptr(pool), ptr(hpool), ptr(cpool), int(hpool.shape[2]), int(horizon),
-             ptr(net.native), ptr(net.actmap), int(net.n_dres), int(net.n_pres), int(net.r_ch), int(net.h_ch),
-             ptr(net.lstm_frag), ptr(t["lstm_b"]), ptr(t["vp_s"]), ptr(t["vp_t"]), ptr(hp["w1t"]), ptr(hp["b1"]),
-             ptr(hp["w2q"]), ptr(hp["b2"]), int(hp["Khd"]), int(hp["off_policy"]), int(hp["Vr"]), int(hp["Vv"]),
-             int(bool(categorical)), *_rec_ptrs(rec), *_rec_ptrs(rec, ("is_reset",)), stream_ptr(stream))
+        self._search_conv("lzm_search_conv_ez", net, S, minmax, seeds, vtp_in, pool, pb_c_base, pb_c_init, discount,
+                          categorical, rec, stream, lstm=(hpool, cpool, horizon))
 
     def set_step(self, count=None, base=0, increment=True, dist=None, values=None, fresh_minmax=False,
                  value_delta_max=0.0):

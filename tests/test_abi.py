@@ -185,6 +185,24 @@ def test_search_mlp_shape_and_plan_queries_validate_on_the_host():
     assert ok(2, 1040, 32, 601) == 0 and ok(2, 64, 1040, 601) == 0 and ok(0, 64, 32, 601) == 0
     out = (ctypes.c_int32 * 4)()
     assert L.lzm_search_mlp_plan(None, 10, 128, 32, 601, 1, out) == -1  # LZM_ERR_ARG
+    # the MuZero and EfficientZero entry points share their bodies: each refuses a null handle first, under its
+    # own name
+    assert L.lzm_last_error().startswith(b"lzm_search_mlp_plan:")
+    assert L.lzm_search_mlp_ez_plan(None, 10, 128, 64, 32, 601, 1, out) == -1
+    assert L.lzm_last_error().startswith(b"lzm_search_mlp_ez_plan:")
+    assert L.lzm_search_mlp(None, 128, 32, 601, 1, None, 10, 19652, 1.25, 0.997, *[None] * 10) == -1
+    assert L.lzm_last_error().startswith(b"lzm_search_mlp: null argument")
+    assert L.lzm_search_mlp_ez(None, 128, 64, 32, 601, 1, None, 10, 5, 19652, 1.25, 0.997, *[None] * 13) == -1
+    assert L.lzm_last_error().startswith(b"lzm_search_mlp_ez: null argument")
+    # one network description: EfficientZero's packed network is MuZero's plus the gate layer over [x ; h_prev]
+    # (weights and bias), its reward head reading the LSTM's Hl outputs in place of the H latent rows
+    for res in (0, 1):
+        for H, Hl, A, F, V in ((128, 64, 2, 32, 601), (64, 128, 3, 16, 21)):
+            gate = (H + Hl) * 4 * Hl + 4 * Hl
+            assert L.lzm_mlp_ez_packed_floats(H, Hl, A, F, V, res) == \
+                L.lzm_mlp_packed_floats(H, A, F, V, res) + gate + (Hl - H) * F
+    assert L.lzm_mlp_ez_packed_floats(128, 0, 2, 32, 601, 1) == -1  # (no LSTM: not MuZero's answer)
+    assert L.lzm_mlp_ez_kernel_floats(128, 0, 2, 32, 601, 1) == -1
 
 
 def test_az_fused_plan_validates_on_the_host():
