@@ -42,8 +42,10 @@ enum lzm_status {
 
 enum lzm_flags {
   LZM_TREE_EZ = 1,  /* EfficientZero value-prefix tree (ctree_efficientzero) instead of MuZero */
-  LZM_RNG_FAST = 2  /* per-root counter-based (Philox4x32-10) tie-break stream instead of the
+  LZM_RNG_FAST = 2, /* per-root counter-based (Philox4x32-10) tie-break stream instead of the
                        batch-serial glibc rand() stream of the reference (parity mode) */
+  LZM_TREE_GUMBEL = 4 /* Gumbel MuZero tree (ctree_gumbel_muzero) instead of MuZero: driven by the lzm_gumbel_*
+                         entry points below; excludes LZM_TREE_EZ; LZM_RNG_FAST is ignored (the tree never draws) */
 };
 
 /* Creates a tree for `num_roots` roots, `action_space` actions, capacity for `max_sims`
@@ -746,6 +748,65 @@ int lzm_ez_lstm_step(int B, int K, int H, const float *xin, const int32_t *xscal
                      const float *bias, const float *cpool, const int32_t *x, const int32_t *search_len, int horizon,
                      float *h1, float *c1, float *hslot, float *cslot, void *workspace, int32_t *err,
                      int32_t *range_err, void *stream);
+
+/* ---- Gumbel MuZero tree (lzero/mcts/ctree/ctree_gumbel_muzero: gmz_tree.pyx, lib/cnode.cpp; line numbers of
+ * cnode.cpp) on handles created with LZM_TREE_GUMBEL. Such a handle also keeps every node's raw_value (:111), the
+ * roots' fixed Gumbel table (64 floats) and the considered-visits row of the last (num_simulations,
+ * max_num_considered_actions) as a device table. lzm_roots_prepare, lzm_get_distributions, lzm_get_values,
+ * lzm_get_trajectories, lzm_gather_latent, lzm_copy_tree and lzm_reserve work on it; lzm_traverse, lzm_backprop,
+ * lzm_decode_backprop(_traverse) and the one-launch searches return LZM_ERR_STATE on it, and the lzm_gumbel_*
+ * device entry points return LZM_ERR_STATE on any other handle, before anything is launched.
+ * One wave per root, four roots per workgroup; no random draw, so no cross-root communication. ---- */
+/* generate_gumbel(scale, 0, n) (:1134-1152): std::mt19937(0) through std::extreme_value_distribution<float>(0, 1),
+ * times scale. Every root holds generate_gumbel(10, 0, legal count) (:66-90), a prefix of one table. Host only. */
+int lzm_gumbel_table(float scale, int n, float *out_host);
+/* The row table[min(m, S)] of get_table_of_considered_visits(m, S) (:1042-1095) that cselect_root_child indexes
+ * by the sum of the children's visits (:727-729); out_host int32[S]. Host only. */
+int lzm_gumbel_considered_visits(int max_num_considered_actions, int num_simulations, int32_t *out_host);
+/* Builds the handle's device considered-visits row for (S, m) now (synchronous H2D; call outside stream capture, as
+ * lzm_set_pb_c). lzm_gumbel_traverse rebuilds it on demand when they change. */
+int lzm_gumbel_set_considered(lzm_handle *h, int num_simulations, int max_num_considered_actions);
+/* The value pool of Roots.prepare / prepare_no_noise (gmz_tree.pyx:36-40; CRoots::prepare :418-455 passes values[i]
+ * to expand, which stores raw_value :111): values float[B] into the roots' raw_value. lzm_roots_prepare has no
+ * value argument and zeroes them; call this after it. */
+int lzm_gumbel_set_root_values(lzm_handle *h, const float *values, void *stream);
+/* batch_traverse (gmz_tree.pyx:91-95; cbatch_traverse :834-898 with cselect_root_child :701-745,
+ * cselect_interior_child :747-790, qtransform_completed_by_mix_value :989-1040, score_considered :1097-1132).
+ * Outputs as lzm_traverse; vtp is virtual_to_play passed through (:895). */
+int lzm_gumbel_traverse(lzm_handle *h, int num_simulations, int max_num_considered_actions, float discount,
+                        const int32_t *virtual_to_play, int32_t *out_x, int32_t *out_y, int32_t *out_action,
+                        int64_t *out_action_i64, int32_t *out_vtp, int32_t *out_len, void *stream);
+/* batch_back_propagate (gmz_tree.pyx:81-88; cbatch_back_propagate :633-652: CNode::expand :94-156 with raw_value =
+ * values[i], cback_propagate :605-631 with no player sign) from raw lists: rewards, values float[B], logits
+ * float[B*A], to_play int32[B] (stored on the node, never read). */
+int lzm_gumbel_backprop(lzm_handle *h, int current_latent_state_index, float discount, float *minmax,
+                        const float *rewards, const float *values, const float *logits, const int32_t *to_play,
+                        void *stream);
+/* lzm_decode_backprop for the Gumbel tree (mcts_ctree.py:1095-1117 in one kernel): the same argument meaning
+ * (categorical or scalar heads, next_latent / pool_slot, out_decoded, the min-max update), no LSTM horizon. */
+int lzm_gumbel_decode_backprop(lzm_handle *h, int current_latent_state_index, float discount, float *minmax,
+                               const float *reward_logits, const float *value_logits, int support_len,
+                               int categorical, const float *policy_logits, const int32_t *to_play,
+                               const float *next_latent, float *pool_slot, int64_t row_elems, float *out_decoded,
+                               void *stream);
+/* One simulation's lzm_gumbel_decode_backprop and the next simulation's lzm_gumbel_traverse in one launch: the wave
+ * that backs up root i walks it again at once (mcts_ctree.py:1067-1117 across two loop iterations). */
+int lzm_gumbel_decode_backprop_traverse(lzm_handle *h, int current_latent_state_index, float discount, float *minmax,
+                                        const float *reward_logits, const float *value_logits, int support_len,
+                                        int categorical, const float *policy_logits, const int32_t *to_play,
+                                        const float *next_latent, float *pool_slot, int64_t row_elems,
+                                        float *out_decoded, int num_simulations, int max_num_considered_actions,
+                                        const int32_t *virtual_to_play, int32_t *out_x, int32_t *out_y,
+                                        int32_t *out_action, int64_t *out_action_i64, int32_t *out_vtp,
+                                        int32_t *out_len, void *stream);
+/* Roots.get_children_values (gmz_tree.pyx:48-49; get_children_value :309-338): the roots' completed Q scattered to
+ * action order, -inf for illegal actions; out float[B*A]. */
+int lzm_gumbel_get_children_values(lzm_handle *h, float discount, float *out, void *stream);
+/* Roots.get_policies (gmz_tree.pyx:51-52; get_policy :355-385): csoftmax over the action space of prior +
+ * completed Q, exactly 0 for illegal actions; out float[B*A]. */
+int lzm_gumbel_get_policies(lzm_handle *h, float discount, float *out, void *stream);
+/* Device logf port (lzm_numerics.h glibc_logf) exposed for checks against the host libm. */
+int lzm_debug_logf(const float *x, float *out, int64_t n, void *stream);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,7 @@ __version__ = "0.1.0"
 
 def __getattr__(name):
     # lazy: importing the package must not touch the GPU
-    if name in ("MuZeroMCTSCtree", "EfficientZeroMCTSCtree"):
+    if name in ("MuZeroMCTSCtree", "EfficientZeroMCTSCtree", "GumbelMuZeroMCTSCtree"):
         from . import mcts_ctree
         return getattr(mcts_ctree, name)
     if name == "InverseScalarTransform":

@@ -26,6 +26,7 @@ LZM_ERR_RANGE = -6
 LZM_ERR_WORDS = 8  # sticky error words per tree handle (lzm_check_errors)
 LZM_TREE_EZ = 1
 LZM_RNG_FAST = 2
+LZM_TREE_GUMBEL = 4
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -158,6 +159,18 @@ SIGNATURES = {
     "lzm_conv_trunk_prepare_p": [_i, _i, _i, _i, _i, _vp, _vp],
     "lzm_conv_trunk_actmap_bound": [_i, _i, _f, _vp],
     "lzm_conv_trunk_p": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "lzm_gumbel_table": [_f, _i, _vp],
+    "lzm_gumbel_considered_visits": [_i, _i, _vp],
+    "lzm_gumbel_set_considered": [_vp, _i, _i],
+    "lzm_gumbel_set_root_values": [_vp, _vp, _vp],
+    "lzm_gumbel_traverse": [_vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "lzm_gumbel_backprop": [_vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],
+    "lzm_gumbel_decode_backprop": [_vp, _i, _f, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
+    "lzm_gumbel_decode_backprop_traverse": [_vp, _i, _f, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _i, _i,
+                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "lzm_gumbel_get_children_values": [_vp, _f, _vp, _vp],
+    "lzm_gumbel_get_policies": [_vp, _f, _vp, _vp],
+    "lzm_debug_logf": [_vp, _vp, _i64, _vp],
     "lzm_conv_trunk_xin_p": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp,
                              _vp],
 }

@@ -15,8 +15,8 @@ ARCH = os.environ.get("LZM_OFFLOAD_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared", "-Wall",
          f"--offload-arch={ARCH}"]
 SOURCES = [os.path.join(HERE, "csrc", "lzm_kernels.hip")]
-DEPS = SOURCES + sorted(glob.glob(os.path.join(HERE, "csrc", "*.h"))) + [
-    os.path.join(REPO, "include", "lzmcts.h")]
+DEPS = SOURCES + sorted(glob.glob(os.path.join(HERE, "csrc", "*.h")) +
+                        glob.glob(os.path.join(HERE, "csrc", "*.inc"))) + [os.path.join(REPO, "include", "lzmcts.h")]
 OUT = os.path.join(HERE, "liblzmcts.so")
 
 

@@ -36,6 +36,7 @@
 #include "lzm_az.h"
 #include "lzm_az_fused.h"
 #include "lzm_tree.h"
+#include "lzm_gumbel.h"
 #include "lzm_search_mlp.h"
 #include "lzm_search_res.h"
 #include "lzm_conv.h"
@@ -431,9 +432,8 @@ __device__ inline bool norm_ok(const int32_t *part, int nparts, int head) {
   return __ballot(bad) == 0ull;
 }
 
-// decode + expand + backup of root i by one wave (all 64 lanes call it)
-template <bool EZ>
-__device__ inline void decode_root(const DecodeArgs &p, const int32_t *norm_part, int i) {
+// the head part of decode_root: files root i's new latent row, decodes its reward and value rows (all 64 lanes)
+__device__ inline void decode_heads(const DecodeArgs &p, const int32_t *norm_part, int i, float *out_r, float *out_v) {
   const TreeView &t = p.t;
   const int lane = threadIdx.x & 63;
   // new latent row into the pool slot (mcts_ctree.py:305)
@@ -457,6 +457,17 @@ __device__ inline void decode_root(const DecodeArgs &p, const int32_t *norm_part
     p.out_decoded[2 * i] = r;
     p.out_decoded[2 * i + 1] = v;
   }
+  *out_r = r;
+  *out_v = v;
+}
+
+// decode + expand + backup of root i by one wave (all 64 lanes call it)
+template <bool EZ>
+__device__ inline void decode_root(const DecodeArgs &p, const int32_t *norm_part, int i) {
+  const TreeView &t = p.t;
+  const int lane = threadIdx.x & 63;
+  float r, v;
+  decode_heads(p, norm_part, i, &r, &v);
   if (t.A <= 64) {
     // one lane per child / path level, bit-identical to the serial form below (lzm_tree.h)
     const int len = t.pathlen[i];
@@ -738,6 +749,63 @@ __global__ __launch_bounds__(kTlbThreads) void decode_traverse_kernel(DecodeArgs
   traverse_lb_finish(q, epoch);
 }
 
+
+// ---- Gumbel MuZero tree (lzm_gumbel.h): one wave per root, four roots per 256-thread workgroup ----
+// root index of this wave, in a scalar register: every loop bound and readlane index below is wave-uniform
+__device__ __forceinline__ int gumbel_wave_root() {
+  return __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+}
+
+__global__ __launch_bounds__(256) void gumbel_traverse_kernel(GumbelTraverseArgs q) {
+  const int i = gumbel_wave_root();
+  if (i < q.t.B) gumbel_traverse_root(q, i);
+}
+
+// CNode::expand (cnode.cpp:94-156, raw_value :111) + cback_propagate (:605-631) of root i's leaf
+__device__ inline void gumbel_expand_backup(const TreeView &t, float *raw, float4 *minmax, int i, int to_play, int cur,
+                                            float reward, float value, const float *logits, float disc) {
+  const int len = t.pathlen[i];
+  const int leaf = t.path[(size_t)len * t.B + i];
+  expand_wave(t, i, leaf, to_play, cur, reward, logits);
+  if ((threadIdx.x & 63) == 0) raw[nidx(t, leaf, i)] = value;
+  backup_wave(t, i, i, t.B, minmax + i, -1, value, disc);  // no player sign (:617-630)
+}
+
+// cbatch_back_propagate (:633-652) from raw lists
+__global__ __launch_bounds__(256) void gumbel_backprop_kernel(BackpropArgs p, GumbelView g) {
+  const int i = gumbel_wave_root();
+  if (i >= p.t.B) return;
+  gumbel_expand_backup(p.t, g.raw, p.minmax, i, p.to_play[i], p.cur, p.rewards[i], p.values[i],
+                       p.logits + (size_t)i * p.t.A, p.disc);
+}
+
+// decode + expand + backup of one simulation (decode_root's Gumbel form) and, with TRAVERSE, the next
+// simulation's walk by the same wave over the records it has just written
+template <bool TRAVERSE>
+__global__ __launch_bounds__(256) void gumbel_decode_kernel(DecodeArgs p, const int32_t *norm_part, GumbelTraverseArgs q) {
+  const int i = gumbel_wave_root();
+  if (i >= p.t.B) return;
+  float r, v;
+  decode_heads(p, norm_part, i, &r, &v);
+  gumbel_expand_backup(p.t, q.g.raw, p.minmax, i, p.to_play[i], p.cur, r, v, p.policy_logits + (size_t)i * p.t.A, p.disc);
+  if (TRAVERSE) {
+    // the backup's stores (other lanes of this wave) complete before the walk reads them
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    gumbel_traverse_root(q, i);
+  }
+}
+
+__global__ __launch_bounds__(256) void gumbel_output_kernel(TreeView t, GumbelView g, float disc, int policy, float *out) {
+  const int i = gumbel_wave_root();
+  if (i < t.B) gumbel_root_output(t, g, i, disc, policy, out);
+}
+
+__global__ void debug_logf_kernel(const float *x, float *out, long long n) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = glibc_logf(x[i]);
+}
+
 }  // namespace lzm
 
 // ============================================================================ host side
@@ -813,6 +881,11 @@ struct lzm_handle {
   // lzm_search_conv_ez's hand-off workspace (LSTM input rows, outputs, split-K partials, flags)
   void *ez_ws = nullptr;
   size_t ez_ws_bytes = 0;
+  // Gumbel MuZero handles (LZM_TREE_GUMBEL) only
+  float *raw = nullptr;           // [cap][B] raw_value per node
+  float *gumbel = nullptr;        // [64] the fixed Gumbel table
+  int32_t *considered = nullptr;  // [cons_cap] considered-visits row of (cons_m, cons_S)
+  int cons_cap = 0, cons_m = -1, cons_S = -1;
 };
 
 // Jump matrices of glibc random_r: row m of J_first expresses z[344+m] (the m-th rand()
@@ -868,9 +941,9 @@ static void dfree(void *p) {
 
 static void free_tree(lzm_handle *h) {
   dfree(h->stat); dfree(h->meta); dfree(h->path); dfree(h->path_act); dfree(h->stream); dfree(h->lut);
-  dfree(h->step_seeds);
+  dfree(h->step_seeds); dfree(h->raw);
   h->stat = nullptr; h->meta = nullptr; h->path = nullptr; h->path_act = nullptr; h->stream = nullptr; h->lut = nullptr;
-  h->step_seeds = nullptr;
+  h->step_seeds = nullptr; h->raw = nullptr;
   h->step_seeds_n = 0;
 }
 
@@ -908,6 +981,10 @@ static int alloc_tree(lzm_handle *h, int sims) {
   LZM_HIP(hipMalloc(&h->meta, nodes * sizeof(NodeMeta)));
   LZM_HIP(hipMemset(h->meta, 0xff, nodes * sizeof(NodeMeta)));  // latent -1: nothing expanded
   LZM_HIP(hipMemset(h->stat, 0, nodes * sizeof(NodeStat)));
+  if (h->flags & LZM_TREE_GUMBEL) {
+    LZM_HIP(hipMalloc(&h->raw, nodes * sizeof(float)));
+    LZM_HIP(hipMemset(h->raw, 0, nodes * sizeof(float)));
+  }
   LZM_HIP(hipMalloc(&h->path, sizeof(int32_t) * (size_t)h->depth_cap * h->B));
   LZM_HIP(hipMalloc(&h->path_act, sizeof(int32_t) * (size_t)h->depth_cap * h->B));
   h->stream_cap = h->B * (sims + 2) + 2 * kMaxWG;
@@ -920,7 +997,7 @@ static int alloc_tree(lzm_handle *h, int sims) {
   // point at the old buffer together with the tree's
   LZM_HIP(hipMalloc(&h->step_seeds, sizeof(int32_t) * (size_t)(sims + 1)));
   h->step_seeds_n = sims + 1;
-  if (!(h->flags & LZM_RNG_FAST)) {
+  if (!(h->flags & (LZM_RNG_FAST | LZM_TREE_GUMBEL))) {
     // parity-mode draw tables and look-back words, allocated here rather than at first use so
     // that a search captured into a HIP graph never allocates
     int rc = ensure_coef(h, h->B * h->depth_cap + 64);
@@ -938,6 +1015,10 @@ const char *lzm_last_error(void) { return g_err; }
 int lzm_create(int B, int A, int max_sims, int flags, lzm_handle **out) {
   if (!out || B <= 0 || A <= 0 || A > kMaxActions || max_sims < 0) {
     set_err("lzm_create: need num_roots > 0, 0 < action_space <= 64, max_sims >= 0");
+    return LZM_ERR_ARG;
+  }
+  if ((flags & LZM_TREE_GUMBEL) && (flags & LZM_TREE_EZ)) {
+    set_err("lzm_create: LZM_TREE_GUMBEL and LZM_TREE_EZ are mutually exclusive");
     return LZM_ERR_ARG;
   }
   lzm_handle *h = new lzm_handle();
@@ -965,6 +1046,14 @@ int lzm_create(int B, int A, int max_sims, int flags, lzm_handle **out) {
     TRY(hipMemcpy(h->jmat, jf.data(), sizeof(uint32_t) * kMaxWG * 31, hipMemcpyHostToDevice) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
     TRY(hipMemcpy(h->jmat + kMaxWG * 31, jn.data(), sizeof(uint32_t) * kMaxWG * 31, hipMemcpyHostToDevice) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
   }
+  if (flags & LZM_TREE_GUMBEL) {
+    float tab[kMaxActions];
+    lzm_gumbel_table(10.0f, kMaxActions, tab);  // CNode::CNode: gumbel_scale 10, gumbel_rng 0 (cnode.cpp:87-89)
+    TRY(hipMalloc(&h->gumbel, sizeof(tab)) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
+    TRY(hipMemcpy(h->gumbel, tab, sizeof(tab), hipMemcpyHostToDevice) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
+    h->cons_cap = max_sims + 64;
+    TRY(hipMalloc(&h->considered, sizeof(int32_t) * h->cons_cap) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
+  }
   TRY(alloc_tree(h, max_sims));
 #undef TRY
   *out = h;
@@ -977,7 +1066,7 @@ int lzm_destroy(lzm_handle *h) {
   dfree(h->legal); dfree(h->nlegal); dfree(h->pathlen); dfree(h->off); dfree(h->diag); dfree(h->err);
   dfree(h->hint); dfree(h->norm_flag); dfree(h->jmat);
   dfree(h->coef); dfree(h->pow16807); dfree(h->lb_flags); dfree(h->epoch); dfree(h->search_diag); dfree(h->phase);
-  dfree(h->ez_ws);
+  dfree(h->ez_ws); dfree(h->gumbel); dfree(h->considered);
   delete h;
   return LZM_OK;
 }
@@ -990,11 +1079,13 @@ int lzm_reserve(lzm_handle *h, int max_sims) {
   LZM_HIP(hipDeviceSynchronize());
   lzm_handle old = *h;
   h->stat = nullptr; h->meta = nullptr; h->path = nullptr; h->path_act = nullptr; h->stream = nullptr; h->lut = nullptr;
+  h->step_seeds = nullptr; h->raw = nullptr;
   int rc = alloc_tree(h, max_sims);
   if (rc == LZM_OK) {
     const size_t nodes = (size_t)old.cap * old.B;
     LZM_HIP(hipMemcpy(h->stat, old.stat, nodes * sizeof(NodeStat), hipMemcpyDeviceToDevice));
     LZM_HIP(hipMemcpy(h->meta, old.meta, nodes * sizeof(NodeMeta), hipMemcpyDeviceToDevice));
+    if (old.raw) LZM_HIP(hipMemcpy(h->raw, old.raw, nodes * sizeof(float), hipMemcpyDeviceToDevice));
     LZM_HIP(hipMemcpy(h->path, old.path, sizeof(int32_t) * (size_t)old.depth_cap * old.B, hipMemcpyDeviceToDevice));
     LZM_HIP(hipMemcpy(h->path_act, old.path_act, sizeof(int32_t) * (size_t)old.depth_cap * old.B, hipMemcpyDeviceToDevice));
     if (old.lut_base >= 0) rc = fill_lut(h, old.lut_base, old.lut_init);
@@ -1009,12 +1100,14 @@ int lzm_set_pb_c(lzm_handle *h, int pb_c_base, float pb_c_init) {
 }
 
 int lzm_copy_tree(lzm_handle *dst, const lzm_handle *src, void *stream) {
-  if (!dst || !src || dst->B != src->B || dst->A != src->A || dst->sims_cap < src->sims_cap) {
-    set_err("lzm_copy_tree: handles differ in shape or destination is smaller");
+  if (!dst || !src || dst->B != src->B || dst->A != src->A || dst->sims_cap < src->sims_cap ||
+      ((dst->flags ^ src->flags) & LZM_TREE_GUMBEL)) {
+    set_err("lzm_copy_tree: handles differ in shape or kind, or destination is smaller");
     return LZM_ERR_ARG;
   }
   hipStream_t s = (hipStream_t)stream;
   const size_t nodes = (size_t)src->cap * src->B;
+  if (src->raw) LZM_HIP(hipMemcpyAsync(dst->raw, src->raw, nodes * sizeof(float), hipMemcpyDeviceToDevice, s));
   LZM_HIP(hipMemcpyAsync(dst->stat, src->stat, nodes * sizeof(NodeStat), hipMemcpyDeviceToDevice, s));
   LZM_HIP(hipMemcpyAsync(dst->meta, src->meta, nodes * sizeof(NodeMeta), hipMemcpyDeviceToDevice, s));
   LZM_HIP(hipMemcpyAsync(dst->legal, src->legal, sizeof(int32_t) * (size_t)src->B * src->A, hipMemcpyDeviceToDevice, s));
@@ -1049,6 +1142,8 @@ int lzm_roots_prepare(lzm_handle *h, const int32_t *legal, const int32_t *count,
   p.logits = logits; p.noise_weight = noise_weight; p.B = h->B; p.A = h->A;
   hipLaunchKernelGGL(prepare_kernel, dim3((h->B + 255) / 256), dim3(256), 0, (hipStream_t)stream, p);
   LZM_CHECK_LAUNCH();
+  // Gumbel handles: the roots' raw_value starts at 0 until lzm_gumbel_set_root_values stores the value pool
+  if (h->raw) LZM_HIP(hipMemsetAsync(h->raw, 0, sizeof(float) * h->B, (hipStream_t)stream));
   return LZM_OK;
 }
 
@@ -1058,6 +1153,10 @@ int lzm_traverse(lzm_handle *h, int pb_c_base, float pb_c_init, float discount, 
   if (!h || !minmax || !seed || !vtp_in || !out_x || !out_y || !out_a || !out_vtp || !out_len) {
     set_err("lzm_traverse: null argument");
     return LZM_ERR_ARG;
+  }
+  if (h->flags & LZM_TREE_GUMBEL) {
+    set_err("lzm_traverse: a Gumbel MuZero handle takes the lzm_gumbel_* entry points");
+    return LZM_ERR_STATE;
   }
   if (pb_c_base <= 0) {
     set_err("lzm_traverse: pb_c_base must be positive");
@@ -1175,6 +1274,10 @@ int lzm_backprop(lzm_handle *h, int cur, float discount, float *minmax, const fl
     set_err("lzm_backprop: null argument");
     return LZM_ERR_ARG;
   }
+  if (h->flags & LZM_TREE_GUMBEL) {
+    set_err("lzm_backprop: a Gumbel MuZero handle takes the lzm_gumbel_* entry points");
+    return LZM_ERR_STATE;
+  }
   int rc = check_cur(h, cur);
   if (rc != LZM_OK) return rc;
   BackpropArgs p;
@@ -1206,6 +1309,10 @@ int lzm_decode_backprop(lzm_handle *h, int cur, float discount, float *minmax, c
   if (!h || !minmax || !reward_logits || !value_logits || !policy_logits || !to_play || support_len <= 0) {
     set_err("lzm_decode_backprop: null argument");
     return LZM_ERR_ARG;
+  }
+  if (h->flags & LZM_TREE_GUMBEL) {
+    set_err("lzm_decode_backprop: a Gumbel MuZero handle takes the lzm_gumbel_* entry points");
+    return LZM_ERR_STATE;
   }
   const int value_len = h->value_support > 0 ? h->value_support : support_len;
   if (categorical && (support_len % 2 == 0 || value_len % 2 == 0)) {
@@ -1246,6 +1353,10 @@ int lzm_decode_backprop_traverse(lzm_handle *h, int cur, float discount, float *
       !vtp_in || !out_x || !out_y || !out_a || !out_vtp || !out_len) {
     set_err("lzm_decode_backprop_traverse: null argument");
     return LZM_ERR_ARG;
+  }
+  if (h->flags & LZM_TREE_GUMBEL) {
+    set_err("lzm_decode_backprop_traverse: a Gumbel MuZero handle takes the lzm_gumbel_* entry points");
+    return LZM_ERR_STATE;
   }
   const int value_len = h->value_support > 0 ? h->value_support : support_len;
   if (categorical && (support_len % 2 == 0 || value_len % 2 == 0)) {
@@ -1343,6 +1454,253 @@ int lzm_get_trajectories(lzm_handle *h, int32_t *out, int tmax, void *stream) {
   if (!h || !out || tmax <= 0) return LZM_ERR_ARG;
   hipLaunchKernelGGL(trajectories_kernel, dim3((h->B + 255) / 256), dim3(256), 0, (hipStream_t)stream, view(h), out,
                      tmax);
+  LZM_CHECK_LAUNCH();
+  return LZM_OK;
+}
+
+// ---- Gumbel MuZero tree (ctree_gumbel_muzero/lib/cnode.cpp) ---------------------------------------------
+// generate_gumbel (cnode.cpp:1134-1152) with gumbel_rng = 0: std::mt19937(0) through
+// std::extreme_value_distribution<float>(0, 1), scaled. Host only.
+int lzm_gumbel_table(float scale, int n, float *out) {
+  if (!out || n < 0) return LZM_ERR_ARG;
+  std::mt19937 gen(0u);
+  std::extreme_value_distribution<float> d(0, 1);
+  for (int i = 0; i < n; ++i) out[i] = scale * d(gen);
+  return LZM_OK;
+}
+
+// The row of get_table_of_considered_visits (cnode.cpp:1079-1095) that cselect_root_child reads (:727-729):
+// get_sequence_of_considered_visits (:1042-1077) for min(m, S) considered actions over S simulations. Host only.
+int lzm_gumbel_considered_visits(int max_num_considered_actions, int num_simulations, int32_t *out) {
+  const int S = num_simulations;
+  if (!out || S < 1 || max_num_considered_actions < 0) return LZM_ERR_ARG;
+  const int m = max_num_considered_actions < S ? max_num_considered_actions : S;
+  if (m <= 1) {
+    for (int i = 0; i < S; ++i) out[i] = i;
+    return LZM_OK;
+  }
+  int log2max = 0;  // ceil(log2(m))
+  while ((1 << log2max) < m) ++log2max;
+  std::vector<int> visits(m, 0);
+  int filled = 0, considered = m;
+  while (filled < S) {
+    int extra = S / (log2max * considered);
+    if (extra < 1) extra = 1;
+    for (int e = 0; e < extra; ++e) {
+      for (int j = 0; j < considered && filled < S; ++j) out[filled++] = visits[j];
+      for (int j = 0; j < considered; ++j) visits[j] += 1;
+    }
+    considered = considered / 2 > 2 ? considered / 2 : 2;
+  }
+  return LZM_OK;
+}
+}  // extern "C"
+
+static int gumbel_kind(lzm_handle *h, const char *name) {
+  if (!h) {
+    snprintf(g_err, sizeof(g_err), "%s: null handle", name);
+    return LZM_ERR_ARG;
+  }
+  if (!(h->flags & LZM_TREE_GUMBEL)) {
+    snprintf(g_err, sizeof(g_err), "%s: not a Gumbel MuZero handle (create it with LZM_TREE_GUMBEL)", name);
+    return LZM_ERR_STATE;
+  }
+  return LZM_OK;
+}
+
+static GumbelView gumbel_view(lzm_handle *h) {
+  GumbelView g;
+  g.raw = h->raw;
+  g.gumbel = h->gumbel;
+  g.considered = h->considered;
+  g.S = h->cons_S;
+  return g;
+}
+
+// the device considered-visits row for (m, S): rebuilt (synchronous copy, outside stream capture) when they change
+static int gumbel_set_considered(lzm_handle *h, int S, int m, const char *name) {
+  if (S < 1 || m < 0) {
+    snprintf(g_err, sizeof(g_err), "%s: need num_simulations >= 1 and max_num_considered_actions >= 0", name);
+    return LZM_ERR_ARG;
+  }
+  if (h->cons_m == m && h->cons_S == S) return LZM_OK;
+  std::vector<int32_t> row(S);
+  lzm_gumbel_considered_visits(m, S, row.data());
+  if (S > h->cons_cap) {
+    LZM_HIP(hipDeviceSynchronize());
+    dfree(h->considered);
+    h->considered = nullptr;
+    h->cons_cap = 0;
+    LZM_HIP(hipMalloc(&h->considered, sizeof(int32_t) * (size_t)(S + 64)));
+    h->cons_cap = S + 64;
+  }
+  LZM_HIP(hipMemcpy(h->considered, row.data(), sizeof(int32_t) * S, hipMemcpyHostToDevice));
+  h->cons_m = m;
+  h->cons_S = S;
+  return LZM_OK;
+}
+
+static GumbelTraverseArgs gumbel_traverse_args(lzm_handle *h, float discount, const int32_t *vtp_in, int32_t *out_x,
+                                               int32_t *out_y, int32_t *out_a, int64_t *out_a64, int32_t *out_vtp,
+                                               int32_t *out_len) {
+  GumbelTraverseArgs q;
+  q.t = view(h);
+  q.g = gumbel_view(h);
+  q.vtp_in = vtp_in;
+  q.out_x = out_x; q.out_y = out_y; q.out_a = out_a; q.out_vtp = out_vtp; q.out_len = out_len;
+  q.out_a64 = (long long *)out_a64;
+  q.disc = discount;
+  return q;
+}
+
+static dim3 gumbel_grid(const lzm_handle *h) { return dim3((h->B + 3) / 4); }
+
+static int gumbel_decode_launch(const char *name, bool with_traverse, lzm_handle *h, int cur, float discount,
+                                float *minmax, const float *reward_logits, const float *value_logits, int support_len,
+                                int categorical, const float *policy_logits, const int32_t *to_play,
+                                const float *next_latent, float *pool_slot, int64_t row_elems, float *out_decoded,
+                                const GumbelTraverseArgs &q, hipStream_t s) {
+  if (!minmax || !reward_logits || !value_logits || !policy_logits || !to_play || support_len <= 0) {
+    snprintf(g_err, sizeof(g_err), "%s: null argument", name);
+    return LZM_ERR_ARG;
+  }
+  const int value_len = h->value_support > 0 ? h->value_support : support_len;
+  if (categorical && (support_len % 2 == 0 || value_len % 2 == 0)) {
+    snprintf(g_err, sizeof(g_err), "%s: categorical support length must be odd (2*support_scale+1)", name);
+    return LZM_ERR_ARG;
+  }
+  int rc = check_cur(h, cur);
+  if (rc != LZM_OK) return rc;
+  if (categorical && !h->ext_norm) {
+    rc = launch_norm_check(h, h->norm_flag, reward_logits, value_logits, h->B, support_len, value_len, s);
+    if (rc != LZM_OK) return rc;
+  }
+  DecodeArgs p;
+  p.t = view(h);
+  p.minmax = (float4 *)minmax;
+  p.reward_logits = reward_logits; p.value_logits = value_logits; p.policy_logits = policy_logits;
+  p.to_play = to_play; p.out_is_reset = nullptr; p.next_latent = next_latent; p.pool_slot = pool_slot;
+  p.row_elems = row_elems; p.V = support_len; p.Vv = value_len; p.categorical = categorical; p.cur = cur; p.horizon = 0;
+  p.disc = discount; p.out_decoded = out_decoded;
+  p.reuse_action = nullptr; p.reuse_value = nullptr;
+  const int32_t *nf = categorical ? (h->ext_norm ? h->ext_norm : h->norm_flag) : nullptr;
+  if (with_traverse) hipLaunchKernelGGL(gumbel_decode_kernel<true>, gumbel_grid(h), dim3(256), 0, s, p, nf, q);
+  else hipLaunchKernelGGL(gumbel_decode_kernel<false>, gumbel_grid(h), dim3(256), 0, s, p, nf, q);
+  LZM_CHECK_LAUNCH();
+  return LZM_OK;
+}
+
+extern "C" {
+
+int lzm_gumbel_set_considered(lzm_handle *h, int num_simulations, int max_num_considered_actions) {
+  int rc = gumbel_kind(h, "lzm_gumbel_set_considered");
+  if (rc != LZM_OK) return rc;
+  return gumbel_set_considered(h, num_simulations, max_num_considered_actions, "lzm_gumbel_set_considered");
+}
+
+int lzm_gumbel_set_root_values(lzm_handle *h, const float *values, void *stream) {
+  int rc = gumbel_kind(h, "lzm_gumbel_set_root_values");
+  if (rc != LZM_OK) return rc;
+  if (!values) return LZM_ERR_ARG;
+  // node 0's row of raw[cap][B]
+  LZM_HIP(hipMemcpyAsync(h->raw, values, sizeof(float) * h->B, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int lzm_gumbel_traverse(lzm_handle *h, int num_simulations, int max_num_considered_actions, float discount,
+                        const int32_t *vtp_in, int32_t *out_x, int32_t *out_y, int32_t *out_a, int64_t *out_a64,
+                        int32_t *out_vtp, int32_t *out_len, void *stream) {
+  int rc = gumbel_kind(h, "lzm_gumbel_traverse");
+  if (rc != LZM_OK) return rc;
+  if (!vtp_in || !out_x || !out_y || !out_a || !out_vtp || !out_len) {
+    set_err("lzm_gumbel_traverse: null argument");
+    return LZM_ERR_ARG;
+  }
+  rc = gumbel_set_considered(h, num_simulations, max_num_considered_actions, "lzm_gumbel_traverse");
+  if (rc != LZM_OK) return rc;
+  const GumbelTraverseArgs q = gumbel_traverse_args(h, discount, vtp_in, out_x, out_y, out_a, out_a64, out_vtp, out_len);
+  hipLaunchKernelGGL(gumbel_traverse_kernel, gumbel_grid(h), dim3(256), 0, (hipStream_t)stream, q);
+  LZM_CHECK_LAUNCH();
+  return LZM_OK;
+}
+
+int lzm_gumbel_backprop(lzm_handle *h, int cur, float discount, float *minmax, const float *rewards, const float *values,
+                        const float *logits, const int32_t *to_play, void *stream) {
+  int rc = gumbel_kind(h, "lzm_gumbel_backprop");
+  if (rc != LZM_OK) return rc;
+  if (!minmax || !rewards || !values || !logits || !to_play) {
+    set_err("lzm_gumbel_backprop: null argument");
+    return LZM_ERR_ARG;
+  }
+  rc = check_cur(h, cur);
+  if (rc != LZM_OK) return rc;
+  BackpropArgs p;
+  p.t = view(h);
+  p.minmax = (float4 *)minmax;
+  p.rewards = rewards; p.values = values; p.logits = logits; p.to_play = to_play; p.is_reset = nullptr;
+  p.cur = cur;
+  p.disc = discount;
+  p.reuse_action = nullptr; p.reuse_value = nullptr;
+  hipLaunchKernelGGL(gumbel_backprop_kernel, gumbel_grid(h), dim3(256), 0, (hipStream_t)stream, p, gumbel_view(h));
+  LZM_CHECK_LAUNCH();
+  return LZM_OK;
+}
+
+int lzm_gumbel_decode_backprop(lzm_handle *h, int cur, float discount, float *minmax, const float *reward_logits,
+                               const float *value_logits, int support_len, int categorical, const float *policy_logits,
+                               const int32_t *to_play, const float *next_latent, float *pool_slot, int64_t row_elems,
+                               float *out_decoded, void *stream) {
+  int rc = gumbel_kind(h, "lzm_gumbel_decode_backprop");
+  if (rc != LZM_OK) return rc;
+  GumbelTraverseArgs q = gumbel_traverse_args(h, discount, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  return gumbel_decode_launch("lzm_gumbel_decode_backprop", false, h, cur, discount, minmax, reward_logits, value_logits,
+                              support_len, categorical, policy_logits, to_play, next_latent, pool_slot, row_elems,
+                              out_decoded, q, (hipStream_t)stream);
+}
+
+int lzm_gumbel_decode_backprop_traverse(lzm_handle *h, int cur, float discount, float *minmax,
+                                        const float *reward_logits, const float *value_logits, int support_len,
+                                        int categorical, const float *policy_logits, const int32_t *to_play,
+                                        const float *next_latent, float *pool_slot, int64_t row_elems,
+                                        float *out_decoded, int num_simulations, int max_num_considered_actions,
+                                        const int32_t *vtp_in, int32_t *out_x, int32_t *out_y, int32_t *out_a,
+                                        int64_t *out_a64, int32_t *out_vtp, int32_t *out_len, void *stream) {
+  int rc = gumbel_kind(h, "lzm_gumbel_decode_backprop_traverse");
+  if (rc != LZM_OK) return rc;
+  if (!vtp_in || !out_x || !out_y || !out_a || !out_vtp || !out_len) {
+    set_err("lzm_gumbel_decode_backprop_traverse: null argument");
+    return LZM_ERR_ARG;
+  }
+  rc = gumbel_set_considered(h, num_simulations, max_num_considered_actions, "lzm_gumbel_decode_backprop_traverse");
+  if (rc != LZM_OK) return rc;
+  const GumbelTraverseArgs q = gumbel_traverse_args(h, discount, vtp_in, out_x, out_y, out_a, out_a64, out_vtp, out_len);
+  return gumbel_decode_launch("lzm_gumbel_decode_backprop_traverse", true, h, cur, discount, minmax, reward_logits,
+                              value_logits, support_len, categorical, policy_logits, to_play, next_latent, pool_slot,
+                              row_elems, out_decoded, q, (hipStream_t)stream);
+}
+
+static int gumbel_output(const char *name, lzm_handle *h, float discount, int policy, float *out, void *stream) {
+  int rc = gumbel_kind(h, name);
+  if (rc != LZM_OK) return rc;
+  if (!out) return LZM_ERR_ARG;
+  hipLaunchKernelGGL(gumbel_output_kernel, gumbel_grid(h), dim3(256), 0, (hipStream_t)stream, view(h), gumbel_view(h),
+                     discount, policy, out);
+  LZM_CHECK_LAUNCH();
+  return LZM_OK;
+}
+
+int lzm_gumbel_get_children_values(lzm_handle *h, float discount, float *out, void *stream) {
+  return gumbel_output("lzm_gumbel_get_children_values", h, discount, 0, out, stream);
+}
+
+int lzm_gumbel_get_policies(lzm_handle *h, float discount, float *out, void *stream) {
+  return gumbel_output("lzm_gumbel_get_policies", h, discount, 1, out, stream);
+}
+
+int lzm_debug_logf(const float *x, float *out, int64_t n, void *stream) {
+  if (!x || !out || n <= 0) return LZM_ERR_ARG;
+  hipLaunchKernelGGL(debug_logf_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, out,
+                     (long long)n);
   LZM_CHECK_LAUNCH();
   return LZM_OK;
 }
@@ -1967,6 +2325,10 @@ int search_mlp(const char *name, bool ez, lzm_handle *h, int H, int Hl, int F, i
       (ez && (!h_pool || !c_pool)) || S <= 0) {
     snprintf(g_err, sizeof(g_err), "%s: null argument or no simulations", name);
     return LZM_ERR_ARG;
+  }
+  if (h->flags & LZM_TREE_GUMBEL) {
+    set_err("one-launch searches do not take a Gumbel MuZero handle");
+    return LZM_ERR_STATE;
   }
   if ((uintptr_t)weights & 15) {
     snprintf(g_err, sizeof(g_err), "%s: weights must be 16-byte aligned (%s output)", name,
@@ -3449,6 +3811,10 @@ static int search_conv_launch(lzm_handle *h, int num_simulations, int pb_c_base,
       (ez && (!ez->hpool || !ez->cpool || !ez->lstm_frag || !ez->lstm_bias || !ez->vp_s || !ez->vp_t))) {
     snprintf(g_err, sizeof(g_err), "%s: null argument or no simulations", name);
     return LZM_ERR_ARG;
+  }
+  if (h->flags & LZM_TREE_GUMBEL) {
+    set_err("one-launch searches do not take a Gumbel MuZero handle");
+    return LZM_ERR_STATE;
   }
   uintptr_t bits = (uintptr_t)trunk_w | (uintptr_t)actmap | (uintptr_t)w1t | (uintptr_t)w2q | (uintptr_t)latent_pool;
   if (ez)

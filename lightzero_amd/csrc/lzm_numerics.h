@@ -57,6 +57,47 @@ __device__ inline float glibc_expf(float x, const uint64_t *tab = kExp2fTab) {
   return (float)y;
 }
 
+// glibc_logf: the Gumbel tree's csoftmax subtracts the host libm logf of its sum
+// (ctree_gumbel_muzero/lib/cnode.cpp:931, float overload). glibc 2.35 on x86-64 dispatches to the FMA
+// build of sysdeps/ieee754/flt-32/e_logf.c: a 16-entry {1/c, log c} table and a cubic in double
+// precision. A restatement of that published algorithm with the same constants and the same fused
+// multiply-adds, every input class included (1 -> +0, +-0 -> -inf, +inf, negative and NaN -> NaN,
+// subnormals rescaled by 2^23). Checked on the host against libm (tools/gumbel_logf_check.c):
+// every float in [1, 64] (the range the tree uses: sums of at most 64 terms in [0, 1], one of them 1)
+// and in [0.5, 1], a stride over all other positive floats, the special classes; on the device by
+// tests/test_gpu_gumbel.py.
+__device__ __constant__ static const uint64_t kLogfTab[16][2] = {
+#include "lzm_logf_tab.inc"
+};
+
+__device__ inline float glibc_logf(float x) {
+  const double Ln2 = 0x1.62e42fefa39efp-1;
+  const double A0 = -0x1.00ea348b88334p-2, A1 = 0x1.5575b0be00b6ap-2, A2 = -0x1.ffffef20a4123p-2;
+  uint32_t ix = __float_as_uint(x);
+  if (ix == 0x3f800000u) return 0.0f;
+  if (ix - 0x00800000u >= 0x7f800000u - 0x00800000u) {  // x < 0x1p-126, inf or nan
+    if (ix * 2 == 0) return -INFINITY;
+    if (ix == 0x7f800000u) return x;
+    if ((ix & 0x80000000u) || ix * 2 >= 0xff000000u) return __uint_as_float(0x7fc00000u);
+    ix = __float_as_uint(x * 0x1p23f);  // subnormal: normalize
+    ix -= 23u << 23;
+  }
+  const uint32_t tmp = ix - 0x3f330000u;
+  const int i = (tmp >> 19) % 16;
+  const int k = (int32_t)tmp >> 23;
+  const uint32_t iz = ix - (tmp & 0xff800000u);
+  const double invc = __longlong_as_double((long long)kLogfTab[i][0]);
+  const double logc = __longlong_as_double((long long)kLogfTab[i][1]);
+  const double z = (double)__uint_as_float(iz);
+  const double r = __fma_rn(z, invc, -1.0);
+  const double y0 = __fma_rn((double)k, Ln2, logc);
+  const double r2 = r * r;
+  double y = __fma_rn(A1, r, A2);
+  y = __fma_rn(A0, r2, y);
+  y = __fma_rn(y, r2, y0 + r);
+  return (float)y;
+}
+
 // x / (float)d for d in {1, 2, 3} (the divisors of the two-action mean-q chain) without the IEEE
 // division sequence: with y = RN(1/d), q0 = x * y, r = fma(-d, q0, x), q = fma(r, y, q0) is the
 // correctly rounded quotient for every finite x but -0, subnormals included (f32 denormals are on in

@@ -58,6 +58,7 @@ class ResultsWrapper:
 
 class _RootsBase:
     EZ = False
+    GUMBEL = False
 
     def __init__(self, root_num, legal_actions_list, fast_rng=False):
         self.fast_rng = bool(fast_rng)
@@ -102,7 +103,7 @@ class _RootsBase:
             return self.tree
         if self.tree is not None:
             POOL.release(self.tree)
-        self.tree = POOL.acquire(self.root_num, A, self._sims, self.EZ, self.fast_rng, device)
+        self.tree = POOL.acquire(self.root_num, A, self._sims, self.EZ, self.fast_rng, device, gumbel=self.GUMBEL)
         return self.tree
 
     def _prepare(self, noise_weight, noises, rewards, logits, to_play, device=None):
@@ -314,3 +315,108 @@ def _backprop_with_reuse(current_latent_state_index, discount_factor, value_pref
     _backprop(cur, discount_factor, full_r.tolist(), full_v.tolist(), full_p.tolist(), min_max_stats_lst, results,
               to_play_batch, is_reset_list)
     t.set_reuse(None)
+
+
+# ----------------------------------------------------------------------------- Gumbel MuZero (gmz_tree.pyx)
+def _require_int(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise TypeError(f"an integer is required for {name}")
+
+
+def _require_type(name, v, cls):
+    if not isinstance(v, cls):
+        raise TypeError(f"Argument '{name}' has incorrect type (expected {cls.__module__}.{cls.__name__}, "
+                        f"got {type(v).__name__})")
+
+
+class _GumbelRootsBase(_RootsBase):
+    """Roots of gmz_tree.pyx:28-65: prepare takes the value pool too (the roots' raw_value), and the
+    completed-Q outputs get_children_values / get_policies exist."""
+    GUMBEL = True
+
+    def __init__(self, root_num, legal_actions_list):
+        super().__init__(root_num, legal_actions_list, fast_rng=False)
+
+    def _set_values(self, value_pool):
+        t = self.tree
+        v = np.ascontiguousarray(np.asarray(value_pool, np.float32).reshape(self.root_num))
+        t.set_root_values(torch.from_numpy(v).to(t.device))
+
+    def prepare(self, root_noise_weight, noises, value_prefix_pool, value_pool, policy_logits_pool, to_play_batch):
+        _require_list("noises", noises)
+        _require_list("value_prefix_pool", value_prefix_pool)
+        _require_list("value_pool", value_pool)
+        _require_list("policy_logits_pool", policy_logits_pool)
+        self._prepare(root_noise_weight, noises, value_prefix_pool, policy_logits_pool, list(to_play_batch))
+        self._set_values(value_pool)
+
+    def prepare_no_noise(self, value_prefix_pool, value_pool, policy_logits_pool, to_play_batch):
+        _require_list("value_prefix_pool", value_prefix_pool)
+        _require_list("value_pool", value_pool)
+        _require_list("policy_logits_pool", policy_logits_pool)
+        self._prepare(0.0, None, value_prefix_pool, policy_logits_pool, list(to_play_batch))
+        self._set_values(value_pool)
+
+    def prepare_device(self, root_noise_weight, noises, rewards, values, logits, to_play):
+        """Device-tensor variant (not in the reference): all arguments torch tensors on the GPU."""
+        super().prepare_device(root_noise_weight, noises, rewards, logits, to_play)
+        self.tree.set_root_values(values.to(logits.device, torch.float32).reshape(self.root_num).contiguous())
+
+    def _root_rows(self, method, discount, action_space_size, fill):
+        _require_int("action_space_size", action_space_size)
+        n = int(action_space_size)
+        if self.tree is None:
+            return [[] for _ in range(self.root_num)]
+        if n < self.tree.A:
+            raise ValueError(f"action_space_size {n} is smaller than the tree's action space {self.tree.A}")
+        rows = getattr(self.tree, method)(_f32(discount)).cpu().numpy()
+        # a wider action space only adds illegal actions: -inf values, and expf(-inf) = +0 terms in the policy's sum
+        return [[float(x) for x in row] + [fill] * (n - self.tree.A) for row in rows]
+
+    def get_children_values(self, discount, action_space_size):
+        return self._root_rows("children_values", discount, action_space_size, float("-inf"))
+
+    def get_policies(self, discount, action_space_size):
+        return self._root_rows("policies", discount, action_space_size, 0.0)
+
+
+def _gumbel_traverse(roots, num_simulations, max_num_considered_actions, discount, results, virtual_to_play_batch):
+    """batch_traverse (gmz_tree.pyx:91-95)."""
+    _require_type("roots", roots, _GumbelRootsBase)
+    _require_int("num_simulations", num_simulations)
+    _require_int("max_num_considered_actions", max_num_considered_actions)
+    _require_type("results", results, ResultsWrapper)
+    _require_list("virtual_to_play_batch", virtual_to_play_batch)
+    t = roots.tree
+    if t is None:
+        raise RuntimeError("batch_traverse: roots not prepared")
+    vtp = torch.tensor(np.asarray(virtual_to_play_batch, np.int32)[:t.B], device=t.device)
+    t.gumbel_traverse(int(num_simulations), int(max_num_considered_actions), _f32(discount), vtp)
+    out = torch.stack([t.x, t.y, t.action, t.vtp, t.search_len]).cpu().numpy()
+    results._search_lens = out[4].tolist()
+    results._tree = t
+    return out[0].tolist(), out[1].tolist(), out[2].tolist(), out[3].tolist()
+
+
+def _gumbel_backprop(current_latent_state_index, discount, value_prefixs, values, policies, min_max_stats_lst, results,
+                     to_play_batch):
+    """batch_back_propagate (gmz_tree.pyx:81-88)."""
+    _require_int("current_latent_state_index", current_latent_state_index)
+    _require_list("value_prefixs", value_prefixs)
+    _require_list("values", values)
+    _require_list("policies", policies)
+    _require_type("min_max_stats_lst", min_max_stats_lst, MinMaxStatsList)
+    _require_type("results", results, ResultsWrapper)
+    _require_list("to_play_batch", to_play_batch)
+    t = getattr(results, "_tree", None)
+    if t is None:
+        raise RuntimeError("batch_back_propagate: results do not come from batch_traverse")
+    cur = int(current_latent_state_index)
+    if cur + 1 > t.sims_capacity + 1:
+        t.reserve(max(cur + 1, 2 * t.sims_capacity))
+    dev, B = t.device, t.B
+    g = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+    t.gumbel_backprop(cur, _f32(discount), min_max_stats_lst._device(dev),
+                      g(np.asarray(value_prefixs).reshape(B), np.float32), g(np.asarray(values).reshape(B), np.float32),
+                      g(np.asarray(policies, np.float32).reshape(B, t.A), np.float32),
+                      g(np.asarray(to_play_batch, np.int32).reshape(B), np.int32))

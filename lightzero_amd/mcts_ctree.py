@@ -1,4 +1,4 @@
-"""Drop-in ``MuZeroMCTSCtree`` / ``EfficientZeroMCTSCtree`` with the search loop on the GPU.
+"""Drop-in ``MuZeroMCTSCtree`` / ``EfficientZeroMCTSCtree`` / ``GumbelMuZeroMCTSCtree`` with the search loop on the GPU.
 
 Same class surface as /root/reference/lzero/mcts/tree_search/mcts_ctree.py:172-420 (MuZero) and
 :623-827 (EfficientZero): class attribute ``config``, ``default_config()``, ``__init__(cfg)``,
@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ctree import ez_tree, mz_tree
+from .ctree import ez_tree, gmz_tree, mz_tree
 from .conv_infer import FoldedCache
 from .fused import NotPackable, PackedCache, pack_efficientzero_mlp
 from .scaling_transform import InverseScalarTransform
@@ -443,7 +443,8 @@ class _MCTSCtree(object):
         t = c.t
         net = _step_net(self, model)
         # warm up every kernel and library handle on a scratch tree (must not touch `t`)
-        scratch = DeviceTree(t.B, t.A, max(c.S, t.sims_capacity), ez=t.ez, fast_rng=t.fast_rng, device=t.device)
+        scratch = DeviceTree(t.B, t.A, max(c.S, t.sims_capacity), ez=t.ez, fast_rng=t.fast_rng, device=t.device,
+                             gumbel=t.gumbel)
         scratch.copy_roots_from(t)
         scratch.set_pb_c(*self._pb_c())
         self._loop(scratch, model, c, net=net)
@@ -799,3 +800,79 @@ class EfficientZeroMCTSCtree(_MCTSCtree):
         self._horizon()
         return self._search_with_reuse(roots, model, latent_state_roots, reward_hidden_state_roots[:2], to_play_batch,
                                        true_action_list, reuse_value_list, seeds)
+
+
+class GumbelMuZeroMCTSCtree(_MCTSCtree):
+    """MCTS for Gumbel MuZero on the GPU (reference: mcts_ctree.py:956-1123). The generic per-simulation loop over
+    the Gumbel tree (lzm_gumbel.h): Gumbel traverse, leaf gather, recurrent_inference (the user's module or the
+    native conv trunk, as _loop chooses), then one launch for this simulation's decode + expand + backup and the
+    next simulation's traverse. Eager, or one HIP graph with cfg.use_hip_graph. The walk draws no random number:
+    there are no seeds and no rng_mode, and search_with_reuse does not exist, as in the reference."""
+
+    config = dict(
+        num_simulations=50,
+        root_dirichlet_alpha=0.3,
+        root_noise_weight=0.25,
+        value_delta_max=0.01,
+    )
+    _tree = gmz_tree
+    reward_name = 'reward'
+    rng_mode = None
+
+    @classmethod
+    def roots(cls: int, active_collect_env_num: int, legal_actions: List[Any]) -> "gmz_tree.Roots":
+        return gmz_tree.Roots(active_collect_env_num, legal_actions)
+
+    def _pb_c(self):
+        return 19652, 1.25  # (the handle's pUCT table, never read by the Gumbel walk)
+
+    def _considered(self):
+        return int(self._cfg.num_simulations), int(self._cfg.max_num_considered_actions)
+
+    def _recorder(self, c):
+        if not self.record:
+            return None
+        return _Recorder(c.S, c.B, c.t.A, c.dev)
+
+    _step = MuZeroMCTSCtree._step
+
+    def _loop(self, t, model, c, rec=None, infer=None, net=None):
+        """The S simulations (mcts_ctree.py:1054-1122) on tree t over c.buf, all enqueued on the current stream:
+        simulation k's backup and simulation k + 1's traverse share a launch."""
+        cfg, buf, S = self._cfg, c.buf, c.S
+        disc, cat, (ns, m) = self._discount(), self._categorical(), self._considered()
+        new_minmax(t.B, cfg.value_delta_max, t.device, out=buf.mm)
+        net = _step_net(self, model) if net is None else net
+        native = _native_trunk(net, buf)
+        with _HeadVerdicts(t, net, buf, native and cat and getattr(net, "heads", None) is not None):
+            for k in range(S):
+                if k == 0:
+                    t.gumbel_traverse(ns, m, disc, buf.vtp_in)
+                out = self._step(t, net, c, k, native)
+                logits = out.policy_logits.float().contiguous()
+                if rec is not None:
+                    rec.step(k, t, logits)
+                reward = out.reward.float().contiguous()
+                value = out.value.float().contiguous()
+                kw = dict(next_latent=None if native else out.latent_state.float().contiguous(),
+                          pool_slot=None if native else buf.pool[k + 1], row_elems=0 if native else c.row,
+                          out_decoded=None if rec is None else rec.decoded[k])
+                if k + 1 < S:
+                    t.gumbel_decode_backprop_traverse(k + 1, disc, buf.mm, reward, value, cat, logits, t.vtp, ns, m,
+                                                      buf.vtp_in, **kw)
+                else:
+                    t.gumbel_decode_backprop(k + 1, disc, buf.mm, reward, value, cat, logits, t.vtp, **kw)
+
+    def search(self, roots: Any, model: torch.nn.Module, latent_state_roots: List[Any],
+               to_play_batch: Union[int, List[Any]]) -> None:
+        with torch.no_grad():
+            c = self._begin("search", roots, model, latent_state_roots)
+            if not getattr(c.t, "gumbel", False):
+                raise TypeError("GumbelMuZeroMCTSCtree.search: roots must come from GumbelMuZeroMCTSCtree.roots")
+            c.t.set_considered(*self._considered())  # (before any capture: a synchronous table copy)
+            self._buffers(c, model, graph=not self.record and self._cfg.get('use_hip_graph', False))
+            c.buf.vtp_in.copy_(_to_play_tensor(to_play_batch, c.B, c.dev))
+            rec = self._recorder(c)
+            self._generic(c, model, rec)
+            self._finish(c, roots, None, rec)
+            self.last_path = "generic"

@@ -61,13 +61,17 @@ def _rec_ptrs(rec, names=("x", "action", "search_len", "decoded", "policy_logits
 
 
 class DeviceTree:
-    def __init__(self, num_roots, action_space, max_sims=64, ez=False, fast_rng=False, device=None):
+    def __init__(self, num_roots, action_space, max_sims=64, ez=False, fast_rng=False, device=None, gumbel=False):
+        """gumbel: a Gumbel MuZero tree (LZM_TREE_GUMBEL; ctree_gumbel_muzero), driven by the gumbel_* methods"""
         _lib.require_gpu()
+        if gumbel and ez:
+            raise ValueError("DeviceTree: gumbel and ez are mutually exclusive")
         self.uid = next(_uids)  # never reused (a handle address can be, after lzm_destroy)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.B, self.A = int(num_roots), int(action_space)
-        self.ez, self.fast_rng = bool(ez), bool(fast_rng)
-        flags = (_lib.LZM_TREE_EZ if ez else 0) | (_lib.LZM_RNG_FAST if fast_rng else 0)
+        self.ez, self.fast_rng, self.gumbel = bool(ez), bool(fast_rng), bool(gumbel)
+        flags = ((_lib.LZM_TREE_EZ if ez else 0) | (_lib.LZM_RNG_FAST if fast_rng else 0)
+                 | (_lib.LZM_TREE_GUMBEL if gumbel else 0))
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             call("lzm_create", self.B, self.A, int(max_sims), flags, ctypes.byref(h))
@@ -204,6 +208,66 @@ class DeviceTree:
              ptr(out_is_reset), ptr(next_latent), ptr(pool_slot), int(row_elems), ptr(out_decoded), int(pb_c_base),
              float(pb_c_init), ptr(seed), ptr(vtp_in), ptr(self.x), ptr(self.y), ptr(self.action), ptr(self.action64),
              ptr(self.vtp), ptr(self.search_len), stream_ptr(stream))
+
+    # -- Gumbel MuZero trees (lzm_gumbel_*; LzmError on any other tree, nothing launched) --------------
+    def set_considered(self, num_simulations, max_num_considered_actions):
+        """the device considered-visits row for (S, m), built now (a synchronous copy: outside graph capture);
+        a change retires captured graphs (generation)"""
+        key = (int(num_simulations), int(max_num_considered_actions))
+        if key != getattr(self, "_considered", None):
+            with torch.cuda.device(self.device):
+                call("lzm_gumbel_set_considered", self.h, *key)
+            if getattr(self, "_considered", None) is not None:
+                self.generation += 1
+            self._considered = key
+
+    def set_root_values(self, values, stream=None):
+        """the roots' raw_value (the value pool of Roots.prepare, gmz_tree.pyx:36-40): float32 device [B],
+        after prepare"""
+        call("lzm_gumbel_set_root_values", self.h, ptr(values), stream_ptr(stream))
+
+    def gumbel_traverse(self, num_simulations, max_num_considered_actions, discount, vtp_in, stream=None):
+        call("lzm_gumbel_traverse", self.h, int(num_simulations), int(max_num_considered_actions), float(discount),
+             ptr(vtp_in), ptr(self.x), ptr(self.y), ptr(self.action), ptr(self.action64), ptr(self.vtp),
+             ptr(self.search_len), stream_ptr(stream))
+        self._considered = (int(num_simulations), int(max_num_considered_actions))
+
+    def gumbel_backprop(self, cur, discount, minmax, rewards, values, logits, to_play, stream=None):
+        call("lzm_gumbel_backprop", self.h, int(cur), float(discount), ptr(minmax), ptr(rewards), ptr(values),
+             ptr(logits), ptr(to_play), stream_ptr(stream))
+
+    def gumbel_decode_backprop(self, cur, discount, minmax, reward_logits, value_logits, categorical, policy_logits,
+                               to_play, next_latent=None, pool_slot=None, row_elems=0, out_decoded=None, stream=None):
+        V = reward_logits.shape[-1] if categorical else 1
+        self._value_support(value_logits.shape[-1] if categorical else 1, V)
+        call("lzm_gumbel_decode_backprop", self.h, int(cur), float(discount), ptr(minmax), ptr(reward_logits),
+             ptr(value_logits), int(V), int(bool(categorical)), ptr(policy_logits), ptr(to_play), ptr(next_latent),
+             ptr(pool_slot), int(row_elems), ptr(out_decoded), stream_ptr(stream))
+
+    def gumbel_decode_backprop_traverse(self, cur, discount, minmax, reward_logits, value_logits, categorical,
+                                        policy_logits, to_play, num_simulations, max_num_considered_actions, vtp_in,
+                                        next_latent=None, pool_slot=None, row_elems=0, out_decoded=None, stream=None):
+        """gumbel_decode_backprop of simulation `cur` and the traverse of the next one in one launch; the traverse
+        outputs overwrite x / y / action / vtp / search_len."""
+        V = reward_logits.shape[-1] if categorical else 1
+        self._value_support(value_logits.shape[-1] if categorical else 1, V)
+        call("lzm_gumbel_decode_backprop_traverse", self.h, int(cur), float(discount), ptr(minmax),
+             ptr(reward_logits), ptr(value_logits), int(V), int(bool(categorical)), ptr(policy_logits), ptr(to_play),
+             ptr(next_latent), ptr(pool_slot), int(row_elems), ptr(out_decoded), int(num_simulations),
+             int(max_num_considered_actions), ptr(vtp_in), ptr(self.x), ptr(self.y), ptr(self.action),
+             ptr(self.action64), ptr(self.vtp), ptr(self.search_len), stream_ptr(stream))
+
+    def children_values(self, discount, stream=None):
+        """Roots.get_children_values: float32 [B, A], the completed Q in action order, -inf where illegal"""
+        out = torch.empty((self.B, self.A), dtype=torch.float32, device=self.device)
+        call("lzm_gumbel_get_children_values", self.h, float(discount), ptr(out), stream_ptr(stream))
+        return out
+
+    def policies(self, discount, stream=None):
+        """Roots.get_policies: float32 [B, A], the improved policy, exactly 0 where illegal"""
+        out = torch.empty((self.B, self.A), dtype=torch.float32, device=self.device)
+        call("lzm_gumbel_get_policies", self.h, float(discount), ptr(out), stream_ptr(stream))
+        return out
 
     def search_mlp(self, dims, weights, S, minmax, seeds, vtp_in, pool, pb_c_base=19652, pb_c_init=1.25,
                    discount=0.997, rec=None, stream=None):
@@ -410,8 +474,8 @@ class TreePool:
         self._free = {}
         self._lock = threading.Lock()
 
-    def acquire(self, B, A, max_sims, ez, fast_rng, device):
-        key = (B, A, ez, fast_rng, str(device))
+    def acquire(self, B, A, max_sims, ez, fast_rng, device, gumbel=False):
+        key = (B, A, ez, fast_rng, str(device), bool(gumbel))
         t = None
         with self._lock:
             lst = self._free.get(key) or []
@@ -422,7 +486,7 @@ class TreePool:
                 if c.h is not None and c.h.value:
                     t = c
         if t is None:
-            t = DeviceTree(B, A, max_sims, ez=ez, fast_rng=fast_rng, device=device)
+            t = DeviceTree(B, A, max_sims, ez=ez, fast_rng=fast_rng, device=device, gumbel=gumbel)
         else:
             t.reserve(max_sims)
             # the previous owner's sticky error words must not surface in this owner's searches
@@ -435,7 +499,7 @@ class TreePool:
     def release(self, t):
         if t is None or t.h is None:
             return
-        key = (t.B, t.A, t.ez, t.fast_rng, str(t.device))
+        key = (t.B, t.A, t.ez, t.fast_rng, str(t.device), t.gumbel)
         with self._lock:
             self._free.setdefault(key, []).append(t)
 
