@@ -684,9 +684,15 @@ int lzm_set_reuse(lzm_handle *h, const int32_t *true_action, const float *reuse_
  * ReLU; value head Linear H->F + BN + ReLU, Linear F->V; policy head Linear H->F + BN + ReLU,
  * Linear F->A) for B observations [B][O]. Replaces model.initial_inference in the collect step
  * (muzero.py:617-690; muzero_model_mlp.py:145-177, common.py:467-517, :883-971). `weights` (device)
- * holds eight BN-folded layers W[K][N] + bias[N]; `offsets` (host, 16 entries) their float offsets
- * in the order R1 w, R1 b, R2 w, R2 b, P1, P2, V1, V2, Q1, Q2. Outputs latent [B][H], value logits
- * [B][V], policy logits [B][A]. */
+ * holds eight BN-folded layers W[K][N] + bias[N]; `offsets` (host, 17 entries): their float offsets
+ * in the order R1 w, R1 b, R2 w, R2 b, P1, P2, V1, V2, Q1, Q2, then the float offset (a multiple of 4,
+ * `weights` 16-byte aligned) of the fast kernel's weight block, or -1 for none. Outputs latent [B][H],
+ * value logits [B][V], policy logits [B][A].
+ * The fast block (only read where lzm_mlp_initial_fast returns 1; 81920 floats) repeats R2, P1, P2,
+ * V1, Q1, V2 as float4 [slot][256 threads]: slot s of thread t holds 4 consecutive k of the thread's
+ * column in ii_dense's map (lzm_initial.h) — for a layer of N < 256 columns column t % N, k =
+ * (t / N) * (K * N / 256) + 4 s + (0..3); for V2 column t + 256 (s / 8), k = 4 (s % 8) + (0..3), zeros
+ * past column V. The launch with it computes the same bits as the launch without. */
 int lzm_mlp_initial_inference(int B, int O, int H, int F, int V, int A, int group, const float *obs,
                               const float *weights, const int64_t *offsets, float *latent, float *value, float *policy,
                               void *stream);
@@ -698,6 +704,10 @@ int lzm_mlp_initial_inference_prepare(lzm_handle *h, int B, int O, int H, int F,
                                       float *value, float *policy, const int32_t *legal, const int32_t *count,
                                       const float *noises, float noise_weight, const float *rewards,
                                       const int32_t *to_play, void *stream);
+/* 1 when the two launches above take the shape-specialised prefetching kernel (initial_fast_kernel) for
+ * this shape, given a fast weight block: H 128, F 32, V 601, group 8, 1 <= A <= 32, 1 <= O <= 16, and the
+ * environment variable LZM_II_FAST (read at each call) not "0"; 0 otherwise. Host-only, no GPU work. */
+int lzm_mlp_initial_fast(int O, int H, int F, int V, int A, int group);
 
 /* EfficientZero reward LSTM, input side (lzm_lstm.h): xin[b] = [r[b] | hpool[x[b]][b]] — the leaf's
  * hidden-state gather and the concat ahead of the gate GEMM. Replaces the per-simulation gathers of

@@ -68,6 +68,7 @@ SIGNATURES = {
     "lzm_mlp_initial_inference": [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "lzm_mlp_initial_inference_prepare": [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _f, _vp, _vp, _vp],
+    "lzm_mlp_initial_fast": [_i, _i, _i, _i, _i, _i],
     "lzm_set_reuse": [_vp, _vp, _vp],
     "lzm_ez_lstm_input": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "lzm_ez_lstm_cell": [_i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp],

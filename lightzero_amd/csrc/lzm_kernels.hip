@@ -4047,6 +4047,27 @@ extern "C" int lzm_ez_lstm_step(int B, int K, int H, const float *xin, const int
   return LZM_OK;
 }
 
+// The shape initial_fast_kernel is compiled for (lzm_initial.h): the resident search kernel's widths
+static bool ii_fast_shape(int O, int H, int F, int V, int A, int group) {
+  return H == kIfH && F == kIfF && V == kIfV && group == kIfG && A >= 1 && A <= kIfMaxA && O >= 1 && O <= kIfMaxO;
+}
+
+static bool ii_fast_enabled() {
+  const char *e = getenv("LZM_II_FAST");  // "0": always the generic kernel; read at each call
+  return !(e && atoi(e) == 0);
+}
+
+extern "C" int lzm_mlp_initial_fast(int O, int H, int F, int V, int A, int group) {
+  return (ii_fast_enabled() && ii_fast_shape(O, H, F, V, A, group)) ? 1 : 0;
+}
+
+// The fast kernel's weight block (offsets[16], 16-byte aligned), or null: the generic kernel
+static const float4 *ii_fast_block(const IiArgs &p, const float *weights, const int64_t *offsets) {
+  if (!ii_fast_enabled() || !ii_fast_shape(p.O, p.H, p.F, p.V, p.A, p.group) || offsets[16] < 0) return nullptr;
+  const float *fw = weights + offsets[16];
+  return (reinterpret_cast<uintptr_t>(fw) & 15) ? nullptr : reinterpret_cast<const float4 *>(fw);
+}
+
 extern "C" int lzm_mlp_initial_inference(int B, int O, int H, int F, int V, int A, int group, const float *obs,
                                          const float *weights, const int64_t *offsets, float *latent, float *value,
                                          float *policy, void *stream) {
@@ -4064,6 +4085,12 @@ extern "C" int lzm_mlp_initial_inference(int B, int O, int H, int F, int V, int 
     p.b[l] = l < 8 ? weights + offsets[2 * l + 1] : nullptr;
   }
   p.latent = latent; p.value = value; p.policy = policy;
+  if (const float4 *fw = ii_fast_block(p, weights, offsets)) {
+    hipLaunchKernelGGL(initial_fast_kernel<false>, dim3(B), dim3(kIiThreads), 0, (hipStream_t)stream, p, fw,
+                       PrepareArgs{});
+    LZM_CHECK_LAUNCH();
+    return LZM_OK;
+  }
   hipLaunchKernelGGL(initial_inference_kernel<false>, dim3((B + kIiEnvs - 1) / kIiEnvs), dim3(kIiThreads), 0,
                      (hipStream_t)stream, p, PrepareArgs{});
   LZM_CHECK_LAUNCH();
@@ -4098,6 +4125,11 @@ extern "C" int lzm_mlp_initial_inference_prepare(lzm_handle *h, int B, int O, in
   q.stat = h->stat; q.meta = h->meta; q.legal = h->legal; q.nlegal = h->nlegal;
   q.legal_in = legal; q.count_in = count; q.to_play = to_play; q.noises = noises; q.rewards = rewards;
   q.logits = policy; q.noise_weight = noise_weight; q.B = h->B; q.A = h->A;
+  if (const float4 *fw = ii_fast_block(p, weights, offsets)) {
+    hipLaunchKernelGGL(initial_fast_kernel<true>, dim3(B), dim3(kIiThreads), 0, (hipStream_t)stream, p, fw, q);
+    LZM_CHECK_LAUNCH();
+    return LZM_OK;
+  }
   hipLaunchKernelGGL(initial_inference_kernel<true>, dim3((B + kIiEnvs - 1) / kIiEnvs), dim3(kIiThreads), 0,
                      (hipStream_t)stream, p, q);
   LZM_CHECK_LAUNCH();

@@ -6,7 +6,9 @@ BatchNorms of the representation network (lzero/model/common.py:467-517: Linear,
 GELU(tanh), Linear, SimNorm) and of the prediction network (common.py:883-971) into their Linears
 (float64 on the host, as fused.py does for the recurrent network) and evaluates both in one kernel.
 It re-folds when the module's parameters or buffers change (tensor version counters), in place,
-so a captured HIP graph stays valid. ``initial_inference(obs)`` returns the module's output type;
+so a captured HIP graph stays valid. At the resident search kernel's widths (``fast_shape``) the packed
+buffer also carries the six wide layers in the [slot][thread] float4 order of the prefetching kernel
+(``fast_block``; initial_fast_kernel, same bits). ``initial_inference(obs)`` returns the module's output type;
 models it does not recognise raise NotPackable (callers fall back to the module).
 """
 import numpy as np
@@ -47,6 +49,35 @@ def describe_initial(model):
     return layers, dict(obs=O, hidden=H, head_hidden=F, support=V, actions=A, group=group)
 
 
+# The shape initial_fast_kernel (csrc/lzm_initial.h) is compiled for: the resident search kernel's widths
+FAST_WIDTHS = dict(hidden=128, head_hidden=32, support=601, group=8)
+FAST_MAX_ACTIONS, FAST_MAX_OBS, FAST_THREADS = 32, 16, 256
+
+
+def fast_shape(dims):
+    """lzm_mlp_initial_fast's shape rule (the library's answer also honours LZM_II_FAST, read at each call)"""
+    return (all(dims[k] == v for k, v in FAST_WIDTHS.items()) and 1 <= dims["actions"] <= FAST_MAX_ACTIONS
+            and 1 <= dims["obs"] <= FAST_MAX_OBS)
+
+
+def fast_block(layers):
+    """The fast kernel's weight block (include/lzmcts.h, lzm_mlp_initial_inference): R2, P1, P2, V1, Q1, V2
+    as float4 [slot][thread], slot s of thread t holding 4 consecutive k of the thread's column."""
+    T, out = FAST_THREADS, []
+    for l in (1, 2, 3, 4, 6):
+        wt = layers[l][0].t()  # [K][N], N < T: thread t has column t % N, K slice t // N
+        K, N = wt.shape
+        KS = T // N
+        out.append(wt.reshape(KS, K // KS // 4, 4, N).permute(1, 0, 3, 2).reshape(-1))  # [s][ks][n][i]
+    wt = layers[5][0].t()  # V2 [K][V]: thread t has columns t, t + T, ...
+    K, V = wt.shape
+    C = -(-V // T)
+    pad = wt.new_zeros((K, C * T))
+    pad[:, :V] = wt
+    out.append(pad.reshape(K // 4, 4, C, T).permute(2, 0, 3, 1).reshape(-1))  # [column][s][t][i]
+    return torch.cat(out)
+
+
 class FusedInitialInference:
     def __init__(self, model):
         self.model = model
@@ -70,6 +101,13 @@ class FusedInitialInference:
             offs += [o, o + wt.numel()]
             o += wt.numel() + b.numel()
             parts += [wt, b.reshape(-1)]
+        # offsets[16]: the fast kernel's block on a 16-byte boundary behind the generic layout, or -1
+        if fast_shape(dims):
+            gap = -o % 4
+            parts += [parts[-1].new_zeros(gap), fast_block(layers)]
+            offs.append(o + gap)
+        else:
+            offs.append(-1)
         flat = torch.cat(parts).to(device=dev, dtype=torch.float32).contiguous()
         if self.flat is None or self.flat.shape != flat.shape:
             self.flat = flat
