@@ -27,7 +27,9 @@
 // draw VALUE — and that tie leaves the leaf's parent (the gathered latent) known, only the action
 // open. So the look-back wait is deferred behind the first layer's latent rows and skipped
 // entirely when no draw value is needed. A tie reaching an expanded child (depth depends on the
-// draw) is resolved by wave 0 after its look-back, which resumes the walk at the tie.
+// draw) is resolved by wave 0 after its look-back, which resumes the walk at the tie. The register
+// walk (mode 5) hands its outcome to the workgroup as one word (hand_pack): the tie's candidates,
+// the pick and wave 0's expand + backup (expand_wave_r, backup_wave_r) are arithmetic on its fields.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -1163,6 +1165,93 @@ __device__ inline int lookback_sum_w0(const SearchArgs &p, int k, int g, int G, 
   return (int)wave_sum(sum);
 }
 
+// The register walk's hand-off word (selection mode 5): the walk's whole outcome in 32 bits, written
+// by lane 0 of wave 0 at the end of the walk and read once by every wave after the walk's barrier.
+// status: 2 bits; len: 8; x: 8, signed; action: 8, signed (-1 at a tie). S + 2 <= 64 bounds all three.
+__device__ __forceinline__ int hand_pack(int status, int len, int x, int action) {
+  return (status & 3) | ((len & 0xff) << 2) | ((x & 0xff) << 10) | ((action & 0xff) << 18);
+}
+struct HandOff {
+  int status, len, x, action;
+};
+__device__ __forceinline__ HandOff hand_unpack(int w) {
+  HandOff h;
+  h.status = w & 3;
+  h.len = (w >> 2) & 0xff;
+  h.x = (int)((unsigned)w << 14) >> 24;
+  h.action = (int)((unsigned)w << 6) >> 24;
+  return h;
+}
+
+// The tail of a mode-5 simulation on wave 0, from the hand-off's scalars (expand_wave_r, then
+// backup_wave_r): expand_wave's part 1 (the leaf's own record) and backup_wave, with no read of
+// pathlen or path[len] on the way. len, leaf and to_play are wave-uniform; len <= 62 (one round of
+// backup_wave). Lane l holds level l: the path reads do not depend on len and are masked by it
+// afterwards. The bootstrap chain runs leaf to root and the min-max update is a max / min, both in
+// backup_wave's exact operation order.
+struct TailPath {
+  int node, pact;  // lane l: level l's node (0 past the leaf) and action
+};
+// the expansion: the path reads in flight, then the leaf's own record (the fields expand_wave's part 1
+// changes), stored before backup_wave_r's reads of the same wave
+__device__ inline TailPath expand_wave_r(const TreeView &t, int len, int leaf, int to_play, int latent, float reward) {
+  const int lane = threadIdx.x & 63;
+  const int lv = min(lane, t.depth_cap - 1);
+  TailPath tp;
+  tp.node = t.path[lv];
+  tp.pact = t.path_act[lv];
+  tp.node = lane <= len ? tp.node : 0;
+  if (lane == 0) {
+    t.meta[leaf].latent = latent;
+    t.meta[leaf].to_play = to_play;
+    t.stat[leaf].reward = reward;
+  }
+  return tp;
+}
+__device__ inline void backup_wave_r(const TreeView &t, const TailPath &tp, int len, int to_play, float value,
+                                     float disc, float4 *mm_ptr) {
+  const int lane = threadIdx.x & 63;
+  const int node = tp.node;
+  const bool act = lane <= len;
+  if (lane < len) t.meta[node].best = tp.pact;
+  NodeStat s = t.stat[node];
+  const int ntp = t.meta[node].to_play;
+  float b = value;  // wave-uniform chain value
+  float bl = 0.0f;
+  for (int j = len; j >= 0; --j) {
+    if (lane == j) bl = b;
+    const float tr = readlane_f(s.reward, j);
+    if (to_play == -1) {
+      b = tr + disc * b;
+    } else {
+      const int nj = __builtin_amdgcn_readlane(ntp, j);
+      b = (nj == to_play) ? (-tr + disc * b) : (tr + disc * b);
+    }
+  }
+  float qmax = -INFINITY, qmin = INFINITY;
+  if (act) {
+    if (to_play == -1 || ntp == to_play)
+      s.value_sum += bl;
+    else
+      s.value_sum += -bl;
+    s.visit += 1;
+    t.stat[node] = s;
+    const float v = node_value(s);
+    if (t.val) t.val[node] = v;
+    const float q = (to_play == -1) ? s.reward + disc * v : s.reward + disc * -v;
+    qmax = fmaxf(qmax, q);
+    qmin = fminf(qmin, q);
+  }
+  qmax = wave_max_dpp(qmax);
+  qmin = -wave_max_dpp(-qmin);
+  if (lane == 0) {
+    float4 mm = *mm_ptr;
+    if (qmax > mm.x) mm.x = qmax;
+    if (qmin < mm.y) mm.y = qmin;
+    *mm_ptr = mm;
+  }
+}
+
 // SMODE: the selection mode (1, 4 or 5: see the simulation loop); RNG: 0 glibc, 1 Philox, -1 p.fast
 // at run time; STAMPS: phase stamps compiled in (LZM_PHASE_TIMING). Production launches fix all
 // three, so the unused paths cost neither code nor registers.
@@ -1228,6 +1317,7 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   __shared__ uint32_t s_z0[31];
   __shared__ int s_players, s_epoch, s_x, s_act, s_status, s_tlevel, s_vtp;
   __shared__ int s_len[1], s_part[kRWaves], s_nlat;
+  __shared__ int s_hand;  // (mode 5) the walk's hand-off word: hand_pack
   __shared__ unsigned long long s_tmask;
   __shared__ WalkState s_walk;
   __shared__ float4 s_mm;
@@ -1427,7 +1517,13 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         } else if (smode == 1) {  // (smode is 4 or 1)
           d = descend_terms<false>(t, NQ, CS, mm, s_vtp, players, draw, nullptr);
         }
-        if (lane == 0) { s_len[0] = d.len; s_x = d.x; s_act = d.action; s_status = 0; }
+        if (lane == 0) {
+          if (regwalk) {
+            s_hand = hand_pack(0, d.len, d.x, d.action);
+          } else {
+            s_len[0] = d.len; s_x = d.x; s_act = d.action; s_status = 0;
+          }
+        }
       } else {
         TieInfo ti;
         auto nodraw = [](int) -> uint32_t { return 0u; };
@@ -1450,8 +1546,13 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           if (lane == 0 && ti.status == 2) s_walk = ws;
         }
         if (lane == 0) {
-          s_len[0] = d.len; s_x = d.x; s_act = d.action;
-          s_status = ti.status; s_tlevel = ti.level; s_tmask = ti.mask;
+          // mode 5 hands the outcome over in one word; the separate scalars only where the status-2
+          // resume reads them (every mode-5 simulation files s_len / s_x / s_act in its tail)
+          if (regwalk) s_hand = hand_pack(ti.status, d.len, d.x, d.action);
+          if (!regwalk || ti.status == 2) {
+            s_len[0] = d.len; s_x = d.x; s_act = d.action;
+            s_status = ti.status; s_tlevel = ti.level; s_tmask = ti.mask;
+          }
           // publish this root's draw count at once (its depth is known unless status 2)
           if (ti.status != 2)
             __hip_atomic_store(&p.flags[(size_t)k * G + g], (epoch << 32) | (unsigned)d.len, __ATOMIC_RELAXED,
@@ -1474,7 +1575,10 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     }
     __syncthreads();
     LZM_STAMP(0);
-    const int status = s_status;
+    // (mode 5) the walk's outcome: one LDS read per wave, scalar from here on
+    HandOff ho = {0, 0, 0, 0};
+    if (regwalk) ho = hand_unpack(__builtin_amdgcn_readfirstlane(s_hand));
+    const int status = regwalk ? ho.status : s_status;
     if (__builtin_expect(status == 2, 0)) {
       // the depth depends on a draw: look back now, then resume the walk at the tie with the draws
       // (exact semantics; the draws of the forced levels above the tie are never read). First
@@ -1588,6 +1692,7 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             atomicAdd(p.diag + 3, 1);
           }
           s_len[0] = d.len; s_x = d.x; s_act = d.action;
+          if (regwalk) s_hand = hand_pack(2, d.len, d.x, d.action);  // the resumed walk's outcome
           if (st == 2)
             __hip_atomic_store(&p.flags[(size_t)k * G + g], (epoch << 32) | (unsigned)d.len, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
@@ -1600,6 +1705,7 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       }
       LZM_SUBSTAMP(22);
       __syncthreads();
+      if (regwalk) ho = hand_unpack(__builtin_amdgcn_readfirstlane(s_hand));
       LZM_SUBSTAMP(23);
     }
     // X0 = pool[x][i], the leaf's parent latent, is in LDS: gathered by the walking wave
@@ -1620,7 +1726,29 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // next-latent row the rest of the network reads. Other leaf ties wait for their draw here.
     bool late = false;
     int act_r[2];
-    if (status == 1) {
+    // (mode 5) a status-1 tie is between the two children of the node at level len - 1 (mask 3): its
+    // candidates are the root's legal actions there, else {0, 1}; all from the hand-off word
+    const int tlevel = regwalk ? ho.len - 1 : 0;
+    if (regwalk) {
+      if (status == 1) {
+        act_r[0] = tlevel == 0 ? rleg[0] : 0;
+        act_r[1] = tlevel == 0 ? rleg[1] : 1;
+        if (n.late_draw) {
+          late = true;
+        } else {
+          // the draw now: every wave draws for itself (as the late pick does), one lane files the pick
+          const int base = lookback_sum(p, k, g, G, epoch, s_part);
+          const uint32_t rr = glibc_draw_wave(p.coef, p.coef_positions, s_z0, base + tlevel, p.diag);
+          ho.action = (rr & 1u) ? act_r[1] : act_r[0];
+          if (tid == 0) {
+            t.path_act[tlevel] = ho.action;
+            t.path[tlevel + 1] = 1 + 2 * ho.x + ho.action;
+            s_act = ho.action;
+          }
+        }
+      }
+      if (!late) act_r[0] = act_r[1] = ho.action;
+    } else if (status == 1) {
       const unsigned long long m = s_tmask;
       const int parent = t.path[s_tlevel];
       if (__popcll(m) == 2 && n.late_draw) {
@@ -1633,7 +1761,7 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         __syncthreads();
       }
     }
-    if (!late) act_r[0] = act_r[1] = s_act;
+    if (!regwalk && !late) act_r[0] = act_r[1] = s_act;
     LZM_SUBSTAMP(17);
     __builtin_amdgcn_sched_barrier(0);
     // + the action's one-hot row, bias, ReLU (muzero_model_mlp.py:188-190)
@@ -1663,7 +1791,27 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     int lrow = 0;  // the late draw's pick: the two-way tie's second candidate when rand() % 2 == 1
     if (late) {
       const unsigned long long w0_ = p.phase ? __builtin_amdgcn_s_memtime() : 0ull;
-      if (G <= kRT) {
+      if (regwalk) {
+        // the pick in closed form (resolve_tie over mask 3 at level len - 1, whose node holds latent
+        // x): three stores from registers, ordered for the tail by the barriers below
+        uint32_t rr;
+        if (G <= kRT) {
+          const int base = lookback_sum_w0(p, k, g, G, epoch);
+          if (p.phase && tid == 0) s_wait += __builtin_amdgcn_s_memtime() - w0_;
+          rr = glibc_draw_wave(p.coef, p.coef_positions, s_z0, base + tlevel, p.diag);
+        } else {
+          const int base = lookback_sum(p, k, g, G, epoch, s_part);
+          if (p.phase && tid == 0) s_wait += __builtin_amdgcn_s_memtime() - w0_;
+          rr = glibc_draw_wave(p.coef, p.coef_positions, s_z0, base + tlevel, p.diag);
+        }
+        lrow = (int)(rr & 1u);
+        ho.action = lrow ? act_r[1] : act_r[0];
+        if (tid == 0) {
+          t.path_act[tlevel] = ho.action;
+          t.path[tlevel + 1] = 1 + 2 * ho.x + ho.action;
+          s_act = ho.action;
+        }
+      } else if (G <= kRT) {
         // every wave looks back and draws for itself, so no barrier hands the pick over; wave 0 files it
         const int base = lookback_sum_w0(p, k, g, G, epoch);
         if (p.phase && tid == 0) s_wait += __builtin_amdgcn_s_memtime() - w0_;
@@ -1776,9 +1924,9 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       reinterpret_cast<float4 *>(p.pool + ((size_t)(k + 1) * B + i) * kRHid)[tid - 64] =
           reinterpret_cast<const float4 *>(NLb)[(tid - 64) + (tid - 64 >= kRHid / 8)];
     if (p.rec_x && tid == 0) {
-      p.rec_x[(size_t)k * B + i] = s_x;
-      p.rec_a[(size_t)k * B + i] = s_act;
-      p.rec_len[(size_t)k * B + i] = s_len[0];
+      p.rec_x[(size_t)k * B + i] = regwalk ? ho.x : s_x;
+      p.rec_a[(size_t)k * B + i] = regwalk ? ho.action : s_act;
+      p.rec_len[(size_t)k * B + i] = regwalk ? ho.len : s_len[0];
     }
     if (p.rec_dec && tid == 0) {
       p.rec_dec[((size_t)k * B + i) * 2] = rdec;
@@ -1793,7 +1941,23 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // ---- expand + backup (cbatch_backpropagate, cnode.cpp:480-500): wave 0 files the leaf's own
     // record and backs up; wave 1 meanwhile initialises the leaf's children (disjoint nodes; the
     // next simulation's terms pass reads both after its barrier)
-    if (wid == 0) {
+    if (regwalk && wid == 0) {
+      // (mode 5) len, the leaf and its player from the hand-off's scalars: no s_len -> path[len] chain
+      const int len = ho.len;
+      const int leaf = len > 0 ? 1 + 2 * ho.x + ho.action : 0;
+      int vtp = s_vtp;
+      if (players > 1 && len > 0) {  // len flips: the first takes any value to 1 / 2, the rest alternate
+        vtp = (vtp == 1) ? 2 : 1;
+        if ((len - 1) & 1) vtp = (vtp == 1) ? 2 : 1;
+      }
+      LZM_SUBSTAMP(31);
+      const TailPath tp = expand_wave_r(t, len, leaf, vtp, k + 1, rdec);
+      LZM_STAMP(14);
+      if (lane == 0) L2N[s_nlat + k] = leaf;  // the leaf now holds latent k + 1 (= s_nlat + k)
+      backup_wave_r(t, tp, len, vtp, vdec, p.disc, &s_mm);
+      // the separate scalars for the write-back (p.pathlen) and any reader of the last walk
+      if (lane == 0) { s_len[0] = len; s_x = ho.x; s_act = ho.action; }
+    } else if (wid == 0) {
       const int len = s_len[0];
       const int leaf = t.path[len];
       int vtp = s_vtp;
