@@ -235,7 +235,7 @@ int lzm_debug_root_wait_cycles(lzm_handle *h, uint64_t *out_host, int n, int res
 
 /* Post-search integrity check (host-synchronous on `stream`): the sticky error counters of every
  * search path on the handle — {look-back spin timeouts, draw positions beyond the coefficient
- * table, serial-traverse fixed-point failures, fused-search errors, split-fp16 range errors, 0, 0, 0}
+ * table, reserved (always 0), fused-search errors, split-fp16 range errors, 0, 0, 0}
  * into out_host[8] (nullable). Returns LZM_ERR_RANGE when word 4 is non-zero (a split-fp16 network
  * value was non-finite or out of range: rerun with LZM_CONV_F32), else LZM_ERR_STATE when any is
  * non-zero (the parity-mode tie-break stream then differs from the reference's); clear != 0 resets
@@ -243,12 +243,13 @@ int lzm_debug_root_wait_cycles(lzm_handle *h, uint64_t *out_host, int n, int res
  * (cnode.cpp:770, :590) and cannot fail this way. */
 int lzm_check_errors(lzm_handle *h, int32_t *out_host, int clear, void *stream);
 
-/* Diagnostics: traverse passes used by the last parity-mode traverse (device int32[1]). */
-int lzm_last_traverse_passes(lzm_handle *h, int32_t *out, void *stream);
-
 /* Device-side numerics helpers exposed for exhaustive checks. */
 int lzm_debug_expf(const float *x, float *out, int64_t n, void *stream);
-int lzm_debug_glibc_rand(uint32_t seed, int n, int32_t *out, void *stream);
+/* out[p] (device int32[n]) = the p-th rand() after srand(seed), through the generator every parity-mode
+ * search draws from: the coefficient table over the state seeded in parallel. form selects the draw:
+ * 0 one thread per position, 1 one wave per position, 2 one wave per 64 positions (the walk's lane draws).
+ * Builds its table for n positions on first use (synchronous; lzm_shutdown frees it). */
+int lzm_debug_glibc_rand(uint32_t seed, int n, int form, int32_t *out, void *stream);
 /* div_small (lzm_numerics.h): out[e] = x[e] / (float)d[e] for d[e] in {1, 2, 3} (device arrays, n elements). */
 int lzm_debug_div_small(const float *x, const int32_t *d, float *out, int64_t n, void *stream);
 /* The register walk's mean-q chain (lzm_search_res.h settle_chain) on a synthetic path of n_levels <= 64

@@ -57,7 +57,6 @@ SIGNATURES = {
     "lzm_get_distributions": [_vp, _vp, _vp],
     "lzm_get_values": [_vp, _vp, _vp],
     "lzm_get_trajectories": [_vp, _vp, _i, _vp],
-    "lzm_last_traverse_passes": [_vp, _vp, _vp],
     "lzm_mlp_packed_floats": [_i, _i, _i, _i, _i],
     "lzm_mlp_kernel_floats": [_i, _i, _i, _i, _i],
     "lzm_search_mlp_kind": [_i, _i, _i, _i, _i, _i],
@@ -114,7 +113,7 @@ SIGNATURES = {
     "lzm_search_set_step": [_vp, _vp, _i64, _i, _vp, _vp, _i, _f],
     "lzm_check_errors": [_vp, _vp, _i, _vp],
     "lzm_debug_expf": [_vp, _vp, _i64, _vp],
-    "lzm_debug_glibc_rand": [_u32, _i, _vp, _vp],
+    "lzm_debug_glibc_rand": [_u32, _i, _i, _vp, _vp],
     "lzm_debug_div_small": [_vp, _vp, _vp, _i64, _vp],
     "lzm_debug_settle_chain": [_vp, _vp, _i, _vp, _vp],
     "lzm_debug_philox": [_vp, _vp, _i, _vp],

@@ -114,8 +114,7 @@ struct GumbelTraverseArgs {
   TreeView t;
   GumbelView g;
   const int32_t *vtp_in;
-  int32_t *out_x, *out_y, *out_a, *out_vtp, *out_len;
-  long long *out_a64;
+  WalkOut out;
   float disc;
 };
 
@@ -157,15 +156,8 @@ __device__ inline void gumbel_traverse_root(const GumbelTraverseArgs &p, int i) 
     ++len;
     latent = __builtin_amdgcn_readlane(c.latent, jsel);
   }
-  if (lane == 0) {
-    p.out_x[i] = parent_latent;
-    p.out_y[i] = i;
-    p.out_a[i] = last_action;
-    if (p.out_a64) p.out_a64[i] = last_action;
-    p.out_vtp[i] = p.vtp_in[i];  // passed through (:895): the Gumbel tree has no player bookkeeping
-    p.out_len[i] = len;
-    t.pathlen[i] = len;
-  }
+  // virtual_to_play is passed through (:895): the Gumbel tree has no player bookkeeping
+  if (lane == 0) store_walk(p.out, t, i, parent_latent, last_action, p.vtp_in[i], len);
 }
 
 // value of the lane holding legal position j, moved to lane legal[j] (action order); `fill` elsewhere

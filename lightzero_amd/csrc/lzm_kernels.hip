@@ -17,6 +17,12 @@
 // -ffp-contract=off, IEEE division/sqrt), expf is the glibc port of lzm_numerics.h, and
 // log((N+base+1)/base)+init and sqrt(N) over the integer parent count N come from a host
 // table built with the host's libm (the very functions the reference calls).
+//
+// Generic search path (any PyTorch network between the launches): traverse_lookback_kernel (parity mode: one
+// wave per root, the batch-serial rand() offsets by decoupled look-back, lzm_traverse_lb.h) or
+// traverse_fast_kernel (Philox), then backprop_kernel from raw lists or decode_backprop_kernel from support
+// logits; decode_traverse_kernel folds the next traverse into the decode's launch; the Gumbel MuZero tree
+// (lzm_gumbel.h) has its own three. On the host one builder per argument struct serves every entry point.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -44,6 +50,8 @@
 #include "lzm_heads.h"
 #include "lzm_lstm.h"
 #include "lzm_initial.h"
+#include "lzm_traverse_lb.h"
+#include "lzm_search_conv.h"
 
 namespace lzm {
 
@@ -52,16 +60,7 @@ struct TraverseArgs {
   const float4 *minmax;
   const uint32_t *seed;
   const int32_t *vtp_in;
-  int32_t *out_x, *out_y, *out_a, *out_vtp, *out_len;
-  long long *out_a64;
-  uint32_t *stream;  // raw glibc stream values (before >> 1)
-  int stream_cap;
-  const uint32_t *jfirst;  // [kMaxWG][31]
-  const uint32_t *jnext;   // [kMaxWG][31]
-  int32_t *off;            // [B]
-  int32_t *diag;           // [0] fixed-point passes of the last call ([1] unused: failures go to err)
-  int32_t *err;            // sticky error counters (lzm_check_errors): [2] fixed point not reached
-  int32_t *hint;           // [0] stream length used by the previous call
+  WalkOut out;
   float disc;
 };
 
@@ -79,152 +78,6 @@ __device__ inline int block_players(const int32_t *vtp, int B) {
   return p;
 }
 
-// Block-wide exclusive scan (blockDim multiple of 64, <= 1024).
-__device__ inline int block_excl_scan(int v, int *s_w, int &total) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    int y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  if (lane == 63) s_w[wid] = x;
-  __syncthreads();
-  if (wid == 0) {
-    int w = lane < nw ? s_w[lane] : 0;
-#pragma unroll
-    for (int d = 1; d < 16; d <<= 1) {
-      int y = __shfl_up(w, d, 64);
-      if (lane >= d) w += y;
-    }
-    if (lane < nw) s_w[lane] = w;
-  }
-  __syncthreads();
-  const int pre = wid > 0 ? s_w[wid - 1] : 0;
-  total = s_w[nw - 1];
-  __syncthreads();
-  return pre + x - v;
-}
-
-// Parity-mode traverse: ONE workgroup walks every root, because the reference consumes one
-// process-wide rand() stream in root order (root i's draws start at sum_{j<i} depth_j).
-// The walk is speculative: descend every root with assumed offsets, scan the depths, and
-// repeat until the offsets reproduce themselves (the unique fixed point = the serial
-// order). A tie among unexpanded children never changes a depth, so two passes is typical.
-// The glibc stream is produced 1 block-width at a time by a jump matrix over Z/2^32:
-// z[n+m] = sum_j J[m][j] * z[n-31+j] (random_r is linear in its 31-word state).
-template <bool EZ>
-__global__ __launch_bounds__(1024) void traverse_glibc_kernel(TraverseArgs p) {
-  const TreeView &t = p.t;
-  const int W = blockDim.x, tid = threadIdx.x, B = t.B;
-  __shared__ uint32_t s_win[31];
-  __shared__ uint32_t s_z0[31];
-  __shared__ uint32_t s_tail[31];
-  __shared__ int s_w[16];
-  __shared__ int s_flag;
-  const int players = block_players(p.vtp_in, B);
-  if (tid == 0) glibc_seed_state(*p.seed, s_z0);
-  uint32_t jn[31];
-#pragma unroll
-  for (int j = 0; j < 31; ++j) jn[j] = p.jnext[tid * 31 + j];
-  __syncthreads();
-  int generated = 0;
-  auto gen_chunk = [&]() {
-    uint32_t v = 0;
-    if (generated == 0) {
-#pragma unroll
-      for (int j = 0; j < 31; ++j) v += p.jfirst[tid * 31 + j] * s_z0[j];
-    } else {
-#pragma unroll
-      for (int j = 0; j < 31; ++j) v += jn[j] * s_win[j];
-    }
-    if (generated + tid < p.stream_cap) p.stream[generated + tid] = v;
-    if (tid >= W - 31) s_tail[tid - (W - 31)] = v;
-    __syncthreads();
-    if (tid < 31) s_win[tid] = s_tail[tid];
-    generated += W;
-    __syncthreads();
-  };
-  // first chunk(s): enough for the previous call's total
-  int want = *p.hint + W;
-  if (want > p.stream_cap) want = p.stream_cap;
-  do {
-    gen_chunk();
-  } while (generated < want);
-
-  const int rounds = (B + W - 1) / W;
-  for (int r = 0; r < rounds; ++r) {
-    int i = r * W + tid;
-    if (i < B) p.off[i] = 0;
-  }
-  __syncthreads();
-  int passes = 0;
-  for (;;) {
-    ++passes;
-    if (tid == 0) s_flag = 0;
-    __syncthreads();
-    int carry = 0, overflow = 0, changed = 0;
-    for (int r = 0; r < rounds; ++r) {
-      const int i = r * W + tid;
-      int depth = 0;
-      if (i < B) {
-        const int off = p.off[i];
-        const int gen = generated;
-        const uint32_t *st = p.stream;
-        auto draw = [&](int level) -> uint32_t {
-          const int pos = off + level;
-          if (pos < gen) return st[pos] >> 1;
-          overflow = 1;
-          return 0u;
-        };
-        Descent d = descend<EZ>(t, i, p.minmax[i], players, p.vtp_in[i], p.disc, draw);
-        depth = d.len;
-        p.out_x[i] = d.x;
-        p.out_y[i] = i;
-        p.out_a[i] = d.action;
-        if (p.out_a64) p.out_a64[i] = d.action;
-        p.out_vtp[i] = d.vtp;
-        p.out_len[i] = d.len;
-        t.pathlen[i] = d.len;
-      }
-      int total;
-      const int ex = block_excl_scan(depth, s_w, total);
-      if (i < B) {
-        const int noff = carry + ex;
-        if (noff != p.off[i]) changed = 1;
-        p.off[i] = noff;
-      }
-      carry += total;
-    }
-    if (changed || overflow) s_flag = 1;  // benign race: every writer stores 1
-    __syncthreads();
-    const int again = s_flag;
-    __syncthreads();
-    if (carry > generated && generated < p.stream_cap) {
-      while (generated < carry && generated < p.stream_cap) gen_chunk();
-    }
-    if (!again) {
-      if (tid == 0) *p.hint = carry;
-      break;
-    }
-    if (passes > B + 2) {  // cannot happen: the fixed point is reached in <= B+1 passes
-      if (tid == 0) atomicAdd(p.err + 2, 1);
-      break;
-    }
-  }
-  // commit best_action along the final paths (cnode.cpp:806)
-  for (int r = 0; r < rounds; ++r) {
-    const int i = r * W + tid;
-    if (i >= B) continue;
-    const int len = t.pathlen[i];
-    for (int l = 0; l < len; ++l) {
-      const int node = t.path[(size_t)l * B + i];
-      t.meta[nidx(t, node, i)].best = t.path_act[(size_t)l * B + i];
-    }
-  }
-  if (tid == 0) p.diag[0] = passes;
-}
-
 // Fast-mode traverse: roots are independent (Philox4x32-10 draw per (seed, root, level)), so
 // one lane per root over as many workgroups as needed.
 template <bool EZ>
@@ -239,20 +92,12 @@ __global__ __launch_bounds__(256) void traverse_fast_kernel(TraverseArgs p) {
     return o.x >> 1;
   };
   Descent d = descend<EZ>(t, i, p.minmax[i], players, p.vtp_in[i], p.disc, draw);
-  p.out_x[i] = d.x;
-  p.out_y[i] = i;
-  p.out_a[i] = d.action;
-  if (p.out_a64) p.out_a64[i] = d.action;
-  p.out_vtp[i] = d.vtp;
-  p.out_len[i] = d.len;
-  t.pathlen[i] = d.len;
+  store_walk(p.out, t, i, d.x, d.action, d.vtp, d.len);
   for (int l = 0; l < d.len; ++l) {
     const int node = t.path[(size_t)l * t.B + i];
     t.meta[nidx(t, node, i)].best = t.path_act[(size_t)l * t.B + i];
   }
 }
-
-
 
 struct BackpropArgs {
   TreeView t;
@@ -296,97 +141,6 @@ __global__ __launch_bounds__(256) void backprop_kernel(BackpropArgs p) {
   else if (EZ)  // the reference sets every leaf's is_reset, expanded or not (ctree_efficientzero cnode.cpp:638)
     t.meta[nidx(t, leaf, i)].is_reset = p.is_reset ? p.is_reset[i] : 0;
   backup<EZ>(t, i, p.minmax + i, tp, v, p.disc);
-}
-
-// InverseScalarTransform (scaling_transform.py:118-128) of one row by one wave:
-// softmax (unless `raw`), expectation over support [-(V-1)/2 .. (V-1)/2], then h^-1.
-// Register form for V <= 64 * NPL: the row is loaded once, every load in flight together (the loop
-// form re-reads it in three passes with one memory latency per iteration). Same per-lane order and
-// the same reductions, so the same bits.
-template <int NPL>
-__device__ inline float wave_support_expectation_reg(const float *row, int V, bool softmax) {
-  const int lane = threadIdx.x & 63;
-  const float half = (float)((V - 1) / 2);
-  float x[NPL];
-#pragma unroll
-  for (int q = 0; q < NPL; ++q) {
-    const int j = lane + 64 * q;
-    x[q] = j < V ? row[j] : 0.0f;
-  }
-  if (!softmax) {
-    float acc = 0.0f;
-#pragma unroll
-    for (int q = 0; q < NPL; ++q)
-      if (lane + 64 * q < V) acc += x[q] * ((float)(lane + 64 * q) - half);
-    acc = xor_sum(acc);
-    return acc;
-  }
-  float mx = -INFINITY;
-#pragma unroll
-  for (int q = 0; q < NPL; ++q)
-    if (lane + 64 * q < V) mx = fmaxf(mx, x[q]);
-  mx = xor_max(mx);
-  float sum = 0.0f;
-#pragma unroll
-  for (int q = 0; q < NPL; ++q)
-    if (lane + 64 * q < V) sum += expf(x[q] - mx);
-  sum = xor_sum(sum);
-  float acc = 0.0f;
-#pragma unroll
-  for (int q = 0; q < NPL; ++q)
-    if (lane + 64 * q < V) acc += (expf(x[q] - mx) / sum) * ((float)(lane + 64 * q) - half);
-  acc = xor_sum(acc);
-  return acc;
-}
-
-__device__ inline float wave_support_expectation_loop(const float *row, int V, bool softmax);
-
-__device__ inline float wave_support_expectation(const float *row, int V, bool softmax) {
-  if (V <= 64 * 2) return wave_support_expectation_reg<2>(row, V, softmax);
-  if (V <= 64 * 10) return wave_support_expectation_reg<10>(row, V, softmax);
-  if (V <= 64 * 16) return wave_support_expectation_reg<16>(row, V, softmax);
-  return wave_support_expectation_loop(row, V, softmax);
-}
-
-__device__ inline float wave_support_expectation_loop(const float *row, int V, bool softmax) {
-  const int lane = threadIdx.x & 63;
-  const float half = (float)((V - 1) / 2);
-  if (!softmax) {
-    float acc = 0.0f;
-    for (int j = lane; j < V; j += 64) acc += row[j] * ((float)j - half);
-    acc = xor_sum(acc);
-    return acc;
-  }
-  float mx = -INFINITY;
-  for (int j = lane; j < V; j += 64) mx = fmaxf(mx, row[j]);
-  mx = xor_max(mx);
-  float sum = 0.0f;
-  for (int j = lane; j < V; j += 64) sum += expf(row[j] - mx);
-  sum = xor_sum(sum);
-  float acc = 0.0f;
-  for (int j = lane; j < V; j += 64) acc += (expf(row[j] - mx) / sum) * ((float)j - half);
-  acc = xor_sum(acc);
-  return acc;
-}
-
-
-__device__ inline float wave_row_sum(const float *row, int V) {
-  const int lane = threadIdx.x & 63;
-  float s = 0.0f;
-  if (V <= 64 * 10) {
-    // every load in flight together; same per-lane order as the loop
-    float x[10];
-#pragma unroll
-    for (int q = 0; q < 10; ++q) x[q] = lane + 64 * q < V ? row[lane + 64 * q] : 0.0f;
-#pragma unroll
-    for (int q = 0; q < 10; ++q)
-      if (lane + 64 * q < V) s += x[q];
-    s = xor_sum(s);
-    return s;
-  }
-  for (int j = lane; j < V; j += 64) s += row[j];
-  s = xor_sum(s);
-  return s;
 }
 
 struct DecodeArgs {
@@ -468,35 +222,21 @@ __device__ inline void decode_root(const DecodeArgs &p, const int32_t *norm_part
   const int lane = threadIdx.x & 63;
   float r, v;
   decode_heads(p, norm_part, i, &r, &v);
-  if (t.A <= 64) {
-    // one lane per child / path level, bit-identical to the serial form below (lzm_tree.h)
-    const int len = t.pathlen[i];
-    const int leaf = t.path[(size_t)len * t.B + i];
-    const int tp = p.to_play[i];
-    const int is_reset = (EZ && p.horizon > 0 && len % p.horizon == 0) ? 1 : 0;
-    if (p.out_is_reset && lane == 0) p.out_is_reset[i] = is_reset;
-    bool no_inf;
-    reuse_leaf(t, i, leaf, len, p.reuse_action, p.reuse_value, &no_inf, &v);
-    if (!no_inf) expand_wave(t, i, leaf, tp, p.cur, r, p.policy_logits + (size_t)i * t.A, EZ ? is_reset : -1);
-    else if (EZ && lane == 0) t.meta[nidx(t, leaf, i)].is_reset = is_reset;  // (cnode.cpp:638, every leaf)
-    if (EZ)
-      backup_wave_ez(t, i, i, t.B, p.minmax + i, tp, v, p.disc);
-    else
-      backup_wave(t, i, i, t.B, p.minmax + i, tp, v, p.disc);
-    return;
-  }
-  if (lane != 0) return;
+  // one lane per child / path level (A <= kMaxActions = 64), bit-identical to backprop_kernel's
+  // expand_leaf / backup (lzm_tree.h)
   const int len = t.pathlen[i];
   const int leaf = t.path[(size_t)len * t.B + i];
-  int is_reset = 0;
-  if (EZ && p.horizon > 0) is_reset = (len % p.horizon == 0) ? 1 : 0;
-  if (p.out_is_reset) p.out_is_reset[i] = is_reset;
   const int tp = p.to_play[i];
+  const int is_reset = (EZ && p.horizon > 0 && len % p.horizon == 0) ? 1 : 0;
+  if (p.out_is_reset && lane == 0) p.out_is_reset[i] = is_reset;
   bool no_inf;
   reuse_leaf(t, i, leaf, len, p.reuse_action, p.reuse_value, &no_inf, &v);
-  if (!no_inf) expand_leaf(t, i, leaf, tp, p.cur, r, p.policy_logits + (size_t)i * t.A, is_reset, EZ);
-  else if (EZ) t.meta[nidx(t, leaf, i)].is_reset = is_reset;
-  backup<EZ>(t, i, p.minmax + i, tp, v, p.disc);
+  if (!no_inf) expand_wave(t, i, leaf, tp, p.cur, r, p.policy_logits + (size_t)i * t.A, EZ ? is_reset : -1);
+  else if (EZ && lane == 0) t.meta[nidx(t, leaf, i)].is_reset = is_reset;  // (cnode.cpp:638, every leaf)
+  if (EZ)
+    backup_wave_ez(t, i, i, t.B, p.minmax + i, tp, v, p.disc);
+  else
+    backup_wave(t, i, i, t.B, p.minmax + i, tp, v, p.disc);
 }
 
 template <bool EZ>
@@ -702,29 +442,31 @@ __global__ void debug_philox_kernel(const uint32_t *ck, uint32_t *out, int n) {
   out[(size_t)i * 4 + 3] = o.w;
 }
 
-__global__ void debug_glibc_kernel(uint32_t seed, int n, int32_t *out, const uint32_t *jfirst, const uint32_t *jnext) {
-  // single workgroup; exercises the same jump-matrix generator as traverse_glibc_kernel
-  __shared__ uint32_t s_z0[31], s_win[31], s_tail[31];
-  const int W = blockDim.x, tid = threadIdx.x;
-  if (tid == 0) glibc_seed_state(seed, s_z0);
+// lzm_debug_glibc_rand: rand() output p < n through the generator every parity search draws from — the
+// coefficient table (glibc_coef_table, n positions) over seed_state_parallel's state — in the form asked
+// for: 0 glibc_draw, one thread per position; 1 glibc_draw_wave, the position wave-uniform; 2 lane_draws,
+// each wave over its 64 positions, read back through operator(). Workgroup g covers positions 256 g ..
+__global__ __launch_bounds__(256) void debug_glibc_kernel(uint32_t seed, int n, int form, int32_t *out,
+                                                          const uint32_t *coef, const uint32_t *pow16807,
+                                                          int32_t *overflow) {
+  __shared__ uint32_t s_z0[31], s_pow[31];
+  const int tid = threadIdx.x, lane = tid & 63;
+  if (tid < 31) s_pow[tid] = pow16807[tid];
   __syncthreads();
-  for (int g = 0; g < n; g += W) {
-    uint32_t v = 0;
-    for (int j = 0; j < 31; ++j) v += (g == 0 ? jfirst[tid * 31 + j] * s_z0[j] : jnext[tid * 31 + j] * s_win[j]);
-    if (g + tid < n) out[g + tid] = (int32_t)(v >> 1);
-    if (tid >= W - 31) s_tail[tid - (W - 31)] = v;
-    __syncthreads();
-    if (tid < 31) s_win[tid] = s_tail[tid];
-    __syncthreads();
+  seed_state_parallel(seed, s_pow, s_z0);
+  __syncthreads();
+  if (form == 0) {
+    const int p = blockIdx.x * 256 + tid;
+    if (p < n) out[p] = (int32_t)glibc_draw(coef, n, s_z0, p, overflow);
+    return;
+  }
+  const int base = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 256 + (tid & ~63)));  // of this wave
+  const LaneDraws draws = lane_draws(coef, n, s_z0, base, 0, 64, overflow);
+  for (int l = 0; l < 64 && base + l < n; ++l) {
+    const uint32_t r = form == 1 ? glibc_draw_wave(coef, n, s_z0, base + l, overflow) : draws(l);
+    if (lane == 0) out[base + l] = (int32_t)r;
   }
 }
-
-}  // namespace lzm
-
-#include "lzm_traverse_lb.h"  // uses block_players above
-#include "lzm_search_conv.h"  // uses wave_support_expectation / wave_row_sum above
-
-namespace lzm {
 
 // Simulation k's decode + expand + backup fused with simulation k + 1's traverse (generic search
 // path, parity mode): the wave that backs up root i walks root i again at once, over the records it
@@ -846,15 +588,12 @@ struct lzm_handle {
   NodeStat *stat = nullptr;
   NodeMeta *meta = nullptr;
   int32_t *legal = nullptr, *nlegal = nullptr, *path = nullptr, *path_act = nullptr, *pathlen = nullptr;
-  int32_t *off = nullptr, *diag = nullptr, *hint = nullptr, *norm_flag = nullptr;
-  int32_t *err = nullptr;  // [4] sticky error counters of the generic path (lzm_check_errors)
-  uint32_t *stream = nullptr;
-  int stream_cap = 0;
+  int32_t *norm_flag = nullptr;
+  int32_t *err = nullptr;  // [kErrWords] sticky error counters (lzm_check_errors)
   float2 *lut = nullptr;
   int lut_n = 0;
   int lut_base = -1;
   float lut_init = -1.0f;
-  uint32_t *jmat = nullptr;  // [2][kMaxWG][31]
   // fused whole-search state (lzm_search_mlp)
   uint32_t *coef = nullptr;  // [coef_positions][31] glibc draw coefficients
   int coef_positions = 0;
@@ -888,35 +627,6 @@ struct lzm_handle {
   int cons_cap = 0, cons_m = -1, cons_S = -1;
 };
 
-// Jump matrices of glibc random_r: row m of J_first expresses z[344+m] (the m-th rand()
-// output before >>1) in the 31-word seeded state; row m of J_next expresses z[n+m] in the
-// window z[n-31..n-1]. Coefficients over Z/2^32 (wrapping uint32 arithmetic).
-static void build_jump_matrices(std::vector<uint32_t> &jf, std::vector<uint32_t> &jn) {
-  const int W = kMaxWG;
-  jf.assign((size_t)W * 31, 0u);
-  jn.assign((size_t)W * 31, 0u);
-  {
-    const int N = 344 + W;
-    std::vector<uint32_t> z((size_t)N * 31, 0u);
-    for (int j = 0; j < 31; ++j) z[(size_t)j * 31 + j] = 1u;
-    for (int j = 31; j < 34; ++j)
-      for (int c = 0; c < 31; ++c) z[(size_t)j * 31 + c] = z[(size_t)(j - 31) * 31 + c];
-    for (int n = 34; n < N; ++n)
-      for (int c = 0; c < 31; ++c) z[(size_t)n * 31 + c] = z[(size_t)(n - 31) * 31 + c] + z[(size_t)(n - 3) * 31 + c];
-    for (int m = 0; m < W; ++m)
-      for (int c = 0; c < 31; ++c) jf[(size_t)m * 31 + c] = z[(size_t)(344 + m) * 31 + c];
-  }
-  {
-    const int N = 31 + W;
-    std::vector<uint32_t> z((size_t)N * 31, 0u);
-    for (int j = 0; j < 31; ++j) z[(size_t)j * 31 + j] = 1u;
-    for (int n = 31; n < N; ++n)
-      for (int c = 0; c < 31; ++c) z[(size_t)n * 31 + c] = z[(size_t)(n - 31) * 31 + c] + z[(size_t)(n - 3) * 31 + c];
-    for (int m = 0; m < W; ++m)
-      for (int c = 0; c < 31; ++c) jn[(size_t)m * 31 + c] = z[(size_t)(31 + m) * 31 + c];
-  }
-}
-
 static TreeView view(lzm_handle *h) {
   TreeView t;
   t.stat = h->stat;
@@ -940,9 +650,9 @@ static void dfree(void *p) {
 }
 
 static void free_tree(lzm_handle *h) {
-  dfree(h->stat); dfree(h->meta); dfree(h->path); dfree(h->path_act); dfree(h->stream); dfree(h->lut);
+  dfree(h->stat); dfree(h->meta); dfree(h->path); dfree(h->path_act); dfree(h->lut);
   dfree(h->step_seeds); dfree(h->raw);
-  h->stat = nullptr; h->meta = nullptr; h->path = nullptr; h->path_act = nullptr; h->stream = nullptr; h->lut = nullptr;
+  h->stat = nullptr; h->meta = nullptr; h->path = nullptr; h->path_act = nullptr; h->lut = nullptr;
   h->step_seeds = nullptr; h->raw = nullptr;
   h->step_seeds_n = 0;
 }
@@ -967,6 +677,37 @@ static int fill_lut(lzm_handle *h, int base, float init) {
   return LZM_OK;
 }
 
+// The parity-mode draw table [positions][31]: row p holds the coefficients of z[344 + p] (the p-th rand()
+// output before >> 1) over the 31 seeded words (random_r is linear over Z/2^32: z[n] = z[n-31] + z[n-3]).
+static std::vector<uint32_t> glibc_coef_table(int positions) {
+  std::vector<uint32_t> tab((size_t)positions * 31);
+  std::vector<uint32_t> ring((size_t)34 * 31, 0u);  // z[n] for n mod 34
+  auto row = [&](long n) { return &ring[(size_t)(n % 34) * 31]; };
+  for (int j = 0; j < 31; ++j) {
+    uint32_t *r = row(j);
+    for (int c = 0; c < 31; ++c) r[c] = (c == j);
+  }
+  for (int j = 31; j < 34; ++j) memcpy(row(j), row(j - 31), 31 * sizeof(uint32_t));
+  const long last = 344L + positions;
+  for (long n = 34; n < last; ++n) {
+    uint32_t tmp[31];
+    const uint32_t *a = row(n - 31), *b = row(n - 3);
+    for (int c = 0; c < 31; ++c) tmp[c] = a[c] + b[c];
+    memcpy(row(n), tmp, sizeof(tmp));
+    if (n >= 344) memcpy(&tab[(size_t)(n - 344) * 31], tmp, sizeof(tmp));
+  }
+  return tab;
+}
+
+// 16807^i mod (2^31 - 1), i < 31: srandom_r's state from a seed in one multiply each (seed_state_parallel)
+static void glibc_pow16807(uint32_t pw[31]) {
+  unsigned long long x = 1;
+  for (int i = 0; i < 31; ++i) {
+    pw[i] = (uint32_t)x;
+    x = (x * 16807ull) % 2147483647ull;
+  }
+}
+
 namespace {
 int ensure_coef(lzm_handle *h, int positions);
 int ensure_flags(lzm_handle *h, int sims, int G);
@@ -987,8 +728,6 @@ static int alloc_tree(lzm_handle *h, int sims) {
   }
   LZM_HIP(hipMalloc(&h->path, sizeof(int32_t) * (size_t)h->depth_cap * h->B));
   LZM_HIP(hipMalloc(&h->path_act, sizeof(int32_t) * (size_t)h->depth_cap * h->B));
-  h->stream_cap = h->B * (sims + 2) + 2 * kMaxWG;
-  LZM_HIP(hipMalloc(&h->stream, sizeof(uint32_t) * (size_t)h->stream_cap));
   h->lut_n = sims + 8;
   LZM_HIP(hipMalloc(&h->lut, sizeof(float2) * h->lut_n));
   h->lut_base = -1;
@@ -1006,6 +745,111 @@ static int alloc_tree(lzm_handle *h, int sims) {
     if (rc != LZM_OK) return rc;
   }
   return fill_lut(h, 19652, 1.25f);
+}
+
+// ---- the generic search path's host side: one refusal / one builder per argument struct, shared by the
+// plain (lzm_traverse, lzm_backprop, lzm_decode_backprop*) and the lzm_gumbel_* entry points. `name` is the
+// public entry point, which every message starts with.
+static int refuse(int code, const char *name, const char *what) {
+  snprintf(g_err, sizeof(g_err), "%s: %s", name, what);
+  return code;
+}
+
+// the handle is there and of the kind `name` serves (gumbel: an lzm_gumbel_* entry point)
+static int check_kind(const char *name, const lzm_handle *h, bool gumbel) {
+  if (!h) return refuse(LZM_ERR_ARG, name, gumbel ? "null handle" : "null argument");
+  if (gumbel == ((h->flags & LZM_TREE_GUMBEL) != 0)) return LZM_OK;
+  return refuse(LZM_ERR_STATE, name, gumbel ? "not a Gumbel MuZero handle (create it with LZM_TREE_GUMBEL)"
+                                            : "a Gumbel MuZero handle takes the lzm_gumbel_* entry points");
+}
+
+static int check_cur(lzm_handle *h, int cur) {
+  if (cur < 1 || 1 + h->A * (cur + 1) > h->cap) {
+    snprintf(g_err, sizeof(g_err), "latent index %d outside reserved capacity (%d simulations)", cur, h->sims_cap);
+    return LZM_ERR_CAPACITY;
+  }
+  return LZM_OK;
+}
+
+static WalkOut walk_out(int32_t *out_x, int32_t *out_y, int32_t *out_a, int64_t *out_a64, int32_t *out_vtp,
+                        int32_t *out_len) {
+  return WalkOut{out_x, out_y, out_a, out_vtp, out_len, (long long *)out_a64};
+}
+static bool walk_out_complete(const WalkOut &o) { return o.out_x && o.out_y && o.out_a && o.out_vtp && o.out_len; }
+
+// The look-back traverse's arguments (lzm_traverse_lb.h) with the handle's draw table and look-back words.
+static int traverse_lb_args(lzm_handle *h, float discount, const float *minmax, const uint32_t *seed,
+                            const int32_t *vtp_in, const WalkOut &out, TraverseLbArgs *q) {
+  int rc = ensure_coef(h, h->B * h->depth_cap + 64);
+  if (rc != LZM_OK) return rc;
+  rc = ensure_flags(h, 1, 1);
+  if (rc != LZM_OK) return rc;
+  q->t = view(h);
+  q->minmax = (const float4 *)minmax;
+  q->seed = seed;
+  q->vtp_in = vtp_in;
+  q->out = out;
+  q->disc = discount;
+  q->coef = h->coef; q->coef_positions = h->coef_positions; q->pow16807 = h->pow16807;
+  q->flags = h->lb_flags; q->epoch = h->epoch; q->err = h->err;
+  q->reuse_action = h->reuse_action; q->reuse_value = h->reuse_value;
+  q->stamps = nullptr;
+  return LZM_OK;
+}
+
+// One backup from raw lists: checks the lists and the latent index, fills BackpropArgs.
+static int backprop_args(const char *name, lzm_handle *h, int cur, float discount, float *minmax, const float *rewards,
+                         const float *values, const float *logits, const int32_t *to_play, const int32_t *is_reset,
+                         const int32_t *reuse_action, const float *reuse_value, BackpropArgs *p) {
+  if (!minmax || !rewards || !values || !logits || !to_play) return refuse(LZM_ERR_ARG, name, "null argument");
+  const int rc = check_cur(h, cur);
+  if (rc != LZM_OK) return rc;
+  p->t = view(h);
+  p->minmax = (float4 *)minmax;
+  p->rewards = rewards; p->values = values; p->logits = logits; p->to_play = to_play; p->is_reset = is_reset;
+  p->cur = cur;
+  p->disc = discount;
+  p->reuse_action = reuse_action; p->reuse_value = reuse_value;
+  return LZM_OK;
+}
+
+static int launch_norm_check(int32_t *flag, const float *a, const float *b, int rows, int V, int Vb, hipStream_t s) {
+  hipLaunchKernelGGL(normalized_check_kernel, dim3(norm_parts(rows)), dim3(256), 0, s, a, b, rows, V, Vb, flag);
+  LZM_CHECK_LAUNCH();
+  return LZM_OK;
+}
+
+// One support decode: checks the rows, the support lengths (the value rows' own length when
+// lzm_set_value_support gave one) and the latent index, fills DecodeArgs and launches the ensure_softmax
+// check unless lzm_conv_heads wrote the verdict words already (lzm_set_norm_words). *nf: the words the decode
+// kernel reads. Nothing is launched when a check refuses.
+static int decode_args(const char *name, lzm_handle *h, int cur, float discount, float *minmax,
+                       const float *reward_logits, const float *value_logits, int support_len, int categorical,
+                       const float *policy_logits, const int32_t *to_play, int horizon, int32_t *out_is_reset,
+                       const float *next_latent, float *pool_slot, int64_t row_elems, float *out_decoded,
+                       const int32_t *reuse_action, const float *reuse_value, hipStream_t s, DecodeArgs *p,
+                       const int32_t **nf) {
+  if (!minmax || !reward_logits || !value_logits || !policy_logits || !to_play || support_len <= 0)
+    return refuse(LZM_ERR_ARG, name, "null argument");
+  const int value_len = h->value_support > 0 ? h->value_support : support_len;
+  if (categorical && (support_len % 2 == 0 || value_len % 2 == 0))
+    return refuse(LZM_ERR_ARG, name, "categorical support length must be odd (2*support_scale+1)");
+  int rc = check_cur(h, cur);
+  if (rc != LZM_OK) return rc;
+  if (categorical && !h->ext_norm) {
+    rc = launch_norm_check(h->norm_flag, reward_logits, value_logits, h->B, support_len, value_len, s);
+    if (rc != LZM_OK) return rc;
+  }
+  p->t = view(h);
+  p->minmax = (float4 *)minmax;
+  p->reward_logits = reward_logits; p->value_logits = value_logits; p->policy_logits = policy_logits;
+  p->to_play = to_play; p->out_is_reset = out_is_reset; p->next_latent = next_latent; p->pool_slot = pool_slot;
+  p->row_elems = row_elems; p->V = support_len; p->Vv = value_len; p->categorical = categorical; p->cur = cur;
+  p->horizon = horizon;
+  p->disc = discount; p->out_decoded = out_decoded;
+  p->reuse_action = reuse_action; p->reuse_value = reuse_value;
+  *nf = categorical ? (h->ext_norm ? h->ext_norm : h->norm_flag) : nullptr;
+  return LZM_OK;
 }
 
 extern "C" {
@@ -1030,22 +874,10 @@ int lzm_create(int B, int A, int max_sims, int flags, lzm_handle **out) {
   TRY(hipMalloc(&h->legal, sizeof(int32_t) * (size_t)B * A) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
   TRY(hipMalloc(&h->nlegal, sizeof(int32_t) * B) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
   TRY(hipMalloc(&h->pathlen, sizeof(int32_t) * B) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
-  TRY(hipMalloc(&h->off, sizeof(int32_t) * B) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
-  TRY(hipMalloc(&h->diag, sizeof(int32_t) * 4) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
   TRY(hipMalloc(&h->err, sizeof(int32_t) * kErrWords) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
   TRY(hipMemset(h->err, 0, sizeof(int32_t) * kErrWords) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
-  TRY(hipMalloc(&h->hint, sizeof(int32_t) * 2) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
   TRY(hipMalloc(&h->norm_flag, sizeof(int32_t) * 2 * norm_parts(B)) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
-  TRY(hipMemset(h->diag, 0, sizeof(int32_t) * 4) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
-  TRY(hipMemset(h->hint, 0, sizeof(int32_t) * 2) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
   TRY(hipMemset(h->pathlen, 0, sizeof(int32_t) * B) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
-  {
-    std::vector<uint32_t> jf, jn;
-    build_jump_matrices(jf, jn);
-    TRY(hipMalloc(&h->jmat, sizeof(uint32_t) * 2 * kMaxWG * 31) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
-    TRY(hipMemcpy(h->jmat, jf.data(), sizeof(uint32_t) * kMaxWG * 31, hipMemcpyHostToDevice) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
-    TRY(hipMemcpy(h->jmat + kMaxWG * 31, jn.data(), sizeof(uint32_t) * kMaxWG * 31, hipMemcpyHostToDevice) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
-  }
   if (flags & LZM_TREE_GUMBEL) {
     float tab[kMaxActions];
     lzm_gumbel_table(10.0f, kMaxActions, tab);  // CNode::CNode: gumbel_scale 10, gumbel_rng 0 (cnode.cpp:87-89)
@@ -1063,8 +895,7 @@ int lzm_create(int B, int A, int max_sims, int flags, lzm_handle **out) {
 int lzm_destroy(lzm_handle *h) {
   if (!h) return LZM_OK;
   free_tree(h);
-  dfree(h->legal); dfree(h->nlegal); dfree(h->pathlen); dfree(h->off); dfree(h->diag); dfree(h->err);
-  dfree(h->hint); dfree(h->norm_flag); dfree(h->jmat);
+  dfree(h->legal); dfree(h->nlegal); dfree(h->pathlen); dfree(h->err); dfree(h->norm_flag);
   dfree(h->coef); dfree(h->pow16807); dfree(h->lb_flags); dfree(h->epoch); dfree(h->search_diag); dfree(h->phase);
   dfree(h->ez_ws); dfree(h->gumbel); dfree(h->considered);
   delete h;
@@ -1078,7 +909,7 @@ int lzm_reserve(lzm_handle *h, int max_sims) {
   if (max_sims <= h->sims_cap) return LZM_OK;
   LZM_HIP(hipDeviceSynchronize());
   lzm_handle old = *h;
-  h->stat = nullptr; h->meta = nullptr; h->path = nullptr; h->path_act = nullptr; h->stream = nullptr; h->lut = nullptr;
+  h->stat = nullptr; h->meta = nullptr; h->path = nullptr; h->path_act = nullptr; h->lut = nullptr;
   h->step_seeds = nullptr; h->raw = nullptr;
   int rc = alloc_tree(h, max_sims);
   if (rc == LZM_OK) {
@@ -1150,65 +981,35 @@ int lzm_roots_prepare(lzm_handle *h, const int32_t *legal, const int32_t *count,
 int lzm_traverse(lzm_handle *h, int pb_c_base, float pb_c_init, float discount, float *minmax, const uint32_t *seed,
                  const int32_t *vtp_in, int32_t *out_x, int32_t *out_y, int32_t *out_a, int64_t *out_a64,
                  int32_t *out_vtp, int32_t *out_len, void *stream) {
-  if (!h || !minmax || !seed || !vtp_in || !out_x || !out_y || !out_a || !out_vtp || !out_len) {
-    set_err("lzm_traverse: null argument");
-    return LZM_ERR_ARG;
-  }
-  if (h->flags & LZM_TREE_GUMBEL) {
-    set_err("lzm_traverse: a Gumbel MuZero handle takes the lzm_gumbel_* entry points");
-    return LZM_ERR_STATE;
-  }
-  if (pb_c_base <= 0) {
-    set_err("lzm_traverse: pb_c_base must be positive");
-    return LZM_ERR_ARG;
-  }
-  int rc = fill_lut(h, pb_c_base, pb_c_init);
+  const char *name = "lzm_traverse";
+  int rc = check_kind(name, h, false);
   if (rc != LZM_OK) return rc;
-  TraverseArgs p;
-  p.t = view(h);
-  p.minmax = (const float4 *)minmax;
-  p.seed = seed;
-  p.vtp_in = vtp_in;
-  p.out_x = out_x; p.out_y = out_y; p.out_a = out_a; p.out_vtp = out_vtp; p.out_len = out_len;
-  p.out_a64 = (long long *)out_a64;
-  p.stream = h->stream;
-  p.stream_cap = h->stream_cap;
-  p.jfirst = h->jmat;
-  p.jnext = h->jmat + kMaxWG * 31;
-  p.off = h->off;
-  p.diag = h->diag;
-  p.err = h->err;
-  p.hint = h->hint;
-  p.disc = discount;
+  const WalkOut out = walk_out(out_x, out_y, out_a, out_a64, out_vtp, out_len);
+  if (!minmax || !seed || !vtp_in || !walk_out_complete(out)) return refuse(LZM_ERR_ARG, name, "null argument");
+  if (pb_c_base <= 0) return refuse(LZM_ERR_ARG, name, "pb_c_base must be positive");
+  if (h->reuse_action && (h->flags & LZM_RNG_FAST))
+    return refuse(LZM_ERR_ARG, name, "search-with-reuse needs parity mode with the look-back traverse");
+  rc = fill_lut(h, pb_c_base, pb_c_init);
+  if (rc != LZM_OK) return rc;
   const bool ez = h->flags & LZM_TREE_EZ;
   hipStream_t s = (hipStream_t)stream;
-  const bool serial = getenv("LZM_TRAVERSE") && strcmp(getenv("LZM_TRAVERSE"), "serial") == 0;
-  if (h->reuse_action && ((h->flags & LZM_RNG_FAST) || serial)) {
-    set_err("lzm_traverse: search-with-reuse needs parity mode with the look-back traverse");
-    return LZM_ERR_ARG;
-  }
   if (h->flags & LZM_RNG_FAST) {
+    TraverseArgs p;
+    p.t = view(h);
+    p.minmax = (const float4 *)minmax;
+    p.seed = seed;
+    p.vtp_in = vtp_in;
+    p.out = out;
+    p.disc = discount;
     dim3 g((h->B + 255) / 256), b(256);
     if (ez) hipLaunchKernelGGL(traverse_fast_kernel<true>, g, b, 0, s, p);
     else hipLaunchKernelGGL(traverse_fast_kernel<false>, g, b, 0, s, p);
-  } else if (!serial) {
-    // one wave per root, decoupled look-back of the draw offsets (lzm_traverse_lb.h)
-    rc = ensure_coef(h, h->B * h->depth_cap + 64);
-    if (rc != LZM_OK) return rc;
-    rc = ensure_flags(h, 1, 1);
-    if (rc != LZM_OK) return rc;
+  } else {
+    // one wave per root and workgroup, decoupled look-back of the draw offsets (lzm_traverse_lb.h)
     TraverseLbArgs q;
-    q.t = p.t; q.minmax = p.minmax; q.seed = seed; q.vtp_in = vtp_in;
-    q.out_x = out_x; q.out_y = out_y; q.out_a = out_a; q.out_vtp = out_vtp; q.out_len = out_len;
-    q.out_a64 = p.out_a64; q.disc = discount;
-    q.coef = h->coef; q.coef_positions = h->coef_positions; q.pow16807 = h->pow16807;
-    q.flags = h->lb_flags; q.epoch = h->epoch; q.diag = h->diag; q.err = h->err;
-    q.reuse_action = h->reuse_action; q.reuse_value = h->reuse_value;
-    q.stamps = nullptr;
-    // LZM_TLB_WAVES (experiments): roots (waves) per workgroup, 1 (default), 2 or 4
-    static const int waves = getenv("LZM_TLB_WAVES") ? atoi(getenv("LZM_TLB_WAVES")) : 1;
-    const int per = (waves == 2 || waves == 4) ? waves : 1;
-    dim3 g((h->B + per - 1) / per), b(64 * per);
+    rc = traverse_lb_args(h, discount, minmax, seed, vtp_in, out, &q);
+    if (rc != LZM_OK) return rc;
+    dim3 g(h->B), b(64);
     static const bool stamps = getenv("LZM_PHASE_TIMING") && atoi(getenv("LZM_PHASE_TIMING")) > 0;
     if (stamps) {  // diagnostic instantiation: per-phase cycles into phase[32..38] (lzm_debug_phase_cycles)
       if (!h->phase) {
@@ -1216,26 +1017,12 @@ int lzm_traverse(lzm_handle *h, int pb_c_base, float pb_c_init, float discount, 
         LZM_HIP(hipMemset(h->phase, 0, (64 + 1024) * sizeof(unsigned long long)));
       }
       q.stamps = h->phase;
-      dim3 g1(h->B), b1(64);
-      if (ez) hipLaunchKernelGGL((traverse_lookback_kernel<true, 1, true>), g1, b1, 0, s, q);
-      else hipLaunchKernelGGL((traverse_lookback_kernel<false, 1, true>), g1, b1, 0, s, q);
-    } else if (per == 1) {
-      if (ez) hipLaunchKernelGGL((traverse_lookback_kernel<true, 1>), g, b, 0, s, q);
-      else hipLaunchKernelGGL((traverse_lookback_kernel<false, 1>), g, b, 0, s, q);
-    } else if (per == 2) {
-      if (ez) hipLaunchKernelGGL((traverse_lookback_kernel<true, 2>), g, b, 0, s, q);
-      else hipLaunchKernelGGL((traverse_lookback_kernel<false, 2>), g, b, 0, s, q);
+      if (ez) hipLaunchKernelGGL((traverse_lookback_kernel<true, true>), g, b, 0, s, q);
+      else hipLaunchKernelGGL((traverse_lookback_kernel<false, true>), g, b, 0, s, q);
     } else {
       if (ez) hipLaunchKernelGGL(traverse_lookback_kernel<true>, g, b, 0, s, q);
       else hipLaunchKernelGGL(traverse_lookback_kernel<false>, g, b, 0, s, q);
     }
-  } else {
-    // LZM_TRAVERSE=serial: one workgroup, speculative fixed-point passes over the stream
-    int W = ((h->B + 63) / 64) * 64;
-    if (W > kMaxWG) W = kMaxWG;
-    if (W < 64) W = 64;
-    if (ez) hipLaunchKernelGGL(traverse_glibc_kernel<true>, dim3(1), dim3(W), 0, s, p);
-    else hipLaunchKernelGGL(traverse_glibc_kernel<false>, dim3(1), dim3(W), 0, s, p);
   }
   LZM_CHECK_LAUNCH();
   return LZM_OK;
@@ -1260,44 +1047,18 @@ int lzm_gather_latent(lzm_handle *h, const float *pool, int64_t row, const int32
   return LZM_OK;
 }
 
-static int check_cur(lzm_handle *h, int cur) {
-  if (cur < 1 || 1 + h->A * (cur + 1) > h->cap) {
-    snprintf(g_err, sizeof(g_err), "latent index %d outside reserved capacity (%d simulations)", cur, h->sims_cap);
-    return LZM_ERR_CAPACITY;
-  }
-  return LZM_OK;
-}
-
 int lzm_backprop(lzm_handle *h, int cur, float discount, float *minmax, const float *rewards, const float *values,
                  const float *logits, const int32_t *to_play, const int32_t *is_reset, void *stream) {
-  if (!h || !minmax || !rewards || !values || !logits || !to_play) {
-    set_err("lzm_backprop: null argument");
-    return LZM_ERR_ARG;
-  }
-  if (h->flags & LZM_TREE_GUMBEL) {
-    set_err("lzm_backprop: a Gumbel MuZero handle takes the lzm_gumbel_* entry points");
-    return LZM_ERR_STATE;
-  }
-  int rc = check_cur(h, cur);
+  const char *name = "lzm_backprop";
+  int rc = check_kind(name, h, false);
   if (rc != LZM_OK) return rc;
   BackpropArgs p;
-  p.t = view(h);
-  p.minmax = (float4 *)minmax;
-  p.rewards = rewards; p.values = values; p.logits = logits; p.to_play = to_play; p.is_reset = is_reset;
-  p.cur = cur;
-  p.disc = discount;
-  p.reuse_action = h->reuse_action; p.reuse_value = h->reuse_value;
+  rc = backprop_args(name, h, cur, discount, minmax, rewards, values, logits, to_play, is_reset, h->reuse_action,
+                     h->reuse_value, &p);
+  if (rc != LZM_OK) return rc;
   dim3 g((h->B + 255) / 256), b(256);
   if (h->flags & LZM_TREE_EZ) hipLaunchKernelGGL(backprop_kernel<true>, g, b, 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(backprop_kernel<false>, g, b, 0, (hipStream_t)stream, p);
-  LZM_CHECK_LAUNCH();
-  return LZM_OK;
-}
-
-static int launch_norm_check(lzm_handle *hflag_owner, int32_t *flag, const float *a, const float *b, int rows, int V,
-                             int Vb, hipStream_t s) {
-  (void)hflag_owner;
-  hipLaunchKernelGGL(normalized_check_kernel, dim3(norm_parts(rows)), dim3(256), 0, s, a, b, rows, V, Vb, flag);
   LZM_CHECK_LAUNCH();
   return LZM_OK;
 }
@@ -1306,36 +1067,17 @@ int lzm_decode_backprop(lzm_handle *h, int cur, float discount, float *minmax, c
                         const float *value_logits, int support_len, int categorical, const float *policy_logits,
                         const int32_t *to_play, int lstm_horizon, int32_t *out_is_reset, const float *next_latent,
                         float *pool_slot, int64_t row_elems, float *out_decoded, void *stream) {
-  if (!h || !minmax || !reward_logits || !value_logits || !policy_logits || !to_play || support_len <= 0) {
-    set_err("lzm_decode_backprop: null argument");
-    return LZM_ERR_ARG;
-  }
-  if (h->flags & LZM_TREE_GUMBEL) {
-    set_err("lzm_decode_backprop: a Gumbel MuZero handle takes the lzm_gumbel_* entry points");
-    return LZM_ERR_STATE;
-  }
-  const int value_len = h->value_support > 0 ? h->value_support : support_len;
-  if (categorical && (support_len % 2 == 0 || value_len % 2 == 0)) {
-    set_err("lzm_decode_backprop: categorical support length must be odd (2*support_scale+1)");
-    return LZM_ERR_ARG;
-  }
-  int rc = check_cur(h, cur);
+  const char *name = "lzm_decode_backprop";
+  int rc = check_kind(name, h, false);
   if (rc != LZM_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (categorical && !h->ext_norm) {
-    rc = launch_norm_check(h, h->norm_flag, reward_logits, value_logits, h->B, support_len, value_len, s);
-    if (rc != LZM_OK) return rc;
-  }
   DecodeArgs p;
-  p.t = view(h);
-  p.minmax = (float4 *)minmax;
-  p.reward_logits = reward_logits; p.value_logits = value_logits; p.policy_logits = policy_logits;
-  p.to_play = to_play; p.out_is_reset = out_is_reset; p.next_latent = next_latent; p.pool_slot = pool_slot;
-  p.row_elems = row_elems; p.V = support_len; p.Vv = value_len; p.categorical = categorical; p.cur = cur; p.horizon = lstm_horizon;
-  p.disc = discount; p.out_decoded = out_decoded;
-  p.reuse_action = h->reuse_action; p.reuse_value = h->reuse_value;
+  const int32_t *nf;
+  rc = decode_args(name, h, cur, discount, minmax, reward_logits, value_logits, support_len, categorical, policy_logits,
+                   to_play, lstm_horizon, out_is_reset, next_latent, pool_slot, row_elems, out_decoded, h->reuse_action,
+                   h->reuse_value, s, &p, &nf);
+  if (rc != LZM_OK) return rc;
   dim3 g((h->B * 64 + 255) / 256), b(256);
-  const int32_t *nf = categorical ? (h->ext_norm ? h->ext_norm : h->norm_flag) : nullptr;
   if (h->flags & LZM_TREE_EZ) hipLaunchKernelGGL(decode_backprop_kernel<true>, g, b, 0, s, p, nf);
   else hipLaunchKernelGGL(decode_backprop_kernel<false>, g, b, 0, s, p, nf);
   LZM_CHECK_LAUNCH();
@@ -1349,60 +1091,29 @@ int lzm_decode_backprop_traverse(lzm_handle *h, int cur, float discount, float *
                                  float *out_decoded, int pb_c_base, float pb_c_init, const uint32_t *seed,
                                  const int32_t *vtp_in, int32_t *out_x, int32_t *out_y, int32_t *out_a,
                                  int64_t *out_a64, int32_t *out_vtp, int32_t *out_len, void *stream) {
-  if (!h || !minmax || !reward_logits || !value_logits || !policy_logits || !to_play || support_len <= 0 || !seed ||
-      !vtp_in || !out_x || !out_y || !out_a || !out_vtp || !out_len) {
-    set_err("lzm_decode_backprop_traverse: null argument");
-    return LZM_ERR_ARG;
-  }
-  if (h->flags & LZM_TREE_GUMBEL) {
-    set_err("lzm_decode_backprop_traverse: a Gumbel MuZero handle takes the lzm_gumbel_* entry points");
-    return LZM_ERR_STATE;
-  }
-  const int value_len = h->value_support > 0 ? h->value_support : support_len;
-  if (categorical && (support_len % 2 == 0 || value_len % 2 == 0)) {
-    set_err("lzm_decode_backprop_traverse: categorical support length must be odd (2*support_scale+1)");
-    return LZM_ERR_ARG;
-  }
-  if (pb_c_base <= 0) {
-    set_err("lzm_decode_backprop_traverse: pb_c_base must be positive");
-    return LZM_ERR_ARG;
-  }
-  if (h->flags & LZM_RNG_FAST) {
-    set_err("lzm_decode_backprop_traverse: parity (glibc) mode only; use lzm_decode_backprop + lzm_traverse");
-    return LZM_ERR_ARG;
-  }
-  int rc = check_cur(h, cur);
+  const char *name = "lzm_decode_backprop_traverse";
+  int rc = check_kind(name, h, false);
   if (rc != LZM_OK) return rc;
+  const WalkOut out = walk_out(out_x, out_y, out_a, out_a64, out_vtp, out_len);
+  if (!seed || !vtp_in || !walk_out_complete(out)) return refuse(LZM_ERR_ARG, name, "null argument");
+  if (pb_c_base <= 0) return refuse(LZM_ERR_ARG, name, "pb_c_base must be positive");
+  if (h->flags & LZM_RNG_FAST)
+    return refuse(LZM_ERR_ARG, name, "parity (glibc) mode only; use lzm_decode_backprop + lzm_traverse");
+  // the host tables first (synchronous copies when they change), then the decode's checks and its launch
   rc = fill_lut(h, pb_c_base, pb_c_init);
   if (rc != LZM_OK) return rc;
-  rc = ensure_coef(h, h->B * h->depth_cap + 64);
-  if (rc != LZM_OK) return rc;
-  rc = ensure_flags(h, 1, 1);
+  TraverseLbArgs q;
+  rc = traverse_lb_args(h, discount, minmax, seed, vtp_in, out, &q);
   if (rc != LZM_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (categorical && !h->ext_norm) {
-    rc = launch_norm_check(h, h->norm_flag, reward_logits, value_logits, h->B, support_len, value_len, s);
-    if (rc != LZM_OK) return rc;
-  }
   DecodeArgs p;
-  p.t = view(h);
-  p.minmax = (float4 *)minmax;
-  p.reward_logits = reward_logits; p.value_logits = value_logits; p.policy_logits = policy_logits;
-  p.to_play = to_play; p.out_is_reset = out_is_reset; p.next_latent = next_latent; p.pool_slot = pool_slot;
-  p.row_elems = row_elems; p.V = support_len; p.Vv = value_len; p.categorical = categorical; p.cur = cur; p.horizon = lstm_horizon;
-  p.disc = discount; p.out_decoded = out_decoded;
-  p.reuse_action = h->reuse_action; p.reuse_value = h->reuse_value;
-  TraverseLbArgs q;
-  q.t = p.t; q.minmax = (const float4 *)minmax; q.seed = seed; q.vtp_in = vtp_in;
-  q.out_x = out_x; q.out_y = out_y; q.out_a = out_a; q.out_vtp = out_vtp; q.out_len = out_len;
-  q.out_a64 = (long long *)out_a64; q.disc = discount;
-  q.coef = h->coef; q.coef_positions = h->coef_positions; q.pow16807 = h->pow16807;
-  q.flags = h->lb_flags; q.epoch = h->epoch; q.diag = h->diag; q.err = h->err;
-  q.reuse_action = h->reuse_action; q.reuse_value = h->reuse_value;
-  q.stamps = nullptr;
+  const int32_t *nf;
+  rc = decode_args(name, h, cur, discount, minmax, reward_logits, value_logits, support_len, categorical, policy_logits,
+                   to_play, lstm_horizon, out_is_reset, next_latent, pool_slot, row_elems, out_decoded, h->reuse_action,
+                   h->reuse_value, s, &p, &nf);
+  if (rc != LZM_OK) return rc;
   const int per = kTlbThreads / 64;
   dim3 g((h->B + per - 1) / per), b(kTlbThreads);
-  const int32_t *nf = categorical ? (h->ext_norm ? h->ext_norm : h->norm_flag) : nullptr;
   if (h->flags & LZM_TREE_EZ) hipLaunchKernelGGL(decode_traverse_kernel<true>, g, b, 0, s, p, nf, q);
   else hipLaunchKernelGGL(decode_traverse_kernel<false>, g, b, 0, s, p, nf, q);
   LZM_CHECK_LAUNCH();
@@ -1411,7 +1122,8 @@ int lzm_decode_backprop_traverse(lzm_handle *h, int cur, float discount, float *
 
 static int32_t *g_scratch_flag = nullptr;
 static int g_scratch_parts = 0;
-static uint32_t *g_debug_jm = nullptr;  // lzm_debug_glibc_rand's jump matrices
+static uint32_t *g_debug_coef = nullptr;  // lzm_debug_glibc_rand: [positions][31] draw table, [31] powers, overflow word
+static int g_debug_positions = 0;
 static std::mutex g_scratch_mu;
 
 int lzm_inverse_scalar_transform(const float *logits, int rows, int V, int categorical, float *out, void *stream) {
@@ -1496,18 +1208,6 @@ int lzm_gumbel_considered_visits(int max_num_considered_actions, int num_simulat
 }
 }  // extern "C"
 
-static int gumbel_kind(lzm_handle *h, const char *name) {
-  if (!h) {
-    snprintf(g_err, sizeof(g_err), "%s: null handle", name);
-    return LZM_ERR_ARG;
-  }
-  if (!(h->flags & LZM_TREE_GUMBEL)) {
-    snprintf(g_err, sizeof(g_err), "%s: not a Gumbel MuZero handle (create it with LZM_TREE_GUMBEL)", name);
-    return LZM_ERR_STATE;
-  }
-  return LZM_OK;
-}
-
 static GumbelView gumbel_view(lzm_handle *h) {
   GumbelView g;
   g.raw = h->raw;
@@ -1540,50 +1240,31 @@ static int gumbel_set_considered(lzm_handle *h, int S, int m, const char *name) 
   return LZM_OK;
 }
 
-static GumbelTraverseArgs gumbel_traverse_args(lzm_handle *h, float discount, const int32_t *vtp_in, int32_t *out_x,
-                                               int32_t *out_y, int32_t *out_a, int64_t *out_a64, int32_t *out_vtp,
-                                               int32_t *out_len) {
+static GumbelTraverseArgs gumbel_traverse_args(lzm_handle *h, float discount, const int32_t *vtp_in,
+                                               const WalkOut &out) {
   GumbelTraverseArgs q;
   q.t = view(h);
   q.g = gumbel_view(h);
   q.vtp_in = vtp_in;
-  q.out_x = out_x; q.out_y = out_y; q.out_a = out_a; q.out_vtp = out_vtp; q.out_len = out_len;
-  q.out_a64 = (long long *)out_a64;
+  q.out = out;
   q.disc = discount;
   return q;
 }
 
 static dim3 gumbel_grid(const lzm_handle *h) { return dim3((h->B + 3) / 4); }
 
+// gumbel_decode_kernel for one simulation; with_traverse: q carries the next walk's request lists
 static int gumbel_decode_launch(const char *name, bool with_traverse, lzm_handle *h, int cur, float discount,
                                 float *minmax, const float *reward_logits, const float *value_logits, int support_len,
                                 int categorical, const float *policy_logits, const int32_t *to_play,
                                 const float *next_latent, float *pool_slot, int64_t row_elems, float *out_decoded,
                                 const GumbelTraverseArgs &q, hipStream_t s) {
-  if (!minmax || !reward_logits || !value_logits || !policy_logits || !to_play || support_len <= 0) {
-    snprintf(g_err, sizeof(g_err), "%s: null argument", name);
-    return LZM_ERR_ARG;
-  }
-  const int value_len = h->value_support > 0 ? h->value_support : support_len;
-  if (categorical && (support_len % 2 == 0 || value_len % 2 == 0)) {
-    snprintf(g_err, sizeof(g_err), "%s: categorical support length must be odd (2*support_scale+1)", name);
-    return LZM_ERR_ARG;
-  }
-  int rc = check_cur(h, cur);
-  if (rc != LZM_OK) return rc;
-  if (categorical && !h->ext_norm) {
-    rc = launch_norm_check(h, h->norm_flag, reward_logits, value_logits, h->B, support_len, value_len, s);
-    if (rc != LZM_OK) return rc;
-  }
   DecodeArgs p;
-  p.t = view(h);
-  p.minmax = (float4 *)minmax;
-  p.reward_logits = reward_logits; p.value_logits = value_logits; p.policy_logits = policy_logits;
-  p.to_play = to_play; p.out_is_reset = nullptr; p.next_latent = next_latent; p.pool_slot = pool_slot;
-  p.row_elems = row_elems; p.V = support_len; p.Vv = value_len; p.categorical = categorical; p.cur = cur; p.horizon = 0;
-  p.disc = discount; p.out_decoded = out_decoded;
-  p.reuse_action = nullptr; p.reuse_value = nullptr;
-  const int32_t *nf = categorical ? (h->ext_norm ? h->ext_norm : h->norm_flag) : nullptr;
+  const int32_t *nf;
+  const int rc = decode_args(name, h, cur, discount, minmax, reward_logits, value_logits, support_len, categorical,
+                             policy_logits, to_play, 0, nullptr, next_latent, pool_slot, row_elems, out_decoded, nullptr,
+                             nullptr, s, &p, &nf);
+  if (rc != LZM_OK) return rc;
   if (with_traverse) hipLaunchKernelGGL(gumbel_decode_kernel<true>, gumbel_grid(h), dim3(256), 0, s, p, nf, q);
   else hipLaunchKernelGGL(gumbel_decode_kernel<false>, gumbel_grid(h), dim3(256), 0, s, p, nf, q);
   LZM_CHECK_LAUNCH();
@@ -1593,13 +1274,13 @@ static int gumbel_decode_launch(const char *name, bool with_traverse, lzm_handle
 extern "C" {
 
 int lzm_gumbel_set_considered(lzm_handle *h, int num_simulations, int max_num_considered_actions) {
-  int rc = gumbel_kind(h, "lzm_gumbel_set_considered");
+  int rc = check_kind("lzm_gumbel_set_considered", h, true);
   if (rc != LZM_OK) return rc;
   return gumbel_set_considered(h, num_simulations, max_num_considered_actions, "lzm_gumbel_set_considered");
 }
 
 int lzm_gumbel_set_root_values(lzm_handle *h, const float *values, void *stream) {
-  int rc = gumbel_kind(h, "lzm_gumbel_set_root_values");
+  int rc = check_kind("lzm_gumbel_set_root_values", h, true);
   if (rc != LZM_OK) return rc;
   if (!values) return LZM_ERR_ARG;
   // node 0's row of raw[cap][B]
@@ -1610,15 +1291,14 @@ int lzm_gumbel_set_root_values(lzm_handle *h, const float *values, void *stream)
 int lzm_gumbel_traverse(lzm_handle *h, int num_simulations, int max_num_considered_actions, float discount,
                         const int32_t *vtp_in, int32_t *out_x, int32_t *out_y, int32_t *out_a, int64_t *out_a64,
                         int32_t *out_vtp, int32_t *out_len, void *stream) {
-  int rc = gumbel_kind(h, "lzm_gumbel_traverse");
+  const char *name = "lzm_gumbel_traverse";
+  int rc = check_kind(name, h, true);
   if (rc != LZM_OK) return rc;
-  if (!vtp_in || !out_x || !out_y || !out_a || !out_vtp || !out_len) {
-    set_err("lzm_gumbel_traverse: null argument");
-    return LZM_ERR_ARG;
-  }
-  rc = gumbel_set_considered(h, num_simulations, max_num_considered_actions, "lzm_gumbel_traverse");
+  const WalkOut out = walk_out(out_x, out_y, out_a, out_a64, out_vtp, out_len);
+  if (!vtp_in || !walk_out_complete(out)) return refuse(LZM_ERR_ARG, name, "null argument");
+  rc = gumbel_set_considered(h, num_simulations, max_num_considered_actions, name);
   if (rc != LZM_OK) return rc;
-  const GumbelTraverseArgs q = gumbel_traverse_args(h, discount, vtp_in, out_x, out_y, out_a, out_a64, out_vtp, out_len);
+  const GumbelTraverseArgs q = gumbel_traverse_args(h, discount, vtp_in, out);
   hipLaunchKernelGGL(gumbel_traverse_kernel, gumbel_grid(h), dim3(256), 0, (hipStream_t)stream, q);
   LZM_CHECK_LAUNCH();
   return LZM_OK;
@@ -1626,21 +1306,12 @@ int lzm_gumbel_traverse(lzm_handle *h, int num_simulations, int max_num_consider
 
 int lzm_gumbel_backprop(lzm_handle *h, int cur, float discount, float *minmax, const float *rewards, const float *values,
                         const float *logits, const int32_t *to_play, void *stream) {
-  int rc = gumbel_kind(h, "lzm_gumbel_backprop");
-  if (rc != LZM_OK) return rc;
-  if (!minmax || !rewards || !values || !logits || !to_play) {
-    set_err("lzm_gumbel_backprop: null argument");
-    return LZM_ERR_ARG;
-  }
-  rc = check_cur(h, cur);
+  const char *name = "lzm_gumbel_backprop";
+  int rc = check_kind(name, h, true);
   if (rc != LZM_OK) return rc;
   BackpropArgs p;
-  p.t = view(h);
-  p.minmax = (float4 *)minmax;
-  p.rewards = rewards; p.values = values; p.logits = logits; p.to_play = to_play; p.is_reset = nullptr;
-  p.cur = cur;
-  p.disc = discount;
-  p.reuse_action = nullptr; p.reuse_value = nullptr;
+  rc = backprop_args(name, h, cur, discount, minmax, rewards, values, logits, to_play, nullptr, nullptr, nullptr, &p);
+  if (rc != LZM_OK) return rc;
   hipLaunchKernelGGL(gumbel_backprop_kernel, gumbel_grid(h), dim3(256), 0, (hipStream_t)stream, p, gumbel_view(h));
   LZM_CHECK_LAUNCH();
   return LZM_OK;
@@ -1650,12 +1321,13 @@ int lzm_gumbel_decode_backprop(lzm_handle *h, int cur, float discount, float *mi
                                const float *value_logits, int support_len, int categorical, const float *policy_logits,
                                const int32_t *to_play, const float *next_latent, float *pool_slot, int64_t row_elems,
                                float *out_decoded, void *stream) {
-  int rc = gumbel_kind(h, "lzm_gumbel_decode_backprop");
+  const char *name = "lzm_gumbel_decode_backprop";
+  int rc = check_kind(name, h, true);
   if (rc != LZM_OK) return rc;
-  GumbelTraverseArgs q = gumbel_traverse_args(h, discount, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-  return gumbel_decode_launch("lzm_gumbel_decode_backprop", false, h, cur, discount, minmax, reward_logits, value_logits,
-                              support_len, categorical, policy_logits, to_play, next_latent, pool_slot, row_elems,
-                              out_decoded, q, (hipStream_t)stream);
+  const GumbelTraverseArgs q = gumbel_traverse_args(h, discount, nullptr, WalkOut{});
+  return gumbel_decode_launch(name, false, h, cur, discount, minmax, reward_logits, value_logits, support_len,
+                              categorical, policy_logits, to_play, next_latent, pool_slot, row_elems, out_decoded, q,
+                              (hipStream_t)stream);
 }
 
 int lzm_gumbel_decode_backprop_traverse(lzm_handle *h, int cur, float discount, float *minmax,
@@ -1665,22 +1337,21 @@ int lzm_gumbel_decode_backprop_traverse(lzm_handle *h, int cur, float discount, 
                                         float *out_decoded, int num_simulations, int max_num_considered_actions,
                                         const int32_t *vtp_in, int32_t *out_x, int32_t *out_y, int32_t *out_a,
                                         int64_t *out_a64, int32_t *out_vtp, int32_t *out_len, void *stream) {
-  int rc = gumbel_kind(h, "lzm_gumbel_decode_backprop_traverse");
+  const char *name = "lzm_gumbel_decode_backprop_traverse";
+  int rc = check_kind(name, h, true);
   if (rc != LZM_OK) return rc;
-  if (!vtp_in || !out_x || !out_y || !out_a || !out_vtp || !out_len) {
-    set_err("lzm_gumbel_decode_backprop_traverse: null argument");
-    return LZM_ERR_ARG;
-  }
-  rc = gumbel_set_considered(h, num_simulations, max_num_considered_actions, "lzm_gumbel_decode_backprop_traverse");
+  const WalkOut out = walk_out(out_x, out_y, out_a, out_a64, out_vtp, out_len);
+  if (!vtp_in || !walk_out_complete(out)) return refuse(LZM_ERR_ARG, name, "null argument");
+  rc = gumbel_set_considered(h, num_simulations, max_num_considered_actions, name);
   if (rc != LZM_OK) return rc;
-  const GumbelTraverseArgs q = gumbel_traverse_args(h, discount, vtp_in, out_x, out_y, out_a, out_a64, out_vtp, out_len);
-  return gumbel_decode_launch("lzm_gumbel_decode_backprop_traverse", true, h, cur, discount, minmax, reward_logits,
-                              value_logits, support_len, categorical, policy_logits, to_play, next_latent, pool_slot,
-                              row_elems, out_decoded, q, (hipStream_t)stream);
+  const GumbelTraverseArgs q = gumbel_traverse_args(h, discount, vtp_in, out);
+  return gumbel_decode_launch(name, true, h, cur, discount, minmax, reward_logits, value_logits, support_len,
+                              categorical, policy_logits, to_play, next_latent, pool_slot, row_elems, out_decoded, q,
+                              (hipStream_t)stream);
 }
 
 static int gumbel_output(const char *name, lzm_handle *h, float discount, int policy, float *out, void *stream) {
-  int rc = gumbel_kind(h, name);
+  int rc = check_kind(name, h, true);
   if (rc != LZM_OK) return rc;
   if (!out) return LZM_ERR_ARG;
   hipLaunchKernelGGL(gumbel_output_kernel, gumbel_grid(h), dim3(256), 0, (hipStream_t)stream, view(h), gumbel_view(h),
@@ -1702,12 +1373,6 @@ int lzm_debug_logf(const float *x, float *out, int64_t n, void *stream) {
   hipLaunchKernelGGL(debug_logf_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, out,
                      (long long)n);
   LZM_CHECK_LAUNCH();
-  return LZM_OK;
-}
-
-int lzm_last_traverse_passes(lzm_handle *h, int32_t *out, void *stream) {
-  if (!h || !out) return LZM_ERR_ARG;
-  LZM_HIP(hipMemcpyAsync(out, h->diag, sizeof(int32_t) * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return LZM_OK;
 }
 
@@ -1754,8 +1419,9 @@ int lzm_shutdown(void) {
   if (g_scratch_flag) LZM_HIP(hipFree(g_scratch_flag));
   g_scratch_flag = nullptr;
   g_scratch_parts = 0;
-  if (g_debug_jm) LZM_HIP(hipFree(g_debug_jm));
-  g_debug_jm = nullptr;
+  if (g_debug_coef) LZM_HIP(hipFree(g_debug_coef));
+  g_debug_coef = nullptr;
+  g_debug_positions = 0;
   return LZM_OK;
 }
 
@@ -1773,20 +1439,29 @@ int lzm_debug_xor(const float *in, float *out, void *stream) {
   return LZM_OK;
 }
 
-int lzm_debug_glibc_rand(uint32_t seed, int n, int32_t *out, void *stream) {
-  if (!out || n <= 0) return LZM_ERR_ARG;
-  uint32_t *&jm = g_debug_jm;
+int lzm_debug_glibc_rand(uint32_t seed, int n, int form, int32_t *out, void *stream) {
+  if (!out || n <= 0 || form < 0 || form > 2) return LZM_ERR_ARG;
+  uint32_t *tab;
+  size_t np;  // words of the table proper
   {
     std::lock_guard<std::mutex> lk(g_scratch_mu);
-    if (!jm) {
-      std::vector<uint32_t> jf, jn;
-      build_jump_matrices(jf, jn);
-      LZM_HIP(hipMalloc(&jm, sizeof(uint32_t) * 2 * kMaxWG * 31));
-      LZM_HIP(hipMemcpy(jm, jf.data(), sizeof(uint32_t) * kMaxWG * 31, hipMemcpyHostToDevice));
-      LZM_HIP(hipMemcpy(jm + kMaxWG * 31, jn.data(), sizeof(uint32_t) * kMaxWG * 31, hipMemcpyHostToDevice));
+    if (g_debug_positions < n) {
+      // ensure_coef's table and powers, for exactly n positions (synchronous; grows outside stream capture)
+      std::vector<uint32_t> host = glibc_coef_table(n);
+      host.resize((size_t)n * 31 + 32, 0u);  // + [31] powers, + the overflow word (stays 0: every p < n)
+      glibc_pow16807(&host[(size_t)n * 31]);
+      if (g_debug_coef) LZM_HIP(hipFree(g_debug_coef));
+      g_debug_coef = nullptr;
+      g_debug_positions = 0;
+      LZM_HIP(hipMalloc(&g_debug_coef, host.size() * sizeof(uint32_t)));
+      LZM_HIP(hipMemcpy(g_debug_coef, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+      g_debug_positions = n;
     }
+    tab = g_debug_coef;
+    np = (size_t)g_debug_positions * 31;
   }
-  hipLaunchKernelGGL(debug_glibc_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, seed, n, out, jm, jm + kMaxWG * 31);
+  hipLaunchKernelGGL(debug_glibc_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, seed, n, form, out,
+                     tab, tab + np, (int32_t *)(tab + np + 31));
   LZM_CHECK_LAUNCH();
   return LZM_OK;
 }
@@ -1886,25 +1561,10 @@ __global__ void mlp_swizzle_kernel(const float *src0, int krows0, const float *s
   dst[d] = v;
 }
 
-// Coefficients of z[344 + p] (the p-th rand() output before >> 1) over the 31 seeded words.
+// The handle's draw table (glibc_coef_table) for at least `positions` draws, and the 16807 powers.
 int ensure_coef(lzm_handle *h, int positions) {
   if (h->coef_positions >= positions) return LZM_OK;
-  std::vector<uint32_t> tab((size_t)positions * 31);
-  std::vector<uint32_t> ring((size_t)34 * 31, 0u);  // z[n] for n mod 34
-  auto row = [&](long n) { return &ring[(size_t)(n % 34) * 31]; };
-  for (int j = 0; j < 31; ++j) {
-    uint32_t *r = row(j);
-    for (int c = 0; c < 31; ++c) r[c] = (c == j);
-  }
-  for (int j = 31; j < 34; ++j) memcpy(row(j), row(j - 31), 31 * sizeof(uint32_t));
-  const long last = 344L + positions;
-  for (long n = 34; n < last; ++n) {
-    uint32_t tmp[31];
-    const uint32_t *a = row(n - 31), *b = row(n - 3);
-    for (int c = 0; c < 31; ++c) tmp[c] = a[c] + b[c];
-    memcpy(row(n), tmp, sizeof(tmp));
-    if (n >= 344) memcpy(&tab[(size_t)(n - 344) * 31], tmp, sizeof(tmp));
-  }
+  const std::vector<uint32_t> tab = glibc_coef_table(positions);
   dfree(h->coef);
   h->coef = nullptr;
   LZM_HIP(hipMalloc(&h->coef, tab.size() * sizeof(uint32_t)));
@@ -1912,11 +1572,7 @@ int ensure_coef(lzm_handle *h, int positions) {
   h->coef_positions = positions;
   if (!h->pow16807) {
     uint32_t pw[31];
-    unsigned long long x = 1;
-    for (int i = 0; i < 31; ++i) {
-      pw[i] = (uint32_t)x;
-      x = (x * 16807ull) % 2147483647ull;
-    }
+    glibc_pow16807(pw);
     LZM_HIP(hipMalloc(&h->pow16807, sizeof(pw)));
     LZM_HIP(hipMemcpy(h->pow16807, pw, sizeof(pw), hipMemcpyHostToDevice));
   }
@@ -2529,8 +2185,8 @@ int lzm_search_diagnostics(lzm_handle *h, int32_t *out, void *stream) {
 // Sticky error counters of every search path on this handle (a look-back spin that
 // times out, or a draw position beyond the coefficient table, would otherwise leave a silently
 // wrong tie-break stream; round 6: split-fp16 activations out of range). Synchronises `stream`;
-// out_host (nullable) gets the kErrWords words {look-back timeouts, draw-table overflows, traverse
-// fixed-point failures, fused-search errors, split-range errors, 0, 0, 0}.
+// out_host (nullable) gets the kErrWords words {look-back timeouts, draw-table overflows, reserved
+// (no kernel writes it: always 0, checked like the others), fused-search errors, split-range errors, 0, 0, 0}.
 int32_t *lzm_error_word(lzm_handle *h, int i) { return (h && i >= 0 && i < kErrWords) ? h->err + i : nullptr; }
 
 int lzm_check_errors(lzm_handle *h, int32_t *out_host, int clear, void *stream) {

@@ -3,8 +3,7 @@
 // cbatch_traverse (lzero/mcts/ctree/ctree_muzero/lib/cnode.cpp:755-824; EfficientZero
 // ctree_efficientzero/lib/cnode.cpp:756-814) walks the roots in order while drawing one rand()
 // per tree level from ONE process-wide glibc stream, so root i's draws start at the sum of the
-// depths of roots < i. traverse_glibc_kernel honours that in one workgroup by iterating the
-// offsets to their fixed point. Here every root gets its own wave, as in the fused search
+// depths of roots < i. Every root gets its own wave, as in the fused search
 // (lzm_search_mlp.h): the walk first runs draw-free (descend_wave CLASSIFY: a tie among
 // unexpanded children ends the walk at the same depth whichever child wins), the root publishes
 // its depth in a 64-bit {epoch, count} word at once, and only a root that needs a draw VALUE
@@ -20,22 +19,20 @@
 
 namespace lzm {
 
-constexpr int kTlbThreads = 256;  // four roots per workgroup, one wave each
+constexpr int kTlbThreads = 256;  // decode_traverse_kernel: four roots per workgroup, one wave each
 
 struct TraverseLbArgs {
   TreeView t;
   const float4 *minmax;
   const uint32_t *seed;
   const int32_t *vtp_in;
-  int32_t *out_x, *out_y, *out_a, *out_vtp, *out_len;
-  long long *out_a64;
+  WalkOut out;
   float disc;
   const uint32_t *coef;  // [coef_positions][31]
   int coef_positions;
   const uint32_t *pow16807;   // [31]
   unsigned long long *flags;  // [B] {epoch, depth}
   uint32_t *epoch;            // [2] epoch, done counter
-  int32_t *diag;              // [0] passes (1)
   int32_t *err;               // sticky error counters (lzm_check_errors): [0] look-back spin timeouts,
                               // [1] draw positions beyond the coefficient table
   const int32_t *reuse_action;  // optional [B] ReZero true actions (search-with-reuse), with
@@ -136,15 +133,7 @@ __device__ inline void traverse_lb_root(const TraverseLbArgs &p, int i, const ui
     }
   }
   const unsigned long long t3 = STAMPS ? __builtin_amdgcn_s_memtime() : 0ull;
-  if (lane == 0) {
-    p.out_x[i] = d.x;
-    p.out_y[i] = i;
-    p.out_a[i] = d.action;
-    if (p.out_a64) p.out_a64[i] = d.action;
-    p.out_vtp[i] = d.vtp;
-    p.out_len[i] = d.len;
-    t.pathlen[i] = d.len;
-  }
+  if (lane == 0) store_walk(p.out, t, i, d.x, d.action, d.vtp, d.len);
   // best_action along the final path (cnode.cpp:806)
   for (int l = lane; l < d.len; l += 64) {
     const int node = t.path[(size_t)l * B + i];
@@ -169,7 +158,6 @@ __device__ inline void traverse_lb_root(const TraverseLbArgs &p, int i, const ui
 __device__ inline void traverse_lb_finish(const TraverseLbArgs &p, unsigned long long epoch) {
   __syncthreads();
   if (threadIdx.x == 0) {
-    if (blockIdx.x == 0) p.diag[0] = 1;
     const uint32_t done = atomicAdd(p.epoch + 1, 1u);
     if (done == gridDim.x - 1) {
       p.epoch[1] = 0;
@@ -178,16 +166,18 @@ __device__ inline void traverse_lb_finish(const TraverseLbArgs &p, unsigned long
   }
 }
 
-// W waves (roots) per workgroup
-template <bool EZ, int W = kTlbThreads / 64, bool STAMPS = false>
-__global__ __launch_bounds__(64 * W) void traverse_lookback_kernel(TraverseLbArgs p) {
+// The stand-alone traverse: one root (one wave) per workgroup
+template <bool EZ, bool STAMPS = false>
+__global__ __launch_bounds__(64) void traverse_lookback_kernel(TraverseLbArgs p) {
   __shared__ uint32_t s_z0[31], s_pow[31];
   __shared__ int s_epoch;
   int players;
   const unsigned long long t0 = STAMPS ? __builtin_amdgcn_s_memtime() : 0ull;
   const unsigned long long epoch = traverse_lb_setup(p, s_z0, s_pow, &s_epoch, &players);
   const unsigned long long t1 = STAMPS ? __builtin_amdgcn_s_memtime() : 0ull;
-  const int i = blockIdx.x * W + (threadIdx.x >> 6);
+  // (the wave term is 0 in a 64-thread workgroup; it keeps the root index a vector value, the form the walk
+  // was tuned and measured in — a scalar index changes the register allocation of the whole kernel)
+  const int i = blockIdx.x + (threadIdx.x >> 6);
   if (i < p.t.B) traverse_lb_root<EZ, STAMPS>(p, i, s_z0, epoch, players, t0, t1);
   traverse_lb_finish(p, epoch);
 }

@@ -19,7 +19,6 @@ namespace lzm {
 constexpr float kFloatMax = 1000000.0f;  // common_lib/cminimax.h:9-10
 constexpr float kFloatMin = -kFloatMax;
 constexpr int kMaxActions = 64;          // tie lists are held as one 64-bit mask
-constexpr int kMaxWG = 1024;
 
 struct alignas(16) NodeStat {
   int visit;
@@ -77,6 +76,24 @@ __device__ inline float mm_normalize(float4 mm, float v) {
 struct Descent {
   int len, x, action, vtp, leaf;
 };
+
+// Where a traverse reports its walks (batch_traverse's return lists and ResultsWrapper.get_search_len):
+// int32[B] each; out_a64 (optional) is the action list again as int64, ready for recurrent_inference.
+struct WalkOut {
+  int32_t *out_x, *out_y, *out_a, *out_vtp, *out_len;
+  long long *out_a64;
+};
+
+// Root i's finished walk into the request lists and pathlen (called by the one thread that holds it).
+__device__ inline void store_walk(const WalkOut &o, const TreeView &t, int i, int x, int action, int vtp, int len) {
+  o.out_x[i] = x;
+  o.out_y[i] = i;
+  o.out_a[i] = action;
+  if (o.out_a64) o.out_a64[i] = action;
+  o.out_vtp[i] = vtp;
+  o.out_len[i] = len;
+  t.pathlen[i] = len;
+}
 
 // One root's selection walk (cbatch_traverse body, cnode.cpp:783-823 with compute_mean_q
 // :169-203, cselect_child :551-596, cucb_score :655-699; EZ variants
@@ -712,6 +729,97 @@ __device__ inline float h_inverse(float value) {
   float tmp = (sqrtf(1.0f + 0.004f * (fabsf(value) + 1.0f + eps)) - 1.0f) * (1.0f / 0.002f);
   float sgn = value > 0.0f ? 1.0f : (value < 0.0f ? -1.0f : 0.0f);
   return sgn * (tmp * tmp - 1.0f);
+}
+
+// InverseScalarTransform (scaling_transform.py:118-128) of one row by one wave:
+// softmax (unless `raw`), expectation over support [-(V-1)/2 .. (V-1)/2], then h^-1.
+// Register form for V <= 64 * NPL: the row is loaded once, every load in flight together (the loop
+// form re-reads it in three passes with one memory latency per iteration). Same per-lane order and
+// the same reductions, so the same bits.
+template <int NPL>
+__device__ inline float wave_support_expectation_reg(const float *row, int V, bool softmax) {
+  const int lane = threadIdx.x & 63;
+  const float half = (float)((V - 1) / 2);
+  float x[NPL];
+#pragma unroll
+  for (int q = 0; q < NPL; ++q) {
+    const int j = lane + 64 * q;
+    x[q] = j < V ? row[j] : 0.0f;
+  }
+  if (!softmax) {
+    float acc = 0.0f;
+#pragma unroll
+    for (int q = 0; q < NPL; ++q)
+      if (lane + 64 * q < V) acc += x[q] * ((float)(lane + 64 * q) - half);
+    acc = xor_sum(acc);
+    return acc;
+  }
+  float mx = -INFINITY;
+#pragma unroll
+  for (int q = 0; q < NPL; ++q)
+    if (lane + 64 * q < V) mx = fmaxf(mx, x[q]);
+  mx = xor_max(mx);
+  float sum = 0.0f;
+#pragma unroll
+  for (int q = 0; q < NPL; ++q)
+    if (lane + 64 * q < V) sum += expf(x[q] - mx);
+  sum = xor_sum(sum);
+  float acc = 0.0f;
+#pragma unroll
+  for (int q = 0; q < NPL; ++q)
+    if (lane + 64 * q < V) acc += (expf(x[q] - mx) / sum) * ((float)(lane + 64 * q) - half);
+  acc = xor_sum(acc);
+  return acc;
+}
+
+__device__ inline float wave_support_expectation_loop(const float *row, int V, bool softmax);
+
+__device__ inline float wave_support_expectation(const float *row, int V, bool softmax) {
+  if (V <= 64 * 2) return wave_support_expectation_reg<2>(row, V, softmax);
+  if (V <= 64 * 10) return wave_support_expectation_reg<10>(row, V, softmax);
+  if (V <= 64 * 16) return wave_support_expectation_reg<16>(row, V, softmax);
+  return wave_support_expectation_loop(row, V, softmax);
+}
+
+__device__ inline float wave_support_expectation_loop(const float *row, int V, bool softmax) {
+  const int lane = threadIdx.x & 63;
+  const float half = (float)((V - 1) / 2);
+  if (!softmax) {
+    float acc = 0.0f;
+    for (int j = lane; j < V; j += 64) acc += row[j] * ((float)j - half);
+    acc = xor_sum(acc);
+    return acc;
+  }
+  float mx = -INFINITY;
+  for (int j = lane; j < V; j += 64) mx = fmaxf(mx, row[j]);
+  mx = xor_max(mx);
+  float sum = 0.0f;
+  for (int j = lane; j < V; j += 64) sum += expf(row[j] - mx);
+  sum = xor_sum(sum);
+  float acc = 0.0f;
+  for (int j = lane; j < V; j += 64) acc += (expf(row[j] - mx) / sum) * ((float)j - half);
+  acc = xor_sum(acc);
+  return acc;
+}
+
+// sum of one row by one wave (ensure_softmax's test, scaling_transform.py:36-62)
+__device__ inline float wave_row_sum(const float *row, int V) {
+  const int lane = threadIdx.x & 63;
+  float s = 0.0f;
+  if (V <= 64 * 10) {
+    // every load in flight together; same per-lane order as the loop
+    float x[10];
+#pragma unroll
+    for (int q = 0; q < 10; ++q) x[q] = lane + 64 * q < V ? row[lane + 64 * q] : 0.0f;
+#pragma unroll
+    for (int q = 0; q < 10; ++q)
+      if (lane + 64 * q < V) s += x[q];
+    s = xor_sum(s);
+    return s;
+  }
+  for (int j = lane; j < V; j += 64) s += row[j];
+  s = xor_sum(s);
+  return s;
 }
 
 // CRoots::prepare / prepare_no_noise (cnode.cpp:321-358): expand each root over its legal list

@@ -169,11 +169,10 @@ def _graph_key(t, model, B, S, shape, extra=()):
 
 
 def _fuse_traverse(cfg, t):
-    """fold each simulation's traverse into the previous simulation's decode launch (parity mode with
-    the look-back traverse; cfg.fuse_traverse, default off: measured even with the two launches at
-    the conv configs; LZM_FUSE=0 forces it off)"""
-    return (cfg.get('fuse_traverse', False) and not t.fast_rng and os.environ.get("LZM_FUSE", "1") != "0"
-            and os.environ.get("LZM_TRAVERSE", "") != "serial")
+    """fold each simulation's traverse into the previous simulation's decode launch (parity mode;
+    cfg.fuse_traverse, default off: measured even with the two launches at the conv configs,
+    DESIGN.md 6.3; LZM_FUSE=0 forces it off)"""
+    return cfg.get('fuse_traverse', False) and not t.fast_rng and os.environ.get("LZM_FUSE", "1") != "0"
 
 
 class _HeadVerdicts:

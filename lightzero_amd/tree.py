@@ -450,11 +450,6 @@ class DeviceTree:
         call("lzm_get_trajectories", self.h, ptr(out), int(tmax), stream_ptr(stream))
         return out
 
-    def traverse_passes(self):
-        out = torch.zeros(2, dtype=torch.int32, device=self.device)
-        call("lzm_last_traverse_passes", self.h, ptr(out), stream_ptr())
-        return out.cpu().tolist()
-
 
 def new_minmax(n, value_delta_max, device, stream=None, out=None):
     mm = torch.empty((n, 4), dtype=torch.float32, device=device) if out is None else out

@@ -2,7 +2,7 @@
 
 - glibc expf port (lzm_numerics.h) vs host libm expf on EVERY float in [-103.97, 0]
   (the domain of logit - max in CNode::expand, ctree_muzero/lib/cnode.cpp:129);
-- glibc rand() jump-matrix generator vs the restatement pinned by libc vectors;
+- glibc rand() coefficient-table generator (every draw form) vs the restatement pinned by libc vectors;
 - Philox4x32-10 vs Random123 known answers;
 - InverseScalarTransform kernel vs a torch fp32 restatement of scaling_transform.py:118-128
   (tolerance: rtol 1e-5, atol 1e-5 * support_scale — the fp32 summation-order bound);
@@ -59,12 +59,25 @@ def test_expf_port_special_values():
     assert np.isnan(got[np.isnan(ref)]).all()
 
 
-@pytest.mark.parametrize("seed", [0, 1, 12345, 999999, 2147483646])
-def test_device_glibc_stream(seed):
+_RAND_REF = {}
+
+
+def _rand_ref(seed, n):
+    if seed not in _RAND_REF:
+        _RAND_REF[seed] = glibc_rand_stream(seed, n)
+    return _RAND_REF[seed]
+
+
+# the generator every parity search draws from (coefficient table over the state seeded in parallel), in its
+# three draw forms: 0 glibc_draw, 1 glibc_draw_wave, 2 lane_draws. Seeds >= 2^31 - 1 take the seeding's
+# serial branch (srandom_r's own loop); glibc_rand_stream agrees with libc's srandom_r / random_r on them.
+@pytest.mark.parametrize("form", [0, 1, 2])
+@pytest.mark.parametrize("seed", [0, 1, 12345, 999999, 2147483646, 2147483647, 4294967295])
+def test_device_glibc_stream(seed, form):
     n = 3000
     out = torch.empty(n, dtype=torch.int32, device=DEV)
-    call("lzm_debug_glibc_rand", seed, n, ptr(out), stream_ptr())
-    assert np.array_equal(out.cpu().numpy().astype(np.int64), glibc_rand_stream(seed, n))
+    call("lzm_debug_glibc_rand", seed, n, form, ptr(out), stream_ptr())
+    assert np.array_equal(out.cpu().numpy().astype(np.int64), _rand_ref(seed, n))
 
 
 def test_device_philox_known_answers():

@@ -55,14 +55,6 @@ def test_gpu_matches_oracle_parity_mode(case):
     assert_same(run_transcript(tr, GpuTree), run_transcript(tr, OracleTree))
 
 
-# parity mode runs one wave per root with a decoupled look-back of the draw offsets
-# (lzm_traverse_lb.h); LZM_TRAVERSE=serial keeps the one-workgroup fixed-point kernel
-@pytest.mark.parametrize("case", [CASES[1], CASES[3], CASES[5], CASES[9]], ids=lambda c: f"b{c[0]}_a{c[2]}_{c[5]}")
-def test_serial_traverse_kernel_matches_oracle(case, monkeypatch):
-    monkeypatch.setenv("LZM_TRAVERSE", "serial")
-    test_gpu_matches_oracle_parity_mode(case)
-
-
 @pytest.mark.parametrize("case", [(256, 50, 2, 1, False), (512, 30, 9, 2, False), (128, 40, 6, 1, True)])
 def test_gpu_matches_oracle_fast_mode(case):
     B, S, A, players, ez = case
@@ -127,8 +119,9 @@ def test_module_api_matches_oracle_and_grows_capacity():
     assert roots.get_trajectories() == [[int(v) for v in row if v >= 0] for row in traj]
 
 
-def test_traverse_passes_small():
-    """Parity mode settles the batch-serial rand() offsets in few speculative passes."""
+def test_parity_traverse_leaves_error_words_clean():
+    """A parity-mode search through traverse / backprop sets no sticky error word (look-back timeout,
+    draw-table overflow)."""
     B, S, A = 256, 30, 2
     tr = random_transcript(B, S, A, seed=5)
     gt = GpuTree(B, A, S)
@@ -137,10 +130,7 @@ def test_traverse_passes_small():
     gt.set_legal(legal, cnt)
     gt.set_delta(np.float32(0.01))
     gt.prepare(np.float32(0.25), tr["noises"], tr["root_reward"], tr["root_logits"], tr["to_play"])
-    passes = []
     for k in range(S):
         o = gt.traverse(19652, np.float32(1.25), np.float32(0.997), int(tr["seeds"][k]), tr["to_play"])
-        passes.append(gt.t.traverse_passes())
         gt.backprop(k + 1, np.float32(0.997), tr["resp_reward"][k], tr["resp_value"][k], tr["resp_logits"][k], o[3])
     gt.t.check_errors()  # raises on a look-back timeout / draw-table overflow (sticky err words)
-    assert max(p[0] for p in passes) <= 4, passes
