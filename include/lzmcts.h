@@ -765,8 +765,9 @@ int lzm_ez_lstm_step(int B, int K, int H, const float *xin, const int32_t *xscal
  * roots' fixed Gumbel table (64 floats) and the considered-visits row of the last (num_simulations,
  * max_num_considered_actions) as a device table. lzm_roots_prepare, lzm_get_distributions, lzm_get_values,
  * lzm_get_trajectories, lzm_gather_latent, lzm_copy_tree and lzm_reserve work on it; lzm_traverse, lzm_backprop,
- * lzm_decode_backprop(_traverse) and the one-launch searches return LZM_ERR_STATE on it, and the lzm_gumbel_*
- * device entry points return LZM_ERR_STATE on any other handle, before anything is launched.
+ * lzm_decode_backprop(_traverse) and the other kinds' one-launch searches return LZM_ERR_STATE on it, and the
+ * lzm_gumbel_* device entry points and lzm_search_mlp_gumbel return LZM_ERR_STATE on any other handle, before
+ * anything is launched.
  * One wave per root, four roots per workgroup; no random draw, so no cross-root communication. ---- */
 /* generate_gumbel(scale, 0, n) (:1134-1152): std::mt19937(0) through std::extreme_value_distribution<float>(0, 1),
  * times scale. Every root holds generate_gumbel(10, 0, legal count) (:66-90), a prefix of one table. Host only. */
@@ -816,6 +817,25 @@ int lzm_gumbel_get_children_values(lzm_handle *h, float discount, float *out, vo
 /* Roots.get_policies (gmz_tree.pyx:51-52; get_policy :355-385): csoftmax over the action space of prior +
  * completed Q, exactly 0 for illegal actions; out float[B*A]. */
 int lzm_gumbel_get_policies(lzm_handle *h, float discount, float *out, void *stream);
+/* GumbelMuZeroMCTSCtree.search's whole loop (mcts_ctree.py:1054-1122) over a MuZeroModelMLP in one launch: the
+ * weight-streaming kernel of lzm_search_mlp with the Gumbel walk, raw_value and the sign-free backup (weights:
+ * lzm_mlp_prepare's output; minmax, vtp_in, latent_pool and the rec_* outputs as lzm_search_mlp; vtp_in passes
+ * through to every expanded node). No seeds: the walk draws nothing, and workgroups exchange nothing. Rebuilds the
+ * considered-visits row like lzm_gumbel_traverse: a synchronous copy when (num_simulations,
+ * max_num_considered_actions) changed, so call lzm_gumbel_set_considered before a stream capture. Shapes:
+ * lzm_search_mlp_supported and actions <= 64. Refused before any launch: a handle without LZM_TREE_GUMBEL or in
+ * collect-step mode (lzm_search_set_step) LZM_ERR_STATE; null arguments, num_simulations <= 0,
+ * max_num_considered_actions < 0 or a refused shape LZM_ERR_ARG; num_simulations beyond the reserved capacity
+ * LZM_ERR_CAPACITY. */
+int lzm_search_mlp_gumbel(lzm_handle *h, int hidden, int head_hidden, int support, int res_dynamics,
+                          const float *weights, int num_simulations, int max_num_considered_actions, float discount,
+                          float *minmax, const int32_t *vtp_in, float *latent_pool, int32_t *rec_x, int32_t *rec_a,
+                          int32_t *rec_len, float *rec_decoded, float *rec_logits, void *stream);
+/* What lzm_search_mlp_gumbel launches on this handle as it stands, by the function the launch itself decides with:
+ * out int32[4] as lzm_search_mlp_plan = {roots per workgroup, kind: 0 weight-streaming or -1 (refused shape, LDS
+ * need — the raw_value slice included — or a handle of another kind), 0, tree_in_lds}. Host only. */
+int lzm_search_mlp_gumbel_plan(const lzm_handle *h, int num_simulations, int hidden, int head_hidden, int support,
+                               int res_dynamics, int32_t *out);
 /* Device logf port (lzm_numerics.h glibc_logf) exposed for checks against the host libm. */
 int lzm_debug_logf(const float *x, float *out, int64_t n, void *stream);
 

@@ -170,6 +170,8 @@ SIGNATURES = {
                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "lzm_gumbel_get_children_values": [_vp, _f, _vp, _vp],
     "lzm_gumbel_get_policies": [_vp, _f, _vp, _vp],
+    "lzm_search_mlp_gumbel": [_vp, _i, _i, _i, _i, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "lzm_search_mlp_gumbel_plan": [_vp, _i, _i, _i, _i, _i, _vp],
     "lzm_debug_logf": [_vp, _vp, _i64, _vp],
     "lzm_conv_trunk_xin_p": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp,
                              _vp],

@@ -66,7 +66,7 @@ __device__ inline GumbelChildren gumbel_children(const TreeView &t, const Gumbel
                                                  float disc) {
   const int lane = threadIdx.x & 63;
   GumbelChildren c;
-  c.n = legal_n(t, i, node);
+  c.n = __builtin_amdgcn_readfirstlane(legal_n(t, i, node));  // wave-uniform: the ordered sums' loop bound
   c.valid = lane < c.n;
   c.a = c.valid ? legal_at(t, i, node, lane) : 0;
   // one round of reads per level: every child's record and latent index, and the node's raw_value; the walk takes
@@ -108,32 +108,28 @@ __device__ __forceinline__ int gumbel_argmax(float score, bool valid) {
   return hit ? __ffsll((long long)hit) - 1 : 0;
 }
 
-// cbatch_traverse's body for root i (:863-896), all 64 lanes of one wave. Writes path / path_act / pathlen,
-// best_action along the path (:879) and the request outputs.
-struct GumbelTraverseArgs {
-  TreeView t;
-  GumbelView g;
-  const int32_t *vtp_in;
-  WalkOut out;
-  float disc;
-};
-
-__device__ inline void gumbel_traverse_root(const GumbelTraverseArgs &p, int i) {
-  const TreeView &t = p.t;
-  const int lane = threadIdx.x & 63, B = t.B;
+// cbatch_traverse's walk of one root (:863-894), all 64 lanes of one wave; every argument wave-uniform. The root
+// is tree index i of t (records, legal lists, raw_value); its path is column `col` of t.path / t.path_act, whose
+// rows are `ps` apart (the generic kernels: i and t.B; the one-launch search: the workgroup's LDS slice, local
+// root and roots per workgroup, wherever the tree itself lives). Writes path / path_act and best_action along
+// the path (:879); returns the request (len, x = the leaf's parent's latent index, action), which the caller
+// files where its kernel keeps requests.
+__device__ inline Descent gumbel_walk(const TreeView &t, const GumbelView &g, float disc, int i, int col, int ps) {
+  const int lane = threadIdx.x & 63;
   int node = 0, len = 0, last_action = -1, parent_latent = -1;
-  int latent = t.meta[nidx(t, 0, i)].latent;  // of `node`
-  if (lane == 0) t.path[i] = 0;
+  // (scalar: the root's record is a per-lane read when the tree is a slice in LDS)
+  int latent = __builtin_amdgcn_readfirstlane(t.meta[nidx(t, 0, i)].latent);  // of `node`
+  if (lane == 0) t.path[col] = 0;
   while (latent >= 0 && len < t.depth_cap - 1) {
-    const GumbelChildren c = gumbel_children(t, p.g, i, node, latent, p.disc);
+    const GumbelChildren c = gumbel_children(t, g, i, node, latent, disc);
     float score;
     if (len == 0) {
       // cselect_root_child: score_considered over the children with the considered visit count
       int si = c.total_visits;
-      si = si < 0 ? 0 : (si >= p.g.S ? p.g.S - 1 : si);  // (past num_simulations the reference reads out of bounds)
-      const int considered = p.g.considered[si];
+      si = si < 0 ? 0 : (si >= g.S ? g.S - 1 : si);  // (past num_simulations the reference reads out of bounds)
+      const int considered = g.considered[si];
       const float pm = wave_max_dpp(c.valid ? c.prior : -INFINITY);
-      const float gl = c.valid ? p.g.gumbel[lane] : 0.0f;
+      const float gl = c.valid ? g.gumbel[lane] : 0.0f;
       float sc = gl + (c.prior - pm) + c.cq;
       sc = (-1e9f < sc) ? sc : -1e9f;  // std::max(low_logit, .)
       score = sc + (c.visit == considered ? 0.0f : -INFINITY);
@@ -147,8 +143,8 @@ __device__ inline void gumbel_traverse_root(const GumbelTraverseArgs &p, int i) 
     const int child = 1 + t.A * latent + action;
     if (lane == 0) {
       t.meta[nidx(t, node, i)].best = action;
-      t.path_act[(size_t)len * B + i] = action;
-      t.path[(size_t)(len + 1) * B + i] = child;
+      t.path_act[(size_t)len * ps + col] = action;
+      t.path[(size_t)(len + 1) * ps + col] = child;
     }
     parent_latent = latent;
     node = child;
@@ -156,8 +152,24 @@ __device__ inline void gumbel_traverse_root(const GumbelTraverseArgs &p, int i) 
     ++len;
     latent = __builtin_amdgcn_readlane(c.latent, jsel);
   }
+  Descent d;
+  d.len = len; d.x = parent_latent; d.action = last_action; d.vtp = 0; d.leaf = node;
+  return d;
+}
+
+// cbatch_traverse's body for root i (:863-896) in the generic kernels: the walk, pathlen and the request lists.
+struct GumbelTraverseArgs {
+  TreeView t;
+  GumbelView g;
+  const int32_t *vtp_in;
+  WalkOut out;
+  float disc;
+};
+
+__device__ inline void gumbel_traverse_root(const GumbelTraverseArgs &p, int i) {
+  const Descent d = gumbel_walk(p.t, p.g, p.disc, i, i, p.t.B);
   // virtual_to_play is passed through (:895): the Gumbel tree has no player bookkeeping
-  if (lane == 0) store_walk(p.out, t, i, parent_latent, last_action, p.vtp_in[i], len);
+  if ((threadIdx.x & 63) == 0) store_walk(p.out, p.t, i, d.x, d.action, p.vtp_in[i], d.len);
 }
 
 // value of the lane holding legal position j, moved to lane legal[j] (action order); `fill` elsewhere

@@ -1634,7 +1634,7 @@ int ensure_phase(lzm_handle *h) {
 int search_preamble(lzm_handle *h, int pb_c_base, float pb_c_init, int S, int G) {
   int rc = fill_lut(h, pb_c_base, pb_c_init);
   if (rc != LZM_OK) return rc;
-  if (!(h->flags & LZM_RNG_FAST)) {
+  if (!(h->flags & (LZM_RNG_FAST | LZM_TREE_GUMBEL))) {  // (the Gumbel walk draws nothing: no draw table)
     rc = ensure_coef(h, h->B * (S + 1) + 64);
     if (rc != LZM_OK) return rc;
   }
@@ -1771,18 +1771,23 @@ bool ez_shape_ok(int H, int Hl, int A, int F, int V) {
   return mlp_shape_ok(H, A, F, V) && Hl > 0 && Hl % kKC == 0 && 4 * Hl <= 4 * kThreads;
 }
 // LDS plan of search_mlp_kernel with R roots per workgroup (float offsets, 16-B aligned); returns bytes.
-// Hl > 0 (EfficientZero): then the gate layer's input [x ; h_prev], the gates, h1 and c_prev
-size_t plan_stream(SearchArgs &p, const lzm_handle *h, int R, int S, int H, int Hl, int A, int F, int V, int res) {
+// Hl > 0 (EfficientZero): then the gate layer's input [x ; h_prev], the gates, h1 and c_prev. gz (Gumbel MuZero):
+// the raw_value slice [cap][R] beside the node records instead of the pUCT table and its caches, and the
+// considered-visits row [S] with the Gumbel table [64] where the seeds would be
+size_t plan_stream(SearchArgs &p, const lzm_handle *h, int R, int S, int H, int Hl, int A, int F, int V, int res,
+                   bool gz) {
   size_t o = 0;
   const size_t tree_floats = (size_t)h->cap * R * 4;
   p.tree_in_lds = (2 * tree_floats * sizeof(float) <= 96 * 1024) ? 1 : 0;
+  const bool puct = p.tree_in_lds && !gz;
   p.off_stat = o; if (p.tree_in_lds) o += tree_floats;
   p.off_meta = o; if (p.tree_in_lds) o += tree_floats;
-  p.off_lut = o; if (p.tree_in_lds) o += round4((size_t)2 * h->lut_n);
+  p.off_raw = o; if (p.tree_in_lds && gz) o += round4((size_t)h->cap * R);
+  p.off_lut = o; if (puct) o += round4((size_t)2 * h->lut_n);
   p.off_legal = o; if (p.tree_in_lds) o += round4((size_t)R * A + R);
-  p.off_val = o; if (p.tree_in_lds) o += round4((size_t)h->cap * R);
+  p.off_val = o; if (puct) o += round4((size_t)h->cap * R);
   // pUCT visit table rows: all of lut when the triangle fits 32 KB (descent falls back to dividing)
-  p.pbt_rows = (p.tree_in_lds && (size_t)h->lut_n * (h->lut_n + 1) / 2 <= 8192) ? h->lut_n : 0;
+  p.pbt_rows = (puct && (size_t)h->lut_n * (h->lut_n + 1) / 2 <= 8192) ? h->lut_n : 0;
   p.off_pbt = o; o += round4((size_t)p.pbt_rows * (p.pbt_rows + 1) / 2);
   p.off_path = o; o += round4((size_t)h->depth_cap * R);
   p.off_pact = o; o += round4((size_t)h->depth_cap * R);
@@ -1795,7 +1800,7 @@ size_t plan_stream(SearchArgs &p, const lzm_handle *h, int R, int S, int H, int 
   p.off_h = o; o += round4(tfl(2 * F));        // [value hidden; policy hidden] (merged layer)
   p.off_logit = o; if (V < kThreads) o += round4((size_t)(V + 1) * R);  // wide supports decode from registers
   p.off_part = o;  // (unused: split-K partials meet through DPP)
-  p.off_misc = o; o += round4((size_t)S + 32);  // staged seeds[S] + 16807^i table
+  p.off_misc = o; o += round4((size_t)S + (gz ? kMaxActions : 32));  // staged seeds[S] + 16807^i table
   if (Hl > 0) {
     p.off_g = o; o += round4(tfl(H + Hl));
     p.off_gates = o; o += round4(tfl(4 * Hl));
@@ -1805,8 +1810,20 @@ size_t plan_stream(SearchArgs &p, const lzm_handle *h, int R, int S, int H, int 
   }
   return o * sizeof(float);
 }
-// What lzm_search_mlp (ez false) or lzm_search_mlp_ez (ez true) launches for this handle, network shape and
-// search length: the one decision behind the launch and the plan queries. kind: 1 network-resident (MuZero
+// The three searches the MLP one-launch path serves, each on handles of its own kind: lzm_search_mlp,
+// lzm_search_mlp_ez and lzm_search_mlp_gumbel
+enum MlpFamily { kMlpMuZero, kMlpEz, kMlpGumbel };
+MlpFamily handle_family(const lzm_handle *h) {
+  return (h->flags & LZM_TREE_GUMBEL) ? kMlpGumbel : (h->flags & LZM_TREE_EZ) ? kMlpEz : kMlpMuZero;
+}
+// the Gumbel kernel's limit on top of the dense steps': one lane per action (lzm_gumbel.h)
+bool gumbel_shape_ok(int H, int A, int F, int V) { return mlp_shape_ok(H, A, F, V) && A <= kMaxActions; }
+bool family_shape_ok(MlpFamily fam, int H, int Hl, int A, int F, int V) {
+  return fam == kMlpEz ? ez_shape_ok(H, Hl, A, F, V) : fam == kMlpGumbel ? gumbel_shape_ok(H, A, F, V)
+                                                                        : mlp_shape_ok(H, A, F, V);
+}
+// What lzm_search_mlp, lzm_search_mlp_ez or lzm_search_mlp_gumbel (fam) launches for this handle, network shape
+// and search length: the one decision behind the launch and the plan queries. kind: 1 network-resident (MuZero
 // only), 0 weight-streaming, -1 none (the shape, or the LDS the streaming kernel would need for it, is
 // refused). mode: the resident kernel's selection mode after its downgrades (0 for the streaming kernel).
 // R: roots per workgroup by roots_per_wg's rule; the EfficientZero kernel takes 1, 2 or 4 (the gate rows
@@ -1815,12 +1832,13 @@ struct MlpPlan {
   int R, kind, mode, tree_in_lds;
   size_t lds;
 };
-MlpPlan mlp_plan(const lzm_handle *h, bool ez, int H, int Hl, int F, int V, int res_dynamics, int S, SearchArgs &p,
-                 ResNet &n) {
+MlpPlan mlp_plan(const lzm_handle *h, MlpFamily fam, int H, int Hl, int F, int V, int res_dynamics, int S,
+                 SearchArgs &p, ResNet &n) {
   const int A = h->A;
+  const bool ez = fam == kMlpEz;
   MlpPlan pl{ez ? std::min(roots_per_wg(h->B), 4) : roots_per_wg(h->B), -1, 0, 0, 0};
-  if (!(ez ? ez_shape_ok(H, Hl, A, F, V) : mlp_shape_ok(H, A, F, V))) return pl;
-  if (!ez && pl.R == 1 && res_enabled() && res_shape_ok(H, A, F, V, res_dynamics)) {
+  if (!family_shape_ok(fam, H, Hl, A, F, V)) return pl;
+  if (fam == kMlpMuZero && pl.R == 1 && res_enabled() && res_shape_ok(H, A, F, V, res_dynamics)) {
     pl.lds = plan_res(p, n, h, S, A);
     if (pl.lds) {
       // the selection mode (lzm_search_res.h, the simulation loop): 1 the wave walk; 4 the two-action
@@ -1838,14 +1856,14 @@ MlpPlan mlp_plan(const lzm_handle *h, bool ez, int H, int Hl, int F, int V, int 
       return pl;
     }
   }
-  pl.lds = plan_stream(p, h, pl.R, S, H, ez ? Hl : 0, A, F, V, res_dynamics);
+  pl.lds = plan_stream(p, h, pl.R, S, H, ez ? Hl : 0, A, F, V, res_dynamics, fam == kMlpGumbel);
   pl.tree_in_lds = p.tree_in_lds;
   pl.kind = pl.lds <= kMaxLds ? 0 : -1;
   return pl;
 }
-// The plan queries' body (ez: lzm_search_mlp_ez_plan); a handle of the other kind answers kind -1
-int mlp_plan_query(const char *name, const lzm_handle *h, bool ez, int S, int H, int Hl, int F, int V, int res_dynamics,
-                   int32_t *out) {
+// The plan queries' body (fam: whose query it is); a handle of another kind answers kind -1
+int mlp_plan_query(const char *name, const lzm_handle *h, MlpFamily fam, int S, int H, int Hl, int F, int V,
+                   int res_dynamics, int32_t *out) {
   if (!h || !out || S <= 0) {
     snprintf(g_err, sizeof(g_err), "%s: null argument or no simulations", name);
     return LZM_ERR_ARG;
@@ -1858,9 +1876,9 @@ int mlp_plan_query(const char *name, const lzm_handle *h, bool ez, int S, int H,
   memset(&p, 0, sizeof(p));
   ResNet n;
   memset(&n, 0, sizeof(n));
-  const MlpPlan pl = mlp_plan(h, ez, H, Hl, F, V, res_dynamics, S, p, n);
+  const MlpPlan pl = mlp_plan(h, fam, H, Hl, F, V, res_dynamics, S, p, n);
   out[0] = pl.R;
-  out[1] = ((h->flags & LZM_TREE_EZ) != 0) == ez ? pl.kind : -1;
+  out[1] = handle_family(h) == fam ? pl.kind : -1;
   out[2] = pl.mode;
   out[3] = pl.tree_in_lds;
   return LZM_OK;
@@ -1928,12 +1946,12 @@ int launch_resident(lzm_handle *h, SearchArgs &p, ResNet &n, const MlpNet &net, 
   return LZM_OK;
 }
 
-// The weight-streaming launch (search_mlp_kernel<R, tree in LDS, EZ>; the EfficientZero kernel serves
+// The weight-streaming launch (search_mlp_kernel<R, tree in LDS, EZ, Gumbel>; the EfficientZero kernel serves
 // R <= 4), with the collect-step mode's prologue (seeds, fresh min-max) and epilogue (root outputs,
 // counter) as one launch each around the search. name: the entry point, for the messages.
 int launch_stream(const char *name, lzm_handle *h, SearchArgs &p, int R, size_t lds, float *minmax, hipStream_t stream) {
   typedef void (*StreamKernel)(SearchArgs);
-  static const StreamKernel kernels[2][4][2] = {  // [EZ][R = 1, 2, 4, 8][tree in LDS, tree in HBM]
+  static const StreamKernel kernels[3][4][2] = {  // [MuZero, EZ, Gumbel][R = 1, 2, 4, 8][tree in LDS, tree in HBM]
       {{search_mlp_kernel<1, true>, search_mlp_kernel<1, false>},
        {search_mlp_kernel<2, true>, search_mlp_kernel<2, false>},
        {search_mlp_kernel<4, true>, search_mlp_kernel<4, false>},
@@ -1941,8 +1959,13 @@ int launch_stream(const char *name, lzm_handle *h, SearchArgs &p, int R, size_t 
       {{search_mlp_kernel<1, true, true>, search_mlp_kernel<1, false, true>},
        {search_mlp_kernel<2, true, true>, search_mlp_kernel<2, false, true>},
        {search_mlp_kernel<4, true, true>, search_mlp_kernel<4, false, true>},
-       {nullptr, nullptr}}};
-  const StreamKernel fn = kernels[p.Hl > 0][R == 1 ? 0 : R == 2 ? 1 : R == 4 ? 2 : 3][p.tree_in_lds ? 0 : 1];
+       {nullptr, nullptr}},
+      {{search_mlp_kernel<1, true, false, true>, search_mlp_kernel<1, false, false, true>},
+       {search_mlp_kernel<2, true, false, true>, search_mlp_kernel<2, false, false, true>},
+       {search_mlp_kernel<4, true, false, true>, search_mlp_kernel<4, false, false, true>},
+       {search_mlp_kernel<8, true, false, true>, search_mlp_kernel<8, false, false, true>}}};
+  const int fam = p.raw ? 2 : p.Hl > 0 ? 1 : 0;  // (p.raw: the Gumbel search's raw_value array)
+  const StreamKernel fn = kernels[fam][R == 1 ? 0 : R == 2 ? 1 : R == 4 ? 2 : 3][p.tree_in_lds ? 0 : 1];
   if (!fn) {
     snprintf(g_err, sizeof(g_err), "%s: no kernel for %d roots per workgroup", name, R);
     return LZM_ERR_STATE;
@@ -1970,21 +1993,28 @@ int launch_stream(const char *name, lzm_handle *h, SearchArgs &p, int R, size_t 
   return LZM_OK;
 }
 
-// lzm_search_mlp (ez false: Hl, horizon and the LSTM pools unused) and lzm_search_mlp_ez. name: the entry
-// point, for the messages.
-int search_mlp(const char *name, bool ez, lzm_handle *h, int H, int Hl, int F, int V, int res_dynamics,
-               const float *weights, int S, int horizon, int pb_c_base, float pb_c_init, float discount, float *minmax,
-               const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool, float *h_pool, float *c_pool,
-               int32_t *rec_x, int32_t *rec_a, int32_t *rec_len, int32_t *rec_reset, float *rec_decoded,
-               float *rec_logits, hipStream_t stream) {
-  if (!h || !weights || !minmax || (!seeds && !h->step_count) || !vtp_in || !latent_pool ||
+// lzm_search_mlp (Hl, horizon and the LSTM pools unused), lzm_search_mlp_ez and lzm_search_mlp_gumbel (fam; the
+// last without seeds, with considered_m = max_num_considered_actions, refused on a handle in collect-step mode:
+// there is no Gumbel collect step). name: the entry point, for the messages.
+int search_mlp(const char *name, MlpFamily fam, lzm_handle *h, int H, int Hl, int F, int V, int res_dynamics,
+               const float *weights, int S, int horizon, int considered_m, int pb_c_base, float pb_c_init,
+               float discount, float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
+               float *h_pool, float *c_pool, int32_t *rec_x, int32_t *rec_a, int32_t *rec_len, int32_t *rec_reset,
+               float *rec_decoded, float *rec_logits, hipStream_t stream) {
+  const bool ez = fam == kMlpEz, gz = fam == kMlpGumbel;
+  if (!h || !weights || !minmax || (!gz && !seeds && !h->step_count) || !vtp_in || !latent_pool ||
       (ez && (!h_pool || !c_pool)) || S <= 0) {
     snprintf(g_err, sizeof(g_err), "%s: null argument or no simulations", name);
     return LZM_ERR_ARG;
   }
-  if (h->flags & LZM_TREE_GUMBEL) {
-    set_err("one-launch searches do not take a Gumbel MuZero handle");
-    return LZM_ERR_STATE;
+  if (gz) {
+    int rc = check_kind(name, h, true);
+    if (rc != LZM_OK) return rc;
+    if (considered_m < 0) return refuse(LZM_ERR_ARG, name, "max_num_considered_actions must be >= 0");
+    if (h->step_count || h->step_fresh || h->step_dist || h->step_vals)
+      return refuse(LZM_ERR_STATE, name, "collect-step mode (lzm_search_set_step) has no Gumbel search");
+  } else if (h->flags & LZM_TREE_GUMBEL) {
+    return refuse(LZM_ERR_STATE, name, "a Gumbel MuZero handle takes lzm_search_mlp_gumbel");
   }
   if ((uintptr_t)weights & 15) {
     snprintf(g_err, sizeof(g_err), "%s: weights must be 16-byte aligned (%s output)", name,
@@ -2000,9 +2030,11 @@ int search_mlp(const char *name, bool ez, lzm_handle *h, int H, int Hl, int F, i
     return LZM_ERR_ARG;
   }
   const int A = h->A;
-  if (!(ez ? ez_shape_ok(H, Hl, A, F, V) : mlp_shape_ok(H, A, F, V))) {
+  if (!family_shape_ok(fam, H, Hl, A, F, V)) {
     snprintf(g_err, sizeof(g_err), "%s: unsupported network shape (%s)", name,
-             ez ? "lzm_search_mlp_ez_supported" : "hidden and head widths must be multiples of 16");
+             ez ? "lzm_search_mlp_ez_supported"
+                : gz ? "lzm_search_mlp_supported, and at most 64 actions"
+                     : "hidden and head widths must be multiples of 16");
     return LZM_ERR_ARG;
   }
   if (S > h->sims_cap) {
@@ -2013,19 +2045,21 @@ int search_mlp(const char *name, bool ez, lzm_handle *h, int H, int Hl, int F, i
   memset(&p, 0, sizeof(p));
   ResNet n;
   memset(&n, 0, sizeof(n));
-  const MlpPlan plan = mlp_plan(h, ez, H, Hl, F, V, res_dynamics, S, p, n);
+  const MlpPlan plan = mlp_plan(h, fam, H, Hl, F, V, res_dynamics, S, p, n);
   if (plan.kind < 0) {
     snprintf(g_err, sizeof(g_err), "%s: %zu B of LDS needed (network or tree too large)", name, plan.lds);
     return LZM_ERR_ARG;
   }
   int rc = search_preamble(h, pb_c_base, pb_c_init, S, (h->B + plan.R - 1) / plan.R);
   if (rc != LZM_OK) return rc;
+  if (gz && (rc = gumbel_set_considered(h, S, considered_m, name)) != LZM_OK) return rc;
   const MlpNet net = mlp_net(H, ez ? Hl : 0, A, F, V, res_dynamics);
   fill_common(p, h, S, discount, seeds, vtp_in, minmax, latent_pool, rec_x, rec_a, rec_len, rec_decoded, rec_logits);
   p.H = H; p.F = F; p.V = V; p.res = net.res;
   p.diag = h->search_diag;
   p.hpool = h_pool; p.cpool = c_pool; p.Hl = net.Hl; p.horizon = horizon; p.rec_reset = rec_reset;
-  if (!ez) {  // the phase stamps and the timing experiments are the MuZero kernels'
+  if (gz) { p.raw = h->raw; p.gumbel = h->gumbel; p.considered = h->considered; }
+  if (fam == kMlpMuZero) {  // the phase stamps and the timing experiments are the MuZero kernels'
     if (phase_timing() && (rc = ensure_phase(h)) != LZM_OK) return rc;
     p.phase = h->phase;
     p.diag_mode = getenv("LZM_DIAG_MODE") ? atoi(getenv("LZM_DIAG_MODE")) : 0;  // timing experiments only
@@ -2073,7 +2107,7 @@ int lzm_search_mlp_supported(int actions, int hidden, int head_hidden, int suppo
 
 int lzm_search_mlp_plan(const lzm_handle *h, int num_simulations, int hidden, int head_hidden, int support,
                         int res_dynamics, int32_t *out) {
-  return mlp_plan_query("lzm_search_mlp_plan", h, false, num_simulations, hidden, 0, head_hidden, support,
+  return mlp_plan_query("lzm_search_mlp_plan", h, kMlpMuZero, num_simulations, hidden, 0, head_hidden, support,
                         res_dynamics, out);
 }
 
@@ -2081,8 +2115,8 @@ int lzm_search_mlp(lzm_handle *h, int hidden, int head_hidden, int support, int 
                    int num_simulations, int pb_c_base, float pb_c_init, float discount, float *minmax,
                    const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool, int32_t *rec_x, int32_t *rec_a,
                    int32_t *rec_len, float *rec_decoded, float *rec_logits, void *stream) {
-  return search_mlp("lzm_search_mlp", false, h, hidden, 0, head_hidden, support, res_dynamics, weights,
-                    num_simulations, 0, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in, latent_pool, nullptr,
+  return search_mlp("lzm_search_mlp", kMlpMuZero, h, hidden, 0, head_hidden, support, res_dynamics, weights,
+                    num_simulations, 0, 0, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in, latent_pool, nullptr,
                     nullptr, rec_x, rec_a, rec_len, nullptr, rec_decoded, rec_logits, (hipStream_t)stream);
 }
 
@@ -2116,7 +2150,7 @@ int lzm_search_mlp_ez_supported(int actions, int hidden, int lstm_hidden, int he
 
 int lzm_search_mlp_ez_plan(const lzm_handle *h, int num_simulations, int hidden, int lstm_hidden, int head_hidden,
                            int support, int res_dynamics, int32_t *out) {
-  return mlp_plan_query("lzm_search_mlp_ez_plan", h, true, num_simulations, hidden, lstm_hidden, head_hidden, support,
+  return mlp_plan_query("lzm_search_mlp_ez_plan", h, kMlpEz, num_simulations, hidden, lstm_hidden, head_hidden, support,
                         res_dynamics, out);
 }
 
@@ -2125,9 +2159,29 @@ int lzm_search_mlp_ez(lzm_handle *h, int hidden, int lstm_hidden, int head_hidde
                       float discount, float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
                       float *h_pool, float *c_pool, int32_t *rec_x, int32_t *rec_a, int32_t *rec_len,
                       int32_t *rec_reset, float *rec_decoded, float *rec_logits, void *stream) {
-  return search_mlp("lzm_search_mlp_ez", true, h, hidden, lstm_hidden, head_hidden, support, res_dynamics, weights,
-                    num_simulations, lstm_horizon_len, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in,
+  return search_mlp("lzm_search_mlp_ez", kMlpEz, h, hidden, lstm_hidden, head_hidden, support, res_dynamics, weights,
+                    num_simulations, lstm_horizon_len, 0, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in,
                     latent_pool, h_pool, c_pool, rec_x, rec_a, rec_len, rec_reset, rec_decoded, rec_logits,
+                    (hipStream_t)stream);
+}
+
+int lzm_search_mlp_gumbel_plan(const lzm_handle *h, int num_simulations, int hidden, int head_hidden, int support,
+                               int res_dynamics, int32_t *out) {
+  return mlp_plan_query("lzm_search_mlp_gumbel_plan", h, kMlpGumbel, num_simulations, hidden, 0, head_hidden, support,
+                        res_dynamics, out);
+}
+
+// The Gumbel MuZero search over MuZeroModelMLP (lzm_mlp_prepare's weights) in one launch. Rebuilds the handle's
+// considered-visits row when (S, m) changed: a synchronous copy, outside stream capture (lzm_gumbel_set_considered
+// before a capture). No seeds and no draw table: the walk draws nothing. The pUCT constants are the handle's
+// defaults (the table is never read).
+int lzm_search_mlp_gumbel(lzm_handle *h, int hidden, int head_hidden, int support, int res_dynamics,
+                          const float *weights, int num_simulations, int max_num_considered_actions, float discount,
+                          float *minmax, const int32_t *vtp_in, float *latent_pool, int32_t *rec_x, int32_t *rec_a,
+                          int32_t *rec_len, float *rec_decoded, float *rec_logits, void *stream) {
+  return search_mlp("lzm_search_mlp_gumbel", kMlpGumbel, h, hidden, 0, head_hidden, support, res_dynamics, weights,
+                    num_simulations, 0, max_num_considered_actions, 19652, 1.25f, discount, minmax, nullptr, vtp_in,
+                    latent_pool, nullptr, nullptr, rec_x, rec_a, rec_len, nullptr, rec_decoded, rec_logits,
                     (hipStream_t)stream);
 }
 

@@ -26,10 +26,16 @@
 // EfficientZero walk, expansion and backup, the reward LSTM's state gathered and filed beside the latents, its
 // gate layer as one more schedule step and its cell after it (ez_cell below). The MuZero instantiations are
 // untouched by it.
+//
+// search_mlp_kernel<R, TL, false, true> is the same launch for GumbelMuZeroMCTSCtree over MuZeroModelMLP
+// (mcts_ctree.py:956-1123): the Gumbel walk (lzm_gumbel.h) in place of the pUCT descent, raw_value beside the
+// node records, and nothing of the draw machinery — the walk draws no random number, so workgroups exchange
+// nothing at all. The network schedule, the gather and the filing are the shared code.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lzm_gumbel.h"
 #include "lzm_lstm.h"
 #include "lzm_numerics.h"
 #include "lzm_tree.h"
@@ -116,6 +122,14 @@ struct SearchArgs {
   int Hl, horizon, cell_after;
   int32_t *rec_reset;  // nullable: is_reset [S][B]
   size_t off_g, off_gates, off_hh, off_cp;
+  // Gumbel MuZero (search_mlp_kernel<R, TL, false, true>; null otherwise, which is how the host tells the
+  // family): the handle's raw_value array [cap][B], the Gumbel table [64] and the considered-visits row [S]
+  // (staged at off_misc, where the other kernels keep their seeds), and the LDS float offset of the raw_value
+  // slice [cap][R] beside stat / meta (tree in LDS only)
+  float *raw;
+  const float *gumbel;
+  const int32_t *considered;
+  size_t off_raw;
 };
 
 // ------------------------------------------------------------------------------ LDS helpers
@@ -700,8 +714,13 @@ __device__ __forceinline__ void ez_cell(const SearchArgs &p, float *smem, int k,
 // EZ: the EfficientZero search over EfficientZeroModelMLP (mcts_ctree.py:756-827): the EfficientZero
 // walk, expansion (is_reset) and backup, the reward LSTM's state gathered from / filed into the state
 // pools beside the latents, its gate layer as a schedule step and its cell after it (ez_cell).
-template <int R, bool TL, bool EZ = false>
+// GZ: the Gumbel MuZero search over MuZeroModelMLP (mcts_ctree.py:1054-1122): wave w walks its roots with
+// gumbel_walk, expansion is the MuZero tree's with virtual_to_play passed through, raw_value is stored after it
+// and the backup has no player sign (gumbel_expand_backup's order). No seeds, draw tables, look-back words,
+// pUCT table or value cache: the instantiation never touches p.seeds, p.coef, p.pow16807, p.flags or p.lut.
+template <int R, bool TL, bool EZ = false, bool GZ = false>
 __global__ __launch_bounds__(kThreads) void search_mlp_kernel(SearchArgs p) {
+  static_assert(!(EZ && GZ), "the Gumbel search is MuZeroModelMLP's");
   extern __shared__ float4 smem4[];
   float *smem = reinterpret_cast<float *>(smem4);
   const int tid = threadIdx.x, g = blockIdx.x, G = gridDim.x;
@@ -741,17 +760,19 @@ __global__ __launch_bounds__(kThreads) void search_mlp_kernel(SearchArgs p) {
         lm[e] = p.meta[(size_t)node * B + i0 + li];
       }
     }
-    for (int e = tid; e < p.lut_n; e += kThreads) llut[e] = p.lut[e];
-    // caches replacing the descent's divisions (bit-identical: same operands, same IEEE division)
-    float *lval = smem + p.off_val;
-    for (int e = tid; e < p.cap * R; e += kThreads) {
-      const int node = e / R, li = e % R;
-      lval[e] = li < nr ? node_value(p.stat[(size_t)node * B + i0 + li]) : 0.0f;
+    if constexpr (!GZ) {  // pUCT only: the Gumbel walk reads neither the table nor the caches
+      for (int e = tid; e < p.lut_n; e += kThreads) llut[e] = p.lut[e];
+      // caches replacing the descent's divisions (bit-identical: same operands, same IEEE division)
+      float *lval = smem + p.off_val;
+      for (int e = tid; e < p.cap * R; e += kThreads) {
+        const int node = e / R, li = e % R;
+        lval[e] = li < nr ? node_value(p.stat[(size_t)node * B + i0 + li]) : 0.0f;
+      }
+      float *lpbt = smem + p.off_pbt;
+      build_pbt(p.lut, p.pbt_rows, lpbt, tid, kThreads);
+      t.val = lval;
+      t.pbt = p.pbt_rows ? lpbt : nullptr;
     }
-    float *lpbt = smem + p.off_pbt;
-    build_pbt(p.lut, p.pbt_rows, lpbt, tid, kThreads);
-    t.val = lval;
-    t.pbt = p.pbt_rows ? lpbt : nullptr;
     for (int e = tid; e < R * A; e += kThreads) llegal[e] = (e / A < nr) ? p.legal[(size_t)i0 * A + e] : 0;
     for (int e = tid; e < R; e += kThreads) llegal[R * A + e] = (e < nr) ? p.nlegal[i0 + e] : 0;
     t.stat = ls;
@@ -770,6 +791,27 @@ __global__ __launch_bounds__(kThreads) void search_mlp_kernel(SearchArgs p) {
   }
   // tree index of local root li: li in the LDS slice, i0 + li in the HBM batch
   auto tix = [i0](int li) { return TL ? li : i0 + li; };
+  // Gumbel: raw_value indexed like the node records (the slice [cap][R] in LDS, or the handle's array), the
+  // considered-visits row and the Gumbel table staged where the other kernels keep their seeds
+  GumbelView gv;
+  if constexpr (GZ) {
+    int32_t *lcons = reinterpret_cast<int32_t *>(smem + p.off_misc);
+    float *lgum = smem + p.off_misc + p.S;
+    for (int e = tid; e < p.S; e += kThreads) lcons[e] = p.considered[e];
+    for (int e = tid; e < kMaxActions; e += kThreads) lgum[e] = p.gumbel[e];
+    gv.raw = p.raw;
+    if constexpr (TL) {
+      float *lraw = smem + p.off_raw;
+      for (int e = tid; e < p.cap * R; e += kThreads) {
+        const int node = e / R, li = e % R;
+        lraw[e] = li < nr ? p.raw[(size_t)node * B + i0 + li] : 0.0f;
+      }
+      gv.raw = lraw;
+    }
+    gv.gumbel = lgum;
+    gv.considered = lcons;
+    gv.S = p.S;
+  }
   if (tid < R && tid < nr) {
     s_mm[tid] = p.minmax[i0 + tid];
     s_vtp[tid] = p.vtp_in[i0 + tid];
@@ -788,9 +830,11 @@ __global__ __launch_bounds__(kThreads) void search_mlp_kernel(SearchArgs p) {
 
   uint32_t *s_seeds = reinterpret_cast<uint32_t *>(smem + p.off_misc);
   uint32_t *s_pow = s_seeds + p.S;
-  for (int e = tid; e < p.S; e += kThreads) s_seeds[e] = p.seeds[e];
-  if (!p.fast)
-    for (int e = tid; e < 31; e += kThreads) s_pow[e] = p.pow16807[e];
+  if constexpr (!GZ) {
+    for (int e = tid; e < p.S; e += kThreads) s_seeds[e] = p.seeds[e];
+    if (!p.fast)
+      for (int e = tid; e < 31; e += kThreads) s_pow[e] = p.pow16807[e];
+  }
   __syncthreads();
   LZM_STAMP(10);
   float *X0 = smem + p.off_x0, *X1 = smem + p.off_x1, *NL = smem + p.off_n;
@@ -803,10 +847,21 @@ __global__ __launch_bounds__(kThreads) void search_mlp_kernel(SearchArgs p) {
   if (kPrefetchAhead == 2) prefetch_step<pre_b<R>()>(p.sched[1], wB, bB);
 
   for (int k = 0; k < p.S; ++k) {
-    const uint32_t seed = s_seeds[k];
-    if (!p.fast) seed_state_parallel(seed, s_pow, s_z0);
+    uint32_t seed = 0u;  // (none in the Gumbel kernel)
+    if constexpr (!GZ) {
+      seed = s_seeds[k];
+      if (!p.fast) seed_state_parallel(seed, s_pow, s_z0);
+    }
     // ---- selection: wave w walks roots w, w + kWaves, ... (one lane per child, descend_wave)
-    for (int li = tid >> 6; li < nr; li += kWaves) {
+    if constexpr (GZ) {
+      // the Gumbel walk (cselect_root_child at level 0, cselect_interior_child below): no draw, so the request
+      // is final here; the root index in a scalar register, as every loop bound and readlane index of the walk
+      for (int li = __builtin_amdgcn_readfirstlane(tid >> 6); li < nr; li += kWaves) {
+        const Descent d = gumbel_walk(t, gv, p.disc, tix(li), li, R);
+        if ((tid & 63) == 0) { s_len[li] = d.len; s_x[li] = d.x; s_act[li] = d.action; }
+      }
+    }
+    for (int li = tid >> 6; !GZ && li < nr; li += kWaves) {  // (the pUCT walks; none in the Gumbel kernel)
       const int i = i0 + li;
       const TreeView &tv = t;
       const int ti = tix(li);
@@ -833,7 +888,7 @@ __global__ __launch_bounds__(kThreads) void search_mlp_kernel(SearchArgs p) {
     }
     __syncthreads();
     LZM_STAMP(0);
-    if (!p.fast) {
+    if (!GZ && !p.fast) {
       // ---- draw offsets: publish this slice's draw count, look back over predecessors
       if (tid == 0) {
         int ambiguous = 0, total = 0;
@@ -1020,9 +1075,16 @@ __global__ __launch_bounds__(kThreads) void search_mlp_kernel(SearchArgs p) {
       const int len = s_len[li];
       const int leaf = tv.path[len * R + li];
       int vtp = s_vtp[li];
-      if (players > 1)
+      if (!GZ && players > 1)
         for (int l = 0; l < len; ++l) vtp = (vtp == 1) ? 2 : 1;
-      if constexpr (EZ) {
+      if constexpr (GZ) {
+        // gumbel_expand_backup's order (ctree_gumbel_muzero/lib/cnode.cpp): CNode::expand with virtual_to_play
+        // as it came in (:895, no per-level flip), raw_value (:111), cback_propagate without a player sign
+        // (:605-631)
+        expand_wave(tv, ti, leaf, vtp, k + 1, s_r[li], X1 + li * A);
+        if ((tid & 63) == 0) gv.raw[nidx(tv, leaf, ti)] = s_v[li];
+        backup_wave(tv, ti, li, R, &s_mm[li], -1, s_v[li], p.disc);
+      } else if constexpr (EZ) {
         // is_reset of every leaf (mcts_ctree.py:810-816), the EfficientZero backup, best_action along the
         // path (ctree_efficientzero/lib/cnode.cpp:482-575, :806)
         expand_wave(tv, ti, leaf, vtp, k + 1, s_r[li], X1 + li * A, (len % p.horizon) == 0 ? 1 : 0);
@@ -1045,6 +1107,7 @@ __global__ __launch_bounds__(kThreads) void search_mlp_kernel(SearchArgs p) {
       if (li < nr) {
         p.stat[(size_t)node * B + i0 + li] = t.stat[e];
         p.meta[(size_t)node * B + i0 + li] = t.meta[e];
+        if constexpr (GZ) p.raw[(size_t)node * B + i0 + li] = gv.raw[e];
       }
     }
   }

@@ -806,17 +806,24 @@ class GumbelMuZeroMCTSCtree(_MCTSCtree):
     the Gumbel tree (lzm_gumbel.h): Gumbel traverse, leaf gather, recurrent_inference (the user's module or the
     native conv trunk, as _loop chooses), then one launch for this simulation's decode + expand + backup and the
     next simulation's traverse. Eager, or one HIP graph with cfg.use_hip_graph. The walk draws no random number:
-    there are no seeds and no rng_mode, and search_with_reuse does not exist, as in the reference."""
+    there are no seeds and no rng_mode, and search_with_reuse does not exist, as in the reference.
+    With cfg.fused_search (off by default here) a MuZeroModelMLP's whole search runs as one launch
+    (lzm_search_mlp_gumbel) where _fused allows it; last_path says which path ran."""
 
     config = dict(
         num_simulations=50,
         root_dirichlet_alpha=0.3,
         root_noise_weight=0.25,
         value_delta_max=0.01,
-    )
+    )  # (the reference's keys only; cfg.fused_search is read with default False: the one-launch search is opt-in)
     _tree = gmz_tree
     reward_name = 'reward'
     rng_mode = None
+    FUSED_WIDE_HIDDEN = 512  # latents wider than this take the one launch only at one root per workgroup (_fused)
+
+    def __init__(self, cfg: EasyDict = None) -> None:
+        super().__init__(cfg)
+        self._packed = PackedCache()
 
     @classmethod
     def roots(cls: int, active_collect_env_num: int, legal_actions: List[Any]) -> "gmz_tree.Roots":
@@ -834,6 +841,30 @@ class GumbelMuZeroMCTSCtree(_MCTSCtree):
         return _Recorder(c.S, c.B, c.t.A, c.dev)
 
     _step = MuZeroMCTSCtree._step
+
+    def _fused(self, model, t, S):
+        """(packed weights, dims) when cfg.fused_search is set and the whole search can run as one
+        lzm_search_mlp_gumbel launch: a MuZeroModelMLP-shaped network with categorical heads, eval-mode BatchNorm
+        and ReLU, whose actions and support match the tree and the config, of a shape the kernel takes on this
+        tree for S simulations by the library's own launch plan (lzm_search_mlp_gumbel_plan: lzm_search_mlp's
+        shapes, at most 64 actions, the LDS the tree slice with its raw_value needs) and the measured routing rule
+        below; None otherwise."""
+        if not self._cfg.get('fused_search', False) or not self._categorical():
+            return None
+        try:
+            packed, dims = self._packed.get(model, t.device)
+        except NotPackable:
+            return None
+        if dims["actions"] != t.A or dims["support"] != 2 * int(self._cfg.model.support_scale) + 1:
+            return None
+        plan = t.search_mlp_gumbel_plan(dims, S)
+        if plan["kernel"] is None:
+            return None
+        # measured (DESIGN.md 10): a latent wider than 512 loses to the graph path once a workgroup holds several
+        # roots (1,024 wide, 1,024 roots: 14.67 against 13.97 ms), and wins with one root per workgroup
+        if dims["hidden"] > self.FUSED_WIDE_HIDDEN and plan["roots_per_wg"] > 1:
+            return None
+        return packed, dims
 
     def _loop(self, t, model, c, rec=None, infer=None, net=None):
         """The S simulations (mcts_ctree.py:1054-1122) on tree t over c.buf, all enqueued on the current stream:
@@ -869,9 +900,18 @@ class GumbelMuZeroMCTSCtree(_MCTSCtree):
             if not getattr(c.t, "gumbel", False):
                 raise TypeError("GumbelMuZeroMCTSCtree.search: roots must come from GumbelMuZeroMCTSCtree.roots")
             c.t.set_considered(*self._considered())  # (before any capture: a synchronous table copy)
-            self._buffers(c, model, graph=not self.record and self._cfg.get('use_hip_graph', False))
+            fz = self._fused(model, c.t, c.S)
+            self._buffers(c, model, graph=fz is None and not self.record and self._cfg.get('use_hip_graph', False))
             c.buf.vtp_in.copy_(_to_play_tensor(to_play_batch, c.B, c.dev))
             rec = self._recorder(c)
-            self._generic(c, model, rec)
+            if fz is None:
+                self._generic(c, model, rec)
+            else:  # the whole search in one launch; the requests' to_play is the roots' (it passes through)
+                packed, dims = fz
+                new_minmax(c.B, self._cfg.value_delta_max, c.dev, out=c.buf.mm)
+                c.t.search_mlp_gumbel(dims, packed, c.S, self._considered()[1], c.buf.mm, c.buf.vtp_in, c.buf.pool,
+                                      self._discount(), rec=rec)
+                if rec is not None:
+                    rec.vtp.copy_(c.buf.vtp_in.expand(c.S, c.B))
             self._finish(c, roots, None, rec)
-            self.last_path = "generic"
+            self.last_path = "generic" if fz is None else "fused-mlp"

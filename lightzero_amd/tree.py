@@ -269,6 +269,26 @@ class DeviceTree:
         call("lzm_gumbel_get_policies", self.h, float(discount), ptr(out), stream_ptr(stream))
         return out
 
+    def search_mlp_gumbel(self, dims, weights, S, m, minmax, vtp_in, pool, discount=0.997, rec=None, stream=None):
+        """One launch for the whole Gumbel MuZero search of a MuZeroModelMLP (lzm_search_mlp_gumbel; dims /
+        weights: the packed network in the kernel layout, as search_mlp's); m: max_num_considered_actions;
+        rec: optional _Recorder-like object (its vtp rows are the caller's: to_play passes through)."""
+        self._unchecked = True
+        with torch.cuda.device(self.device):  # (a changed (S, m) rebuilds the considered-visits row)
+            call("lzm_search_mlp_gumbel", self.h, dims["hidden"], dims["head_hidden"], dims["support"],
+                 int(dims["res"]), ptr(weights), int(S), int(m), float(discount), ptr(minmax), ptr(vtp_in), ptr(pool),
+                 *_rec_ptrs(rec), stream_ptr(stream))
+        self._considered = (int(S), int(m))
+
+    def search_mlp_gumbel_plan(self, dims, S):
+        """What search_mlp_gumbel(dims, ..., S) launches on this handle as it stands (lzm_search_mlp_gumbel_plan;
+        host only): dict(roots_per_wg, kernel 'streaming' / None when the kernel refuses the shape, its LDS need
+        or a handle that is no Gumbel tree, mode 0, tree_in_lds)."""
+        out = (ctypes.c_int32 * 4)()
+        call("lzm_search_mlp_gumbel_plan", self.h, int(S), dims["hidden"], dims["head_hidden"], dims["support"],
+             int(dims["res"]), out)
+        return dict(roots_per_wg=out[0], kernel={0: "streaming"}.get(out[1]), mode=out[2], tree_in_lds=bool(out[3]))
+
     def search_mlp(self, dims, weights, S, minmax, seeds, vtp_in, pool, pb_c_base=19652, pb_c_init=1.25,
                    discount=0.997, rec=None, stream=None):
         """One launch for the whole search (lzm_search_mlp); rec: optional _Recorder-like object."""

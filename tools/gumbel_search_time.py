@@ -1,19 +1,22 @@
-"""Times one search over a MuZeroModelMLP with device events on the search's stream: GumbelMuZeroMCTSCtree replayed
-as one HIP graph (--kind gumbel), or the yardstick it is compared with, MuZeroMCTSCtree forced onto its generic
-per-simulation graph path (--kind muzero: cfg.fused_search off, cfg.use_hip_graph on). One JSON line: the path
-taken, the milliseconds of each timed search (roots prepared before the events; the search call alone is timed),
-their median, and a checksum of the visit counts and root values.
+"""Times one search over a MuZeroModelMLP with device events on the search's stream: GumbelMuZeroMCTSCtree
+(--kind gumbel) or MuZeroMCTSCtree (--kind muzero), each on its generic per-simulation path replayed as one HIP
+graph (--fused 0, the default: cfg.fused_search off, cfg.use_hip_graph on) or as its one-launch search
+(--fused 1: cfg.fused_search on; LZM_FUSED_RES=0 in the environment keeps MuZero on the weight-streaming kernel the
+Gumbel search shares). One JSON line: the path taken, the milliseconds of each timed search (roots prepared before
+the events; the search call alone is timed), their median, and a checksum of the visit counts and root values.
 
-    python tools/gumbel_search_time.py --kind gumbel|muzero [--roots N] [--sims S] [--actions A] [--considered M]
-                                       [--hidden H] [--graph 0|1] [--warmup W] [--reps R]
+    python tools/gumbel_search_time.py --kind gumbel|muzero [--fused 0|1] [--roots N] [--sims S] [--actions A]
+                                       [--considered M] [--hidden H] [--graph 0|1] [--warmup W] [--reps R]
 
---considered defaults to min(16, A). A measurement session alternates the two kinds, one process per line, each
+--considered defaults to min(16, A). A measurement session alternates the variants, one process per line, each
 under its own time limit:
 
     for i in 1 2 3; do
       for a in 2 18; do
-        timeout -k 10 120 python tools/gumbel_search_time.py --kind gumbel --actions $a &&
-        timeout -k 10 120 python tools/gumbel_search_time.py --kind muzero --actions $a || break 2
+        timeout -k 10 120 python tools/gumbel_search_time.py --kind gumbel --fused 1 --actions $a &&
+        timeout -k 10 120 python tools/gumbel_search_time.py --kind gumbel --fused 0 --actions $a &&
+        LZM_FUSED_RES=0 timeout -k 10 120 python tools/gumbel_search_time.py --kind muzero --fused 1 --actions $a \
+          || break 2
       done
     done
 """
@@ -33,6 +36,7 @@ def main():
     p.add_argument("--actions", type=int, default=2)
     p.add_argument("--considered", type=int, default=0)
     p.add_argument("--hidden", type=int, default=128)
+    p.add_argument("--fused", type=int, default=0, help="cfg.fused_search: the one-launch search where it applies")
     p.add_argument("--graph", type=int, default=1, help="cfg.use_hip_graph")
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--reps", type=int, default=5)
@@ -56,7 +60,7 @@ def main():
     cls = GumbelMuZeroMCTSCtree if gumbel else MuZeroMCTSCtree
     cfg = cls.default_config()
     cfg.update(dict(num_simulations=S, max_num_considered_actions=m, discount_factor=0.997, device=dev,
-                    use_hip_graph=bool(args.graph), fused_search=False, env_type='not_board_games',
+                    use_hip_graph=bool(args.graph), fused_search=bool(args.fused), env_type='not_board_games',
                     model=dict(support_scale=300, categorical_distribution=True)))
     mcts = cls(EasyDict(cfg))
     rng = np.random.default_rng(0)
@@ -87,7 +91,7 @@ def main():
             ms.append(e0.elapsed_time(e1))
     t = roots.tree
     check = float(t.distributions().clamp(min=0).double().sum().item() + t.values().double().sum().item())
-    print(json.dumps(dict(kind=args.kind, path=mcts.last_path, graph=bool(args.graph), roots=N, sims=S, actions=A,
+    print(json.dumps(dict(kind=args.kind, fused=bool(args.fused), path=mcts.last_path, graph=bool(args.graph), roots=N, sims=S, actions=A,
                           considered=m if gumbel else None, hidden=args.hidden, ms=[round(v, 4) for v in ms],
                           median_ms=round(float(np.median(ms)), 4), checksum=check)))
 
