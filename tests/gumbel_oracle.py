@@ -242,12 +242,29 @@ class GumbelTree:
         return out
 
 
+def legal_lists(g):
+    """a transcript's root legal lists, in the order the reference was given them: the stored legal_lists
+    (int32 [B, A], -1 padded) when present, the mask's ascending order otherwise"""
+    if "legal_lists" in g.files:
+        return [[int(a) for a in row if a >= 0] for row in g["legal_lists"]]
+    B, A = g["legal_mask"].shape
+    return [[a for a in range(A) if g["legal_mask"][i, a]] for i in range(B)]
+
+
+def visits_full():
+    """gmz_visits_full.npz as [(m, S, row)]: the reference's considered-visits row of every m in [0, 66] and
+    S in {1..64, 100, 200}"""
+    f = np.load(os.path.join(GOLDEN, "gmz_visits_full.npz"))
+    rows = f["rows"]
+    return [(int(m), int(S), rows[off:off + S].tolist()) for m, S, off in f["index"]]
+
+
 def replay(g, feed=None):
     """Run the restatement over a transcript's inputs (a loaded gmz_*.npz) and its fed outputs (or `feed`: dict
     with resp_reward / resp_value / resp_logits). Returns the tree and the per-simulation requests."""
     B, S, A, m, noise = (int(v) for v in g["meta"])
     disc, nw = F(g["consts"][0]), F(g["consts"][1])
-    legal = [[a for a in range(A) if g["legal_mask"][i, a]] for i in range(B)]
+    legal = legal_lists(g)
     t = GumbelTree(legal, A)
     noises = [g["noises"][i, :len(legal[i])] for i in range(B)] if noise else None
     t.prepare(nw, noises, g["root_reward"], g["root_value"], g["root_logits"], g["to_play"])

@@ -19,7 +19,7 @@ from lightzero_amd import _lib  # noqa: E402
 
 DEV = torch.device("cuda", 0)
 CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(go.GOLDEN, "gmz_*.npz"))
-               if not p.endswith("gmz_tables.npz"))
+               if not p.endswith(("gmz_tables.npz", "gmz_visits_full.npz")))
 RAGGED = [[0, 1, 2, 3], [1, 3], [2]]
 
 
@@ -57,7 +57,7 @@ def test_module_api_replays_reference_transcript(name):
     g = np.load(os.path.join(go.GOLDEN, name + ".npz"))
     B, S, A, m, noise = (int(v) for v in g["meta"])
     disc, nw = float(g["consts"][0]), float(g["consts"][1])
-    legal = [[a for a in range(A) if g["legal_mask"][i, a]] for i in range(B)]
+    legal = go.legal_lists(g)  # in the order the reference was given them: lane j is legal position j
     to_play = g["to_play"].tolist()
     roots = gmz_tree.Roots(B, legal)
     if noise:
@@ -93,8 +93,65 @@ def test_module_api_replays_reference_transcript(name):
     roots.clear()
 
 
+@pytest.mark.parametrize("name", CASES)
+def test_decode_backprop_traverse_replays_transcripts(name):
+    """the launch the search loop really uses (gumbel_decode_backprop_traverse; gumbel_decode_backprop for the last
+    simulation) over every transcript's inputs: the scripted reward / value go in as scalar-head outputs, so the
+    kernel decodes them (the inverse scalar transform) and the restatement is fed what the kernel decoded"""
+    from lightzero_amd.tree import DeviceTree, new_minmax
+    g = np.load(os.path.join(go.GOLDEN, name + ".npz"))
+    B, S, A, m, noise = (int(v) for v in g["meta"])
+    disc, nw = float(g["consts"][0]), float(g["consts"][1])
+    lists = go.legal_lists(g)
+    d = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(DEV)
+    vtp = d(g["to_play"], np.int32)
+    t = DeviceTree(B, A, S, gumbel=True, device=DEV)
+    t.prepare(d(go.pad(lists, A), np.int32), d([len(l) for l in lists], np.int32),
+              d(g["noises"], np.float32) if noise else None, nw if noise else 0.0, d(g["root_reward"], np.float32),
+              d(g["root_logits"], np.float32), vtp)
+    t.set_root_values(d(g["root_value"], np.float32))
+    mm = new_minmax(B, 0.01, DEV)
+    r, v = d(g["resp_reward"][..., None], np.float32), d(g["resp_value"][..., None], np.float32)
+    p = d(g["resp_logits"], np.float32)
+    decoded = torch.zeros((S, B, 2), dtype=torch.float32, device=DEV)
+    req = torch.zeros((S, 5, B), dtype=torch.int32, device=DEV)
+    t.gumbel_traverse(S, m, disc, vtp)
+    for k in range(S):
+        req[k] = torch.stack([t.x, t.y, t.action, t.vtp, t.search_len])
+        args = (k + 1, disc, mm, r[k], v[k], False, p[k], t.vtp)
+        if k + 1 < S:
+            t.gumbel_decode_backprop_traverse(*args, S, m, vtp, out_decoded=decoded[k])
+        else:
+            t.gumbel_decode_backprop(*args, out_decoded=decoded[k])
+    dec, req = decoded.cpu().numpy(), req.cpu().numpy()
+    assert np.all(np.isfinite(dec))
+    ot, want = go.replay(g, dict(resp_reward=dec[..., 0], resp_value=dec[..., 1], resp_logits=g["resp_logits"]))
+    for j, key in enumerate(("x", "y", "a", "vtp", "len")):
+        assert np.array_equal(req[:, j], want[key]), key
+    dv = dict(dist=t.distributions().cpu().numpy(), values=t.values().cpu().numpy(),
+              traj=t.trajectories(S + 2).cpu().numpy(), policies=t.policies(disc).cpu().numpy(),
+              children=t.children_values(disc).cpu().numpy())
+    mmv = mm[:, :2].cpu().numpy()
+    t.close()
+    assert_same_outputs(dv, oracle_outputs(ot, disc, A, S))
+    assert same_bits(mmv, np.array(ot.minmax, np.float32))
+
+
 # ------------------------------------------------------------------------------------------- the search
-def mlp_model(A, H=32, zero_heads=False, categorical=True, seed=0, support_scale=10):
+def sharpen_heads(model, k):
+    """the weights and bias of the last linear layer of the policy, value and reward heads times k: at k = 30 the
+    policy logits spread past 104 (expf underflows: priors that are exact zeros) and the categorical heads collapse
+    onto single support bins (decoded values on a sparse, wide grid with many exact ties)"""
+    with torch.no_grad():
+        for head in (model.prediction_network.fc_policy_head, model.prediction_network.fc_value_head,
+                     model.dynamics_network.fc_reward_head):
+            last = [mod for mod in head.modules() if isinstance(mod, torch.nn.Linear)][-1]
+            last.weight.mul_(k)
+            last.bias.mul_(k)
+    return model
+
+
+def mlp_model(A, H=32, zero_heads=False, categorical=True, seed=0, support_scale=10, sharpen=None):
     from lightzero_amd.model_mlp import MuZeroModelMLP
     torch.manual_seed(seed)
     V = 2 * support_scale + 1
@@ -107,6 +164,8 @@ def mlp_model(A, H=32, zero_heads=False, categorical=True, seed=0, support_scale
             with torch.no_grad():
                 mod.running_mean.copy_(torch.randn(mod.running_mean.shape, generator=g) * 0.1)
                 mod.running_var.copy_(torch.rand(mod.running_var.shape, generator=g) * 0.5 + 0.75)
+    if sharpen is not None:
+        sharpen_heads(m, sharpen)
     return m.to(DEV).eval()
 
 

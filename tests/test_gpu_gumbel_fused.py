@@ -26,7 +26,7 @@ from mlp_numerics import check_search_network  # noqa: E402
 DEV = torch.device("cuda", 0)
 
 
-def wide_model(A, H, F, scale, seed=0, zero_heads=False):
+def wide_model(A, H, F, scale, seed=0, zero_heads=False, sharpen=None):
     """test_gpu_gumbel.mlp_model with the heads' hidden width F"""
     from lightzero_amd.model_mlp import MuZeroModelMLP
     torch.manual_seed(seed)
@@ -41,6 +41,8 @@ def wide_model(A, H, F, scale, seed=0, zero_heads=False):
             with torch.no_grad():
                 mod.running_mean.copy_(torch.randn(mod.running_mean.shape, generator=g) * 0.1)
                 mod.running_var.copy_(torch.rand(mod.running_var.shape, generator=g) * 0.5 + 0.75)
+    if sharpen is not None:
+        tg.sharpen_heads(m, sharpen)
     return m.to(DEV).eval()
 
 
@@ -86,8 +88,8 @@ def prepare(roots, x, noise, to_play):
 
 def run_search(model, B, A, S, m, legal=None, noise=True, discount=0.997, categorical=True, seed=0, support_scale=10,
                to_play=None, fused=True, path="fused-mlp", R=1, reserve=None):
-    """test_gpu_gumbel.run_search with cfg.fused_search; path: the path the search must report; R: the roots per
-    workgroup the plan must report; reserve: a fresh handle reserved for that many simulations (closed by
+    """test_gpu_gumbel.run_search with cfg.fused_search; path: the path the search must report (None: the one
+    launch exactly when the library's plan takes the shape); R: the roots per workgroup the plan must report; reserve: a fresh handle reserved for that many simulations (closed by
     finish()) instead of a pooled one of the default capacity. Returns its result dict plus model, pool, plan."""
     from lightzero_amd.mcts_ctree import GumbelMuZeroMCTSCtree
     from lightzero_amd.tree import DeviceTree
@@ -99,6 +101,9 @@ def run_search(model, B, A, S, m, legal=None, noise=True, discount=0.997, catego
         roots.tree = DeviceTree(B, A, reserve, gumbel=True, device=DEV)
     prepare(roots, x, noise, to_play)
     mcts.search(roots, model, x["lat0"], to_play)
+    if path is None:
+        took = roots.tree.search_mlp_gumbel_plan(mcts._packed.get(model, DEV)[1], S)["kernel"] is not None
+        path = "fused-mlp" if took else "generic"
     assert mcts.last_path == path
     plan = None
     if path == "fused-mlp":
@@ -162,6 +167,85 @@ def test_zeroed_heads_all_ties():
     assert np.all(r["rec"]["policy_logits"] == r["rec"]["policy_logits"][..., :1])
     assert np.all(r["rec"]["decoded"] == 0)
     tg.assert_matches_restatement(r, 5, 12, 4)
+    finish(r)
+
+
+# ------------------------------------------------------------------------------------------- float and shape edges
+A64_RAGGED = [list(range(64)), [a for a in range(64) if a % 3 != 0], [63]]
+PERM9 = [list(range(9))[::-1], [8, 2], [5, 0, 7, 1, 3], [4]]
+
+
+def assert_sharp(r, extreme):
+    """extreme (sharpen 400): the policy logits spread past 104, where expf underflows and priors become exact
+    zeros, and the categorical heads sit on single support bins, so decoded values repeat exactly (these models'
+    logits spread about 0.34 per unit of sharpening: 10 at 30, 34 at 100, 135 at 400)"""
+    dec = r["rec"]["decoded"]
+    assert np.all(np.isfinite(dec)) and np.all(np.isfinite(r["rec"]["policy_logits"]))
+    if extreme:
+        assert np.ptp(r["rec"]["policy_logits"], axis=-1).min() > 104
+        assert np.unique(dec[..., 1]).size < dec[..., 1].size
+
+
+@pytest.mark.parametrize("sharpen", [30, 100, 400])
+@pytest.mark.parametrize("fused", [True, None])
+def test_sharpened_heads(sharpen, fused):
+    """(fused None: the twin on the generic path, so both kernels see the same regime)"""
+    B, A, S, m = 4, 6, 30, 4
+    model = tg.mlp_model(A, seed=B + A, sharpen=sharpen)
+    r = run_search(model, B, A, S, m, seed=B + S, fused=fused, path="generic" if fused is None else "fused-mlp")
+    assert_sharp(r, sharpen >= 400)
+    tg.assert_matches_restatement(r, A, S, m)
+    finish(r)
+
+
+def test_sharpened_heads_wide_ragged():
+    """A = 64 = H with ragged roots that miss action 0 or hold only action 63; 4,161 nodes per root: the tree in HBM"""
+    B, A, S, m = 3, 64, 40, 16
+    model = tg.mlp_model(A, H=64, seed=B + A, sharpen=30)
+    r = run_search(model, B, A, S, m, legal=A64_RAGGED, seed=B + S)
+    assert r["plan"]["tree_in_lds"] is False
+    assert_sharp(r, False)
+    tg.assert_matches_restatement(r, A, S, m)
+    finish(r)
+
+
+def test_deepest_path():
+    """one action, 64 simulations: every walk one node longer than the last, the 64th 64 long, at the pooled
+    handle's full capacity (depth_cap = 66 path entries in the workgroup's LDS slice)"""
+    B, A, S, m = 3, 1, 64, 4
+    r = run_search(tg.mlp_model(A, seed=B + A), B, A, S, m, seed=B + S, path=None)
+    assert r["roots"].tree.sims_capacity == S
+    assert r["rec"]["search_len"].tolist() == [[k + 1] * B for k in range(S)]
+    if r["plan"] is not None:
+        assert r["plan"]["tree_in_lds"] is True
+    tg.assert_matches_restatement(r, A, S, m)
+    finish(r)
+
+
+@pytest.mark.parametrize("S,m", [(33, 0), (33, 3), (33, 5), (33, 7), (64, 5)])
+def test_odd_considered_counts(S, m):
+    """sequential halving with m no power of two and m = 0; (64, 5) at the pooled handle's full capacity"""
+    B, A = 4, 9
+    r = run_search(tg.mlp_model(A, seed=B + A + m), B, A, S, m, seed=S + m)
+    tg.assert_matches_restatement(r, A, S, m)
+    finish(r)
+
+
+@pytest.mark.parametrize("R", [1, 2])
+def test_permuted_legal_lists(R, monkeypatch):
+    """legal lists that are not ascending: lane j is legal position j, the noise and the Gumbel vector are by
+    position, and only the root outputs map position back to action"""
+    monkeypatch.setenv("LZM_ROOTS_PER_WG", str(R))
+    B, A, S, m = 4, 9, 20, 4
+    r = run_search(tg.mlp_model(A, seed=B + A), B, A, S, m, legal=PERM9, seed=B + S, R=R)
+    tg.assert_matches_restatement(r, A, S, m)
+    finish(r)
+
+
+def test_discount_zero():
+    B, A, S, m = 4, 4, 8, 4
+    r = run_search(tg.mlp_model(A, seed=B + A), B, A, S, m, seed=B + S, discount=0.0)
+    tg.assert_matches_restatement(r, A, S, m)
     finish(r)
 
 

@@ -46,6 +46,18 @@ def test_considered_visits_rows(tables):
     assert L.lzm_gumbel_considered_visits(4, 8, None) == _lib.LZM_ERR_ARG
 
 
+def test_considered_visits_every_row():
+    """every reference row m in [0, 66] x S in {1..64, 100, 200}: m = 0, m no power of two, m > S"""
+    full = np.load(os.path.join(GOLDEN, "gmz_visits_full.npz"))
+    rows, index = full["rows"], full["index"]
+    assert len(index) == 4422
+    L = _lib.load()
+    for m, S, off in index.tolist():
+        out = (ctypes.c_int32 * S)()
+        assert L.lzm_gumbel_considered_visits(m, S, out) == _lib.LZM_OK, (m, S)
+        assert list(out) == rows[off:off + S].tolist(), (m, S)
+
+
 def test_gmz_tree_surface_and_type_errors():
     from lightzero_amd.ctree import gmz_tree
     assert sorted(gmz_tree.__all__) == sorted(
