@@ -458,6 +458,26 @@ void lzo_get_values(const lzo_tree *t, float *out) { /* CRoots::get_values, cnod
   for (i = 0; i < t->B; ++i) out[i] = node_value(t, NODE(t, i, 0));
 }
 
+/* The reference has no getter for these two (tests only): each root's (maximum, minimum) min-max pair as the
+ * last backup left it, and the root children's priors after the noise mix, in legal-list order, -1 padded. */
+void lzo_get_minmax(const lzo_tree *t, float *out) {
+  int i;
+  for (i = 0; i < t->B; ++i) {
+    out[2 * i] = t->mms[i].maximum;
+    out[2 * i + 1] = t->mms[i].minimum;
+  }
+}
+
+void lzo_get_root_priors(const lzo_tree *t, float *out) {
+  int i, j;
+  for (i = 0; i < t->B; ++i) {
+    for (j = 0; j < t->A; ++j) out[(size_t)i * t->A + j] = -1.0f;
+    if (t->latent[NODE(t, i, 0)] < 0) continue;
+    for (j = 0; j < t->nlegal[i]; ++j)
+      out[(size_t)i * t->A + j] = t->prior[NODE(t, i, child_of(t, i, 0, t->legal[(size_t)i * t->A + j]))];
+  }
+}
+
 /* CRoots::get_trajectories / CNode::get_trajectory, cnode.cpp:237-257, :369-385 */
 int lzo_get_trajectories(const lzo_tree *t, int32_t *out, int tmax) {
   int i, longest = 0;

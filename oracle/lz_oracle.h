@@ -49,6 +49,10 @@ void lzo_backprop(lzo_tree *t, int current_latent_state_index, float discount, c
 void lzo_get_distributions(const lzo_tree *t, int32_t *out /*[B][A], -1 padded*/);
 void lzo_get_values(const lzo_tree *t, float *out);
 int lzo_get_trajectories(const lzo_tree *t, int32_t *out /*[B][tmax], -1 padded*/, int tmax);
+/* Not in the reference (tests only): the (maximum, minimum) pair of every root's min-max stats, and the root
+ * children's priors after the noise mix in legal-list order. */
+void lzo_get_minmax(const lzo_tree *t, float *out /*[B][2]*/);
+void lzo_get_root_priors(const lzo_tree *t, float *out /*[B][A], -1 padded*/);
 /* Diagnostics (tests only). lzo_get_path_actions: root i's last traverse path as actions, returns its
  * length. lzo_path_scores: the pUCT scores cselect_child computes at each level of root i's walk down
  * `actions` (n of them) in the tree as it stands — the mean-q chain as cbatch_traverse carries it from

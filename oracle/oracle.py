@@ -48,6 +48,8 @@ def lib():
                                    ctypes.c_void_p, _i32p]
         L.lzo_get_distributions.argtypes = [ctypes.c_void_p, _i32p]
         L.lzo_get_values.argtypes = [ctypes.c_void_p, _f32p]
+        L.lzo_get_minmax.argtypes = [ctypes.c_void_p, _f32p]
+        L.lzo_get_root_priors.argtypes = [ctypes.c_void_p, _f32p]
         L.lzo_get_trajectories.restype = ctypes.c_int
         L.lzo_get_trajectories.argtypes = [ctypes.c_void_p, _i32p, ctypes.c_int]
         L.lzo_glibc_srand.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
@@ -130,6 +132,18 @@ class OracleTree:
         lib().lzo_get_values(self._h, out)
         return out
 
+    def minmax(self):
+        """float32 [B, 2]: every root's (maximum, minimum) as the last backup left it (no getter in the reference)"""
+        out = np.zeros((self.B, 2), np.float32)
+        lib().lzo_get_minmax(self._h, out)
+        return out
+
+    def root_priors(self):
+        """float32 [B, A]: the root children's priors after the noise mix, in legal-list order, -1 padded"""
+        out = np.zeros((self.B, self.A), np.float32)
+        lib().lzo_get_root_priors(self._h, out)
+        return out
+
     def path_actions(self, i):
         """root i's last traverse path as actions (diagnostics)"""
         out = np.zeros(self.B * 4 + 64, np.int32)
@@ -167,14 +181,26 @@ def load_transcript(path):
         return {k: z[k] for k in z.files}
 
 
-def replay_transcript(tr, tree_factory=None, check=True):
+def transcript_legal(tr):
+    """(legal int32 [B, A] -1 padded, count int32 [B]): the root legal lists in the order the reference was given
+    them: the stored ``legal_lists`` where a transcript has them, ascending from the mask otherwise"""
+    if "legal_lists" not in tr:
+        return legal_from_mask(tr["legal_mask"])
+    legal = np.ascontiguousarray(tr["legal_lists"], np.int32)
+    return legal, (legal >= 0).sum(axis=1).astype(np.int32)
+
+
+def replay_transcript(tr, tree_factory=None, check=True, keep=None):
     """Replay a golden transcript through a tree object with the OracleTree interface.
 
-    Returns a dict of mismatches (empty when everything is bit-exact)."""
+    Returns a dict of mismatches (empty when everything is bit-exact). keep: a dict that receives the tree
+    ("tree") as the replay left it."""
     B, S, A, players, noise, ez, horizon = [int(v) for v in tr["meta"]]
     pb_c_base, pb_c_init, disc, vdm, nw = [float(v) for v in tr["consts"]]
     t = (tree_factory or OracleTree)(B, A, S, ez=bool(ez))
-    legal, cnt = legal_from_mask(tr["legal_mask"])
+    if keep is not None:
+        keep["tree"] = t
+    legal, cnt = transcript_legal(tr)
     t.set_legal(legal, cnt)
     t.set_delta(np.float32(vdm))
     t.prepare(np.float32(nw), tr["noises"] if noise else None, tr["root_reward"], tr["root_logits"], tr["to_play"])

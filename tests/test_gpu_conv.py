@@ -42,7 +42,8 @@ def conv_model(kind, seed=0, zero_heads=False, factory=None):
 
 
 def run_search(kind, B, S, seed, graph=False, record=True, model=None, mcts=None, fused=True, rng="glibc",
-               horizon=5, discount=0.997, legal=None, to_play=None, categorical=True, scales=None, direct=False, check=False, fresh_tree=False):
+               horizon=5, discount=0.997, legal=None, to_play=None, categorical=True, scales=None, direct=False, check=False, fresh_tree=False,
+               pb_c_base=PB_C_BASE, pb_c_init=float(PB_C_INIT), value_delta_max=float(VDM)):
     """horizon: lstm_horizon_len; legal: per-root legal action lists (default: every action); to_play: per-root
     players (default -1: one player); categorical / scales = (reward, value) support scales: the heads' kind
     (default: categorical with the Atari scale of `kind` for both); direct: the search is fed random
@@ -75,7 +76,8 @@ def run_search(kind, B, S, seed, graph=False, record=True, model=None, mcts=None
         logits0 = out.policy_logits.float().cpu().numpy()
     noises = rng_np.dirichlet([0.3] * A, size=B).astype(np.float32)
     cfg = EasyDict(dict(num_simulations=S, discount_factor=discount, device=DEV, lstm_horizon_len=horizon,
-                        use_hip_graph=graph, fused_search=fused,
+                        use_hip_graph=graph, fused_search=fused, pb_c_base=int(pb_c_base), pb_c_init=float(pb_c_init),
+                        value_delta_max=float(value_delta_max),
                         model=dict(support_scale=scales[0], categorical_distribution=categorical)))
     cls = EfficientZeroMCTSCtree if kind == "ez" else MuZeroMCTSCtree
     mcts = cls(cfg) if mcts is None else mcts
@@ -104,7 +106,8 @@ def run_search(kind, B, S, seed, graph=False, record=True, model=None, mcts=None
     res = dict(dist=t.distributions().cpu().numpy(), values=t.values().cpu().numpy(),
                traj=t.trajectories(S + 2).cpu().numpy(), noises=noises, logits0=logits0, model=model,
                lat0=lat0, hidden0=hidden0, A=A, scale=scales[0], scales=scales, categorical=categorical,
-               horizon=horizon, discount=discount, legal=legal, to_play=to_play,
+               horizon=horizon, discount=discount, legal=legal, to_play=to_play, pb_c_base=int(pb_c_base),
+               pb_c_init=np.float32(pb_c_init), value_delta_max=np.float32(value_delta_max),
                errors=t.check_errors() if check else None)
     res["rec"] = None if mcts.last_record is None else mcts.last_record.numpy() | (
         {"is_reset": mcts.last_record.is_reset.cpu().numpy()} if kind == "ez" else {})
@@ -125,10 +128,11 @@ def oracle_replay(kind, res, B, S):
         for i, l in enumerate(res["legal"]):
             la[i, :len(l)] = l
         ot.set_legal(la, np.array([len(l) for l in res["legal"]], np.int32))
-    ot.set_delta(VDM)
+    ot.set_delta(res.get("value_delta_max", VDM))
     ot.prepare(NOISE_W, res["noises"], np.zeros(B, np.float32), res["logits0"], to_play)
     for k in range(S):
-        x, y, a, vtp, slen = ot.traverse(PB_C_BASE, PB_C_INIT, disc, int(rec["seeds"][k]), to_play)
+        x, y, a, vtp, slen = ot.traverse(res.get("pb_c_base", PB_C_BASE), res.get("pb_c_init", PB_C_INIT), disc,
+                                         int(rec["seeds"][k]), to_play)
         assert np.array_equal(x, rec["x"][k]), f"sim {k}: latent index differs"
         assert np.array_equal(a, rec["action"][k]), f"sim {k}: action differs"
         assert np.array_equal(slen, rec["search_len"][k]), f"sim {k}: search_len differs"

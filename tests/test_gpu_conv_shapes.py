@@ -23,7 +23,8 @@ planes 2 / 6 / 14, head planes 2 .. 16); dead K-parts of the head hidden layers 
 off_policy != Khd / 2; the MuZero output loop at N2 <= 768, = 768, = 769 and three rounds; the EfficientZero
 single-round / multi-round output forms on either side of 256 columns; scalar heads; unequal reward / value
 supports; 1 .. 18 actions, ragged legal sets, two players, discount 1 and 0.9; lstm_horizon_len 1, 3 and
-S + 1; LSTM widths 128 / 256 / 1024 with 1 .. 129 roots (row blocks holding one live row, more roots than
+S + 1, and at A = 2 the settings away from the defaults (pb_c_base / pb_c_init (5, 0) and (100, 2.5),
+value_delta_max 0 and 10, discount 1 and 0.5, horizon 1 and S + 5); LSTM widths 128 / 256 / 1024 with 1 .. 129 roots (row blocks holding one live row, more roots than
 tiles, 2 T > B); S = 1, 2, the pb_c table switch and the LDS boundary; Philox mode and the all-tie search.
 Shapes the kernels refuse (supports past 1024, more than 8 residual blocks, a hidden width other than 32, a tree
 past the LDS plan, a grid that cannot be co-resident) take another path without raising and equal the oracle.
@@ -166,6 +167,22 @@ CASES = [
     c("ez-H128-B65-philox", "ez", 65, 8, 1, dict(H=128), rng="philox", plan=dict(lstm_tiles=16, workgroups=65)),
     c("mz-head6x10-zero", "mz", 14, 10, 1, dict(hv=6, hp=10), zero=True),
     c("ez-rch6-zero", "ez", 13, 10, 3, dict(r_ch=6), zero=True, plan=EZ1),
+    # ---- settings away from the reference's defaults, at the A = 2 shape: the pb_c table (and the triangular table
+    # built from it), mm_normalize's value_delta_max branch never / always taken, the discount, the horizon's ends
+    c("mz-pbc5-init0", "mz", 7, 10, 1, dict(A=2), dict(pb_c_base=5, pb_c_init=0.0)),
+    c("mz-pbc100-init2.5", "mz", 7, 10, 1, dict(A=2), dict(pb_c_base=100, pb_c_init=2.5)),
+    c("mz-vdm0", "mz", 7, 10, 1, dict(A=2), dict(value_delta_max=0.0)),
+    c("mz-vdm10", "mz", 7, 10, 1, dict(A=2), dict(value_delta_max=10.0)),
+    c("mz-A2-disc1", "mz", 7, 10, 1, dict(A=2), dict(discount=1.0)),
+    c("mz-A2-disc05", "mz", 7, 10, 1, dict(A=2), dict(discount=0.5)),
+    c("ez-pbc5-init0", "ez", 7, 10, 1, dict(A=2), dict(pb_c_base=5, pb_c_init=0.0), plan=EZ1),
+    c("ez-pbc100-init2.5", "ez", 7, 10, 1, dict(A=2), dict(pb_c_base=100, pb_c_init=2.5), plan=EZ1),
+    c("ez-vdm0", "ez", 7, 10, 1, dict(A=2), dict(value_delta_max=0.0), plan=EZ1),
+    c("ez-vdm10", "ez", 7, 10, 1, dict(A=2), dict(value_delta_max=10.0), plan=EZ1),
+    c("ez-A2-disc1", "ez", 7, 10, 1, dict(A=2), dict(discount=1.0), plan=EZ1),
+    c("ez-A2-disc05", "ez", 7, 10, 1, dict(A=2), dict(discount=0.5), plan=EZ1),
+    c("ez-A2-horizon1", "ez", 7, 10, 1, dict(A=2), dict(horizon=1), plan=EZ1),
+    c("ez-A2-horizonS5", "ez", 7, 10, 1, dict(A=2), dict(horizon=15), plan=EZ1),
 ]
 
 

@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 from oracle.oracle import OracleTree  # noqa: E402
 from tests.helpers import DISC, NOISE_W, PB_C_BASE, PB_C_INIT, VDM  # noqa: E402
 from tests.mlp_numerics import check_scaled, inverse_scalar_transform64  # noqa: E402
-from tests.test_gpu_fused import DEV  # noqa: E402
+from tests.test_gpu_fused import DEV, SETTINGS, settings_id  # noqa: E402
 
 
 def make_ez_model(A, H, Hl, zero_heads=False, seed=0, support_scale=300, res=False):
@@ -43,7 +43,7 @@ def make_ez_model(A, H, Hl, zero_heads=False, seed=0, support_scale=300, res=Fal
 
 
 def ez_fused_search(B, S, A=2, H=128, Hl=128, horizon=5, zero_heads=False, players=1, fast=False, seed=0,
-                    support_scale=300, res=False, fused=True, ragged=False):
+                    support_scale=300, res=False, fused=True, ragged=False, settings=None):
     """tests/test_gpu_fused.py's fused_search for EfficientZeroMCTSCtree over an EfficientZeroModelMLP: a seeded
     model with randomised BatchNorm statistics, Dirichlet noise, SequentialSeeds and record = True; the roots'
     LSTM state is random. ragged: random legal subsets per root. Returns the record (with is_reset),
@@ -64,8 +64,8 @@ def ez_fused_search(B, S, A=2, H=128, Hl=128, horizon=5, zero_heads=False, playe
     legal = [list(range(A))] * B
     if ragged:
         legal = [sorted(rng.choice(A, size=int(rng.integers(1, A + 1)), replace=False).tolist()) for _ in range(B)]
-    cfg = EasyDict(dict(num_simulations=S, discount_factor=float(DISC), device=DEV, lstm_horizon_len=horizon,
-                        model=dict(support_scale=support_scale, categorical_distribution=True)))
+    cfg = EasyDict(dict(dict(num_simulations=S, discount_factor=float(DISC), device=DEV, lstm_horizon_len=horizon,
+                             model=dict(support_scale=support_scale, categorical_distribution=True)), **(settings or {})))
     cls = EfficientZeroMCTSCtree
     old = cls.rng_mode
     cls.rng_mode = "philox" if fast else "glibc"
@@ -98,7 +98,18 @@ def ez_fused_search(B, S, A=2, H=128, Hl=128, horizon=5, zero_heads=False, playe
         cls.rng_mode = old
 
 
-def check_oracle(r):
+def check_tree_exact(B, S, pb_c_base=PB_C_BASE, pb_c_init=PB_C_INIT, value_delta_max=VDM, discount=DISC, horizon=5,
+                     **search_kw):
+    """tests/test_gpu_fused.py's check_tree_exact for the EfficientZero search: the settings go both to the search
+    cfg and to the oracle; the root values bit for bit"""
+    pb_c_init, value_delta_max, discount = np.float32(pb_c_init), np.float32(value_delta_max), np.float32(discount)
+    settings = dict(pb_c_base=int(pb_c_base), pb_c_init=float(pb_c_init), value_delta_max=float(value_delta_max),
+                    discount_factor=float(discount))
+    r = fused(ez_fused_search(B, S, horizon=horizon, settings=settings, **search_kw))
+    return check_oracle(r, pb_c_base, pb_c_init, value_delta_max, discount, exact_values=True)
+
+
+def check_oracle(r, pb_c_base=PB_C_BASE, pb_c_init=PB_C_INIT, value_delta_max=VDM, discount=DISC, exact_values=False):
     """OracleTree(ez=True) fed the recorded network outputs and is_reset reproduces the run
     (tests/test_gpu_conv.py's oracle_replay, with the Philox form of tests/test_gpu_fused.py)"""
     rec, B, S, A, horizon = r["rec"], r["B"], r["S"], r["A"], r["horizon"]
@@ -109,20 +120,22 @@ def check_oracle(r):
     for i, l in enumerate(r["legal"]):
         la[i, :len(l)] = l
     ot.set_legal(la, np.array([len(l) for l in r["legal"]], np.int32))
-    ot.set_delta(VDM)
+    ot.set_delta(value_delta_max)
     ot.prepare(NOISE_W, r["noises"], np.zeros(B, np.float32), r["logits0"], r["to_play"])
     for k in range(S):
-        x, y, a, vtp, slen = ot.traverse(PB_C_BASE, PB_C_INIT, DISC, int(rec["seeds"][k]), r["to_play"])
+        x, y, a, vtp, slen = ot.traverse(pb_c_base, pb_c_init, discount, int(rec["seeds"][k]), r["to_play"])
         assert np.array_equal(x, rec["x"][k]), f"sim {k}: latent index differs"
         assert np.array_equal(a, rec["action"][k]), f"sim {k}: action differs"
         assert np.array_equal(slen, rec["search_len"][k]), f"sim {k}: search_len differs"
         is_reset = (slen % horizon == 0).astype(np.int32)
         assert np.array_equal(is_reset, rec["is_reset"][k]), f"sim {k}: is_reset differs"
-        ot.backprop(k + 1, DISC, rec["decoded"][k][:, 0], rec["decoded"][k][:, 1], rec["policy_logits"][k], vtp,
+        ot.backprop(k + 1, discount, rec["decoded"][k][:, 0], rec["decoded"][k][:, 1], rec["policy_logits"][k], vtp,
                     is_reset)
     assert np.array_equal(r["dist"], ot.distributions())
     assert np.array_equal(r["traj"], ot.trajectories(S + 2))
     np.testing.assert_allclose(r["values"], ot.values(), rtol=0, atol=1e-5)
+    if exact_values:
+        assert np.array_equal(r["values"].view(np.uint32), ot.values().view(np.uint32))
     return r
 
 
@@ -245,6 +258,20 @@ def test_all_tie_trees_resolved_serially():
 @pytest.mark.parametrize("zero_heads", [False, True], ids=["rand", "zero"])
 def test_philox(zero_heads):
     check_oracle(fused(ez_fused_search(16, 20, zero_heads=zero_heads, fast=True, seed=4)))
+
+
+# tests/test_gpu_fused.py's settings on the EfficientZero kernel (it has the weight-streaming form only), and the
+# horizon's two ends: every leaf resets, none does (S + 5)
+@pytest.mark.parametrize("A", [2, 3])
+@pytest.mark.parametrize("settings", SETTINGS + [dict(horizon=1), dict(horizon=35)], ids=settings_id)
+def test_one_launch_kernel_at_other_settings(settings, A):
+    B, S = 16, 30
+    r = check_tree_exact(B, S, A=A, H=64, Hl=128, seed=A, **settings)
+    assert r["plan"]["kernel"] == "streaming", r["plan"]  # (ez_fused_search asserts last_path == "fused-mlp")
+    rst = r["rec"]["is_reset"]
+    if "horizon" in settings:
+        assert rst.all() if settings["horizon"] == 1 else not rst.any()
+    assert r["rec"]["search_len"].max() >= 3
 
 
 def test_refused_width_takes_the_generic_path():

@@ -43,11 +43,12 @@ def make_model(A, H, zero_heads, seed=0, support_scale=300, res=True, head_hidde
 
 
 def fused_search(B, S, A, H, zero_heads, players, fast, seed, support_scale=300, tree_sims=None, fused=True,
-                 **model_kw):
+                 settings=None, **model_kw):
     """tree_sims: run on a fresh tree handle of that simulation capacity (closed afterwards) instead of a
     pooled one of the default capacity: the handle's capacity sizes the resident kernel's LDS plan, so it
     decides which kernel runs (res["plan"], DeviceTree.search_mlp_plan). fused=False: the model is
-    expected to take the generic per-simulation path. model_kw: further make_model arguments."""
+    expected to take the generic per-simulation path. settings: search cfg entries that replace the defaults
+    (pb_c_base, pb_c_init, value_delta_max, discount_factor). model_kw: further make_model arguments."""
     from lightzero_amd.mcts_ctree import MuZeroMCTSCtree
     from lightzero_amd.tree import DeviceTree, SequentialSeeds, set_seed_source
     from lightzero_amd.utils import EasyDict
@@ -59,8 +60,8 @@ def fused_search(B, S, A, H, zero_heads, players, fast, seed, support_scale=300,
     logits0 = out.policy_logits.float().cpu().numpy()
     noises = rng.dirichlet([0.3] * A, size=B).astype(np.float32)
     to_play = [-1] * B if players == 1 else rng.integers(1, 3, size=B).tolist()
-    cfg = EasyDict(dict(num_simulations=S, discount_factor=float(DISC), device=DEV,
-                        model=dict(support_scale=support_scale, categorical_distribution=True)))
+    cfg = EasyDict(dict(dict(num_simulations=S, discount_factor=float(DISC), device=DEV,
+                             model=dict(support_scale=support_scale, categorical_distribution=True)), **(settings or {})))
     cls = MuZeroMCTSCtree
     old = cls.rng_mode
     cls.rng_mode = "philox" if fast else "glibc"
@@ -155,25 +156,51 @@ def test_resident_kernel_serves_config2():
     assert L.lzm_search_mlp_kind(4096, 2, 128, 32, 601, 1) == 0  # several roots per workgroup
 
 
-def check_tree_exact(case):
+def check_tree_exact(case, pb_c_base=PB_C_BASE, pb_c_init=PB_C_INIT, value_delta_max=VDM, discount=DISC, **search_kw):
+    """pb_c_base / pb_c_init / value_delta_max / discount: passed both to the search cfg and to the oracle"""
     B, S, A, H, zero, players, fast = case
-    r = fused_search(B, S, A, H, zero, players, fast, seed=B + S + A)
+    pb_c_init, value_delta_max, discount = np.float32(pb_c_init), np.float32(value_delta_max), np.float32(discount)
+    settings = dict(pb_c_base=int(pb_c_base), pb_c_init=float(pb_c_init), value_delta_max=float(value_delta_max),
+                    discount_factor=float(discount))
+    r = fused_search(B, S, A, H, zero, players, fast, seed=B + S + A, settings=settings, **search_kw)
     rec = r["rec"]
     assert r["diag"][0] == 0, "look-back spin timeout or depth speculation mismatch"
     assert r["diag"][3] == 0, "depth speculation mismatch"
     ot = OracleTree(B, A, S, fast_rng=fast)
-    ot.set_delta(VDM)
+    ot.set_delta(value_delta_max)
     ot.prepare(NOISE_W, r["noises"], np.zeros(B, np.float32), r["logits0"], r["to_play"])
     for k in range(S):
-        x, y, a, vtp, slen = ot.traverse(PB_C_BASE, PB_C_INIT, DISC, int(rec["seeds"][k]), r["to_play"])
+        x, y, a, vtp, slen = ot.traverse(pb_c_base, pb_c_init, discount, int(rec["seeds"][k]), r["to_play"])
         assert np.array_equal(x, rec["x"][k]), f"x differs at sim {k}"
         assert np.array_equal(a, rec["action"][k]), f"action differs at sim {k}"
         assert np.array_equal(slen, rec["search_len"][k]), f"search_len differs at sim {k}"
-        ot.backprop(k + 1, DISC, rec["decoded"][k][:, 0], rec["decoded"][k][:, 1], rec["policy_logits"][k], vtp)
+        ot.backprop(k + 1, discount, rec["decoded"][k][:, 0], rec["decoded"][k][:, 1], rec["policy_logits"][k], vtp)
     assert np.array_equal(r["dist"], ot.distributions())
     assert np.array_equal(r["values"], ot.values())
     assert np.array_equal(r["traj"], ot.trajectories(S + 2))
     return r
+
+
+# settings away from the reference's defaults: the pb_c table (and the resident kernel's triangular table built from
+# it), mm_normalize's value_delta_max branch never / always taken, the discount at 1 and 0.5
+SETTINGS = [dict(pb_c_base=5, pb_c_init=0.0), dict(pb_c_base=100, pb_c_init=2.5), dict(value_delta_max=0.0),
+            dict(value_delta_max=10.0), dict(discount=1.0), dict(discount=0.5)]
+
+
+def settings_id(s):
+    return "_".join(f"{k}{v}" for k, v in s.items())
+
+
+# the smallest shapes: the resident kernel takes latent width 128 only (and a handle reserved for the search's own
+# length at A = 3), the weight-streaming kernel runs width 64
+@pytest.mark.parametrize("kernel,H", [("resident", 128), ("streaming", 64)])
+@pytest.mark.parametrize("A", [2, 3])
+@pytest.mark.parametrize("settings", SETTINGS, ids=settings_id)
+def test_one_launch_kernels_at_other_settings(settings, A, kernel, H):
+    B, S = 16, 30
+    r = check_tree_exact((B, S, A, H, False, 1, False), tree_sims=S, **settings)
+    assert r["path"] == "fused-mlp" and r["plan"]["kernel"] == kernel, (r["path"], r["plan"])
+    assert r["rec"]["search_len"].max() >= 3
 
 
 # support 601 decodes from registers across the workgroup; support 21 (< 512 lanes) through LDS

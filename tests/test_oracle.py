@@ -24,6 +24,89 @@ def test_oracle_reproduces_reference_transcript(path):
     assert not bad, bad
 
 
+# ---------------------------------------------------------------------- the setting, float, depth and list-order edges
+TREE_DIR = os.path.join(GOLDEN, "tree")
+EDGE_TRANSCRIPTS = sorted(glob.glob(os.path.join(TREE_DIR, "*.npz")))
+
+
+def edge_case_names():
+    """the names tests/golden/gen_golden.py lists (it imports nothing of the reference before main())"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("gen_golden", os.path.join(GOLDEN, "gen_golden.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return sorted(c["name"] for c in mod.EDGE_CASES)
+
+
+def test_every_edge_transcript_is_present():
+    """a missing fixture fails here: the parametrised replays below would only run fewer cases"""
+    names = edge_case_names()
+    assert len(names) == 44 and len(set(names)) == len(names)
+    assert [os.path.basename(p)[:-4] for p in EDGE_TRANSCRIPTS] == names
+
+
+def idea_of(path):
+    return os.path.basename(path)[:-4].split("_", 1)[1].rsplit("_b", 1)[0]
+
+
+@pytest.mark.parametrize("path", EDGE_TRANSCRIPTS, ids=lambda p: os.path.basename(p)[:-4])
+def test_oracle_reproduces_edge_transcript(path):
+    tr = load_transcript(path)
+    keep = {}
+    bad = replay_transcript(tr, keep=keep)
+    assert not bad, bad
+    # what the reference cannot show (it has no getter): read from the restatement after its bit-exact replay
+    t, idea = keep["tree"], idea_of(path)
+    B, S, A = (int(v) for v in tr["meta"][:3])
+    vdm = np.float32(tr["consts"][3])
+    mm = t.minmax()
+    span = mm[:, 0] - mm[:, 1]
+    if idea == "vdm_big":    # mm_normalize's delta < value_delta_max branch for the whole search
+        assert vdm == 10 and np.all(span > 0) and np.all(span < vdm), span
+    if idea == "vdm0":       # never
+        assert vdm == 0 and np.all(span > 0), span
+    if idea in ("big", "huge"):
+        assert np.all(np.isfinite(mm)), mm
+    if idea == "nw1":        # noise weight 1: the prior is the noise entry, exact zeros included
+        cnt = tr["legal_mask"].sum(axis=1)
+        pri = t.root_priors()
+        assert all(np.array_equal(pri[i, :cnt[i]], tr["noises"][i, :cnt[i]]) for i in range(B))
+        assert any(np.any(pri[i, :cnt[i]] == 0) for i in range(B))
+    if idea == "nw0":        # noise weight 0: every prior is CNode::expand's softmax, no zero among these logits
+        pri = t.root_priors()
+        assert np.all(pri[:, :A] > 0) and np.any(tr["noises"] == 0)
+    if idea == "a1_deep":
+        assert tr["out_traj"].shape[1] > 64 and tr["req_len"].max() > 64
+    if "legal_lists" in tr and idea in ("a64_perm", "perm_small"):
+        assert any(np.any(np.diff(row[row >= 0]) < 0) for row in tr["legal_lists"])
+
+
+@pytest.mark.parametrize("tree", ["mz", "ez"])
+def test_a64_alltie_first_walk_is_a_64_way_tie(tree):
+    """the scores cselect_child sees at every root before the first simulation: 64 equal ones, so the tie list
+    holds all 64 actions; again once every child has been visited once (simulation 64)"""
+    from tests.helpers import tie_list
+    from oracle.oracle import transcript_legal
+    path, = [p for p in EDGE_TRANSCRIPTS if os.path.basename(p).startswith(tree + "_a64_alltie")]
+    tr = load_transcript(path)
+    B, S, A, players, noise, ez, horizon = (int(v) for v in tr["meta"])
+    base, init, disc, vdm, nw = (float(v) for v in tr["consts"])
+    t = OracleTree(B, A, S, ez=bool(ez))
+    t.set_legal(*transcript_legal(tr))
+    t.set_delta(np.float32(vdm))
+    t.prepare(np.float32(nw), None, tr["root_reward"], tr["root_logits"], tr["to_play"])
+    for k in range(S):
+        if k in (0, 64):
+            for i in range(B):
+                sc = t.path_scores(i, np.zeros(0, np.int32), int(base), init, disc, players)
+                assert sc.shape[0] == 1 and tie_list(sc[0]) == list(range(64)), (k, i)
+        x, y, a, vtp, slen = t.traverse(base, np.float32(init), np.float32(disc), int(tr["seeds"][k]), tr["to_play"])
+        assert np.array_equal(a, tr["req_a"][k])
+        t.backprop(k + 1, np.float32(disc), tr["resp_reward"][k], tr["resp_value"][k], tr["resp_logits"][k], vtp,
+                   tr["resp_is_reset"][k] if ez else None)
+    assert np.any(tr["req_a"] == 63)
+
+
 def test_glibc_rand_restatement_matches_libc_vectors():
     g = np.load(os.path.join(GOLDEN, "glibc_rand.npz"))
     for seed, draws in zip(g["seeds"], g["draws"]):
