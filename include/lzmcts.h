@@ -333,6 +333,30 @@ int lzm_pong_collect_step(int n, int A, int T, int E, const int32_t *visits, con
                           int32_t *rec_action, float *rec_reward, int32_t *rec_visits, float *rec_value,
                           float *rec_pred, int32_t *ep_len, int32_t *ep_count, float *ep_return, int max_steps,
                           uint32_t seed, const int64_t *counter, void *stream);
+/* The Gumbel MuZero collect steps (muzero_collector.py under policy_config.gumbel_algo with
+ * policy/gumbel_muzero.py:582-589): lzm_cartpole_collect_step / lzm_atari_collect_step (the Breakout game) with the
+ * action GIVEN — action int32[n], lzm_gumbel_collect_outputs' first maximum of the improved policy; there is no
+ * temperature, no `deterministic` and no purpose-2 draw — and two more records per transition: rec_policy
+ * float[n][E][T][A] = policy float[n][A] (store_search_stats' improved_policy, :509-511) and rec_cq float[n][E][T],
+ * the mean over the A entries of completed_q float[n][A] added up in action order in float32 (:542-543). The
+ * recording, the env step, the auto-reset, ep_return, the next root's noise (purpose 4) and the resets (purpose 3)
+ * are the same kernel body. Pong is EfficientZero's game and has no such step. */
+int lzm_cartpole_collect_step_gumbel(int n, int A, int T, int E, const int32_t *visits, const float *root_value,
+                                     const float *pred_value, const int32_t *action, const float *policy,
+                                     const float *completed_q, double *state, int32_t *steps, float *obs,
+                                     float *noises, float noise_alpha, float *rec_obs, int32_t *rec_action,
+                                     float *rec_reward, int32_t *rec_visits, float *rec_value, float *rec_pred,
+                                     float *rec_policy, float *rec_cq, int32_t *ep_len, int32_t *ep_count,
+                                     float *ep_return, int max_steps, uint32_t seed, const int64_t *counter,
+                                     void *stream);
+int lzm_atari_collect_step_gumbel(int n, int A, int T, int E, const int32_t *visits, const float *root_value,
+                                  const float *pred_value, const int32_t *action, const float *policy,
+                                  const float *completed_q, int32_t *state, int32_t *steps, uint8_t *cur, float *obs,
+                                  float *noises, float noise_alpha, uint8_t *rec_frames, int32_t *rec_action,
+                                  float *rec_reward, int32_t *rec_visits, float *rec_value, float *rec_pred,
+                                  float *rec_policy, float *rec_cq, int32_t *ep_len, int32_t *ep_count,
+                                  float *ep_return, int max_steps, uint32_t seed, const int64_t *counter,
+                                  void *stream);
 
 /* Device packing of a collector's finished episodes for the trajectory return (SURVEY.md §8(e);
  * replaces the host loop over envs that builds GameSegments' arrays, muzero_collector.py:612-632, and
@@ -354,6 +378,16 @@ int lzm_episodes_pack(int n, int E, int T, int A, int has_pred, int64_t frame_by
                       const int32_t *rec_visits, const float *rec_value, const float *rec_pred,
                       const float *ep_return, void *out_frames, float *out_scalars, int64_t *out_index,
                       void *stream);
+/* lzm_episodes_pack for a Gumbel collector's block: out_scalars [rows][3 + A (+1) + A + 1], the same columns
+ * followed by [improved policy (A) | completed value] from rec_policy [n][E][T][A] and rec_cq [n][E][T] (row L:
+ * zeros there too). */
+int lzm_episodes_pack_gumbel(int n, int E, int T, int A, int has_pred, int64_t frame_bytes, const int32_t *ep_count,
+                             const int32_t *ep_len, int32_t *consumed, const int32_t *env_ep_off,
+                             const int64_t *env_row_off, const void *rec_frames, const int32_t *rec_action,
+                             const float *rec_reward, const int32_t *rec_visits, const float *rec_value,
+                             const float *rec_pred, const float *rec_policy, const float *rec_cq,
+                             const float *ep_return, void *out_frames, float *out_scalars, int64_t *out_index,
+                             void *stream);
 
 /* The representation network's DownSample stages (lzero/model/common.py:164-265: conv 3x3/2 -> 32, a 32-channel
  * residual block at 32 x 32, the downsample block (3x3/2 -> 64 with a 3x3/2 shortcut), a 64-channel residual
@@ -817,6 +851,15 @@ int lzm_gumbel_get_children_values(lzm_handle *h, float discount, float *out, vo
 /* Roots.get_policies (gmz_tree.pyx:51-52; get_policy :355-385): csoftmax over the action space of prior +
  * completed Q, exactly 0 for illegal actions; out float[B*A]. */
 int lzm_gumbel_get_policies(lzm_handle *h, float discount, float *out, void *stream);
+/* What GumbelMuZeroPolicy._forward_collect reads from the roots after a search (policy/gumbel_muzero.py:562-589),
+ * in one launch from one evaluation of each root's completed Q: dist int32[B*A] and values float[B] as
+ * lzm_get_root_outputs writes them (visit counts in legal order, -1 past the legal count); completed_q float[B*A],
+ * lzm_gumbel_get_children_values with the policy's mask applied (0, not -inf, for illegal actions); policy
+ * float[B*A], lzm_gumbel_get_policies bit for bit; action int32[B], the action id of the first maximum of the
+ * policy row (np.argmax over the masked row: illegal entries are exact zeros). count (int64, device; nullable): the
+ * collect step's counter, advanced by 1. LZM_ERR_STATE on a handle without LZM_TREE_GUMBEL, before any launch. */
+int lzm_gumbel_collect_outputs(lzm_handle *h, float discount, int32_t *dist, float *values, float *completed_q,
+                               float *policy, int32_t *action, int64_t *count, void *stream);
 /* GumbelMuZeroMCTSCtree.search's whole loop (mcts_ctree.py:1054-1122) over a MuZeroModelMLP in one launch: the
  * weight-streaming kernel of lzm_search_mlp with the Gumbel walk, raw_value and the sign-free backup (weights:
  * lzm_mlp_prepare's output; minmax, vtp_in, latent_pool and the rec_* outputs as lzm_search_mlp; vtp_in passes

@@ -170,6 +170,10 @@ SIGNATURES = {
                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "lzm_gumbel_get_children_values": [_vp, _f, _vp, _vp],
     "lzm_gumbel_get_policies": [_vp, _f, _vp, _vp],
+    "lzm_gumbel_collect_outputs": [_vp, _f] + [_vp] * 7,
+    "lzm_cartpole_collect_step_gumbel": [_i] * 4 + [_vp] * 10 + [_f] + [_vp] * 11 + [_i, _u32, _vp, _vp],
+    "lzm_atari_collect_step_gumbel": [_i] * 4 + [_vp] * 11 + [_f] + [_vp] * 11 + [_i, _u32, _vp, _vp],
+    "lzm_episodes_pack_gumbel": [_i] * 5 + [_i64] + [_vp] * 18,
     "lzm_search_mlp_gumbel": [_vp, _i, _i, _i, _i, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "lzm_search_mlp_gumbel_plan": [_vp, _i, _i, _i, _i, _i, _vp],
     "lzm_debug_logf": [_vp, _vp, _i64, _vp],

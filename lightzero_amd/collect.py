@@ -12,6 +12,14 @@ reference's per-call srand(tv_usec) values) are derived on the device from a rep
 usec_k = (1000003 * seed + n) mod 10^6 for the n-th traverse of the run (the SequentialSeeds rule
 of tests and bench), so every replay is a fresh search.
 
+With `algo="gumbel"` the step is GumbelMuZeroPolicy._forward_collect (policy/gumbel_muzero.py:495-602) for a MuZero
+model: initial_inference -> the root values decoded on the device (inverse_scalar_transform) -> the 6-argument
+Roots.prepare -> GumbelMuZeroMCTSCtree.search (the one-launch search where it takes the network, cfg.fused_search on
+by default here; otherwise the per-simulation loop inside the same captured graph) -> one launch for everything the
+policy reads from the roots (lzm_gumbel_collect_outputs: visit counts, values, the masked completed Q, the improved
+policy and its first maximum, the action). The Gumbel search draws nothing: there are no seeds, and the step
+counter only keys the epilogue's streams.
+
 Inputs are static device buffers the caller refills before `step()` (obs, Dirichlet noises,
 to_play) — or that a captured `epilogue` rewrites on the device (the collector's env step);
 outputs are static device tensors overwritten by each step (visit counts per legal action, root
@@ -21,14 +29,20 @@ import torch
 
 from .conv_infer import FoldedConvInitial, folded_initial_or_none
 from .initial import FusedInitialInference, fused_initial_or_none
-from .mcts_ctree import EfficientZeroMCTSCtree, MuZeroMCTSCtree, _step_net
+from .mcts_ctree import EfficientZeroMCTSCtree, GumbelMuZeroMCTSCtree, MuZeroMCTSCtree, _step_net
+from .scaling_transform import InverseScalarTransform
 from .utils import EasyDict
 
 
 class DeviceSearchStep:
     def __init__(self, model, num_envs, num_simulations, legal_actions, obs_shape, device, noise_weight=0.25,
                  discount_factor=0.997, support_scale=300, seed=0, rng_mode="glibc", graph=True, cfg_extra=None,
-                 epilogue=None, fused_initial=True):
+                 epilogue=None, fused_initial=True, algo=None, max_num_considered_actions=16):
+        """algo: None (MuZero or EfficientZero, picked from the model) or "gumbel" (Gumbel MuZero over a MuZero
+        model, with max_num_considered_actions)."""
+        if algo not in (None, "gumbel"):
+            raise ValueError(f"DeviceSearchStep: unknown algo {algo!r} (None or 'gumbel')")
+        self.gumbel = algo == "gumbel"
         self.model = model.eval()
         # initial_inference as one HIP launch when the model is a MuZeroModelMLP (lightzero_amd.initial);
         # for the conv MuZeroModel family its BatchNorm-folded form (conv_infer.FoldedConvInitial)
@@ -44,10 +58,19 @@ class DeviceSearchStep:
         self.ez = hasattr(getattr(model, "dynamics_network", None), "lstm")
         cfg = dict(num_simulations=self.S, discount_factor=float(discount_factor), device=self.device,
                    model=dict(support_scale=int(support_scale), categorical_distribution=True))
+        if self.gumbel and self.ez:
+            raise ValueError("DeviceSearchStep: algo='gumbel' takes a MuZero model (an EfficientZero model has no "
+                             "Gumbel search)")
         if self.ez:
             cfg["lstm_horizon_len"] = 5
+        if self.gumbel:
+            # the one-launch search where _fused takes the network (the class's own default is off)
+            cfg.update(max_num_considered_actions=int(max_num_considered_actions), fused_search=True)
         cfg.update(cfg_extra or {})
-        self.mcts_cls = EfficientZeroMCTSCtree if self.ez else MuZeroMCTSCtree
+        self.mcts_cls = GumbelMuZeroMCTSCtree if self.gumbel else (
+            EfficientZeroMCTSCtree if self.ez else MuZeroMCTSCtree)
+        self._value_transform = InverseScalarTransform(int(cfg["model"]["support_scale"]), self.device, bool(
+            cfg["model"].get("categorical_distribution", True))) if self.gumbel else None
         self.rng_mode = rng_mode
         self.mcts = self.mcts_cls(EasyDict(cfg))
         self.legal = [list(l) for l in legal_actions]
@@ -74,7 +97,36 @@ class DeviceSearchStep:
         if to_play is not None:
             self.to_play.copy_(to_play)
 
+    def _body_gumbel(self):
+        """_forward_collect's sequence for Gumbel MuZero, every step a launch on the current stream. The search
+        sets the considered-visits row first (DeviceTree.set_considered: a synchronous table copy, not capturable), so it
+        must have run before a capture: build_graph's two eager passes do that, and the captured pass finds the row
+        in place."""
+        with torch.no_grad():
+            if self.roots is None:
+                self.roots = self.mcts_cls.roots(self.B, self.legal)
+            pool0 = self._root_slot() if isinstance(self.initial, FusedInitialInference) else None
+            if pool0 is not None:  # the latent straight into the search's root slot (the search skips its copy)
+                out = self.initial.initial_inference(self.obs, latent_out=pool0)
+            else:
+                out = (self.initial or self.model).initial_inference(self.obs)
+            values = self._value_transform(out.value).reshape(-1)  # pred_values, on the device
+            self.roots.prepare_device(self.noise_weight, self.noises, self.rewards, values, out.policy_logits,
+                                      self.to_play)
+            self.mcts.search(self.roots, self.model, out.latent_state, self.to_play)
+            t = self.roots.tree
+            # everything the policy reads from the roots, the action and the counter increment in one launch
+            # (in place of the other searches' `step=` glue); an epilogue reads the advanced counter
+            res = t.collect_outputs(self.mcts._discount(), count=self._count)
+            res.update(latent_state=out.latent_state, policy_logits=out.policy_logits, value_logits=out.value,
+                       pred_values=values)
+            if self.epilogue is not None:
+                self.epilogue(res)
+            return res
+
     def _body(self):
+        if self.gumbel:
+            return self._body_gumbel()
         with torch.no_grad():
             old = self.mcts_cls.rng_mode
             self.mcts_cls.rng_mode = self.rng_mode
@@ -163,7 +215,9 @@ class DeviceSearchStep:
             self.initial.refresh()
         if self.roots is not None and self.roots.tree is not None:
             fused = getattr(self.mcts, "_fused", None)  # (MuZero's packed-MLP one-launch search)
-            if fused is None or fused(self.model, self.roots.tree) is None:
+            # (the Gumbel _fused takes S: its launch plan depends on it)
+            args = (self.model, self.roots.tree, self.S) if self.gumbel else (self.model, self.roots.tree)
+            if fused is None or fused(*args) is None:
                 # conv models (MuZero or EfficientZero): the folded step network re-folds in place
                 _step_net(self.mcts, self.model)
 

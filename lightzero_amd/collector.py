@@ -30,6 +30,13 @@ lzm_episodes_scan / lzm_episodes_pack, one 24-byte read-back); MuZeroCollector's
 (lightzero_amd.worker.muzero_collector) cuts episodes into game_segment_length blocks with the
 reference's rollover / pad_over / priorities (lightzero_amd.worker.segments). Random streams are
 Philox, not numpy's (the host-parity mode is MuZeroCollector over MuZeroCollectPolicy).
+
+`algo="gumbel"` collects for a Gumbel MuZero policy (GumbelMuZeroPolicy._forward_collect,
+policy/gumbel_muzero.py:495-602; muzero_collector.py under policy_config.gumbel_algo): the step is
+DeviceSearchStep(algo="gumbel"), the env kernels take the search's action (the first maximum of the improved policy:
+no sampling, no temperature) and also record the improved policy and the mean masked completed Q of every step
+(rec_policy [n, E, T, A], rec_cq [n, E, T]), and the returned blocks are Gumbel blocks (trajectory.py). CartPole and
+Breakout; Pong is EfficientZero's.
 """
 import time
 import weakref
@@ -41,8 +48,8 @@ import torch.distributed as dist
 from . import _lib
 from ._lib import call, ptr, stream_ptr
 from .collect import DeviceSearchStep
-from .trajectory import TrajBlock, all_gather_packed, allreduce_stats, gather_packed, scalar_width, unpack_episodes, \
-    wire_bytes
+from .trajectory import TrajBlock, all_gather_packed, allreduce_stats, block_layout, gather_packed, scalar_width, \
+    unpack_episodes, wire_bytes
 
 
 class CartPoleDevice:
@@ -71,6 +78,14 @@ class CartPoleDevice:
              ptr(c.rec_action), ptr(c.rec_reward), ptr(c.rec_visits), ptr(c.rec_value), ptr(c.rec_pred),
              ptr(c.ep_len), ptr(c.ep_count), ptr(c.ep_return), int(c.T), c.seed, ptr(c.search.step_counter),
              stream_ptr())
+
+    def collect_step_gumbel(self, c, out, pred):
+        call("lzm_cartpole_collect_step_gumbel", c.n, self.A, c.T, c.E, ptr(out["distributions"]), ptr(out["values"]),
+             ptr(pred), ptr(out["action"]), ptr(out["improved_policy"]), ptr(out["completed_q"]), ptr(self.state),
+             ptr(self.steps), ptr(c.search.obs), ptr(c.search.noises), float(c.noise_alpha), ptr(c.rec_frames),
+             ptr(c.rec_action), ptr(c.rec_reward), ptr(c.rec_visits), ptr(c.rec_value), ptr(c.rec_pred),
+             ptr(c.rec_policy), ptr(c.rec_cq), ptr(c.ep_len), ptr(c.ep_count), ptr(c.ep_return), int(c.T), c.seed,
+             ptr(c.search.step_counter), stream_ptr())
 
 
 class BreakoutDevice:
@@ -103,6 +118,14 @@ class BreakoutDevice:
              ptr(c.ep_len), ptr(c.ep_count), ptr(c.ep_return), int(c.T), c.seed, ptr(c.search.step_counter),
              stream_ptr())
 
+    def collect_step_gumbel(self, c, out, pred):
+        call("lzm_atari_collect_step_gumbel", c.n, self.A, c.T, c.E, ptr(out["distributions"]), ptr(out["values"]),
+             ptr(pred), ptr(out["action"]), ptr(out["improved_policy"]), ptr(out["completed_q"]), ptr(self.state),
+             ptr(self.steps), ptr(self.cur), ptr(c.search.obs), ptr(c.search.noises), float(c.noise_alpha),
+             ptr(c.rec_frames), ptr(c.rec_action), ptr(c.rec_reward), ptr(c.rec_visits), ptr(c.rec_value),
+             ptr(c.rec_pred), ptr(c.rec_policy), ptr(c.rec_cq), ptr(c.ep_len), ptr(c.ep_count), ptr(c.ep_return),
+             int(c.T), c.seed, ptr(c.search.step_counter), stream_ptr())
+
 
 class PongDevice(BreakoutDevice):
     """Config 3's Atari image env on the device (lzm_pong_*, the same collect kernel as Breakout's with the Pong
@@ -125,6 +148,8 @@ class PongDevice(BreakoutDevice):
              ptr(c.ep_len), ptr(c.ep_count), ptr(c.ep_return), int(c.T), c.seed, ptr(c.search.step_counter),
              stream_ptr())
 
+    collect_step_gumbel = None  # (EfficientZero's game: no Gumbel step)
+
 
 DEVICE_ENVS = {"cartpole": CartPoleDevice, "breakout": BreakoutDevice, "pong": PongDevice}
 
@@ -133,12 +158,20 @@ class DeviceCollector:
     def __init__(self, model, env_num, num_simulations, device="cuda", max_episode_steps=200, episode_slots=8,
                  temperature=1.0, deterministic=False, noise_alpha=0.3, noise_weight=0.25, seed=0,
                  rng_mode="glibc", graph=True, poll_every=8, record_pred=False, support_scale=None,
-                 categorical_distribution=True, env="cartpole", search_cfg=None):
-        """search_cfg: the search's config keys (discount_factor, lstm_horizon_len, ...: the policy's)"""
+                 categorical_distribution=True, env="cartpole", search_cfg=None, algo=None,
+                 max_num_considered_actions=16):
+        """search_cfg: the search's config keys (discount_factor, lstm_horizon_len, ...: the policy's).
+        algo: None, or "gumbel" with max_num_considered_actions (Gumbel MuZero: the action is the search's, so
+        temperature and deterministic are not used)."""
         _lib.require_gpu()
+        if algo not in (None, "gumbel"):
+            raise ValueError(f"DeviceCollector: unknown algo {algo!r} (None or 'gumbel')")
+        self.gumbel = algo == "gumbel"
         self.n, self.S = int(env_num), int(num_simulations)
         self.dev = torch.device(device)
         env_cls = DEVICE_ENVS[env] if isinstance(env, str) else env
+        if self.gumbel and getattr(env_cls, "collect_step_gumbel", None) is None:
+            raise ValueError(f"DeviceCollector: env {env!r} has no Gumbel collect step (cartpole and breakout do)")
         self.env = env_cls(self.n, self.dev)
         self.A = self.env.A
         self.T = int(max_episode_steps)
@@ -156,8 +189,11 @@ class DeviceCollector:
         self.rec_visits = torch.zeros((n, E, T, A), dtype=torch.int32, device=dev)
         self.rec_value = torch.zeros((n, E, T), dtype=torch.float32, device=dev)
         self.rec_pred = torch.zeros((n, E, T), dtype=torch.float32, device=dev) if record_pred else None
+        # Gumbel MuZero: store_search_stats' improved_policy and the step's mean completed value
+        self.rec_policy = torch.zeros((n, E, T, A), dtype=torch.float32, device=dev) if self.gumbel else None
+        self.rec_cq = torch.zeros((n, E, T), dtype=torch.float32, device=dev) if self.gumbel else None
         self._pred_transform = None
-        if record_pred:
+        if record_pred and not self.gumbel:  # (the Gumbel step decodes the root values itself: pred_values)
             from .scaling_transform import InverseScalarTransform
             # the value head's own encoding (policy config model.categorical_distribution)
             self._pred_transform = InverseScalarTransform(support_scale, dev, bool(categorical_distribution))
@@ -181,7 +217,8 @@ class DeviceCollector:
         self.search = DeviceSearchStep(model, n, self.S, [list(range(A))] * n, self.env.obs_shape, dev,
                                        noise_weight=noise_weight, seed=seed, rng_mode=rng_mode, graph=graph,
                                        epilogue=epilogue, support_scale=support_scale,
-                                       discount_factor=sc.pop("discount_factor", 0.997), cfg_extra=sc)
+                                       discount_factor=sc.pop("discount_factor", 0.997), cfg_extra=sc, algo=algo,
+                                       max_num_considered_actions=max_num_considered_actions)
         self.search.build_graph()
         self.reset()
 
@@ -192,6 +229,9 @@ class DeviceCollector:
 
     def _env_step(self, out):
         pred = None
+        if self.gumbel:
+            self.env.collect_step_gumbel(self, out, out["pred_values"] if self.rec_pred is not None else None)
+            return
         if self._pred_transform is not None:  # predicted root value for priorities (muzero.py:667)
             pred = self._pred_transform(out["value_logits"]).reshape(-1)
         self.env.collect_step(self, out, pred)
@@ -201,6 +241,9 @@ class DeviceCollector:
         bakes it in, so a change re-captures the graph."""
         t = float(temperature)
         d = self.deterministic if deterministic is None else bool(deterministic)
+        if self.gumbel:  # the action is the search's: nothing is baked into the captured step
+            self.temperature, self.deterministic = t, d
+            return
         if t != self.temperature or d != self.deterministic:
             self.temperature, self.deterministic = t, d
             if self.search.graph is not None:
@@ -354,16 +397,23 @@ class DeviceCollector:
             raise RuntimeError("episode slots overwritten before collection: raise episode_slots or lower poll_every")
         has_pred = self.rec_pred is not None
         frames = torch.empty((rows,) + tuple(self.env.frame_shape), dtype=self.env.frame_dtype, device=self.dev)
-        scalars = torch.empty((rows, scalar_width(self.A, has_pred)), dtype=torch.float32, device=self.dev)
+        scalars = torch.empty((rows, scalar_width(self.A, has_pred, self.gumbel)), dtype=torch.float32,
+                              device=self.dev)
         index = torch.empty((n_ep, 3), dtype=torch.int64, device=self.dev)
         fbytes = int(np.prod(self.env.frame_shape)) * self.rec_frames.element_size()
-        if n_ep:
+        if n_ep and self.gumbel:
+            call("lzm_episodes_pack_gumbel", n, E, self.T, self.A, int(has_pred), fbytes, ptr(self.ep_count),
+                 ptr(self.ep_len), ptr(self._consumed_dev), ptr(self._ep_off), ptr(self._row_off), ptr(self.rec_frames),
+                 ptr(self.rec_action), ptr(self.rec_reward), ptr(self.rec_visits), ptr(self.rec_value),
+                 ptr(self.rec_pred), ptr(self.rec_policy), ptr(self.rec_cq), ptr(self.ep_return), ptr(frames),
+                 ptr(scalars), ptr(index), stream_ptr())
+        elif n_ep:
             call("lzm_episodes_pack", n, E, self.T, self.A, int(has_pred), fbytes, ptr(self.ep_count), ptr(self.ep_len),
                  ptr(self._consumed_dev), ptr(self._ep_off), ptr(self._row_off), ptr(self.rec_frames),
                  ptr(self.rec_action), ptr(self.rec_reward), ptr(self.rec_visits), ptr(self.rec_value),
                  ptr(self.rec_pred), ptr(self.ep_return), ptr(frames), ptr(scalars), ptr(index), stream_ptr())
         self._consumed = snap[4:].astype(np.int64)  # lzm_episodes_pack sets consumed = ep_count on the device
-        return TrajBlock(frames, scalars, index, self.env.frame_scale)
+        return TrajBlock(frames, scalars, index, self.env.frame_scale, block_layout(has_pred, self.gumbel))
 
     def pull_new(self):
         """The episodes finished since the last pull, on the host (one device pack + one copy):

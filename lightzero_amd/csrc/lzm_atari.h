@@ -73,6 +73,12 @@ struct AtariArgs {
   int32_t *ep_len;             // [n][E]
   int32_t *ep_count;           // [n]
   float *ep_return;            // [n][E] unclipped score of the finished episode in each slot (nullable)
+  // the Gumbel MuZero step (atari_collect_kernel<GAME, true>) only, as CollectArgs'
+  const int32_t *action;       // [n]
+  const float *policy;         // [n][A]
+  const float *completed_q;    // [n][A]
+  float *rec_policy;           // [n][E][T][A]
+  float *rec_cq;               // [n][E][T]
 };
 
 __device__ inline bool at_brick(const int32_t *s, int r, int c) {
@@ -312,7 +318,8 @@ __global__ void __launch_bounds__(kAtThreads) atari_reset_kernel(int n, int32_t 
   for (int k = 0; k < kAtStack; ++k) at_store_obs16(ob, k, tid, px);  // the reset window: 4 x the first frame
 }
 
-template <int GAME>
+// GUMBEL: the Gumbel MuZero step, as cartpole_collect_kernel's flag (lzm_collect.h)
+template <int GAME, bool GUMBEL>
 __global__ void __launch_bounds__(kAtThreads) atari_collect_kernel(AtariArgs p) {
   const int i = blockIdx.x, tid = threadIdx.x;
   __shared__ int32_t s1[kAtStateWords], s0[kAtStateWords];
@@ -325,7 +332,10 @@ __global__ void __launch_bounds__(kAtThreads) atari_collect_kernel(AtariArgs p) 
     // ---- select_action: p_a = v_a^(1/T) / sum (float64), sample, or argmax (first max)
     const int32_t *v = p.visits + (size_t)i * A;
     int action = 0;
-    if (p.deterministic) {
+    if constexpr (GUMBEL) {
+      action = p.action[i];
+      action = action < 0 ? 0 : (action >= A ? A - 1 : action);
+    } else if (p.deterministic) {
       for (int a = 1; a < A; ++a)
         if (v[a] > v[action]) action = a;
     } else {
@@ -352,6 +362,9 @@ __global__ void __launch_bounds__(kAtThreads) atari_collect_kernel(AtariArgs p) 
       for (int a = 0; a < A; ++a) p.rec_visits[(slot * p.T + t) * A + a] = v[a];
       p.rec_value[slot * p.T + t] = p.root_value[i];
       if (p.rec_pred) p.rec_pred[slot * p.T + t] = p.pred_value[i];
+      if constexpr (GUMBEL)
+        record_gumbel(p.rec_policy, p.rec_cq, p.policy + (size_t)i * A, p.completed_q + (size_t)i * A, slot * p.T + t,
+                      A);
     }
     // ---- env step
     for (int k = 0; k < kAtStateWords; ++k) s1[k] = p.state[(size_t)i * kAtStateWords + k];

@@ -43,7 +43,25 @@ struct CollectArgs {
   int32_t *ep_len;             // [n][E] length of the finished episode in each slot
   int32_t *ep_count;           // [n] finished episodes (slot of the running one = ep_count % E)
   float *ep_return;            // [n][E] return of the finished episode in each slot (nullable)
+  // the Gumbel MuZero step (cartpole_collect_kernel<true>) only: the action is given, not drawn
+  const int32_t *action;       // [n] the search's action (lzm_gumbel_collect_outputs)
+  const float *policy;         // [n][A] the improved policy
+  const float *completed_q;    // [n][A] the masked completed Q
+  float *rec_policy;           // [n][E][T][A]
+  float *rec_cq;               // [n][E][T] mean over the A entries of the completed-Q row
 };
+
+// the Gumbel step's two extra records of transition s = slot * T + t: the improved policy row and the mean of the
+// masked completed-Q row, added up in action order in float32 (muzero_collector.py:542-543: np.mean of the row)
+__device__ inline void record_gumbel(float *rec_policy, float *rec_cq, const float *policy, const float *cq, size_t s,
+                                     int A) {
+  float sum = 0.0f;
+  for (int a = 0; a < A; ++a) {
+    rec_policy[s * A + a] = policy[a];
+    sum += cq[a];
+  }
+  rec_cq[s] = sum / (float)A;
+}
 
 // uniform in (0, 1) from one Philox output word (53-bit double from two words)
 __device__ inline double u01(uint32_t a, uint32_t b) {
@@ -123,6 +141,9 @@ __global__ void cartpole_reset_kernel(int n, double *state, int32_t *steps, floa
   for (int j = 0; j < 4; ++j) obs[(size_t)i * 4 + j] = (float)s[j];
 }
 
+// GUMBEL: the Gumbel MuZero step — the action is the search's (the first maximum of the improved policy: no purpose-2
+// draw, no temperature), and the improved policy and the mean completed Q are recorded too; all else is the same.
+template <bool GUMBEL>
 __global__ void cartpole_collect_kernel(CollectArgs p) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.n) return;
@@ -132,7 +153,10 @@ __global__ void cartpole_collect_kernel(CollectArgs p) {
   // ---- select_action: p_a = v_a^(1/T) / sum (float64), sample, or argmax (first max)
   const int32_t *v = p.visits + (size_t)i * A;
   int action = 0;
-  if (p.deterministic) {
+  if constexpr (GUMBEL) {
+    action = p.action[i];
+    action = action < 0 ? 0 : (action >= A ? A - 1 : action);  // (an id outside the env's action set never steps it)
+  } else if (p.deterministic) {
     for (int a = 1; a < A; ++a)
       if (v[a] > v[action]) action = a;
   } else {
@@ -161,6 +185,8 @@ __global__ void cartpole_collect_kernel(CollectArgs p) {
     for (int a = 0; a < A; ++a) p.rec_visits[(slot * p.T + t) * A + a] = v[a];
     p.rec_value[slot * p.T + t] = p.root_value[i];
     if (p.rec_pred) p.rec_pred[slot * p.T + t] = p.pred_value[i];
+    if constexpr (GUMBEL)
+      record_gumbel(p.rec_policy, p.rec_cq, p.policy + (size_t)i * A, p.completed_q + (size_t)i * A, slot * p.T + t, A);
   }
   // ---- env step
   double *s = p.state + (size_t)i * 4;

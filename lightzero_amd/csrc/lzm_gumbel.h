@@ -201,4 +201,47 @@ __device__ inline void gumbel_root_output(const TreeView &t, const GumbelView &g
   if (lane < t.A) row[lane] = x;
 }
 
+// What GumbelMuZeroPolicy._forward_collect reads from a root after the search (policy/gumbel_muzero.py:562-589),
+// from ONE evaluation of the root's completed Q: get_distributions (visit counts in legal order, -1 past the legal
+// count: lzm_get_root_outputs' rows), get_values, get_children_values with the policy's mask applied (0 where
+// illegal), get_policies, and the action the policy takes — np.argmax over the masked policy row, its first maximum.
+struct GumbelCollectOut {
+  int32_t *dist;    // [B][A]
+  float *values;    // [B]
+  float *cq;        // [B][A] action order
+  float *policy;    // [B][A] action order
+  int32_t *action;  // [B]
+};
+
+__device__ inline void gumbel_collect_output(const TreeView &t, const GumbelView &g, int i, float disc,
+                                             const GumbelCollectOut &o) {
+  const int lane = threadIdx.x & 63;
+  const NodeMeta m = t.meta[nidx(t, 0, i)];
+  const size_t row = (size_t)i * t.A;
+  if (lane == 0) o.values[i] = node_value(t.stat[nidx(t, 0, i)]);
+  if (m.latent < 0) {  // not prepared: no children
+    if (lane < t.A) {
+      o.dist[row + lane] = -1;
+      o.cq[row + lane] = 0.0f;
+      o.policy[row + lane] = 0.0f;
+    }
+    if (lane == 0) o.action[i] = 0;
+    return;
+  }
+  const GumbelChildren c = gumbel_children(t, g, i, 0, m.latent, disc);
+  if (lane < t.A) o.dist[row + lane] = c.valid ? c.visit : -1;
+  // to action order as gumbel_root_output does; the masked completed Q is 0 where the policy row is exactly 0
+  const float q = gumbel_scatter(c.cq, c.a, c.n, 0.0f);
+  float x = gumbel_scatter(c.prior + c.cq, c.a, c.n, -INFINITY);
+  x = gumbel_softmax(x, lane < t.A, t.A);
+  if (lane < t.A) {
+    o.cq[row + lane] = q;
+    o.policy[row + lane] = x;
+  }
+  // illegal entries are exact zeros below the row's maximum (the row sums to 1), so the first maximum over all A
+  // lanes is the first maximum over the legal ones: the lane index is the action id
+  const int a = gumbel_argmax(x, lane < t.A);
+  if (lane == 0) o.action[i] = a;
+}
+
 }  // namespace lzm

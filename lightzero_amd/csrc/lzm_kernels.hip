@@ -543,6 +543,14 @@ __global__ __launch_bounds__(256) void gumbel_output_kernel(TreeView t, GumbelVi
   if (i < t.B) gumbel_root_output(t, g, i, disc, policy, out);
 }
 
+// the root outputs of one collect step (gumbel_collect_output) and, with `count`, the step counter's increment
+__global__ __launch_bounds__(256) void gumbel_collect_kernel(TreeView t, GumbelView g, float disc, GumbelCollectOut o,
+                                                             int64_t *count) {
+  const int i = gumbel_wave_root();
+  if (i < t.B) gumbel_collect_output(t, g, i, disc, o);
+  if (count && blockIdx.x == 0 && threadIdx.x == 0) *count += 1;
+}
+
 __global__ void debug_logf_kernel(const float *x, float *out, long long n) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = glibc_logf(x[i]);
@@ -1366,6 +1374,20 @@ int lzm_gumbel_get_children_values(lzm_handle *h, float discount, float *out, vo
 
 int lzm_gumbel_get_policies(lzm_handle *h, float discount, float *out, void *stream) {
   return gumbel_output("lzm_gumbel_get_policies", h, discount, 1, out, stream);
+}
+
+int lzm_gumbel_collect_outputs(lzm_handle *h, float discount, int32_t *dist, float *values, float *completed_q,
+                               float *policy, int32_t *action, int64_t *count, void *stream) {
+  const char *name = "lzm_gumbel_collect_outputs";
+  int rc = check_kind(name, h, true);
+  if (rc != LZM_OK) return rc;
+  if (!dist || !values || !completed_q || !policy || !action) return refuse(LZM_ERR_ARG, name, "null argument");
+  GumbelCollectOut o;
+  o.dist = dist; o.values = values; o.cq = completed_q; o.policy = policy; o.action = action;
+  hipLaunchKernelGGL(gumbel_collect_kernel, gumbel_grid(h), dim3(256), 0, (hipStream_t)stream, view(h), gumbel_view(h),
+                     discount, o, count);
+  LZM_CHECK_LAUNCH();
+  return LZM_OK;
 }
 
 int lzm_debug_logf(const float *x, float *out, int64_t n, void *stream) {
@@ -2287,16 +2309,27 @@ int lzm_cartpole_reset(int n, double *state, int32_t *steps, float *obs, uint32_
   return LZM_OK;
 }
 
-int lzm_cartpole_collect_step(int n, int A, int T, int E, const int32_t *visits, const float *root_value,
-                              const float *pred_value, double *state, int32_t *steps, float *obs, float *noises,
-                              float noise_alpha, float temperature, int deterministic, float *rec_obs,
-                              int32_t *rec_action, float *rec_reward, int32_t *rec_visits, float *rec_value,
-                              float *rec_pred, int32_t *ep_len, int32_t *ep_count, float *ep_return, int max_steps,
-                              uint32_t seed, const int64_t *counter, void *stream) {
+// what the Gumbel collect steps take in place of (temperature, deterministic), and record on top
+struct GumbelStepIO {
+  const int32_t *action;
+  const float *policy, *completed_q;
+  float *rec_policy, *rec_cq;
+  bool complete() const { return action && policy && completed_q && rec_policy && rec_cq; }
+};
+
+// lzm_cartpole_collect_step (gz null) and lzm_cartpole_collect_step_gumbel
+static int cartpole_collect_step_g(const char *name, const GumbelStepIO *gz, int n, int A, int T, int E,
+                                   const int32_t *visits, const float *root_value, const float *pred_value,
+                                   double *state, int32_t *steps, float *obs, float *noises, float noise_alpha,
+                                   float temperature, int deterministic, float *rec_obs, int32_t *rec_action,
+                                   float *rec_reward, int32_t *rec_visits, float *rec_value, float *rec_pred,
+                                   int32_t *ep_len, int32_t *ep_count, float *ep_return, int max_steps, uint32_t seed,
+                                   const int64_t *counter, void *stream) {
   if (n <= 0 || A <= 0 || A > 64 || T <= 0 || E <= 0 || !visits || !root_value || !state || !steps || !obs ||
       !noises || !rec_obs || !rec_action || !rec_reward || !rec_visits || !rec_value || !ep_len || !ep_count ||
-      !counter || !(temperature > 0.0f) || !(noise_alpha > 0.0f) || (!pred_value) != (!rec_pred)) {
-    set_err("lzm_cartpole_collect_step: bad arguments");
+      !counter || !(temperature > 0.0f) || !(noise_alpha > 0.0f) || (!pred_value) != (!rec_pred) ||
+      (gz && !gz->complete())) {
+    snprintf(g_err, sizeof(g_err), "%s: bad arguments", name);
     return LZM_ERR_ARG;
   }
   CollectArgs a;
@@ -2306,9 +2339,40 @@ int lzm_cartpole_collect_step(int n, int A, int T, int E, const int32_t *visits,
   a.rec_obs = rec_obs; a.rec_action = rec_action; a.rec_reward = rec_reward; a.rec_visits = rec_visits;
   a.rec_value = rec_value; a.pred_value = pred_value; a.rec_pred = rec_pred; a.ep_len = ep_len;
   a.ep_count = ep_count; a.ep_return = ep_return;
-  hipLaunchKernelGGL(cartpole_collect_kernel, dim3((n + 127) / 128), dim3(128), 0, (hipStream_t)stream, a);
+  a.action = gz ? gz->action : nullptr; a.policy = gz ? gz->policy : nullptr;
+  a.completed_q = gz ? gz->completed_q : nullptr; a.rec_policy = gz ? gz->rec_policy : nullptr;
+  a.rec_cq = gz ? gz->rec_cq : nullptr;
+  hipLaunchKernelGGL(gz ? cartpole_collect_kernel<true> : cartpole_collect_kernel<false>, dim3((n + 127) / 128),
+                     dim3(128), 0, (hipStream_t)stream, a);
   LZM_CHECK_LAUNCH();
   return LZM_OK;
+}
+
+int lzm_cartpole_collect_step(int n, int A, int T, int E, const int32_t *visits, const float *root_value,
+                              const float *pred_value, double *state, int32_t *steps, float *obs, float *noises,
+                              float noise_alpha, float temperature, int deterministic, float *rec_obs,
+                              int32_t *rec_action, float *rec_reward, int32_t *rec_visits, float *rec_value,
+                              float *rec_pred, int32_t *ep_len, int32_t *ep_count, float *ep_return, int max_steps,
+                              uint32_t seed, const int64_t *counter, void *stream) {
+  return cartpole_collect_step_g("lzm_cartpole_collect_step", nullptr, n, A, T, E, visits, root_value, pred_value,
+                                 state, steps, obs, noises, noise_alpha, temperature, deterministic, rec_obs,
+                                 rec_action, rec_reward, rec_visits, rec_value, rec_pred, ep_len, ep_count, ep_return,
+                                 max_steps, seed, counter, stream);
+}
+
+int lzm_cartpole_collect_step_gumbel(int n, int A, int T, int E, const int32_t *visits, const float *root_value,
+                                     const float *pred_value, const int32_t *action, const float *policy,
+                                     const float *completed_q, double *state, int32_t *steps, float *obs,
+                                     float *noises, float noise_alpha, float *rec_obs, int32_t *rec_action,
+                                     float *rec_reward, int32_t *rec_visits, float *rec_value, float *rec_pred,
+                                     float *rec_policy, float *rec_cq, int32_t *ep_len, int32_t *ep_count,
+                                     float *ep_return, int max_steps, uint32_t seed, const int64_t *counter,
+                                     void *stream) {
+  const GumbelStepIO gz{action, policy, completed_q, rec_policy, rec_cq};
+  return cartpole_collect_step_g("lzm_cartpole_collect_step_gumbel", &gz, n, A, T, E, visits, root_value, pred_value,
+                                 state, steps, obs, noises, noise_alpha, 1.0f, 1, rec_obs, rec_action, rec_reward,
+                                 rec_visits, rec_value, rec_pred, ep_len, ep_count, ep_return, max_steps, seed, counter,
+                                 stream);
 }
 
 static int atari_reset_g(int game, const char *name, int n, int32_t *state, int32_t *steps, uint8_t *cur, float *obs,
@@ -2323,8 +2387,10 @@ static int atari_reset_g(int game, const char *name, int n, int32_t *state, int3
   return LZM_OK;
 }
 
-static int atari_collect_step_g(int game, const char *name, int n, int A, int T, int E, const int32_t *visits,
-                                const float *root_value, const float *pred_value, int32_t *state, int32_t *steps,
+// gz: the Gumbel step's extra arrays (lzm_atari_collect_step_gumbel), else null
+static int atari_collect_step_g(int game, const char *name, const GumbelStepIO *gz, int n, int A, int T, int E,
+                                const int32_t *visits, const float *root_value, const float *pred_value,
+                                int32_t *state, int32_t *steps,
                                 uint8_t *cur, float *obs, float *noises, float noise_alpha, float temperature,
                                 int deterministic, uint8_t *rec_frames, int32_t *rec_action, float *rec_reward,
                                 int32_t *rec_visits, float *rec_value, float *rec_pred, int32_t *ep_len,
@@ -2333,7 +2399,7 @@ static int atari_collect_step_g(int game, const char *name, int n, int A, int T,
   if (n <= 0 || A <= 0 || A > 64 || T <= 0 || E <= 0 || max_steps <= 0 || !visits || !root_value || !state || !steps ||
       !cur || !obs || !noises || !rec_frames || !rec_action || !rec_reward || !rec_visits || !rec_value || !ep_len ||
       !ep_count || !counter || !(temperature > 0.0f) || !(noise_alpha > 0.0f) || (!pred_value) != (!rec_pred) ||
-      (((uintptr_t)cur | (uintptr_t)obs | (uintptr_t)rec_frames) & 15)) {
+      (((uintptr_t)cur | (uintptr_t)obs | (uintptr_t)rec_frames) & 15) || (gz && (game || !gz->complete()))) {
     snprintf(g_err, sizeof(g_err), "%s: bad arguments", name);
     return LZM_ERR_ARG;
   }
@@ -2344,8 +2410,13 @@ static int atari_collect_step_g(int game, const char *name, int n, int A, int T,
   a.noises = noises; a.rec_frames = rec_frames; a.rec_action = rec_action; a.rec_reward = rec_reward;
   a.rec_visits = rec_visits; a.rec_value = rec_value; a.pred_value = pred_value; a.rec_pred = rec_pred;
   a.ep_len = ep_len; a.ep_count = ep_count; a.ep_return = ep_return;
-  hipLaunchKernelGGL(game ? atari_collect_kernel<1> : atari_collect_kernel<0>, dim3(n), dim3(kAtThreads), 0,
-                     (hipStream_t)stream, a);
+  a.action = gz ? gz->action : nullptr; a.policy = gz ? gz->policy : nullptr;
+  a.completed_q = gz ? gz->completed_q : nullptr; a.rec_policy = gz ? gz->rec_policy : nullptr;
+  a.rec_cq = gz ? gz->rec_cq : nullptr;
+  // (Pong is EfficientZero's game: no Gumbel step)
+  void (*const kernel)(AtariArgs) = gz ? atari_collect_kernel<0, true>
+                                       : game ? atari_collect_kernel<1, false> : atari_collect_kernel<0, false>;
+  hipLaunchKernelGGL(kernel, dim3(n), dim3(kAtThreads), 0, (hipStream_t)stream, a);
   LZM_CHECK_LAUNCH();
   return LZM_OK;
 }
@@ -2360,10 +2431,25 @@ int lzm_atari_collect_step(int n, int A, int T, int E, const int32_t *visits, co
                            int32_t *rec_action, float *rec_reward, int32_t *rec_visits, float *rec_value,
                            float *rec_pred, int32_t *ep_len, int32_t *ep_count, float *ep_return, int max_steps,
                            uint32_t seed, const int64_t *counter, void *stream) {
-  return atari_collect_step_g(0, "lzm_atari_collect_step", n, A, T, E, visits, root_value, pred_value, state, steps,
-                              cur, obs, noises, noise_alpha, temperature, deterministic, rec_frames, rec_action,
+  return atari_collect_step_g(0, "lzm_atari_collect_step", nullptr, n, A, T, E, visits, root_value, pred_value, state,
+                              steps, cur, obs, noises, noise_alpha, temperature, deterministic, rec_frames, rec_action,
                               rec_reward, rec_visits, rec_value, rec_pred, ep_len, ep_count, ep_return, max_steps, seed,
                               counter, stream);
+}
+
+int lzm_atari_collect_step_gumbel(int n, int A, int T, int E, const int32_t *visits, const float *root_value,
+                                  const float *pred_value, const int32_t *action, const float *policy,
+                                  const float *completed_q, int32_t *state, int32_t *steps, uint8_t *cur, float *obs,
+                                  float *noises, float noise_alpha, uint8_t *rec_frames, int32_t *rec_action,
+                                  float *rec_reward, int32_t *rec_visits, float *rec_value, float *rec_pred,
+                                  float *rec_policy, float *rec_cq, int32_t *ep_len, int32_t *ep_count,
+                                  float *ep_return, int max_steps, uint32_t seed, const int64_t *counter,
+                                  void *stream) {
+  const GumbelStepIO gz{action, policy, completed_q, rec_policy, rec_cq};
+  return atari_collect_step_g(0, "lzm_atari_collect_step_gumbel", &gz, n, A, T, E, visits, root_value, pred_value,
+                              state, steps, cur, obs, noises, noise_alpha, 1.0f, 1, rec_frames, rec_action, rec_reward,
+                              rec_visits, rec_value, rec_pred, ep_len, ep_count, ep_return, max_steps, seed, counter,
+                              stream);
 }
 
 int lzm_pong_reset(int n, int32_t *state, int32_t *steps, uint8_t *cur, float *obs, uint32_t seed, void *stream) {
@@ -2376,8 +2462,8 @@ int lzm_pong_collect_step(int n, int A, int T, int E, const int32_t *visits, con
                           int32_t *rec_action, float *rec_reward, int32_t *rec_visits, float *rec_value,
                           float *rec_pred, int32_t *ep_len, int32_t *ep_count, float *ep_return, int max_steps,
                           uint32_t seed, const int64_t *counter, void *stream) {
-  return atari_collect_step_g(1, "lzm_pong_collect_step", n, A, T, E, visits, root_value, pred_value, state, steps,
-                              cur, obs, noises, noise_alpha, temperature, deterministic, rec_frames, rec_action,
+  return atari_collect_step_g(1, "lzm_pong_collect_step", nullptr, n, A, T, E, visits, root_value, pred_value, state,
+                              steps, cur, obs, noises, noise_alpha, temperature, deterministic, rec_frames, rec_action,
                               rec_reward, rec_visits, rec_value, rec_pred, ep_len, ep_count, ep_return, max_steps, seed,
                               counter, stream);
 }
@@ -2427,32 +2513,66 @@ int lzm_bias_add_relu(float *y, const float *bias, const float *z, int N, int C,
   return LZM_OK;
 }
 
-int lzm_episodes_pack(int n, int E, int T, int A, int has_pred, int64_t frame_bytes, const int32_t *ep_count,
-                      const int32_t *ep_len, int32_t *consumed, const int32_t *env_ep_off, const int64_t *env_row_off,
-                      const void *rec_frames, const int32_t *rec_action, const float *rec_reward,
-                      const int32_t *rec_visits, const float *rec_value, const float *rec_pred,
-                      const float *ep_return, void *out_frames, float *out_scalars, int64_t *out_index,
-                      void *stream) {
+}  // extern "C"
+
+// lzm_episodes_pack (rec_policy and rec_cq null) and lzm_episodes_pack_gumbel (both given: A + 1 more columns)
+static int episodes_pack_g(const char *name, int n, int E, int T, int A, int has_pred, int64_t frame_bytes,
+                           const int32_t *ep_count, const int32_t *ep_len, int32_t *consumed, const int32_t *env_ep_off,
+                           const int64_t *env_row_off, const void *rec_frames, const int32_t *rec_action,
+                           const float *rec_reward, const int32_t *rec_visits, const float *rec_value,
+                           const float *rec_pred, const float *rec_policy, const float *rec_cq, const float *ep_return,
+                           void *out_frames, float *out_scalars, int64_t *out_index, void *stream) {
   if (n <= 0 || E <= 0 || T <= 0 || A <= 0 || frame_bytes <= 0 || !ep_count || !ep_len || !consumed ||
       !env_ep_off || !env_row_off || !rec_frames || !rec_action || !rec_reward || !rec_visits || !rec_value ||
-      (has_pred && !rec_pred) || !out_frames || !out_scalars || !out_index) {
-    set_err("lzm_episodes_pack: bad arguments");
+      (has_pred && !rec_pred) || (!rec_policy) != (!rec_cq) || !out_frames || !out_scalars || !out_index) {
+    snprintf(g_err, sizeof(g_err), "%s: bad arguments", name);
     return LZM_ERR_ARG;
   }
   PackArgs a;
-  a.n = n; a.E = E; a.T = T; a.A = A; a.W = 3 + A + (has_pred ? 1 : 0); a.has_pred = has_pred ? 1 : 0;
+  a.n = n; a.E = E; a.T = T; a.A = A; a.has_pred = has_pred ? 1 : 0;
+  a.W = 3 + A + a.has_pred + (rec_policy ? A + 1 : 0);
+  a.rec_policy = rec_policy; a.rec_cq = rec_cq;
   a.frame_bytes = frame_bytes; a.ep_count = ep_count; a.ep_len = ep_len; a.env_ep_off = env_ep_off;
   a.consumed = consumed; a.env_row_off = env_row_off;
   a.rec_frames = (const uint8_t *)rec_frames; a.rec_action = rec_action; a.rec_reward = rec_reward;
   a.rec_visits = rec_visits; a.rec_value = rec_value; a.rec_pred = rec_pred; a.ep_return = ep_return;
   a.out_frames = (uint8_t *)out_frames; a.out_scalars = out_scalars; a.out_index = out_index;
   if ((frame_bytes & 15) == 0 && (((uintptr_t)rec_frames | (uintptr_t)out_frames) & 15)) {
-    set_err("lzm_episodes_pack: frame buffers must be 16-B aligned when frames are multiples of 16 B");
+    snprintf(g_err, sizeof(g_err), "%s: frame buffers must be 16-B aligned when frames are multiples of 16 B", name);
     return LZM_ERR_ARG;
   }
   hipLaunchKernelGGL(episodes_pack_kernel, dim3(n), dim3(kTrPackThreads), 0, (hipStream_t)stream, a);
   LZM_CHECK_LAUNCH();
   return LZM_OK;
+}
+
+extern "C" {
+
+int lzm_episodes_pack(int n, int E, int T, int A, int has_pred, int64_t frame_bytes, const int32_t *ep_count,
+                      const int32_t *ep_len, int32_t *consumed, const int32_t *env_ep_off, const int64_t *env_row_off,
+                      const void *rec_frames, const int32_t *rec_action, const float *rec_reward,
+                      const int32_t *rec_visits, const float *rec_value, const float *rec_pred,
+                      const float *ep_return, void *out_frames, float *out_scalars, int64_t *out_index,
+                      void *stream) {
+  return episodes_pack_g("lzm_episodes_pack", n, E, T, A, has_pred, frame_bytes, ep_count, ep_len, consumed, env_ep_off,
+                         env_row_off, rec_frames, rec_action, rec_reward, rec_visits, rec_value, rec_pred, nullptr,
+                         nullptr, ep_return, out_frames, out_scalars, out_index, stream);
+}
+
+int lzm_episodes_pack_gumbel(int n, int E, int T, int A, int has_pred, int64_t frame_bytes, const int32_t *ep_count,
+                             const int32_t *ep_len, int32_t *consumed, const int32_t *env_ep_off,
+                             const int64_t *env_row_off, const void *rec_frames, const int32_t *rec_action,
+                             const float *rec_reward, const int32_t *rec_visits, const float *rec_value,
+                             const float *rec_pred, const float *rec_policy, const float *rec_cq,
+                             const float *ep_return, void *out_frames, float *out_scalars, int64_t *out_index,
+                             void *stream) {
+  if (!rec_policy || !rec_cq) {
+    set_err("lzm_episodes_pack_gumbel: bad arguments");
+    return LZM_ERR_ARG;
+  }
+  return episodes_pack_g("lzm_episodes_pack_gumbel", n, E, T, A, has_pred, frame_bytes, ep_count, ep_len, consumed,
+                         env_ep_off, env_row_off, rec_frames, rec_action, rec_reward, rec_visits, rec_value, rec_pred,
+                         rec_policy, rec_cq, ep_return, out_frames, out_scalars, out_index, stream);
 }
 
 }  // extern "C"

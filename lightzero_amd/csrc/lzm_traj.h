@@ -10,7 +10,8 @@
 //   episodes_pack_kernel  one workgroup per env: its episodes' index entries (env, L, first row), the
 //                         frames of each episode as ONE contiguous copy (slot rows 0..L are adjacent in
 //                         rec_frames [n][E][T+1][frame]), the scalar rows [action | reward | visits (A) |
-//                         root value (| predicted value)] with row L zero except its reward column, which
+//                         root value (| predicted value) (| improved policy (A) | completed value: Gumbel
+//                         blocks)] with row L zero except its reward column, which
 //                         carries the episode's return (the env's eval_episode_return; 0 when the
 //                         collector records none), and consumed[i] = ep_count[i].
 // Env-major order, each env's episodes in finishing order — the order of the host loop it replaces.
@@ -83,7 +84,11 @@ struct PackArgs {
   const float *rec_value;      // [n][E][T]
   const float *rec_pred;       // [n][E][T] (nullable)
   const float *ep_return;      // [n][E] (nullable)
-  uint8_t *out_frames;         // [rows][frame_bytes]
+  // Gumbel blocks (lzm_episodes_pack_gumbel; both null otherwise): A + 1 more columns behind the others,
+  // [improved policy (A) | completed value]
+  const float *rec_policy;     // [n][E][T][A]
+  const float *rec_cq;         // [n][E][T]
+  uint8_t *out_frames;       // [rows][frame_bytes]
   float *out_scalars;          // [rows][W]
   int64_t *out_index;          // [n_ep][3]
 };
@@ -129,6 +134,11 @@ __global__ void __launch_bounds__(kTrPackThreads) episodes_pack_kernel(PackArgs 
       for (int a = 0; a < p.A; ++a) o[2 + a] = (float)p.rec_visits[s * p.A + a];
       o[2 + p.A] = p.rec_value[s];
       if (p.has_pred) o[3 + p.A] = p.rec_pred[s];
+      if (p.rec_policy) {
+        float *g = o + 3 + p.A + p.has_pred;
+        for (int a = 0; a < p.A; ++a) g[a] = p.rec_policy[s * p.A + a];
+        g[p.A] = p.rec_cq[s];
+      }
     }
     row += L + 1;
   }

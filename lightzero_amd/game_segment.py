@@ -162,12 +162,14 @@ class GameSegment:
 
     @classmethod
     def from_arrays(cls, action_space, game_segment_length, config, obs, action, reward, child_visits, root_value,
-                    action_mask, to_play):
+                    action_mask, to_play, improved_policy=None):
         """A finished segment in array form, as game_segment_to_array leaves it (fields already cut
-        and padded by the caller; lightzero_amd.worker.segments)."""
+        and padded by the caller; lightzero_amd.worker.segments). improved_policy: the Gumbel MuZero policy
+        targets [len + pad, A] (store_search_stats' improved_policy); absent, the empty array a segment of any
+        other algorithm ends with."""
         g = cls(action_space, game_segment_length, config)
         g.obs_segment, g.action_segment, g.reward_segment = obs, action, reward
         g.child_visit_segment, g.root_value_segment = child_visits, root_value
-        g.improved_policy_probs = np.array([])
+        g.improved_policy_probs = np.array([]) if improved_policy is None else np.asarray(improved_policy)
         g.action_mask_segment, g.to_play_segment = action_mask, to_play
         return g

@@ -16,6 +16,13 @@ mode with Philox streams.
 search gets the initial inference's reward_hidden_state roots (the LSTM (c, h), zeros at the root:
 efficientzero_model.py:199-233) through the drop-in `EfficientZeroMCTSCtree`.
 
+`GumbelMuZeroCollectPolicy` restates GumbelMuZeroPolicy._forward_collect / _forward_eval
+(lzero/policy/gumbel_muzero.py:495-602, :615-702) over the drop-in `GumbelMuZeroMCTSCtree`: the 6-argument
+Roots.prepare with the decoded root values, get_children_values / get_policies after the search, and the action the
+first maximum of the masked improved policy. select_action's result is used for the entropy alone, but its
+`np.random.choice` draw is still made (collect mode), so the numpy stream stays the reference's. Its config
+defaults are GUMBEL_COLLECT_DEFAULTS (`gumbel_policy_config`).
+
 `eval_mode.forward(data, action_mask, to_play, ready_env_id)` on either restates _forward_eval
 (muzero.py:783-867; efficientzero.py:690-770): prepare_no_noise, the search, and the argmax action
 (select_action with deterministic=True) — no random draw at all.
@@ -30,7 +37,7 @@ import numpy as np
 import torch
 from scipy.stats import entropy
 
-from .mcts_ctree import EfficientZeroMCTSCtree, MuZeroMCTSCtree
+from .mcts_ctree import EfficientZeroMCTSCtree, GumbelMuZeroMCTSCtree, MuZeroMCTSCtree
 from .scaling_transform import InverseScalarTransform
 from .utils import EasyDict
 
@@ -46,13 +53,27 @@ COLLECT_DEFAULTS = dict(
 )
 
 
-def policy_config(**overrides):
-    """MuZeroPolicy-style config: COLLECT_DEFAULTS with nested overrides (EasyDict)."""
+# GumbelMuZeroPolicy's (policy/gumbel_muzero.py:29-228): the same keys with its type, gumbel_algo and the
+# sequential-halving width
+GUMBEL_COLLECT_DEFAULTS = dict(COLLECT_DEFAULTS, type='gumbel_muzero', gumbel_algo=True, max_num_considered_actions=4)
+
+
+def _merged(defaults, overrides):
     def merge(a, b):
         for k, v in b.items():
             a[k] = merge(dict(a[k]), v) if isinstance(v, dict) and isinstance(a.get(k), dict) else v
         return a
-    return EasyDict(merge(copy.deepcopy(COLLECT_DEFAULTS), overrides))
+    return EasyDict(merge(copy.deepcopy(defaults), overrides))
+
+
+def policy_config(**overrides):
+    """MuZeroPolicy-style config: COLLECT_DEFAULTS with nested overrides (EasyDict)."""
+    return _merged(COLLECT_DEFAULTS, overrides)
+
+
+def gumbel_policy_config(**overrides):
+    """GumbelMuZeroPolicy-style config: GUMBEL_COLLECT_DEFAULTS with nested overrides (EasyDict)."""
+    return _merged(GUMBEL_COLLECT_DEFAULTS, overrides)
 
 
 def select_action(visit_counts, temperature: float = 1, deterministic: bool = True):
@@ -238,3 +259,83 @@ class EfficientZeroCollectPolicy(MuZeroCollectPolicy):
 
     def _search(self, mcts, roots, latent, hidden, to_play):
         mcts.search(roots, self._collect_model, latent, hidden, to_play)
+
+
+class GumbelMuZeroCollectPolicy(MuZeroCollectPolicy):
+    """GumbelMuZeroPolicy._forward_collect / _forward_eval (gumbel_muzero.py:495-602, :615-702). `record = True`
+    keeps per forward what the tests' host restatement of the tree needs to replay the step: root logits, the
+    decoded root values, legal lists, noises and the search's per-simulation record."""
+    mcts_cls = GumbelMuZeroMCTSCtree
+
+    def __init__(self, cfg, model):
+        for k in ('type', 'gumbel_algo', 'max_num_considered_actions'):
+            if k not in cfg:  # GumbelMuZeroPolicy's defaults
+                cfg = EasyDict(dict(cfg, **{k: GUMBEL_COLLECT_DEFAULTS[k]}))
+        super().__init__(cfg, model)
+
+    def _gumbel_forward(self, model, mcts, data, action_mask, to_play, ready_env_id, collect):
+        cfg = self._cfg
+        model.eval()
+        n = data.shape[0]
+        if ready_env_id is None:
+            ready_env_id = np.arange(n)
+        output = {i: None for i in ready_env_id}
+        A = int(cfg.model.action_space_size)
+        disc = cfg.discount_factor
+        with torch.no_grad():
+            out = model.initial_inference(data)
+            latent, reward_roots, value, logits, _ = self._unpack(out)
+            pred_values = self.inverse_scalar_transform_handle(value).detach().cpu().numpy()
+            policy_logits = logits.detach().cpu().numpy().tolist()
+            legal_actions = [[i for i, x in enumerate(action_mask[j]) if x == 1] for j in range(n)]
+            noises = None
+            if collect:  # (the only difference between collect and eval is the dirichlet noise, :546)
+                noises = [np.random.dirichlet([cfg.root_dirichlet_alpha] * int(sum(action_mask[j]))).astype(np.float32)
+                          .tolist() for j in range(n)]
+            rec = None
+            if self.record:
+                rec = dict(mode='collect' if collect else 'eval', data=data.detach().cpu().numpy(),
+                           root_logits=np.asarray(policy_logits, np.float32), pred_values=pred_values.copy(),
+                           legal=legal_actions, to_play=list(to_play), reward_roots=list(reward_roots), noises=noises)
+                self.records.append(rec)
+            roots = self._roots(n, legal_actions)
+            if collect:
+                roots.prepare(cfg.root_noise_weight, noises, reward_roots, list(pred_values), policy_logits,
+                              list(to_play))
+            else:
+                roots.prepare_no_noise(reward_roots, list(pred_values), policy_logits, list(to_play))
+            mcts.record = self.record
+            mcts.search(roots, model, latent, list(to_play))
+            dists = roots.get_distributions()
+            values = roots.get_values()
+            completed = roots.get_children_values(disc, A) if collect else None
+            improved = np.array(roots.get_policies(disc, A))
+            if rec is not None:
+                rec.update(search=mcts.last_record.numpy(), dist=dists, values=values, policies=improved.copy(),
+                           children_values=None if completed is None else np.array(completed, np.float32))
+            for i, env_id in enumerate(ready_env_id):
+                d, v, p = dists[i], values[i], improved[i]
+                # used for the entropy alone; in collect mode it still makes its np.random.choice draw (:582-584)
+                _, ent = select_action(d, temperature=self._collect_mcts_temperature if collect else 1,
+                                       deterministic=not collect)
+                action = np.argmax([x for x in np.where(action_mask[i] == 1.0, p, 0.0)])
+                output[env_id] = {'action': action, 'visit_count_distributions': d,
+                                  'visit_count_distribution_entropy': ent, 'searched_value': v}
+                if collect:
+                    output[env_id].update(
+                        roots_completed_value=np.where(action_mask[i] == 1.0, completed[i], 0.0),
+                        improved_policy_probs=p)
+                output[env_id].update(predicted_value=pred_values[i], predicted_policy_logits=policy_logits[i])
+            roots.clear()
+        return output
+
+    def forward(self, data, action_mask=None, temperature: float = 1, to_play=(-1,), epsilon: float = 0.25,
+                ready_env_id=None):
+        self._collect_mcts_temperature = temperature
+        self.collect_epsilon = epsilon
+        return self._gumbel_forward(self._collect_model, self._mcts_collect, data, action_mask, to_play, ready_env_id,
+                                    collect=True)
+
+    def forward_eval(self, data, action_mask, to_play=(-1,), ready_env_id=None):
+        return self._gumbel_forward(self._eval_model, self._mcts_eval, data, action_mask, to_play, ready_env_id,
+                                    collect=False)

@@ -22,20 +22,34 @@ TrajBlock layout, episode j of length L occupying L + 1 consecutive rows:
           (the env's eval_episode_return, muzero_collector.py:596-603 — for Atari the UNCLIPPED score,
           while reward_t is clipped);
   index   [n_ep, 3] int64 — (env_id, L, first row).
+A Gumbel MuZero collector's block (DeviceCollector(algo="gumbel")) has A + 1 more columns behind those:
+[... | improved policy_t (A) | completed value_t] — store_search_stats' improved_policy
+(muzero_collector.py:509-511) and the mean over the actions of the masked completed Q (:542-543); W = 4 + 2A (+ 1).
+The width alone does not say which columns a row holds (A = 1: 3 + A + 1 with predicted values is 3 + 2A), so a
+block carries `layout` — LAYOUT_PRED | LAYOUT_GUMBEL bits, set by pack_episodes and the device packing — and the
+header exchange of the gathers puts it on the wire beside (rows, episodes). A block built without it (layout None)
+is read by its width, as before.
 Actions and visit counts are small integers, exact in float32. `frame_scale` maps a stored frame to
 the observation the reference's GameSegment holds (1 / 255 for u8 grey frames: the wrappers'
 ScaledFloatFrame; 1 for float observations).
 """
 from dataclasses import dataclass
-from typing import List, Tuple, Union
+from typing import List, Optional, Tuple, Union
 
 import numpy as np
 import torch
 import torch.distributed as dist
 
 
-def scalar_width(A: int, pred: bool = False) -> int:
-    return 3 + A + int(bool(pred))
+LAYOUT_PRED, LAYOUT_GUMBEL = 1, 2
+
+
+def scalar_width(A: int, pred: bool = False, gumbel: bool = False) -> int:
+    return 3 + A + int(bool(pred)) + (A + 1 if gumbel else 0)
+
+
+def block_layout(pred: bool, gumbel: bool = False) -> int:
+    return (LAYOUT_PRED if pred else 0) | (LAYOUT_GUMBEL if gumbel else 0)
 
 
 @dataclass
@@ -44,6 +58,7 @@ class TrajBlock:
     scalars: Union[torch.Tensor, np.ndarray]
     index: Union[torch.Tensor, np.ndarray]
     frame_scale: float = 1.0
+    layout: Optional[int] = None  # LAYOUT_* bits; None: unmarked, the columns are inferred from the width
 
     @property
     def num_episodes(self) -> int:
@@ -60,24 +75,30 @@ class TrajBlock:
 
     def numpy(self) -> "TrajBlock":
         f = (lambda x: x.cpu().numpy()) if torch.is_tensor(self.scalars) else (lambda x: x)
-        return TrajBlock(f(self.frames), f(self.scalars), f(self.index), self.frame_scale)
+        return TrajBlock(f(self.frames), f(self.scalars), f(self.index), self.frame_scale, self.layout)
 
 
 def pack_episodes(rec_frames, rec_action, rec_reward, rec_visits, rec_value, episodes: List[Tuple[int, int, int]],
-                  rec_pred=None, frame_scale: float = 1.0, ep_return=None) -> TrajBlock:
+                  rec_pred=None, frame_scale: float = 1.0, ep_return=None, rec_policy=None, rec_cq=None) -> TrajBlock:
     """episodes: [(env_id, slot, L)] -> TrajBlock on the buffers' device (torch ops; the device
     collector packs with the lzm_episodes_* kernels, same layout). ep_return [n, E] (optional): the
-    slots' episode returns, written to each episode's row L."""
+    slots' episode returns, written to each episode's row L. rec_policy [n, E, T, A] and rec_cq [n, E, T]
+    (both or neither): a Gumbel block's improved policies and completed values."""
+    if (rec_policy is None) != (rec_cq is None):
+        raise ValueError("pack_episodes: rec_policy and rec_cq go together")
+    gumbel = rec_policy is not None
     dev = rec_frames.device
     frame_shape = tuple(rec_frames.shape[3:])
     A = rec_visits.shape[-1]
-    W = scalar_width(A, rec_pred is not None)
+    W = scalar_width(A, rec_pred is not None, gumbel)
+    layout = block_layout(rec_pred is not None, gumbel)
     lens = np.array([L for _, _, L in episodes], np.int64)
     rows = int((lens + 1).sum())
     index = np.zeros((len(episodes), 3), np.int64)
     if not episodes:
         return TrajBlock(torch.zeros((0,) + frame_shape, dtype=rec_frames.dtype, device=dev),
-                         torch.zeros((0, W), dtype=torch.float32, device=dev), torch.from_numpy(index), frame_scale)
+                         torch.zeros((0, W), dtype=torch.float32, device=dev), torch.from_numpy(index), frame_scale,
+                         layout)
     ii = np.repeat([i for i, _, _ in episodes], lens + 1)
     ee = np.repeat([e for _, e, _ in episodes], lens + 1)
     starts = np.concatenate([[0], np.cumsum(lens + 1)[:-1]])
@@ -95,22 +116,34 @@ def pack_episodes(rec_frames, rec_action, rec_reward, rec_visits, rec_value, epi
     sc[:, 1:2] = rec_reward[i_t, e_t, tc].unsqueeze(1) * keep
     sc[:, 2:2 + A] = rec_visits[i_t, e_t, tc].to(torch.float32) * keep
     sc[:, 2 + A:3 + A] = rec_value[i_t, e_t, tc].unsqueeze(1) * keep
+    g0 = 3 + A + int(rec_pred is not None)
     if rec_pred is not None:
-        sc[:, 3 + A:] = rec_pred[i_t, e_t, tc].unsqueeze(1) * keep
+        sc[:, 3 + A:4 + A] = rec_pred[i_t, e_t, tc].unsqueeze(1) * keep
+    if gumbel:
+        sc[:, g0:g0 + A] = rec_policy[i_t, e_t, tc].to(torch.float32) * keep
+        sc[:, g0 + A:] = rec_cq[i_t, e_t, tc].unsqueeze(1) * keep
     if ep_return is not None:
         lt = torch.from_numpy(last).to(dev)
         sc[lt, 1] = ep_return[i_t[lt], e_t[lt]].to(torch.float32)
-    return TrajBlock(frames, sc, torch.from_numpy(index), frame_scale)
+    return TrajBlock(frames, sc, torch.from_numpy(index), frame_scale, layout)
 
 
 def unpack_episodes(block: TrajBlock, A: int, rank: int = 0) -> List[dict]:
     """GameSegment-shaped dicts from one rank's block (host arrays). obs_segment holds the L + 1
     observations as the reference stores them (float32, frame * frame_scale); child_visit_segment is
     store_search_stats' visit / sum in float64; `visits` keeps the raw counts; `episode_return` is the
-    env's eval_episode_return (row L's reward column)."""
+    env's eval_episode_return (row L's reward column). A Gumbel block's episodes also hold
+    improved_policy_segment [L, A] float32 and completed_value, the mean of the steps' completed values
+    (muzero_collector.py:740-760 logs it)."""
     b = block.numpy()
     eps = []
-    has_pred = b.scalars.shape[1] == scalar_width(A, True)
+    if b.layout is None:  # an unmarked block: today's two widths
+        has_pred, gumbel = b.scalars.shape[1] == scalar_width(A, True), False
+    else:
+        has_pred, gumbel = bool(b.layout & LAYOUT_PRED), bool(b.layout & LAYOUT_GUMBEL)
+        if b.scalars.shape[1] != scalar_width(A, has_pred, gumbel):
+            raise ValueError(f"block of width {b.scalars.shape[1]} does not hold layout {b.layout} for {A} actions")
+    g0 = 3 + A + int(has_pred)
     for env_id, L, r0 in np.asarray(b.index, np.int64):
         sc = b.scalars[r0:r0 + L + 1]
         fr = b.frames[r0:r0 + L + 1]
@@ -124,6 +157,10 @@ def unpack_episodes(block: TrajBlock, A: int, rank: int = 0) -> List[dict]:
                  action_mask_segment=np.ones((L, A), np.int8), episode_return=float(sc[L, 1]))
         if has_pred:
             e["pred_value_segment"] = sc[:L, 3 + A].copy()
+        if gumbel:
+            e["improved_policy_segment"] = sc[:L, g0:g0 + A].copy()
+            e["completed_value_segment"] = sc[:L, g0 + A].copy()
+            e["completed_value"] = float(np.mean(sc[:L, g0 + A], dtype=np.float64))
         eps.append(e)
     return eps
 
@@ -162,14 +199,24 @@ def flatten_block(block: TrajBlock, device=None) -> torch.Tensor:
 
 
 def unflatten_block(buf: torch.Tensor, rows: int, n_ep: int, frame_shape, frame_dtype, W: int,
-                    frame_scale: float) -> TrajBlock:
-    """the TrajBlock a flat wire buffer holds (views into `buf`, no copy)"""
+                    frame_scale: float, layout: Optional[int] = None) -> TrajBlock:
+    """the TrajBlock a flat wire buffer holds (views into `buf`, no copy); layout: the sender's marker, which
+    travels in the header (block_header), not in the buffer"""
     fb = int(np.prod(tuple(frame_shape), dtype=np.int64)) * torch.empty((), dtype=frame_dtype).element_size()
     o_f, o_s, o_i, n = _flat_layout(rows, n_ep, fb, W)
     frames = buf[o_f:o_f + rows * fb].view(frame_dtype).reshape((rows,) + tuple(frame_shape))
     scalars = buf[o_s:o_s + rows * W * 4].view(torch.float32).reshape(rows, W)
     index = buf[o_i:n].view(torch.int64).reshape(n_ep, 3)
-    return TrajBlock(frames, scalars, index, frame_scale)
+    return TrajBlock(frames, scalars, index, frame_scale, layout)
+
+
+def block_header(block: TrajBlock) -> Tuple[int, int, int]:
+    """what a rank says about its block before the payload: (rows, episodes, layout marker; -1 when unmarked)"""
+    return block.rows, block.num_episodes, -1 if block.layout is None else int(block.layout)
+
+
+def header_layout(word: int) -> Optional[int]:
+    return None if word < 0 else int(word)
 
 
 def _wire_device(block: TrajBlock, group):
@@ -180,9 +227,9 @@ def _wire_device(block: TrajBlock, group):
 
 
 def _exchange_sizes(block: TrajBlock, dev, group):
-    """(rows, episodes) of every rank's block: one all-gather of 16 bytes per rank"""
+    """block_header of every rank's block: one all-gather of 24 bytes per rank"""
     world = dist.get_world_size(group)
-    sizes = torch.tensor([block.rows, block.num_episodes], dtype=torch.int64, device=dev)
+    sizes = torch.tensor(block_header(block), dtype=torch.int64, device=dev)
     all_sizes = [torch.zeros_like(sizes) for _ in range(world)]
     dist.all_gather(all_sizes, sizes, group=group)
     return [tuple(int(v) for v in s.cpu().tolist()) for s in all_sizes]
@@ -199,15 +246,15 @@ def all_gather_packed(block: TrajBlock, group=None, to_host: bool = True) -> Lis
     all_sizes = _exchange_sizes(block, dev, group)
     fshape, fdtype, W = tuple(block.frames.shape[1:]), block.frames.dtype, block.scalars.shape[1]
     fb = _frame_bytes(block)
-    lens = [_flat_layout(r, e, fb, W)[3] for r, e in all_sizes]
+    lens = [_flat_layout(r, e, fb, W)[3] for r, e, _ in all_sizes]
     flat = flatten_block(block, dev)
     padded = torch.zeros(max(1, max(lens)), dtype=torch.uint8, device=dev)
     padded[:flat.numel()] = flat
     recv = [torch.empty_like(padded) for _ in range(world)]
     dist.all_gather(recv, padded, group=group)
     out = []
-    for r, (nr, ne) in enumerate(all_sizes):
-        blk = unflatten_block(recv[r], nr, ne, fshape, fdtype, W, block.frame_scale)
+    for r, (nr, ne, lay) in enumerate(all_sizes):
+        blk = unflatten_block(recv[r], nr, ne, fshape, fdtype, W, block.frame_scale, header_layout(lay))
         out.append(blk.numpy() if to_host else blk)
     return out
 
@@ -224,7 +271,7 @@ def gather_packed(block: TrajBlock, dst: int = 0, group=None, to_host: bool = Tr
     all_sizes = _exchange_sizes(block, dev, group)
     fshape, fdtype, W = tuple(block.frames.shape[1:]), block.frames.dtype, block.scalars.shape[1]
     fb = _frame_bytes(block)
-    lens = [_flat_layout(r, e, fb, W)[3] for r, e in all_sizes]
+    lens = [_flat_layout(r, e, fb, W)[3] for r, e, _ in all_sizes]
     peer = (lambda r: r) if group is None else (lambda r: dist.get_global_rank(group, r))
     ops, bufs = [], {}
     if rank == dst:
@@ -239,14 +286,14 @@ def gather_packed(block: TrajBlock, dst: int = 0, group=None, to_host: bool = Tr
     if rank != dst:
         return []
     out = []
-    for r, (nr, ne) in enumerate(all_sizes):
+    for r, (nr, ne, lay) in enumerate(all_sizes):
         if r == dst:
             blk = block
         elif lens[r]:
-            blk = unflatten_block(bufs[r], nr, ne, fshape, fdtype, W, block.frame_scale)
+            blk = unflatten_block(bufs[r], nr, ne, fshape, fdtype, W, block.frame_scale, header_layout(lay))
         else:
             blk = unflatten_block(torch.zeros(0, dtype=torch.uint8, device=dev), 0, 0, fshape, fdtype, W,
-                                  block.frame_scale)
+                                  block.frame_scale, header_layout(lay))
         out.append(blk.numpy() if to_host else blk)
     return out
 

@@ -269,6 +269,20 @@ class DeviceTree:
         call("lzm_gumbel_get_policies", self.h, float(discount), ptr(out), stream_ptr(stream))
         return out
 
+    def collect_outputs(self, discount, out=None, count=None, stream=None):
+        """The roots' outputs a Gumbel collect step reads, in one launch (lzm_gumbel_collect_outputs): dict of
+        distributions int32 [B, A] (legal order, -1 past the legal count), values [B], completed_q [B, A] (action
+        order, 0 where illegal), improved_policy [B, A] and action int32 [B] (the first maximum of the policy row);
+        `out`: such a dict to write into; count: the int64 device step counter to advance by 1."""
+        if out is None:
+            f32, i32 = dict(dtype=torch.float32, device=self.device), dict(dtype=torch.int32, device=self.device)
+            out = dict(distributions=torch.empty((self.B, self.A), **i32), values=torch.empty(self.B, **f32),
+                       completed_q=torch.empty((self.B, self.A), **f32),
+                       improved_policy=torch.empty((self.B, self.A), **f32), action=torch.empty(self.B, **i32))
+        call("lzm_gumbel_collect_outputs", self.h, float(discount), ptr(out["distributions"]), ptr(out["values"]),
+             ptr(out["completed_q"]), ptr(out["improved_policy"]), ptr(out["action"]), ptr(count), stream_ptr(stream))
+        return out
+
     def search_mlp_gumbel(self, dims, weights, S, m, minmax, vtp_in, pool, discount=0.997, rec=None, stream=None):
         """One launch for the whole Gumbel MuZero search of a MuZeroModelMLP (lzm_search_mlp_gumbel; dims /
         weights: the packed network in the kernel layout, as search_mlp's); m: max_num_considered_actions;

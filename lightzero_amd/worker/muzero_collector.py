@@ -25,6 +25,12 @@ Two paths behind the one surface:
   ready-env / remain_episode schedule on their lengths and cuts the counted episodes into the same
   segments, flags, priorities and pool order (lightzero_amd.worker.segments).
 
+Under `policy_config.gumbel_algo` (a `lightzero_amd.policy.GumbelMuZeroCollectPolicy`) both paths do what the
+reference does for Gumbel MuZero: store_search_stats gets the improved policy (:509-511), pad_over the next
+segment's first improved policies (:269-275), and every episode's info carries `completed_value`, the mean over
+its steps of the mean masked completed Q (:542-543, :606-607), logged at :740-760. The device path builds its
+DeviceCollector with algo="gumbel".
+
 DI-engine is absent: logging goes to the `logging` module (and `tb_logger.add_scalar` when one is
 given), rank / world size and the statistics all-reduce come from torch.distributed.
 """
@@ -260,6 +266,9 @@ class MuZeroCollector:
         last_game_priorities = [None] * env_nums
         search_values_lst = [[] for _ in range(env_nums)]
         pred_values_lst = [[] for _ in range(env_nums)]
+        gumbel = bool(cfg.gumbel_algo)
+        improved_policy_lst = [[] for _ in range(env_nums)] if gumbel else None  # (:381-382)
+        completed_value_lst = np.zeros(env_nums) if gumbel else None  # (:386-387)
         eps_steps_lst, visit_entropies_lst = np.zeros(env_nums), np.zeros(env_nums)
         collected_episode = collected_step = 0
         ready_env_id = set()
@@ -298,6 +307,9 @@ class MuZeroCollector:
                     seg = game_segments[env_id]
                     if collect_with_pure_policy:
                         seg.store_search_stats(pure_visits, 0)
+                    elif gumbel:  # (:509-511)
+                        seg.store_search_stats(out['visit_count_distributions'], out['searched_value'],
+                                               improved_policy=out['improved_policy_probs'])
                     else:
                         seg.store_search_stats(out['visit_count_distributions'], out['searched_value'])
                     if chance_dict is not None:
@@ -314,10 +326,14 @@ class MuZeroCollector:
                     dones[env_id] = False if cfg.ignore_done else done
                     if not collect_with_pure_policy:
                         visit_entropies_lst[env_id] += out['visit_count_distribution_entropy']
+                        if gumbel:  # (:542-543)
+                            completed_value_lst[env_id] += np.mean(np.array(out['roots_completed_value']))
                     eps_steps_lst[env_id] += 1
                     if cfg.use_priority:
                         pred_values_lst[env_id].append(out['predicted_value'])
                         search_values_lst[env_id].append(out['searched_value'])
+                        if gumbel and not collect_with_pure_policy:  # (:555-556)
+                            improved_policy_lst[env_id].append(out['improved_policy_probs'])
                     windows[env_id].append(_to_ndarray(obs_t['observation']))
                     if seg.is_full():  # rollover: pad + save the previous block, this one becomes it
                         if last_game_segments[env_id] is not None:
@@ -326,6 +342,8 @@ class MuZeroCollector:
                         priorities = self._compute_priorities(env_id, pred_values_lst, search_values_lst)
                         pred_values_lst[env_id] = []
                         search_values_lst[env_id] = []
+                        if gumbel and not collect_with_pure_policy:  # (:578-579)
+                            improved_policy_lst[env_id] = []
                         last_game_segments[env_id] = seg
                         last_game_priorities[env_id] = priorities
                         game_segments[env_id] = self._new_segment()
@@ -339,6 +357,8 @@ class MuZeroCollector:
                         'step': self._env_info[env_id]['step']}
                 if not collect_with_pure_policy:
                     info['visit_entropy'] = visit_entropies_lst[env_id] / eps_steps_lst[env_id]
+                    if gumbel:  # (:606-607)
+                        info['completed_value'] = completed_value_lst[env_id] / eps_steps_lst[env_id]
                 collected_episode += 1
                 self._episode_info.append(info)
                 if last_game_segments[env_id] is not None:
@@ -366,6 +386,9 @@ class MuZeroCollector:
                 search_values_lst[env_id] = []
                 eps_steps_lst[env_id] = 0
                 visit_entropies_lst[env_id] = 0
+                if gumbel:
+                    completed_value_lst[env_id] = 0
+                    improved_policy_lst[env_id] = []
                 self._policy.reset([env_id])
                 self._reset_stat(env_id)
                 ready_env_id.remove(env_id)
@@ -391,11 +414,18 @@ class MuZeroCollector:
                 and not collect_with_pure_policy and not cfg.eps.eps_greedy_exploration_in_collect
                 and cfg.model.frame_stack_num == self._env.frame_stack)
 
+    def _gumbel_policy(self):
+        from ..policy import GumbelMuZeroCollectPolicy
+        return isinstance(self._policy, GumbelMuZeroCollectPolicy)
+
     def _device_collector(self, temperature):
         from ..collector import DeviceCollector
         cfg = self.policy_config
         if self._device is None:
             env = self._env
+            gz = {}
+            if self._gumbel_policy():  # GumbelMuZeroPolicy._forward_collect on the device
+                gz = dict(algo="gumbel", max_num_considered_actions=int(cfg.get('max_num_considered_actions', 4)))
             self._device = DeviceCollector(
                 self._policy._model, env.env_num, cfg.num_simulations, device=cfg.device,
                 max_episode_steps=env.max_episode_steps, episode_slots=cfg.get('device_episode_slots', 8),
@@ -405,7 +435,7 @@ class MuZeroCollector:
                 support_scale=cfg.model.support_scale, env=env.env_kind,
                 categorical_distribution=bool(cfg.model.get('categorical_distribution', True)),
                 search_cfg=dict(discount_factor=float(cfg.get('discount_factor', 0.997)),
-                                lstm_horizon_len=int(cfg.get('lstm_horizon_len', 5))))
+                                lstm_horizon_len=int(cfg.get('lstm_horizon_len', 5))), **gz)
         else:
             self._device.set_temperature(temperature)
         return self._device
@@ -435,13 +465,16 @@ class MuZeroCollector:
                 for it, k, seg, prio, d in episode_segments(cfg, self._env.action_space, e["obs_segment"],
                                                             e["action_segment"], e["reward_segment"], e["visits"],
                                                             e["root_value_segment"], e.get("pred_value_segment"),
-                                                            start, mask, -1):
+                                                            start, mask, -1,
+                                                            improved_policy=e.get("improved_policy_segment")):
                     pool.append((it, i, k, seg, prio, d))
                 collected_step += L
                 # the env's eval_episode_return (muzero_collector.py:596-603): the unclipped game score
                 # for Atari, the reward sum for CartPole (recorded on the device, lzm_*_collect_step)
                 infos.append({'reward': float(e["episode_return"]), 'time': 0.0, 'step': L,
                               'visit_entropy': self._visit_entropy(e["visits"], temperature)})
+                if "completed_value" in e:  # a Gumbel block's episode (:606-607)
+                    infos[-1]['completed_value'] = e["completed_value"]
         # the loop's wall time is the collect duration (all envs step together on the device); each
         # counted episode gets the share of it its steps make up, so the per-episode times sum to it
         wall = time.perf_counter() - t_start
@@ -484,6 +517,9 @@ class MuZeroCollector:
             'total_envstep_count': self._total_envstep_count, 'total_episode_count': self._total_episode_count,
             'total_duration': self._total_duration, 'visit_entropy': np.mean(ent),
         }
+        completed = [d['completed_value'] for d in eps if 'completed_value' in d]
+        if self.policy_config.gumbel_algo and completed:  # (:740-760; pure-policy episodes carry none)
+            info['completed_value'] = np.mean(completed)
         self._episode_info.clear()
         self._logger.info("collect end:\n{}".format('\n'.join('{}: {}'.format(k, v) for k, v in info.items())))
         if self._tb_logger is not None:

@@ -12,7 +12,8 @@ pool — are computed from one episode's arrays at once:
   observations start with the frame-stack window ending at o_{s_j} (the reset frame repeated at the
   episode start); the pad from segment j + 1 (n' of its transitions) adds
   o_{s_{j+1}+1 .. +min(U, n')}, visit distributions [: min(U, n')], rewards [: min(U + TD - 1, n')]
-  and root values [: min(U + TD, n')]; a full last segment is padded with the empty segment that
+  and root values [: min(U + TD, n')] (and, under gumbel_algo, improved policies [: min(U + TD, n')],
+  :269-275); a full last segment is padded with the empty segment that
   follows it, a partial last segment is saved unpadded.
 
 Save order key (iteration, env_id, k): the collector appends to its pool while it walks one
@@ -25,12 +26,13 @@ from ..game_segment import GameSegment
 
 
 def episode_segments(cfg, action_space, obs, action, reward, visits, root_value, pred_value, start_iter,
-                     action_mask, to_play):
+                     action_mask, to_play, improved_policy=None):
     """One finished episode -> [(iteration, k, GameSegment, priorities, done)].
 
     obs [L + 1, ...] (o_0 the reset frame), action [L] int, reward [L], visits [L, A] int
     (legal-order counts), root_value [L], pred_value [L] or None (priorities need it),
-    start_iter: the collector iteration of transition 0."""
+    start_iter: the collector iteration of transition 0. improved_policy [L, A] or None: the Gumbel MuZero
+    policy targets, cut and padded like the root values into each segment's improved_policy_probs."""
     L = int(len(action))
     gsl = int(cfg.game_segment_length)
     U, TD = int(cfg.num_unroll_steps), int(cfg.td_steps)
@@ -43,6 +45,7 @@ def episode_segments(cfg, action_space, obs, action, reward, visits, root_value,
     rew = np.asarray(reward, np.float64)
     val = np.asarray(root_value, np.float32).astype(np.float64)
     act = np.asarray(action, np.int64)
+    pol = None if improved_policy is None else np.asarray(improved_policy)
     # frame-stack window: fs copies of o_0, then o_1 .. o_L
     frames = np.concatenate([np.repeat(obs[:1], fs - 1, axis=0), obs], axis=0) if fs > 1 else obs
     m = -(-L // gsl)  # non-empty segments
@@ -63,12 +66,16 @@ def episode_segments(cfg, action_space, obs, action, reward, visits, root_value,
         r = rew[s:s + n]
         v = val[s:s + n]
         c = child[s:s + n]
+        ip = None if pol is None else pol[s:s + n]
         if padded:
             r = np.concatenate([r, rew[s2:s2 + min(U + TD - 1, n2)]])
             v = np.concatenate([v, val[s2:s2 + min(U + TD, n2)]])
             c = np.concatenate([c, child[s2:s2 + min(U, n2)]], axis=0)
+            if pol is not None:
+                ip = np.concatenate([ip, pol[s2:s2 + min(U + TD, n2)]], axis=0)
         seg = GameSegment.from_arrays(action_space, gsl, cfg, o, act[s:s + n], r, c, v,
-                                      np.repeat(np.asarray(action_mask)[None], n, axis=0), np.full(n, to_play, np.int64))
+                                      np.repeat(np.asarray(action_mask)[None], n, axis=0),
+                                      np.full(n, to_play, np.int64), improved_policy=ip)
         prio = None
         if use_priority:
             prio = np.abs(np.asarray(pred_value[s:s + n], np.float32) - np.asarray(root_value[s:s + n], np.float32)) \
