@@ -369,7 +369,12 @@ int lzm_atari_collect_step_gumbel(int n, int A, int T, int E, const int32_t *vis
  * each episode, copied from rec_frames [n][E][T+1][frame_bytes]), out_scalars [rows][3 + A (+1)] =
  * [action | reward | visit counts (A) | root value (| predicted value)] with each episode's row L
  * zero but for its reward column, which holds ep_return [n][E] of the slot (nullable: 0); then
- * consumed[i] = ep_count[i]. Env-major order, each env's episodes in finishing order. */
+ * consumed[i] = ep_count[i]. Env-major order, each env's episodes in finishing order.
+ * Contract: every ep_len the pack reads is <= T. The slots hold T steps and T + 1 frames, and an episode of L
+ * steps is copied as rows 0..L of its slot, so a longer one would be read outside rec_*. A collect step called
+ * with max_steps > T records such lengths (it stops recording at step T but goes on counting: ep_len = the step
+ * count, the final frame dropped; tests/test_gpu_env_edges.py); such slots must not be packed. DeviceCollector
+ * always passes T == max_steps, so its slots never hold one. */
 int lzm_episodes_scan(int n, int E, const int32_t *ep_count, const int32_t *consumed, const int32_t *ep_len,
                       int32_t *env_ep_off, int64_t *env_row_off, int64_t *totals, void *stream);
 int lzm_episodes_pack(int n, int E, int T, int A, int has_pred, int64_t frame_bytes, const int32_t *ep_count,
