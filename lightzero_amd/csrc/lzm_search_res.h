@@ -1024,8 +1024,10 @@ struct NoSide {
 };
 // side(j) runs at the top of slot j: a weight prefetch spread over the layer, one or two buffer
 // loads per slot, instead of a burst that stalls the wave at issue (the texture path takes a
-// 1 KiB wave-load per 16 cycles and four waves share it)
-template <int NR, typename WF, typename SF = NoSide>
+// 1 KiB wave-load per 16 cycles and four waves share it). POST: side(j) runs behind slot j's
+// FMAs instead, when w(j)'s register is free: the rolling refill of the stream buffer, whose slot j
+// takes the next streamed layer's slot j
+template <int NR, bool POST = false, typename WF, typename SF = NoSide>
 __device__ __forceinline__ void dense128n(const float *x, WF w, float *z, SF side = SF()) {
   const int e = threadIdx.x & 7;
   float4 xv[NR][4];
@@ -1042,10 +1044,11 @@ __device__ __forceinline__ void dense128n(const float *x, WF w, float *z, SF sid
   for (int j = 0; j < 4; ++j)
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      side(4 * j + c);
+      if (!POST) side(4 * j + c);
       const float4 q = w(4 * j + c);
 #pragma unroll
       for (int r = 0; r < NR; ++r) fma4(xv[r][j], q, a[r][c]);
+      if (POST) side(4 * j + c);
     }
 #pragma unroll
   for (int r = 0; r < NR; ++r)
@@ -1788,6 +1791,14 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     }
     __syncthreads();
     LZM_SUBSTAMP(33);
+    // the stream buffer is free again: stage fc_dynamics_2[0]'s LDS slots in it, every read issued
+    // here, behind the barrier (in front of it the barrier would wait for them) and in front of the
+    // look-back's first flag load, so a late draw's wait covers them; glibc_draw_wave's seed-state
+    // read is the first LDS consumer behind them. Every path to the layer passes here.
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < kRSlotsD; ++j) P[j] = WD2[j * kRT + tid];
+    __builtin_amdgcn_sched_barrier(0);
     int lrow = 0;  // the late draw's pick: the two-way tie's second candidate when rand() % 2 == 1
     if (late) {
       const unsigned long long w0_ = p.phase ? __builtin_amdgcn_s_memtime() : 0ull;
@@ -1832,12 +1843,12 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     LZM_STAMP(3);
     // The reward chain (fc_dynamics_2 -> reward head) and the prediction chain (prediction
     // common -> value / policy heads) both start from the next latent: one step per layer pair.
-    // ---- [fc_dynamics_2[0] (LDS) | fc_prediction_common[0] (registers)]
+    // ---- [fc_dynamics_2[0] (LDS, staged in P above) | fc_prediction_common[0] (registers)]
     {
       float z2, z6;
-      // fc_prediction_common[1] into P (used by the next pair), one slot per slot of this layer
+      // fc_prediction_common[1] into P (used by the next pair): slot j behind this layer's slot j
       const __amdgpu_buffer_rsrc_t rd5 = wave_rsrc(res_blk4(n, kRbD + 5), kRSlotsD * kRT * 16);
-      dense128n<1>(NLb, [&](int j) { return WD2[j * kRT + tid]; }, &z2, [&](int j) {
+      dense128n<1, true>(NLb, [&](int j) { return P[j]; }, &z2, [&](int j) {
         const f32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rd5, tid * 16, j * kRT * 16, 0);
         P[j] = make_float4(v.x, v.y, v.z, v.w);
       });
@@ -1854,24 +1865,21 @@ __global__ __launch_bounds__(kRT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // ---- [fc_prediction_common[1] (streamed) | fc_dynamics_2[1] (registers)]
     {
       float z7, z3;
-      dense128n<1>(U2, [&](int j) { return P[j]; }, &z7);
-      LZM_SUBSTAMP(37);
-      // the value support head into P (two steps on): half before this layer, half after it (a
-      // 20-load burst stalls the wave at issue)
-      __builtin_amdgcn_sched_barrier(0);
+      // the value support head into P (two steps on): slot j behind this layer's slot j, slots
+      // 16-19 (free since the previous simulation's support_logits) behind the layer
       const __amdgpu_buffer_rsrc_t rvs = wave_rsrc(res_blk4(n, kRbVS), kRSlotsS * kRT * 16);
-      auto fetch_vs = [&](int q0, int q1) {
-#pragma unroll
-        for (int q = q0; q < q1; ++q) {
-          const f32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rvs, tid * 16, q * kRT * 16, 0);
-          P[q] = make_float4(v.x, v.y, v.z, v.w);
-        }
+      auto fetch_vs = [&](int q) {
+        const f32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rvs, tid * 16, q * kRT * 16, 0);
+        P[q] = make_float4(v.x, v.y, v.z, v.w);
       };
-      fetch_vs(0, kRSlotsS / 2);
+      dense128n<1, true>(U2, [&](int j) { return P[j]; }, &z7, fetch_vs);
+      LZM_SUBSTAMP(37);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int q = kRSlotsD; q < kRSlotsS; ++q) fetch_vs(q);
       dense128n<1>(T2, [&](int j) { return wD3[j]; }, &z3);
       LZM_SUBSTAMP(38);
       __builtin_amdgcn_sched_barrier(0);
-      fetch_vs(kRSlotsS / 2, kRSlotsS);
       if (pD == 0) {
         T3[rpad(cD)] = fmaxf(z3 + BD[3 * kRHid + cD], 0.0f);
         U3[rpad(cD)] = fmaxf(z7 + BD[5 * kRHid + cD], 0.0f);
