@@ -805,7 +805,7 @@ int lzm_ez_lstm_step(int B, int K, int H, const float *xin, const int32_t *xscal
  * max_num_considered_actions) as a device table. lzm_roots_prepare, lzm_get_distributions, lzm_get_values,
  * lzm_get_trajectories, lzm_gather_latent, lzm_copy_tree and lzm_reserve work on it; lzm_traverse, lzm_backprop,
  * lzm_decode_backprop(_traverse) and the other kinds' one-launch searches return LZM_ERR_STATE on it, and the
- * lzm_gumbel_* device entry points and lzm_search_mlp_gumbel return LZM_ERR_STATE on any other handle, before
+ * lzm_gumbel_* device entry points, lzm_search_mlp_gumbel and lzm_search_conv_gumbel return LZM_ERR_STATE on any other handle, before
  * anything is launched.
  * One wave per root, four roots per workgroup; no random draw, so no cross-root communication. ---- */
 /* generate_gumbel(scale, 0, n) (:1134-1152): std::mt19937(0) through std::extreme_value_distribution<float>(0, 1),
@@ -884,6 +884,35 @@ int lzm_search_mlp_gumbel(lzm_handle *h, int hidden, int head_hidden, int suppor
  * need — the raw_value slice included — or a handle of another kind), 0, tree_in_lds}. Host only. */
 int lzm_search_mlp_gumbel_plan(const lzm_handle *h, int num_simulations, int hidden, int head_hidden, int support,
                                int res_dynamics, int32_t *out);
+/* GumbelMuZeroMCTSCtree.search's whole loop over a conv MuZeroModel (64 x 8 x 8 latent) in one launch per root
+ * slice: lzm_search_conv's kernel — trunk, head MLPs, support decode and ensure_softmax verdict unchanged — with the
+ * Gumbel walk on the root's tree slice in LDS (its raw_value slice, the Gumbel table and the considered-visits row
+ * staged beside it), raw_value stored after the expansion and the sign-free backup. The trunk and head arguments,
+ * minmax, latent_pool and the rec_* outputs are lzm_search_conv's; vtp_in passes through to every expanded node.
+ * No seeds and no pb_c arguments: the walk draws nothing, so roots exchange nothing — no epoch, no look-back
+ * words, no collect step — and batches past 1,024 roots (or past max_roots, 0 = no cap) are consecutive
+ * independent launches by lzm_conv_slice_roots' MuZero rule; a batch that fits one slice is a single launch. The
+ * root outputs stay lzm_gumbel_collect_outputs' launch. Rebuilds the considered-visits row like
+ * lzm_gumbel_traverse: a synchronous copy when (num_simulations, max_num_considered_actions) changed, so call
+ * lzm_gumbel_set_considered before a stream capture. Refused before any launch: a handle without LZM_TREE_GUMBEL
+ * or in collect-step mode (lzm_search_set_step) LZM_ERR_STATE; num_simulations beyond the reserved capacity
+ * LZM_ERR_CAPACITY; null arguments, num_simulations <= 0, max_num_considered_actions < 0, max_roots < 0, a network
+ * shape lzm_search_conv refuses, or an LDS plan (with the raw_value slice and the tables) over the limit
+ * LZM_ERR_ARG. */
+int lzm_search_conv_gumbel(lzm_handle *h, int num_simulations, int max_num_considered_actions, float discount,
+                           float *minmax, const int32_t *vtp_in, float *latent_pool, const float *trunk_w,
+                           const float *actmap, int n_dres, int n_pres, int r_ch, int h_ch, const float *w1t,
+                           const float *b1, const float *w2q, const float *b2, int Kr, int Khd, int off_policy,
+                           int Vr, int Vv, int categorical, int32_t *rec_x, int32_t *rec_a, int32_t *rec_len,
+                           float *rec_decoded, float *rec_logits, int max_roots, void *stream);
+/* What lzm_search_conv_gumbel launches for this handle, shape and max_roots, by the function the launch itself
+ * decides with: out int32 [11] as lzm_search_conv_sliced_plan ([0] the code the launch would return, [1]
+ * workgroups of the largest slice, [3] dynamic LDS bytes, [4] pinned head half-heads, [6] output rounds, [8]
+ * slices, [9] roots per slice, [10] roots in the last slice; [2], [5], [7] are 0). LZM_ERR_ARG for a null handle or
+ * output, num_simulations <= 0 or max_roots < 0, with out untouched; launches nothing. */
+int lzm_search_conv_gumbel_plan(const lzm_handle *h, int num_simulations, int n_dres, int n_pres, int r_ch, int h_ch,
+                                int Kr, int Khd, int off_policy, int Vr, int Vv, int categorical, int max_roots,
+                                int32_t *out);
 /* Device logf port (lzm_numerics.h glibc_logf) exposed for checks against the host libm. */
 int lzm_debug_logf(const float *x, float *out, int64_t n, void *stream);
 

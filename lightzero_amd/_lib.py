@@ -176,6 +176,9 @@ SIGNATURES = {
     "lzm_episodes_pack_gumbel": [_i] * 5 + [_i64] + [_vp] * 18,
     "lzm_search_mlp_gumbel": [_vp, _i, _i, _i, _i, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "lzm_search_mlp_gumbel_plan": [_vp, _i, _i, _i, _i, _i, _vp],
+    "lzm_search_conv_gumbel": [_vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i,
+                               _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
+    "lzm_search_conv_gumbel_plan": [_vp] + [_i] * 12 + [_vp],
     "lzm_debug_logf": [_vp, _vp, _i64, _vp],
     "lzm_conv_trunk_xin_p": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp,
                              _vp],

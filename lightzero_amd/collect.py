@@ -15,7 +15,8 @@ of tests and bench), so every replay is a fresh search.
 With `algo="gumbel"` the step is GumbelMuZeroPolicy._forward_collect (policy/gumbel_muzero.py:495-602) for a MuZero
 model: initial_inference -> the root values decoded on the device (inverse_scalar_transform) -> the 6-argument
 Roots.prepare -> GumbelMuZeroMCTSCtree.search (the one-launch search where it takes the network, cfg.fused_search on
-by default here; otherwise the per-simulation loop inside the same captured graph) -> one launch for everything the
+by default here — a MuZeroModelMLP; a conv MuZeroModel's one-launch search with fused_conv=True, off by default;
+otherwise the per-simulation loop inside the same captured graph) -> one launch for everything the
 policy reads from the roots (lzm_gumbel_collect_outputs: visit counts, values, the masked completed Q, the improved
 policy and its first maximum, the action). The Gumbel search draws nothing: there are no seeds, and the step
 counter only keys the epilogue's streams.
@@ -37,9 +38,11 @@ from .utils import EasyDict
 class DeviceSearchStep:
     def __init__(self, model, num_envs, num_simulations, legal_actions, obs_shape, device, noise_weight=0.25,
                  discount_factor=0.997, support_scale=300, seed=0, rng_mode="glibc", graph=True, cfg_extra=None,
-                 epilogue=None, fused_initial=True, algo=None, max_num_considered_actions=16):
+                 epilogue=None, fused_initial=True, algo=None, max_num_considered_actions=16, fused_conv=False):
         """algo: None (MuZero or EfficientZero, picked from the model) or "gumbel" (Gumbel MuZero over a MuZero
-        model, with max_num_considered_actions)."""
+        model, with max_num_considered_actions). fused_conv (algo="gumbel" only): sets cfg.fused_conv_search, the
+        one-launch Gumbel search of a conv MuZeroModel (lzm_search_conv_gumbel); off by default, where a conv model
+        takes the per-simulation loop."""
         if algo not in (None, "gumbel"):
             raise ValueError(f"DeviceSearchStep: unknown algo {algo!r} (None or 'gumbel')")
         self.gumbel = algo == "gumbel"
@@ -65,7 +68,8 @@ class DeviceSearchStep:
             cfg["lstm_horizon_len"] = 5
         if self.gumbel:
             # the one-launch search where _fused takes the network (the class's own default is off)
-            cfg.update(max_num_considered_actions=int(max_num_considered_actions), fused_search=True)
+            cfg.update(max_num_considered_actions=int(max_num_considered_actions), fused_search=True,
+                       fused_conv_search=bool(fused_conv))
         cfg.update(cfg_extra or {})
         self.mcts_cls = GumbelMuZeroMCTSCtree if self.gumbel else (
             EfficientZeroMCTSCtree if self.ez else MuZeroMCTSCtree)
@@ -218,7 +222,8 @@ class DeviceSearchStep:
             # (the Gumbel _fused takes S: its launch plan depends on it)
             args = (self.model, self.roots.tree, self.S) if self.gumbel else (self.model, self.roots.tree)
             if fused is None or fused(*args) is None:
-                # conv models (MuZero or EfficientZero): the folded step network re-folds in place
+                # conv models (MuZero, EfficientZero or Gumbel MuZero): the folded step network re-folds in place —
+                # the trunk, the heads and the action map the one-launch conv searches and the loop both read
                 _step_net(self.mcts, self.model)
 
     def step(self):

@@ -159,10 +159,11 @@ class DeviceCollector:
                  temperature=1.0, deterministic=False, noise_alpha=0.3, noise_weight=0.25, seed=0,
                  rng_mode="glibc", graph=True, poll_every=8, record_pred=False, support_scale=None,
                  categorical_distribution=True, env="cartpole", search_cfg=None, algo=None,
-                 max_num_considered_actions=16):
+                 max_num_considered_actions=16, fused_conv=False):
         """search_cfg: the search's config keys (discount_factor, lstm_horizon_len, ...: the policy's).
         algo: None, or "gumbel" with max_num_considered_actions (Gumbel MuZero: the action is the search's, so
-        temperature and deterministic are not used)."""
+        temperature and deterministic are not used) and fused_conv (DeviceSearchStep's: a conv model's Gumbel
+        search in one launch, cfg.fused_conv_search; off by default)."""
         _lib.require_gpu()
         if algo not in (None, "gumbel"):
             raise ValueError(f"DeviceCollector: unknown algo {algo!r} (None or 'gumbel')")
@@ -218,7 +219,7 @@ class DeviceCollector:
                                        noise_weight=noise_weight, seed=seed, rng_mode=rng_mode, graph=graph,
                                        epilogue=epilogue, support_scale=support_scale,
                                        discount_factor=sc.pop("discount_factor", 0.997), cfg_extra=sc, algo=algo,
-                                       max_num_considered_actions=max_num_considered_actions)
+                                       max_num_considered_actions=max_num_considered_actions, fused_conv=fused_conv)
         self.search.build_graph()
         self.reset()
 

@@ -3339,12 +3339,15 @@ extern "C" int lzm_conv_slice_roots(int ez, int B, int H, int resident_workgroup
   }
   return kLsRows * m;
 }
-// lower bits shared by both kinds: tree, walk and head buffers after the activation buffers (float offsets)
-static size_t conv_plan_lds(const lzm_handle *h, int S, int Kr, int Khd, int Vr, int Vv, size_t o, ConvSearchArgs &p) {
+// lower bits shared by both kinds: tree, walk and head buffers after the activation buffers (float offsets).
+// gz (the Gumbel instantiation): the root's raw_value slice where the value cache is, no pUCT table, and the
+// Gumbel table with the considered-visits row (64 + S words) where the seeds and the 16807^i table are (S + 32).
+static size_t conv_plan_lds(const lzm_handle *h, int S, int Kr, int Khd, int Vr, int Vv, size_t o, ConvSearchArgs &p,
+                            bool gz = false) {
   p.off_stat = (int)o; o += (size_t)h->cap * 4;
   p.off_meta = (int)o; o += (size_t)h->cap * 4;
   p.off_val = (int)o; o += round4((size_t)h->cap);
-  p.off_lut = (int)o; o += round4((size_t)2 * h->lut_n);
+  p.off_lut = (int)o; o += gz ? 0 : round4((size_t)2 * h->lut_n);
   p.off_legal = (int)o; o += round4((size_t)h->A + 1);
   p.off_path = (int)o; o += round4((size_t)h->depth_cap);
   p.off_pact = (int)o; o += round4((size_t)h->depth_cap);
@@ -3354,7 +3357,7 @@ static size_t conv_plan_lds(const lzm_handle *h, int S, int Kr, int Khd, int Vr,
   p.off_hid = (int)o; o += 96;
   p.off_part = (int)o; o += 3 * kHdParts * 32;
   p.off_lg = (int)o; o += round4((size_t)Vr + Vv + h->A);
-  p.off_seed = (int)o; o += round4((size_t)S + 32);
+  p.off_seed = (int)o; o += round4((size_t)S + (gz ? kMaxActions : 32));
   p.off_lmax = (int)o; o += round4((size_t)S + 1);
   return o;
 }
@@ -3366,21 +3369,34 @@ static bool conv_shape_ok(int n_dres, int n_pres, int r_ch, int h_ch, int Khd, i
          Vv <= 1024 && (categorical || (Vr == 1 && Vv == 1));
 }
 // max_roots < 0: the whole batch in one launch (lzm_search_conv); >= 0: root slices by lzm_conv_slice_roots.
+// gz: lzm_search_conv_gumbel's plan — a Gumbel MuZero handle outside collect-step mode (LZM_ERR_STATE otherwise),
+// the same network shapes, the Gumbel instantiation's LDS plan; always sliced (its roots are independent).
 static ConvPlan conv_plan_mz(const lzm_handle *h, int S, int n_dres, int n_pres, int r_ch, int h_ch, int Kr, int Khd,
-                             int off_policy, int Vr, int Vv, int categorical, ConvSearchArgs &p, int max_roots = -1) {
+                             int off_policy, int Vr, int Vv, int categorical, ConvSearchArgs &p, int max_roots = -1,
+                             bool gz = false) {
   ConvPlan pl{LZM_ERR_ARG, 0, 0, 0, 0, 0, 0, 0, 0};
+  const char *name = gz ? "lzm_search_conv_gumbel" : "lzm_search_conv";
+  if (gz) {
+    if ((pl.rc = check_kind(name, h, true)) != LZM_OK) return pl;
+    pl.rc = LZM_ERR_STATE;
+    if (h->step_count || h->step_fresh || h->step_dist || h->step_vals) {
+      refuse(LZM_ERR_STATE, name, "collect-step mode (lzm_search_set_step): there is no Gumbel collect step");
+      return pl;
+    }
+    pl.rc = LZM_ERR_ARG;
+  }
   if (h->flags & LZM_TREE_EZ) {
     set_err("lzm_search_conv: MuZero trees only");
     return pl;
   }
   if (!conv_shape_ok(n_dres, n_pres, r_ch, h_ch, Khd, off_policy, Vr, Vv, categorical) || Kr != r_ch * 64 ||
       (Kr % 128)) {
-    set_err("lzm_search_conv: unsupported network shape (64x8x8 latent, <= 8 residual blocks per network, <= 32 "
-            "reward / head planes, K per head a multiple of 128 and <= 1024, supports <= 1024)");
+    snprintf(g_err, sizeof(g_err), "%s: unsupported network shape (64x8x8 latent, <= 8 residual blocks per network, "
+             "<= 32 reward / head planes, K per head a multiple of 128 and <= 1024, supports <= 1024)", name);
     return pl;
   }
   if (S > h->sims_cap) {
-    snprintf(g_err, sizeof(g_err), "lzm_search_conv: %d simulations > reserved %d (lzm_reserve)", S, h->sims_cap);
+    snprintf(g_err, sizeof(g_err), "%s: %d simulations > reserved %d (lzm_reserve)", name, S, h->sims_cap);
     pl.rc = LZM_ERR_CAPACITY;
     return pl;
   }
@@ -3392,14 +3408,14 @@ static ConvPlan conv_plan_mz(const lzm_handle *h, int S, int n_dres, int n_pres,
     return pl;
   }
   if (roots > kScMaxRoots) {
-    snprintf(g_err, sizeof(g_err), "lzm_search_conv: %d roots > %d", roots, kScMaxRoots);
+    snprintf(g_err, sizeof(g_err), "%s: %d roots > %d", name, roots, kScMaxRoots);
     return pl;
   }
   // dynamic LDS plan (float offsets, 16-B aligned): the two split-fp16 activation buffers first
   p.pbt_rows = 0;  // (no pb_c table: the MuZero conv walk divides, same bits)
-  size_t o = conv_plan_lds(h, S, Kr, Khd, Vr, Vv, (size_t)2 * kBxBuf / 2, p);
+  size_t o = conv_plan_lds(h, S, Kr, Khd, Vr, Vv, (size_t)2 * kBxBuf / 2, p, gz);
   if (o * sizeof(float) > kMaxLds) {
-    snprintf(g_err, sizeof(g_err), "lzm_search_conv: %zu B of LDS needed (tree too large: lower num_simulations)",
+    snprintf(g_err, sizeof(g_err), "%s: %zu B of LDS needed (tree too large: lower num_simulations)", name,
              o * sizeof(float));
     return pl;
   }
@@ -3425,6 +3441,10 @@ static ConvPlan conv_plan_mz(const lzm_handle *h, int S, int n_dres, int n_pres,
 
 // the conv search kernel for a tree kind, an RNG and phase stamps
 typedef void (*ConvKernel)(ConvSearchArgs);
+// (the Gumbel walk draws nothing: one instantiation per stamps setting, on the draw-free side of the RNG flag)
+static ConvKernel conv_gumbel_kernel_fn(bool stamps) {
+  return stamps ? search_conv_kernel<kBxAhead, true, true, true> : search_conv_kernel<kBxAhead, true, false, true>;
+}
 static ConvKernel conv_kernel_fn(bool ez, bool fast, bool stamps) {
   static const ConvKernel kernels[2][2][2] = {  // [EZ][stamps, none][Philox, glibc]
       {{search_conv_kernel<kBxAhead, true, true>, search_conv_kernel<kBxAhead, false, true>},
@@ -3540,13 +3560,13 @@ static ConvPlan conv_plan_ez(const lzm_handle *h, int S, int H, int horizon, int
 // >= 0: the sliced launch with that cap, out[8 .. 10] as well.
 static int conv_plan_query(const lzm_handle *h, int S, int ez, int H, int horizon, int n_dres, int n_pres, int r_ch,
                            int h_ch, int Kr, int Khd, int off_policy, int Vr, int Vv, int categorical, int max_roots,
-                           int32_t *out) {
+                           int32_t *out, bool gz = false) {
   ConvSearchArgs p;
   memset(&p, 0, sizeof(p));
   const ConvPlan pl = ez ? conv_plan_ez(h, S, H, horizon, n_dres, n_pres, r_ch, h_ch, Khd, off_policy, Vr, Vv,
                                         categorical, p, max_roots)
                          : conv_plan_mz(h, S, n_dres, n_pres, r_ch, h_ch, Kr, Khd, off_policy, Vr, Vv, categorical, p,
-                                        max_roots);
+                                        max_roots, gz);
   out[0] = pl.rc; out[1] = pl.G; out[2] = pl.T; out[3] = (int32_t)pl.lds; out[4] = pl.npin; out[5] = pl.pbt_rows;
   out[6] = pl.out_rounds; out[7] = pl.r_one_round;
   if (max_roots < 0) return LZM_OK;
@@ -3627,22 +3647,26 @@ static int conv_ez_attach(lzm_handle *h, ConvSearchArgs &p, const ConvEzIn &z, i
 // inside the launch; Kr is then the LSTM's width).
 // max_roots < 0: the whole batch in one launch; >= 0: the sliced entry points (every root slice, EfficientZero's
 // each a co-resident grid of its own, enqueued on the stream, lowest roots first).
+// gumbel_m >= 0: lzm_search_conv_gumbel (max_num_considered_actions; -1: the pUCT searches) — the Gumbel
+// instantiation on a Gumbel MuZero handle: no seeds, the considered-visits row set as lzm_search_mlp_gumbel does,
+// the handle's raw_value array and tables attached, no collect step; its slices are independent launches.
 static int search_conv_launch(lzm_handle *h, int num_simulations, int pb_c_base, float pb_c_init, float discount,
                               float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
                               const float *trunk_w, const float *actmap, int n_dres, int n_pres, int r_ch, int h_ch,
                               const float *w1t, const float *b1, const float *w2q, const float *b2, int Kr, int Khd,
                               int off_policy, int Vr, int Vv, int categorical, int32_t *rec_x, int32_t *rec_a,
                               int32_t *rec_len, float *rec_decoded, float *rec_logits, void *stream, int max_roots,
-                              const ConvEzIn *ez) {
-  const char *name = ez ? "lzm_search_conv_ez" : "lzm_search_conv";
+                              const ConvEzIn *ez, int gumbel_m = -1) {
+  const bool gz = gumbel_m >= 0;
+  const char *name = gz ? "lzm_search_conv_gumbel" : ez ? "lzm_search_conv_ez" : "lzm_search_conv";
   const int S = num_simulations;
-  if (!h || !minmax || (!seeds && !h->step_count) || !vtp_in || !latent_pool || !trunk_w || !actmap || !w1t || !b1 ||
-      !w2q || !b2 || S <= 0 ||
+  if (!h || !minmax || (!gz && !seeds && !h->step_count) || !vtp_in || !latent_pool || !trunk_w || !actmap || !w1t ||
+      !b1 || !w2q || !b2 || S <= 0 ||
       (ez && (!ez->hpool || !ez->cpool || !ez->lstm_frag || !ez->lstm_bias || !ez->vp_s || !ez->vp_t))) {
     snprintf(g_err, sizeof(g_err), "%s: null argument or no simulations", name);
     return LZM_ERR_ARG;
   }
-  if (h->flags & LZM_TREE_GUMBEL) {
+  if (!gz && (h->flags & LZM_TREE_GUMBEL)) {
     set_err("one-launch searches do not take a Gumbel MuZero handle");
     return LZM_ERR_STATE;
   }
@@ -3659,22 +3683,27 @@ static int search_conv_launch(lzm_handle *h, int num_simulations, int pb_c_base,
   const ConvPlan plan = ez ? conv_plan_ez(h, S, ez->H, ez->horizon, n_dres, n_pres, r_ch, h_ch, Khd, off_policy, Vr,
                                           Vv, categorical, p, max_roots)
                            : conv_plan_mz(h, S, n_dres, n_pres, r_ch, h_ch, Kr, Khd, off_policy, Vr, Vv, categorical,
-                                          p, max_roots);
+                                          p, max_roots, gz);
   if (plan.rc != LZM_OK) return plan.rc;
   int rc = search_preamble(h, pb_c_base, pb_c_init, S, h->B);
   if (rc != LZM_OK) return rc;
+  if (gz && (rc = gumbel_set_considered(h, S, gumbel_m, name)) != LZM_OK) return rc;
   if (ez && (rc = conv_ez_attach(h, p, *ez, S, r_ch)) != LZM_OK) return rc;
   fill_common(p, h, S, discount, seeds, vtp_in, minmax, latent_pool, rec_x, rec_a, rec_len, rec_decoded, rec_logits);
   p.w = trunk_w; p.actmap = actmap; p.n_dres = n_dres; p.n_pres = n_pres; p.r_ch = r_ch; p.h_ch = h_ch;
   p.w1t = w1t; p.b1 = b1; p.w2q = w2q; p.b2 = b2; p.Kr = ez ? ez->H : Kr; p.Khd = Khd; p.off_policy = off_policy;
   p.Vr = Vr; p.Vv = Vv; p.categorical = categorical ? 1 : 0;
   p.err = h->err; p.sdiag = h->search_diag;
-  p.step_count = h->step_count; p.step_base = h->step_base; p.step_inc = h->step_inc; p.step_fresh = h->step_fresh;
-  p.step_delta = h->step_delta; p.out_dist = h->step_dist; p.out_values = h->step_vals;
+  if (gz) {  // (the plan refused collect-step mode: the step fields stay zero)
+    p.raw = h->raw; p.gumbel = h->gumbel; p.considered = h->considered;
+  } else {
+    p.step_count = h->step_count; p.step_base = h->step_base; p.step_inc = h->step_inc; p.step_fresh = h->step_fresh;
+    p.step_delta = h->step_delta; p.out_dist = h->step_dist; p.out_values = h->step_vals;
+  }
   const bool stamps = phase_timing();
   if (stamps && (rc = ensure_phase(h)) != LZM_OK) return rc;
   p.stamps = stamps ? h->phase : nullptr;
-  const ConvKernel fn = conv_kernel_fn(ez != nullptr, p.fast != 0, stamps);
+  const ConvKernel fn = gz ? conv_gumbel_kernel_fn(stamps) : conv_kernel_fn(ez != nullptr, p.fast != 0, stamps);
   LZM_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
   for (int root0 = 0; root0 < h->B; root0 += plan.roots) {  // (EfficientZero slices start at multiples of 64 roots)
     p.root0 = root0;
@@ -3734,6 +3763,40 @@ extern "C" int lzm_search_conv_ez(lzm_handle *h, int num_simulations, int pb_c_b
   return search_conv_launch(h, num_simulations, pb_c_base, pb_c_init, discount, minmax, seeds, vtp_in, latent_pool,
                             trunk_w, actmap, n_dres, n_pres, r_ch, h_ch, w1t, b1, w2q, b2, 0, Khd, off_policy, Vr, Vv,
                             categorical, rec_x, rec_a, rec_len, rec_decoded, rec_logits, stream, -1, &ez);
+}
+
+// GumbelMuZeroMCTSCtree.search's whole loop over a conv MuZeroModel in one launch per root slice (lzm_search_conv.h,
+// the GZ instantiation), on lzm_search_conv_sliced's plan-and-launch path. No seeds and no pb_c arguments (the
+// handle's default table is set and never read). Rebuilds the considered-visits row when (S, m) changed: a
+// synchronous copy, outside stream capture (lzm_gumbel_set_considered before a capture).
+extern "C" int lzm_search_conv_gumbel(lzm_handle *h, int num_simulations, int max_num_considered_actions,
+                                      float discount, float *minmax, const int32_t *vtp_in, float *latent_pool,
+                                      const float *trunk_w, const float *actmap, int n_dres, int n_pres, int r_ch,
+                                      int h_ch, const float *w1t, const float *b1, const float *w2q, const float *b2,
+                                      int Kr, int Khd, int off_policy, int Vr, int Vv, int categorical,
+                                      int32_t *rec_x, int32_t *rec_a, int32_t *rec_len, float *rec_decoded,
+                                      float *rec_logits, int max_roots, void *stream) {
+  if (max_roots < 0 || max_num_considered_actions < 0) {
+    set_err("lzm_search_conv_gumbel: max_roots >= 0 (0: no cap) and max_num_considered_actions >= 0");
+    return LZM_ERR_ARG;
+  }
+  return search_conv_launch(h, num_simulations, 19652, 1.25f, discount, minmax, nullptr, vtp_in, latent_pool, trunk_w,
+                            actmap, n_dres, n_pres, r_ch, h_ch, w1t, b1, w2q, b2, Kr, Khd, off_policy, Vr, Vv,
+                            categorical, rec_x, rec_a, rec_len, rec_decoded, rec_logits, stream, max_roots, nullptr,
+                            max_num_considered_actions);
+}
+
+// What lzm_search_conv_gumbel would do with the same max_roots, by the launch's own decision (conv_plan_mz):
+// lzm_search_conv_sliced_plan's eleven words. Launches nothing.
+extern "C" int lzm_search_conv_gumbel_plan(const lzm_handle *h, int num_simulations, int n_dres, int n_pres, int r_ch,
+                                           int h_ch, int Kr, int Khd, int off_policy, int Vr, int Vv, int categorical,
+                                           int max_roots, int32_t *out) {
+  if (!h || !out || num_simulations <= 0 || max_roots < 0) {
+    set_err("lzm_search_conv_gumbel_plan: null argument, no simulations or max_roots < 0");
+    return LZM_ERR_ARG;
+  }
+  return conv_plan_query(h, num_simulations, 0, 0, 0, n_dres, n_pres, r_ch, h_ch, Kr, Khd, off_policy, Vr, Vv,
+                         categorical, max_roots, out, true);
 }
 
 // lzm_search_conv_ez over root slices (lzm_conv_slice_roots with the launch's own residency bound; max_roots: the

@@ -21,6 +21,11 @@
 // Every arithmetic step is the generic path's own device code in the same order, so the fused
 // search equals the generic one bit for bit (tests/test_gpu_conv.py).
 //
+// The same launch serves GumbelMuZeroMCTSCtree (search_conv_kernel's GZ flag, lzm_search_conv_gumbel): steps 2-4
+// unchanged, step 1 the Gumbel walk (lzm_gumbel.h) on the LDS slice with the root's raw_value beside it, no draw
+// and therefore no flags, no look-back and no epoch; equal to the generic Gumbel loop bit for bit
+// (tests/test_gpu_gumbel_conv.py).
+//
 // ensure_softmax (scaling_transform.py:36-62) is a batch-wide verdict per simulation: softmax is
 // skipped only when EVERY row sums to 1. A workgroup whose own row fails the check knows the
 // verdict (softmax); one whose own row passes cannot decide alone and counts an integrity error
@@ -45,6 +50,7 @@
 #include <stdint.h>
 
 #include "lzm_conv.h"
+#include "lzm_gumbel.h"
 #include "lzm_heads.h"
 #include "lzm_lstm.h"
 #include "lzm_search_mlp.h"
@@ -126,6 +132,13 @@ struct ConvSearchArgs {
   // ends the search (its last workgroup advances the epoch and the collect step's counter).
   int root0, nroots, last_slice;
   int nmb_s, T_s;  // EfficientZero: the slice's own row blocks and LSTM tiles (nmb, T: the whole batch's)
+  // Gumbel MuZero (search_conv_kernel<AHEAD, true, STAMPS, true>; null otherwise): the handle's raw_value array
+  // [cap][B], the Gumbel table [64] and the considered-visits row [S] (lzm_gumbel.h). The LDS plan of this
+  // instantiation keeps the root's raw_value slice at off_val (it has no value cache) and the two tables at
+  // off_seed (64 + S words; it has no seeds).
+  float *raw;
+  const float *gumbel;
+  const int32_t *considered;
 };
 
 // Bounded waits of the one-launch conv searches (their grid must be co-resident; the host checks the static
@@ -450,7 +463,14 @@ __device__ __forceinline__ unsigned long long sc_wait_word(const unsigned long l
   return v;
 }
 
-template <int AHEAD, bool FAST, bool STAMPS = false>
+// GZ: the Gumbel MuZero search over the same network (mcts_ctree.py:1054-1122; lzm_search_conv_gumbel). The trunk,
+// the heads, the decode and the sdiag verdict are the code below; the tree side is lzm_gumbel.h's: wave 0 walks
+// with gumbel_walk on the LDS slice (the root's raw_value slice, the Gumbel table and the considered-visits row
+// staged beside it), the leaf is expanded with the root's to_play as it came in, raw_value is stored after it and
+// the backup has no player sign (gumbel_expand_backup's order). The walk draws nothing, so roots are independent:
+// no seeds, no 16807^i table, no players scan, no depth flags, no look-back, no late draw, no epoch, no collect
+// step; neither the pUCT table nor the value cache is staged. Slices of a batch need no ordering.
+template <int AHEAD, bool FAST, bool STAMPS = false, bool GZ = false>
 __global__ __launch_bounds__(kScThreads) __attribute__((amdgpu_waves_per_eu(1, 1))) void search_conv_kernel(
     ConvSearchArgs p) {
   extern __shared__ uint4 sc_lds4[];
@@ -482,49 +502,60 @@ __global__ __launch_bounds__(kScThreads) __attribute__((amdgpu_waves_per_eu(1, 1
   t.A = A; t.cap = p.cap; t.lut_n = p.lut_n; t.depth_cap = p.depth_cap; t.B = 1;
   NodeStat *ls = reinterpret_cast<NodeStat *>(smem + p.off_stat);
   NodeMeta *lm = reinterpret_cast<NodeMeta *>(smem + p.off_meta);
-  float *lval = smem + p.off_val;
+  float *lval = smem + p.off_val;  // (Gumbel: the root's raw_value slice in the value cache's place)
   float2 *llut = reinterpret_cast<float2 *>(smem + p.off_lut);
   int32_t *llegal = reinterpret_cast<int32_t *>(smem + p.off_legal);
   for (int e = tid; e < p.cap; e += kScThreads) {
     const NodeStat s = p.stat[(size_t)e * B + b];
     ls[e] = s;
     lm[e] = p.meta[(size_t)e * B + b];
-    lval[e] = node_value(s);
+    if constexpr (GZ) lval[e] = p.raw[(size_t)e * B + b];
+    else lval[e] = node_value(s);
   }
-  for (int e = tid; e < p.lut_n; e += kScThreads) llut[e] = p.lut[e];
+  if constexpr (!GZ)
+    for (int e = tid; e < p.lut_n; e += kScThreads) llut[e] = p.lut[e];
   for (int e = tid; e < A; e += kScThreads) llegal[e] = p.legal[(size_t)b * A + e];
   if (tid == 0) llegal[A] = p.nlegal[b];
-  t.stat = ls; t.meta = lm; t.val = lval; t.lut = llut; t.legal = llegal; t.nlegal = llegal + A;
+  t.stat = ls; t.meta = lm; t.val = GZ ? nullptr : lval; t.lut = llut; t.legal = llegal; t.nlegal = llegal + A;
   t.pbt = nullptr;  // the walk divides (same bits) instead of a dependent table read: Breakout walk -3%
   t.path = reinterpret_cast<int32_t *>(smem + p.off_path);
   t.path_act = reinterpret_cast<int32_t *>(smem + p.off_pact);
   t.pathlen = s_len;
   uint32_t *s_seed = reinterpret_cast<uint32_t *>(smem + p.off_seed);
   uint32_t *s_pow = s_seed + S;
-  if (p.step_count) {
-    const long long cnt = *p.step_count;  // (read before the last workgroup's increment)
-    for (int e = tid; e < S; e += kScThreads) s_seed[e] = (uint32_t)((p.step_base + cnt * (long long)S + e) % 1000000ll);
+  GumbelView gv;  // (Gumbel: the two tables where the other instantiations keep their seeds, 64 + S words)
+  if constexpr (GZ) {
+    float *lgum = smem + p.off_seed;
+    int32_t *lcons = reinterpret_cast<int32_t *>(lgum + kMaxActions);
+    for (int e = tid; e < kMaxActions; e += kScThreads) lgum[e] = p.gumbel[e];
+    for (int e = tid; e < S; e += kScThreads) lcons[e] = p.considered[e];
+    gv.raw = lval; gv.gumbel = lgum; gv.considered = lcons; gv.S = S;
   } else {
-    for (int e = tid; e < S; e += kScThreads) s_seed[e] = p.seeds[e];
+    if (p.step_count) {
+      const long long cnt = *p.step_count;  // (read before the last workgroup's increment)
+      for (int e = tid; e < S; e += kScThreads) s_seed[e] = (uint32_t)((p.step_base + cnt * (long long)S + e) % 1000000ll);
+    } else {
+      for (int e = tid; e < S; e += kScThreads) s_seed[e] = p.seeds[e];
+    }
+    if (!FAST && tid < 31) s_pow[tid] = p.pow16807[tid];
   }
-  if (!FAST && tid < 31) s_pow[tid] = p.pow16807[tid];
   bx_zero_borders(sc_lds4, tid, kScThreads);
   float4 *lpin = reinterpret_cast<float4 *>(smem + p.off_wpin);
   sc_stage_wpin(lpin, p.npin, p.w1t, tid);
   if (tid == 0) {
-    s_mm[0] = p.step_fresh ? make_float4(kFloatMin, kFloatMax, p.step_delta, 0.0f) : p.minmax[b];
+    s_mm[0] = (!GZ && p.step_fresh) ? make_float4(kFloatMin, kFloatMax, p.step_delta, 0.0f) : p.minmax[b];
     s_vtp0 = p.vtp_in[b];
-    s_epoch = (int)__hip_atomic_load(p.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (!GZ) s_epoch = (int)__hip_atomic_load(p.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  if (tid < 64) {  // players (cnode.cpp:776-781), every load in flight at once
+  if (!GZ && tid < 64) {  // players (cnode.cpp:776-781), every load in flight at once
     int m = INT_MIN;
     for (int q = tid; q < B; q += 64) m = max(m, p.vtp_in[q]);
     m = xor_max(m);
     if (tid == 0) s_players = (m == -1) ? 1 : 2;
   }
   __syncthreads();
-  const int players = s_players;
-  const unsigned long long epoch = (unsigned long long)(uint32_t)s_epoch;
+  const int players = GZ ? 1 : s_players;
+  const unsigned long long epoch = GZ ? 0ull : (unsigned long long)(uint32_t)s_epoch;
   float *lr = smem + p.off_r, *lhd = smem + p.off_hd, *lhid = smem + p.off_hid, *lpart = smem + p.off_part;
   float *llg = smem + p.off_lg;
   const int N2 = p.Vr + p.Vv + A;
@@ -557,15 +588,24 @@ __global__ __launch_bounds__(kScThreads) __attribute__((amdgpu_waves_per_eu(1, 1
     // ---- selection (wave 0; parity mode: draw-free walk, depth flag, look-back only for a value)
     // the dynamics conv's first weight chunks, in flight during the walk
     bx_prefetch<18, AHEAD, 0>(ring, wave_stream(p.w + L.dyn), lane);
-    if (!FAST && tid < 31) seed_state_parallel(s_seed[k], s_pow, s_z0);
+    if (!GZ && !FAST && tid < 31) seed_state_parallel(s_seed[k], s_pow, s_z0);
     __syncthreads();
     if (STAMPS && tid == 0) st_prev = __builtin_amdgcn_s_memtime();
-    if (tid == 0) s_late = 0;
+    if (!GZ && tid == 0) s_late = 0;
     if (wv == 0) {
       const float4 mm = s_mm[0];
       Descent d;
       if (STAMPS && tid == 0) st_w0 = __builtin_amdgcn_s_memtime();
-      if (FAST) {
+      if constexpr (GZ) {
+        // cselect_root_child at level 0, cselect_interior_child below: no draw, so the request is final here;
+        // its to_play is the root's, passed through (ctree_gumbel_muzero/lib/cnode.cpp:895)
+        d = gumbel_walk(t, gv, p.disc, 0, 0, 1);
+        d.vtp = s_vtp0;
+        if (STAMPS && tid == 0) {
+          st_acc[10] += __builtin_amdgcn_s_memtime() - st_w0;
+          st_acc[11] += d.len;  // levels walked (diagnostics)
+        }
+      } else if (FAST) {
         const uint32_t seed = s_seed[k];
         auto draw = [seed, b](int level) -> uint32_t {
           uint4 o = philox4x32_10(make_uint4((uint32_t)level, (uint32_t)b, 0u, 0u), make_uint2(seed, 0x4c5a4d43u));
@@ -621,7 +661,7 @@ __global__ __launch_bounds__(kScThreads) __attribute__((amdgpu_waves_per_eu(1, 1
     // ---- trunk: the leaf's parent latent pool[x][b] and the action's map (registers; loads in flight
     // together), then the layers
     {
-      const bool late = s_late != 0;
+      const bool late = !GZ && s_late != 0;
       const float *src = p.pool + ((size_t)max(s_x, 0) * B + b) * (kCvCh * kCvPix);
       float xres[16];
       float4 am[4];
@@ -762,7 +802,12 @@ __global__ __launch_bounds__(kScThreads) __attribute__((amdgpu_waves_per_eu(1, 1
       const int leaf = t.path[s_len[0]];
       const float *plg = llg + p.Vr + p.Vv;
       expand_wave(t, 0, leaf, s_leafvtp, k + 1, r, plg, -1, kExp2fTab, 1);
-      backup_wave(t, 0, 0, 1, s_mm, s_leafvtp, v, p.disc);
+      if constexpr (GZ) {  // gumbel_expand_backup's order: raw_value after the expansion, a backup without a sign
+        if (lane == 0) gv.raw[leaf] = v;
+        backup_wave(t, 0, 0, 1, s_mm, -1, v, p.disc);
+      } else {
+        backup_wave(t, 0, 0, 1, s_mm, s_leafvtp, v, p.disc);
+      }
       if (p.rec_dec) {
         if (lane < 2) p.rec_dec[((size_t)k * B + b) * 2 + lane] = lane ? v : r;
         if (lane < A) p.rec_logits[((size_t)k * B + b) * A + lane] = plg[lane];
@@ -773,10 +818,11 @@ __global__ __launch_bounds__(kScThreads) __attribute__((amdgpu_waves_per_eu(1, 1
     stamp(6);
   }
   __syncthreads();
-  // ---- write back the slice (tree, last path, min-max)
+  // ---- write back the slice (tree, last path, min-max; Gumbel: raw_value too)
   for (int e = tid; e < p.cap; e += kScThreads) {
     p.stat[(size_t)e * B + b] = ls[e];
     p.meta[(size_t)e * B + b] = lm[e];
+    if constexpr (GZ) p.raw[(size_t)e * B + b] = lval[e];
   }
   for (int l = tid; l < p.depth_cap; l += kScThreads) {
     p.path[(size_t)l * B + b] = t.path[l];
@@ -787,23 +833,26 @@ __global__ __launch_bounds__(kScThreads) __attribute__((amdgpu_waves_per_eu(1, 1
     for (int n = 0; n < 13; ++n) atomicAdd(p.stamps + 40 + n, st_acc[n]);
   }
   // collect-step root outputs (root_outputs_kernel's values): visit counts per legal action, the root value
-  if (p.out_dist && tid < A) {
+  if (!GZ && p.out_dist && tid < A) {
     const int rl = lm[0].latent;
     p.out_dist[(size_t)b * A + tid] = (rl >= 0 && tid < llegal[A]) ? ls[1 + A * rl + llegal[tid]].visit : -1;
   }
-  if (p.out_values && tid == 0) p.out_values[b] = node_value(ls[0]);
+  if (!GZ && p.out_values && tid == 0) p.out_values[b] = node_value(ls[0]);
   if (tid == 0) {
     if (range_bad) atomicAdd(p.err + 4, 1);  // split activations out of the fp16 range (lzm_conv.h)
     p.minmax[b] = s_mm[0];
     p.pathlen[b] = s_len[0];
     // the last workgroup advances the epoch (no release fence: the kernel boundary orders the
-    // write-back for every later reader) and the collect step's counter (every workgroup has read it)
-    const uint32_t done = atomicAdd(p.epoch + 1, 1u);
-    if (done == (uint32_t)gridDim.x - 1) {
-      p.epoch[1] = 0;
-      if (p.last_slice) {  // (the slices of one search share the epoch and the counter's value)
-        __hip_atomic_store(p.epoch, (uint32_t)(epoch + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p.step_count && p.step_inc) *p.step_count += 1;
+    // write-back for every later reader) and the collect step's counter (every workgroup has read it);
+    // the Gumbel search has neither
+    if constexpr (!GZ) {
+      const uint32_t done = atomicAdd(p.epoch + 1, 1u);
+      if (done == (uint32_t)gridDim.x - 1) {
+        p.epoch[1] = 0;
+        if (p.last_slice) {  // (the slices of one search share the epoch and the counter's value)
+          __hip_atomic_store(p.epoch, (uint32_t)(epoch + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (p.step_count && p.step_inc) *p.step_count += 1;
+        }
       }
     }
   }

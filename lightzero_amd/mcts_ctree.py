@@ -476,14 +476,15 @@ class _MCTSCtree(object):
         n = (self.last_plan or {}).get("slices", 1)
         return name if n <= 1 else f"{name} ({n} slices)"
 
-    def _native_conv_net(self, model, t, shape):
-        """What both _fused_conv start from: the native split-precision step network of this class's family,
-        with packed heads, when cfg.fused_search (default on) and LZM_FUSED_CONV allow a one-launch search of
-        a 64 x 8 x 8 latent on tree t; None otherwise. Clears last_plan (the plan of this search, when the
-        library is asked)."""
+    def _native_conv_net(self, model, t, shape, on=None):
+        """What every _fused_conv starts from: the native split-precision step network of this class's family,
+        with packed heads, when `on` (default: cfg.fused_search, itself default on) and LZM_FUSED_CONV allow a
+        one-launch search of a 64 x 8 x 8 latent on tree t; None otherwise. Clears last_plan (the plan of this
+        search, when the library is asked)."""
         self.last_plan = None
         ez = self._tree.Roots.EZ
-        if not self._cfg.get('fused_search', True) or t.ez != ez or os.environ.get("LZM_FUSED_CONV", "1") == "0":
+        on = self._cfg.get('fused_search', True) if on is None else on
+        if not on or t.ez != ez or os.environ.get("LZM_FUSED_CONV", "1") == "0":
             return None
         net = _step_net(self, model)
         hp = getattr(net, "heads", None)
@@ -808,14 +809,17 @@ class GumbelMuZeroMCTSCtree(_MCTSCtree):
     next simulation's traverse. Eager, or one HIP graph with cfg.use_hip_graph. The walk draws no random number:
     there are no seeds and no rng_mode, and search_with_reuse does not exist, as in the reference.
     With cfg.fused_search (off by default here) a MuZeroModelMLP's whole search runs as one launch
-    (lzm_search_mlp_gumbel) where _fused allows it; last_path says which path ran."""
+    (lzm_search_mlp_gumbel) where _fused allows it; with cfg.fused_conv_search (a key of its own, off by default)
+    a conv MuZeroModel's runs as one launch per root slice (lzm_search_conv_gumbel) where _fused_conv allows it;
+    last_path says which path ran."""
 
     config = dict(
         num_simulations=50,
         root_dirichlet_alpha=0.3,
         root_noise_weight=0.25,
         value_delta_max=0.01,
-    )  # (the reference's keys only; cfg.fused_search is read with default False: the one-launch search is opt-in)
+    )  # (the reference's keys only; cfg.fused_search and cfg.fused_conv_search are read with default False: the
+    #    one-launch searches are opt-in)
     _tree = gmz_tree
     reward_name = 'reward'
     rng_mode = None
@@ -866,6 +870,25 @@ class GumbelMuZeroMCTSCtree(_MCTSCtree):
             return None
         return packed, dims
 
+    def _max_roots(self):
+        return int(self._cfg.get('sliced_search_max_roots', 0) or 0)
+
+    def _fused_conv(self, model, t, shape, S):
+        """The native split-precision FoldedConvNet (_native_conv_net's packing) when cfg.fused_conv_search is set
+        and the whole search of S simulations can run as lzm_search_conv_gumbel launches: a conv MuZeroModel with a
+        64 x 8 x 8 latent whose trunk and heads are packed, of a shape and tree size the launch itself accepts —
+        asked of the library (DeviceTree.search_conv_gumbel_plan: lzm_search_conv's shapes, the tree slice with its
+        raw_value and the Gumbel tables in the workgroup's LDS, any number of roots in slices of up to 1,024 or
+        cfg.sliced_search_max_roots); None otherwise (the generic per-simulation path). The plan is left in
+        last_plan. The key is not cfg.fused_search: DeviceSearchStep(algo="gumbel") sets that one for the MLP
+        search, and a conv model keeps the generic path unless asked."""
+        net = self._native_conv_net(model, t, shape, on=bool(self._cfg.get('fused_conv_search', False)))
+        if net is None:
+            return None
+        self.last_plan = t.search_conv_gumbel_plan(net, S, categorical=self._categorical(),
+                                                   max_roots=self._max_roots())
+        return net if self.last_plan["supported"] else None
+
     def _loop(self, t, model, c, rec=None, infer=None, net=None):
         """The S simulations (mcts_ctree.py:1054-1122) on tree t over c.buf, all enqueued on the current stream:
         simulation k's backup and simulation k + 1's traverse share a launch."""
@@ -901,17 +924,25 @@ class GumbelMuZeroMCTSCtree(_MCTSCtree):
                 raise TypeError("GumbelMuZeroMCTSCtree.search: roots must come from GumbelMuZeroMCTSCtree.roots")
             c.t.set_considered(*self._considered())  # (before any capture: a synchronous table copy)
             fz = self._fused(model, c.t, c.S)
-            self._buffers(c, model, graph=fz is None and not self.record and self._cfg.get('use_hip_graph', False))
+            cz = self._fused_conv(model, c.t, c.shape, c.S) if fz is None else None
+            one_launch = fz is not None or cz is not None
+            self._buffers(c, model, graph=not one_launch and not self.record and self._cfg.get('use_hip_graph', False))
             c.buf.vtp_in.copy_(_to_play_tensor(to_play_batch, c.B, c.dev))
             rec = self._recorder(c)
-            if fz is None:
+            if not one_launch:
                 self._generic(c, model, rec)
             else:  # the whole search in one launch; the requests' to_play is the roots' (it passes through)
-                packed, dims = fz
                 new_minmax(c.B, self._cfg.value_delta_max, c.dev, out=c.buf.mm)
-                c.t.search_mlp_gumbel(dims, packed, c.S, self._considered()[1], c.buf.mm, c.buf.vtp_in, c.buf.pool,
-                                      self._discount(), rec=rec)
+                if cz is not None:  # the conv network (lzm_search_conv_gumbel; one launch per root slice)
+                    c.t.search_conv_gumbel(cz, c.S, self._considered()[1], c.buf.mm, c.buf.vtp_in, c.buf.pool,
+                                           self._discount(), self._categorical(), rec=rec,
+                                           max_roots=self._max_roots())
+                else:
+                    packed, dims = fz
+                    c.t.search_mlp_gumbel(dims, packed, c.S, self._considered()[1], c.buf.mm, c.buf.vtp_in,
+                                          c.buf.pool, self._discount(), rec=rec)
                 if rec is not None:
                     rec.vtp.copy_(c.buf.vtp_in.expand(c.S, c.B))
             self._finish(c, roots, None, rec)
-            self.last_path = "generic" if fz is None else "fused-mlp"
+            # (independent slices are one search: their count is last_plan["slices"], not part of the path's name)
+            self.last_path = "fused-conv" if cz is not None else ("fused-mlp" if fz is not None else "generic")

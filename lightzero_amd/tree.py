@@ -303,6 +303,38 @@ class DeviceTree:
              int(dims["res"]), out)
         return dict(roots_per_wg=out[0], kernel={0: "streaming"}.get(out[1]), mode=out[2], tree_in_lds=bool(out[3]))
 
+    def search_conv_gumbel(self, net, S, m, minmax, vtp_in, pool, discount=0.997, categorical=True, rec=None,
+                           max_roots=0, stream=None):
+        """One launch per root slice for the whole Gumbel MuZero search of a conv MuZeroModel
+        (lzm_search_conv_gumbel; net: a native split-precision conv_infer.FoldedConvNet, as search_conv's);
+        m: max_num_considered_actions; max_roots: a cap on the slice (0: the library's 1,024); rec: optional
+        _Recorder-like object (its vtp rows are the caller's: to_play passes through)."""
+        hp = net.heads
+        self._unchecked = True
+        with torch.cuda.device(self.device):  # (a changed (S, m) rebuilds the considered-visits row)
+            call("lzm_search_conv_gumbel", self.h, int(S), int(m), float(discount), ptr(minmax), ptr(vtp_in),
+                 ptr(pool), ptr(net.native), ptr(net.actmap), int(net.n_dres), int(net.n_pres), int(net.r_ch),
+                 int(net.h_ch), ptr(hp["w1t"]), ptr(hp["b1"]), ptr(hp["w2q"]), ptr(hp["b2"]), int(hp["Kr"]),
+                 int(hp["Khd"]), int(hp["off_policy"]), int(hp["Vr"]), int(hp["Vv"]), int(bool(categorical)),
+                 *_rec_ptrs(rec), int(max_roots), stream_ptr(stream))
+        self._considered = (int(S), int(m))
+
+    def search_conv_gumbel_plan(self, net, S, categorical=True, max_roots=0):
+        """What search_conv_gumbel(net, S, ..., max_roots=max_roots) launches on this handle as it stands
+        (lzm_search_conv_gumbel_plan: the launch's own decision; host only, nothing is launched):
+        search_conv_sliced_plan's dict — supported, code, reason, workgroups (of the largest slice), lds_bytes
+        (the raw_value slice and the Gumbel tables included), pinned, out_rounds, slices, slice_roots,
+        last_slice_roots."""
+        hp = net.heads
+        out = (ctypes.c_int32 * 11)()
+        call("lzm_search_conv_gumbel_plan", self.h, int(S), int(net.n_dres), int(net.n_pres), int(net.r_ch),
+             int(net.h_ch), int(hp["Kr"]), int(hp["Khd"]), int(hp["off_policy"]), int(hp["Vr"]), int(hp["Vv"]),
+             int(bool(categorical)), int(max_roots), out)
+        reason = None if out[0] == 0 else _lib.load().lzm_last_error().decode()
+        return dict(supported=out[0] == 0, code=out[0], reason=reason, workgroups=out[1], lstm_tiles=out[2],
+                    lds_bytes=out[3], pinned=out[4], pbt_rows=out[5], out_rounds=out[6], out_one_round=False,
+                    reward_one_round=bool(out[7]), slices=out[8], slice_roots=out[9], last_slice_roots=out[10])
+
     def search_mlp(self, dims, weights, S, minmax, seeds, vtp_in, pool, pb_c_base=19652, pb_c_init=1.25,
                    discount=0.997, rec=None, stream=None):
         """One launch for the whole search (lzm_search_mlp); rec: optional _Recorder-like object."""

@@ -425,7 +425,8 @@ class MuZeroCollector:
             env = self._env
             gz = {}
             if self._gumbel_policy():  # GumbelMuZeroPolicy._forward_collect on the device
-                gz = dict(algo="gumbel", max_num_considered_actions=int(cfg.get('max_num_considered_actions', 4)))
+                gz = dict(algo="gumbel", max_num_considered_actions=int(cfg.get('max_num_considered_actions', 4)),
+                          fused_conv=bool(cfg.get('fused_conv_search', False)))  # (conv models: opt-in)
             self._device = DeviceCollector(
                 self._policy._model, env.env_num, cfg.num_simulations, device=cfg.device,
                 max_episode_steps=env.max_episode_steps, episode_slots=cfg.get('device_episode_slots', 8),

@@ -1,7 +1,12 @@
-"""Times one CartPole collect step of a Gumbel MuZero policy with device events on the step's stream.
+"""Times one CartPole (or, --env breakout, Breakout) collect step of a Gumbel MuZero policy with device events on the
+step's stream.
 
-    python tools/gumbel_collect_time.py --variant device|host|muzero [--envs N] [--sims S] [--considered M]
-                                        [--warmup W] [--reps R]
+    python tools/gumbel_collect_time.py --variant device|host|muzero [--env cartpole|breakout] [--fused-conv]
+                                        [--envs N] [--sims S] [--considered M] [--warmup W] [--reps R]
+
+--env breakout (--variant device or muzero): the Breakout device env with bench.build_conv_model's conv MuZeroModel;
+  --fused-conv turns DeviceCollector(fused_conv=True) on: the one-launch conv Gumbel search in the step's graph
+  instead of the per-simulation loop.
 
 --variant device: DeviceCollector(algo="gumbel"), one graph replay per step (initial inference, root values, the
   6-argument prepare, the one-launch Gumbel search, lzm_gumbel_collect_outputs, the env kernel).
@@ -33,6 +38,8 @@ HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--variant", choices=("device", "host", "muzero"), default="device")
+    p.add_argument("--env", choices=("cartpole", "breakout"), default="cartpole")
+    p.add_argument("--fused-conv", action="store_true", help="DeviceCollector(fused_conv=True)")
     p.add_argument("--envs", type=int, default=256)
     p.add_argument("--sims", type=int, default=50)
     p.add_argument("--considered", type=int, default=16)
@@ -49,7 +56,14 @@ def main():
     dev = torch.device("cuda", 0)
     N, S, m, A = args.envs, args.sims, args.considered, 2
     torch.manual_seed(0)
-    model = cartpole_muzero_model(random_heads=True).to(dev).eval()
+    breakout = args.env == "breakout"
+    if breakout:
+        if args.variant == "host" or (args.fused_conv and args.variant != "device"):
+            raise SystemExit("gumbel_collect_time: --env breakout takes --variant device [--fused-conv] or muzero")
+        import bench
+        model = bench.build_conv_model(dev, seed=0)
+    else:
+        model = cartpole_muzero_model(random_heads=True).to(dev).eval()
     ms, wall = [], []
 
     def timed(fn, it):
@@ -67,7 +81,13 @@ def main():
     if args.variant in ("device", "muzero"):
         from lightzero_amd.collector import DeviceCollector
         kw = dict(algo="gumbel", max_num_considered_actions=m) if args.variant == "device" else {}
-        col = DeviceCollector(model, N, S, device=dev, seed=0, graph=True, episode_slots=8, **kw)
+        if breakout:
+            kw.update(env="breakout", episode_slots=2, max_episode_steps=64)
+            if args.variant == "device":
+                kw.update(fused_conv=bool(args.fused_conv))
+        else:
+            kw.update(episode_slots=8)
+        col = DeviceCollector(model, N, S, device=dev, seed=0, graph=True, **kw)
         for it in range(args.warmup + args.reps):
             timed(col.step, it)
         path = col.search.mcts.last_path
@@ -106,7 +126,8 @@ def main():
             timed(step, it)
         path = mcts.last_path
         check = float(last["dist"].double().sum().item() + last["values"].double().sum().item())
-    out = dict(variant=args.variant, path=path, envs=N, sims=S, considered=m if args.variant != "muzero" else None,
+    out = dict(variant=args.variant, env=args.env, fused_conv=bool(args.fused_conv), path=path, envs=N, sims=S,
+               considered=m if args.variant != "muzero" else None,
                ms=[round(v, 4) for v in ms], median_ms=round(float(np.median(ms)), 4), checksum=check)
     if args.variant == "host":
         out.update(wall_ms=[round(v, 4) for v in wall], median_wall_ms=round(float(np.median(wall)), 4))
