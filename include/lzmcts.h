@@ -44,8 +44,11 @@ enum lzm_flags {
   LZM_TREE_EZ = 1,  /* EfficientZero value-prefix tree (ctree_efficientzero) instead of MuZero */
   LZM_RNG_FAST = 2, /* per-root counter-based (Philox4x32-10) tie-break stream instead of the
                        batch-serial glibc rand() stream of the reference (parity mode) */
-  LZM_TREE_GUMBEL = 4 /* Gumbel MuZero tree (ctree_gumbel_muzero) instead of MuZero: driven by the lzm_gumbel_*
-                         entry points below; excludes LZM_TREE_EZ; LZM_RNG_FAST is ignored (the tree never draws) */
+  LZM_TREE_GUMBEL = 4, /* Gumbel MuZero tree (ctree_gumbel_muzero) instead of MuZero: driven by the lzm_gumbel_*
+                          entry points below; excludes LZM_TREE_EZ; LZM_RNG_FAST is ignored (the tree never draws) */
+  LZM_TREE_STOCHASTIC = 8 /* Stochastic MuZero tree (ctree_stochastic_muzero): set by lzm_stochastic_create, driven
+                             by the lzm_stochastic_* entry points below; excludes LZM_TREE_EZ and LZM_TREE_GUMBEL;
+                             always draws from per-root Philox streams, whatever LZM_RNG_FAST says */
 };
 
 /* Creates a tree for `num_roots` roots, `action_space` actions, capacity for `max_sims`
@@ -913,6 +916,69 @@ int lzm_search_conv_gumbel(lzm_handle *h, int num_simulations, int max_num_consi
 int lzm_search_conv_gumbel_plan(const lzm_handle *h, int num_simulations, int n_dres, int n_pres, int r_ch, int h_ch,
                                 int Kr, int Khd, int off_policy, int Vr, int Vv, int categorical, int max_roots,
                                 int32_t *out);
+/* ---- Stochastic MuZero tree (ctree_stochastic_muzero; lzm_stochastic.h) --------------------------------------
+ * Levels alternate: the root and every even depth are decision nodes (pUCT with the 1e-6 tie rule over
+ * `action_space` children), odd depths are chance nodes (an outcome drawn from the children's priors, over
+ * `chance_space_size` children). A walk's leaf is a chance node iff its search_len is odd. A chance leaf is
+ * expanded from the afterstate half of the network (a policy row of width chance_space_size, reward 0), a
+ * decision leaf from the dynamics half (reward, policy row of width action_space).
+ *
+ * lzm_stochastic_create makes such a handle (flags: LZM_TREE_STOCHASTIC is set for you; LZM_TREE_EZ or
+ * LZM_TREE_GUMBEL LZM_ERR_ARG). action_space or chance_space_size below 1 or above 64 is LZM_ERR_ARG. The handle's
+ * child blocks are W = max(action_space, chance_space_size) wide and lzm_action_space returns W: on such a handle
+ * every [B][A] row of the shared entry points (lzm_roots_prepare's legal lists, noises and logits,
+ * lzm_get_distributions' rows) is W wide, and lzm_roots_prepare wants every root's legal count given (a count <= 0
+ * would mean W actions). lzm_roots_prepare, lzm_get_distributions, lzm_get_values, lzm_get_trajectories (actions
+ * and outcomes alternate), lzm_gather_latent, lzm_copy_tree, lzm_reserve and lzm_minmax_init serve it unchanged.
+ * Every other family's traverse, backprop and one-launch entry point returns LZM_ERR_STATE on it, and the
+ * lzm_stochastic_* entry points return LZM_ERR_STATE on any other handle, before any launch.
+ *
+ * Draws (the reference seeds its chance draw from std::random_device: nothing to stay in parity with), Philox4x32-10
+ * under key (*seed, 0x4c5a4d43): the tie draw of decision level l of root i is word 0 >> 1 of counter (l, i, 0, 0)
+ * modulo the tie count (the LZM_RNG_FAST traverse's draw); the chance draw of chance level l is u in (0, 1) from
+ * words 0 and 1 of counter (l, i, 1, 0) (53 bits, + 0.5, * 2^-53) and takes the first outcome, in outcome order,
+ * whose running double sum of the float32 priors exceeds u * total — an outcome of prior exactly 0 is never taken;
+ * if rounding leaves none, the last outcome with a non-zero prior. */
+int lzm_stochastic_create(int num_roots, int action_space, int chance_space_size, int max_sims, int flags,
+                          lzm_handle **out);
+int lzm_chance_space(const lzm_handle *h);            /* 0 on any other handle */
+int lzm_stochastic_action_space(const lzm_handle *h); /* the action space given at creation; 0 on any other handle */
+/* batch_traverse (stochastic_mz_tree.pyx:85-90): lzm_traverse's arguments and out_is_chance int32 [B]
+ * (leaf_node_is_chance), which the handle also keeps for the backups that follow. */
+int lzm_stochastic_traverse(lzm_handle *h, int pb_c_base, float pb_c_init, float discount, float *minmax,
+                            const uint32_t *seed, const int32_t *vtp_in, int32_t *out_x, int32_t *out_y,
+                            int32_t *out_a, int64_t *out_a64, int32_t *out_vtp, int32_t *out_len,
+                            int32_t *out_is_chance, void *stream);
+/* batch_backpropagate (stochastic_mz_tree.pyx:75-83) from raw lists: entry k of rewards / values [n] and logits
+ * [n][width] serves root leaf_idx[k] (leaf_idx null: n = num_roots, entry k serves root k; num_leaves ignored);
+ * to_play is per root [B]. width (the child count) is action_space or chance_space_size; each root's leaf kind is
+ * the last walk's (a chance leaf's reward is 0). LZM_ERR_STATE before the first lzm_stochastic_traverse. */
+int lzm_stochastic_backprop(lzm_handle *h, int current_latent_state_index, float discount, float *minmax,
+                            const float *rewards, const float *values, const float *logits, int width,
+                            const int32_t *to_play, const int32_t *leaf_idx, int num_leaves, void *stream);
+/* One simulation's support decode + expand + backup from both halves of the network, each run over the whole
+ * batch: root i reads the chance set (value logits [B][Vv], policy [B][chance_space_size], next latent rows) when
+ * its leaf is a chance node, the decision set (reward logits [B][V], value logits [B][Vv], policy
+ * [B][action_space], next latent rows) otherwise, and files that set's latent row into pool_slot [B][row_elems].
+ * Support decode as lzm_decode_backprop's (ensure_softmax judged per head tensor over all B rows; the value rows'
+ * length by lzm_set_value_support). */
+int lzm_stochastic_decode_backprop(lzm_handle *h, int current_latent_state_index, float discount, float *minmax,
+                                   const float *chance_value, const float *chance_policy, const float *chance_latent,
+                                   const float *decision_reward, const float *decision_value,
+                                   const float *decision_policy, const float *decision_latent, int support_len,
+                                   int categorical, const int32_t *to_play, float *pool_slot, int64_t row_elems,
+                                   float *out_decoded, void *stream);
+/* ... and the next simulation's lzm_stochastic_traverse in the same launch, by the wave that backed the root up. */
+int lzm_stochastic_decode_backprop_traverse(lzm_handle *h, int current_latent_state_index, float discount,
+                                            float *minmax, const float *chance_value, const float *chance_policy,
+                                            const float *chance_latent, const float *decision_reward,
+                                            const float *decision_value, const float *decision_policy,
+                                            const float *decision_latent, int support_len, int categorical,
+                                            const int32_t *to_play, float *pool_slot, int64_t row_elems,
+                                            float *out_decoded, int pb_c_base, float pb_c_init, const uint32_t *seed,
+                                            const int32_t *vtp_in, int32_t *out_x, int32_t *out_y, int32_t *out_a,
+                                            int64_t *out_a64, int32_t *out_vtp, int32_t *out_len,
+                                            int32_t *out_is_chance, void *stream);
 /* Device logf port (lzm_numerics.h glibc_logf) exposed for checks against the host libm. */
 int lzm_debug_logf(const float *x, float *out, int64_t n, void *stream);
 

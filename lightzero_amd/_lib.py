@@ -27,6 +27,7 @@ LZM_ERR_WORDS = 8  # sticky error words per tree handle (lzm_check_errors)
 LZM_TREE_EZ = 1
 LZM_RNG_FAST = 2
 LZM_TREE_GUMBEL = 4
+LZM_TREE_STOCHASTIC = 8
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -180,6 +181,14 @@ SIGNATURES = {
                                _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
     "lzm_search_conv_gumbel_plan": [_vp] + [_i] * 12 + [_vp],
     "lzm_debug_logf": [_vp, _vp, _i64, _vp],
+    "lzm_stochastic_create": [_i, _i, _i, _i, _i, ctypes.POINTER(_vp)],
+    "lzm_chance_space": [_vp],
+    "lzm_stochastic_action_space": [_vp],
+    "lzm_stochastic_traverse": [_vp, _i, _f, _f] + [_vp] * 11,
+    "lzm_stochastic_backprop": [_vp, _i, _f, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp],
+    "lzm_stochastic_decode_backprop": [_vp, _i, _f] + [_vp] * 8 + [_i, _i, _vp, _vp, _i64, _vp, _vp],
+    "lzm_stochastic_decode_backprop_traverse": [_vp, _i, _f] + [_vp] * 8 + [_i, _i, _vp, _vp, _i64, _vp, _i, _f]
+                                               + [_vp] * 10,
     "lzm_conv_trunk_xin_p": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp,
                              _vp],
 }

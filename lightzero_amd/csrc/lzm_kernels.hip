@@ -43,6 +43,7 @@
 #include "lzm_az_fused.h"
 #include "lzm_tree.h"
 #include "lzm_gumbel.h"
+#include "lzm_stochastic.h"
 #include "lzm_search_mlp.h"
 #include "lzm_search_res.h"
 #include "lzm_conv.h"
@@ -551,6 +552,42 @@ __global__ __launch_bounds__(256) void gumbel_collect_kernel(TreeView t, GumbelV
   if (count && blockIdx.x == 0 && threadIdx.x == 0) *count += 1;
 }
 
+// ---- Stochastic MuZero tree (lzm_stochastic.h): one wave per root, four roots per 256-thread workgroup ----
+__global__ __launch_bounds__(256) void stochastic_traverse_kernel(StochasticTraverseArgs q) {
+  const int i = gumbel_wave_root();
+  if (i < q.t.B) stochastic_traverse_root(q, i);
+}
+
+// cbatch_backpropagate from raw lists: one wave per list entry
+__global__ __launch_bounds__(256) void stochastic_backprop_kernel(StochasticBackpropArgs p) {
+  const int k = gumbel_wave_root();
+  if (k < p.n) stochastic_backprop_entry(p, k);
+}
+
+// decode + expand + backup of one simulation from the head set of each root's leaf kind and, with NEXT_WALK, the
+// next simulation's walk by the same wave over the records it has just written. norm_part: ensure_softmax's
+// verdict words, {decision reward, decision value} then {chance value, chance value} (normalized_check_kernel twice)
+template <bool NEXT_WALK>
+__global__ __launch_bounds__(256) void stochastic_decode_kernel(StochasticDecodeArgs p, const int32_t *norm_part,
+                                                                StochasticTraverseArgs q) {
+  const int i = gumbel_wave_root();
+  if (i >= p.t.B) return;
+  bool sm_cv = false, sm_dr = false, sm_dv = false;
+  if (p.categorical) {
+    const int np = norm_parts(p.t.B);
+    sm_dr = !norm_ok(norm_part, np, 0);
+    sm_dv = !norm_ok(norm_part, np, 1);
+    sm_cv = !norm_ok(norm_part + 2 * np, np, 0);
+  }
+  stochastic_decode_root(p, i, sm_cv, sm_dr, sm_dv);
+  if (NEXT_WALK) {
+    // the backup's stores (other lanes of this wave) complete before the walk reads them
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    stochastic_traverse_root(q, i);
+  }
+}
+
 __global__ void debug_logf_kernel(const float *x, float *out, long long n) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = glibc_logf(x[i]);
@@ -633,6 +670,10 @@ struct lzm_handle {
   float *gumbel = nullptr;        // [64] the fixed Gumbel table
   int32_t *considered = nullptr;  // [cons_cap] considered-visits row of (cons_m, cons_S)
   int cons_cap = 0, cons_m = -1, cons_S = -1;
+  // Stochastic MuZero handles (LZM_TREE_STOCHASTIC) only: A above is the child-block width max(act, chance)
+  int act = 0, chance = 0;        // action space, chance space
+  int32_t *is_chance = nullptr;   // [B] kind of the last walk's leaf
+  bool walked = false;            // a stochastic traverse has run (lzm_stochastic_backprop's call order)
 };
 
 static TreeView view(lzm_handle *h) {
@@ -744,7 +785,7 @@ static int alloc_tree(lzm_handle *h, int sims) {
   // point at the old buffer together with the tree's
   LZM_HIP(hipMalloc(&h->step_seeds, sizeof(int32_t) * (size_t)(sims + 1)));
   h->step_seeds_n = sims + 1;
-  if (!(h->flags & (LZM_RNG_FAST | LZM_TREE_GUMBEL))) {
+  if (!(h->flags & (LZM_RNG_FAST | LZM_TREE_GUMBEL | LZM_TREE_STOCHASTIC))) {
     // parity-mode draw tables and look-back words, allocated here rather than at first use so
     // that a search captured into a HIP graph never allocates
     int rc = ensure_coef(h, h->B * h->depth_cap + 64);
@@ -763,12 +804,19 @@ static int refuse(int code, const char *name, const char *what) {
   return code;
 }
 
-// the handle is there and of the kind `name` serves (gumbel: an lzm_gumbel_* entry point)
-static int check_kind(const char *name, const lzm_handle *h, bool gumbel) {
-  if (!h) return refuse(LZM_ERR_ARG, name, gumbel ? "null handle" : "null argument");
-  if (gumbel == ((h->flags & LZM_TREE_GUMBEL) != 0)) return LZM_OK;
-  return refuse(LZM_ERR_STATE, name, gumbel ? "not a Gumbel MuZero handle (create it with LZM_TREE_GUMBEL)"
-                                            : "a Gumbel MuZero handle takes the lzm_gumbel_* entry points");
+// the handle is there and of the kind `name` serves (kind 0: the MuZero / EfficientZero entry points, 1 = true: an
+// lzm_gumbel_* entry point, kStochasticKind: an lzm_stochastic_* entry point)
+constexpr int kStochasticKind = 2;
+static int check_kind(const char *name, const lzm_handle *h, int kind) {
+  if (!h) return refuse(LZM_ERR_ARG, name, kind ? "null handle" : "null argument");
+  const int is = (h->flags & LZM_TREE_STOCHASTIC) ? kStochasticKind : (h->flags & LZM_TREE_GUMBEL) ? 1 : 0;
+  if (is == kind) return LZM_OK;
+  if (is == kStochasticKind)
+    return refuse(LZM_ERR_STATE, name, "a Stochastic MuZero handle takes the lzm_stochastic_* entry points");
+  if (kind == kStochasticKind)
+    return refuse(LZM_ERR_STATE, name, "not a Stochastic MuZero handle (create it with lzm_stochastic_create)");
+  return refuse(LZM_ERR_STATE, name, kind ? "not a Gumbel MuZero handle (create it with LZM_TREE_GUMBEL)"
+                                          : "a Gumbel MuZero handle takes the lzm_gumbel_* entry points");
 }
 
 static int check_cur(lzm_handle *h, int cur) {
@@ -864,19 +912,15 @@ extern "C" {
 
 const char *lzm_last_error(void) { return g_err; }
 
-int lzm_create(int B, int A, int max_sims, int flags, lzm_handle **out) {
-  if (!out || B <= 0 || A <= 0 || A > kMaxActions || max_sims < 0) {
-    set_err("lzm_create: need num_roots > 0, 0 < action_space <= 64, max_sims >= 0");
-    return LZM_ERR_ARG;
-  }
-  if ((flags & LZM_TREE_GUMBEL) && (flags & LZM_TREE_EZ)) {
-    set_err("lzm_create: LZM_TREE_GUMBEL and LZM_TREE_EZ are mutually exclusive");
-    return LZM_ERR_ARG;
-  }
+// lzm_create (chance 0) and lzm_stochastic_create (A: the action space; the handle's block width is max(A, chance))
+static int create_handle(int B, int A, int chance, int max_sims, int flags, lzm_handle **out) {
   lzm_handle *h = new lzm_handle();
   h->B = B;
-  h->A = A;
+  h->A = A > chance ? A : chance;
+  h->act = chance ? A : 0;
+  h->chance = chance;
   h->flags = flags;
+  A = h->A;
   int rc;
 #define TRY(x) do { rc = (x); if (rc != LZM_OK) { lzm_destroy(h); return rc; } } while (0)
   TRY(hipMalloc(&h->legal, sizeof(int32_t) * (size_t)B * A) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
@@ -884,7 +928,10 @@ int lzm_create(int B, int A, int max_sims, int flags, lzm_handle **out) {
   TRY(hipMalloc(&h->pathlen, sizeof(int32_t) * B) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
   TRY(hipMalloc(&h->err, sizeof(int32_t) * kErrWords) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
   TRY(hipMemset(h->err, 0, sizeof(int32_t) * kErrWords) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
-  TRY(hipMalloc(&h->norm_flag, sizeof(int32_t) * 2 * norm_parts(B)) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
+  // (a stochastic handle judges two head sets: twice the verdict words)
+  TRY(hipMalloc(&h->norm_flag, sizeof(int32_t) * (chance ? 4 : 2) * norm_parts(B)) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
+  if (chance) TRY(hipMalloc(&h->is_chance, sizeof(int32_t) * B) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
+  if (chance) TRY(hipMemset(h->is_chance, 0, sizeof(int32_t) * B) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
   TRY(hipMemset(h->pathlen, 0, sizeof(int32_t) * B) == hipSuccess ? LZM_OK : LZM_ERR_HIP);
   if (flags & LZM_TREE_GUMBEL) {
     float tab[kMaxActions];
@@ -900,12 +947,42 @@ int lzm_create(int B, int A, int max_sims, int flags, lzm_handle **out) {
   return LZM_OK;
 }
 
+int lzm_create(int B, int A, int max_sims, int flags, lzm_handle **out) {
+  if (!out || B <= 0 || A <= 0 || A > kMaxActions || max_sims < 0) {
+    set_err("lzm_create: need num_roots > 0, 0 < action_space <= 64, max_sims >= 0");
+    return LZM_ERR_ARG;
+  }
+  if ((flags & LZM_TREE_GUMBEL) && (flags & LZM_TREE_EZ)) {
+    set_err("lzm_create: LZM_TREE_GUMBEL and LZM_TREE_EZ are mutually exclusive");
+    return LZM_ERR_ARG;
+  }
+  if (flags & LZM_TREE_STOCHASTIC) {
+    set_err("lzm_create: a Stochastic MuZero handle needs its chance space (lzm_stochastic_create)");
+    return LZM_ERR_ARG;
+  }
+  return create_handle(B, A, 0, max_sims, flags, out);
+}
+
+int lzm_stochastic_create(int B, int A, int chance_space_size, int max_sims, int flags, lzm_handle **out) {
+  if (!out || B <= 0 || A < 1 || A > kMaxActions || chance_space_size < 1 || chance_space_size > kMaxActions ||
+      max_sims < 0) {
+    set_err("lzm_stochastic_create: need num_roots > 0, 1 <= action_space <= 64, 1 <= chance_space_size <= 64, "
+            "max_sims >= 0");
+    return LZM_ERR_ARG;
+  }
+  if (flags & (LZM_TREE_EZ | LZM_TREE_GUMBEL)) {
+    set_err("lzm_stochastic_create: LZM_TREE_STOCHASTIC excludes LZM_TREE_EZ and LZM_TREE_GUMBEL");
+    return LZM_ERR_ARG;
+  }
+  return create_handle(B, A, chance_space_size, max_sims, flags | LZM_TREE_STOCHASTIC, out);
+}
+
 int lzm_destroy(lzm_handle *h) {
   if (!h) return LZM_OK;
   free_tree(h);
   dfree(h->legal); dfree(h->nlegal); dfree(h->pathlen); dfree(h->err); dfree(h->norm_flag);
   dfree(h->coef); dfree(h->pow16807); dfree(h->lb_flags); dfree(h->epoch); dfree(h->search_diag); dfree(h->phase);
-  dfree(h->ez_ws); dfree(h->gumbel); dfree(h->considered);
+  dfree(h->ez_ws); dfree(h->gumbel); dfree(h->considered); dfree(h->is_chance);
   delete h;
   return LZM_OK;
 }
@@ -940,7 +1017,8 @@ int lzm_set_pb_c(lzm_handle *h, int pb_c_base, float pb_c_init) {
 
 int lzm_copy_tree(lzm_handle *dst, const lzm_handle *src, void *stream) {
   if (!dst || !src || dst->B != src->B || dst->A != src->A || dst->sims_cap < src->sims_cap ||
-      ((dst->flags ^ src->flags) & LZM_TREE_GUMBEL)) {
+      ((dst->flags ^ src->flags) & (LZM_TREE_GUMBEL | LZM_TREE_STOCHASTIC)) || dst->chance != src->chance ||
+      dst->act != src->act) {
     set_err("lzm_copy_tree: handles differ in shape or kind, or destination is smaller");
     return LZM_ERR_ARG;
   }
@@ -954,6 +1032,10 @@ int lzm_copy_tree(lzm_handle *dst, const lzm_handle *src, void *stream) {
   LZM_HIP(hipMemcpyAsync(dst->path, src->path, sizeof(int32_t) * (size_t)src->depth_cap * src->B, hipMemcpyDeviceToDevice, s));
   LZM_HIP(hipMemcpyAsync(dst->path_act, src->path_act, sizeof(int32_t) * (size_t)src->depth_cap * src->B, hipMemcpyDeviceToDevice, s));
   LZM_HIP(hipMemcpyAsync(dst->pathlen, src->pathlen, sizeof(int32_t) * src->B, hipMemcpyDeviceToDevice, s));
+  if (src->is_chance) {
+    LZM_HIP(hipMemcpyAsync(dst->is_chance, src->is_chance, sizeof(int32_t) * src->B, hipMemcpyDeviceToDevice, s));
+    dst->walked = src->walked;
+  }
   return LZM_OK;
 }
 
@@ -1388,6 +1470,155 @@ int lzm_gumbel_collect_outputs(lzm_handle *h, float discount, int32_t *dist, flo
                      discount, o, count);
   LZM_CHECK_LAUNCH();
   return LZM_OK;
+}
+
+// ---- Stochastic MuZero tree (ctree_stochastic_muzero/lib/cnode.cpp; lzm_stochastic.h) -------------------
+}  // extern "C"
+
+static StochasticView stochastic_view(lzm_handle *h) { return StochasticView{h->act, h->chance, h->is_chance}; }
+
+static int stochastic_traverse_args(const char *name, lzm_handle *h, int pb_c_base, float pb_c_init, float discount,
+                                    const float *minmax, const uint32_t *seed, const int32_t *vtp_in,
+                                    const WalkOut &out, int32_t *out_is_chance, StochasticTraverseArgs *q) {
+  if (!minmax || !seed || !vtp_in || !walk_out_complete(out)) return refuse(LZM_ERR_ARG, name, "null argument");
+  if (pb_c_base <= 0) return refuse(LZM_ERR_ARG, name, "pb_c_base must be positive");
+  const int rc = fill_lut(h, pb_c_base, pb_c_init);
+  if (rc != LZM_OK) return rc;
+  q->t = view(h);
+  q->sv = stochastic_view(h);
+  q->minmax = (const float4 *)minmax;
+  q->seed = seed;
+  q->vtp_in = vtp_in;
+  q->out = out;
+  q->out_is_chance = out_is_chance;
+  q->disc = discount;
+  return LZM_OK;
+}
+
+// stochastic_decode_kernel for one simulation; walk: the next simulation's traverse arguments, or null
+static int stochastic_decode_launch(const char *name, lzm_handle *h, int cur, float discount, float *minmax,
+                                    const float *c_value, const float *c_policy, const float *c_latent,
+                                    const float *d_reward, const float *d_value, const float *d_policy,
+                                    const float *d_latent, int support_len, int categorical, const int32_t *to_play,
+                                    float *pool_slot, int64_t row_elems, float *out_decoded,
+                                    const StochasticTraverseArgs *walk, hipStream_t s) {
+  if (!minmax || !c_value || !c_policy || !c_latent || !d_reward || !d_value || !d_policy || !d_latent || !to_play ||
+      !pool_slot || row_elems <= 0 || support_len <= 0)
+    return refuse(LZM_ERR_ARG, name, "null argument");
+  if (!h->walked) return refuse(LZM_ERR_STATE, name, "no stochastic traverse has run on this handle");
+  const int value_len = h->value_support > 0 ? h->value_support : support_len;
+  if (categorical && (support_len % 2 == 0 || value_len % 2 == 0))
+    return refuse(LZM_ERR_ARG, name, "categorical support length must be odd (2*support_scale+1)");
+  int rc = check_cur(h, cur);
+  if (rc != LZM_OK) return rc;
+  if (categorical) {
+    // ensure_softmax per head tensor: {decision reward, decision value}, then the chance value rows
+    rc = launch_norm_check(h->norm_flag, d_reward, d_value, h->B, support_len, value_len, s);
+    if (rc != LZM_OK) return rc;
+    rc = launch_norm_check(h->norm_flag + 2 * norm_parts(h->B), c_value, c_value, h->B, value_len, value_len, s);
+    if (rc != LZM_OK) return rc;
+  }
+  StochasticDecodeArgs p;
+  p.t = view(h);
+  p.sv = stochastic_view(h);
+  p.minmax = (float4 *)minmax;
+  p.c_value = c_value; p.c_policy = c_policy; p.c_latent = c_latent;
+  p.d_reward = d_reward; p.d_value = d_value; p.d_policy = d_policy; p.d_latent = d_latent;
+  p.to_play = to_play; p.pool_slot = pool_slot; p.row_elems = row_elems;
+  p.V = support_len; p.Vv = value_len; p.categorical = categorical; p.cur = cur;
+  p.disc = discount; p.out_decoded = out_decoded;
+  if (walk) hipLaunchKernelGGL(stochastic_decode_kernel<true>, gumbel_grid(h), dim3(256), 0, s, p, h->norm_flag, *walk);
+  else hipLaunchKernelGGL(stochastic_decode_kernel<false>, gumbel_grid(h), dim3(256), 0, s, p, h->norm_flag,
+                          StochasticTraverseArgs{});
+  LZM_CHECK_LAUNCH();
+  return LZM_OK;
+}
+
+extern "C" {
+
+int lzm_chance_space(const lzm_handle *h) { return h ? h->chance : LZM_ERR_ARG; }
+int lzm_stochastic_action_space(const lzm_handle *h) { return h ? h->act : LZM_ERR_ARG; }
+
+int lzm_stochastic_traverse(lzm_handle *h, int pb_c_base, float pb_c_init, float discount, float *minmax,
+                            const uint32_t *seed, const int32_t *vtp_in, int32_t *out_x, int32_t *out_y,
+                            int32_t *out_a, int64_t *out_a64, int32_t *out_vtp, int32_t *out_len,
+                            int32_t *out_is_chance, void *stream) {
+  const char *name = "lzm_stochastic_traverse";
+  int rc = check_kind(name, h, kStochasticKind);
+  if (rc != LZM_OK) return rc;
+  if (!out_is_chance) return refuse(LZM_ERR_ARG, name, "null argument");
+  StochasticTraverseArgs q;
+  rc = stochastic_traverse_args(name, h, pb_c_base, pb_c_init, discount, minmax, seed, vtp_in,
+                                walk_out(out_x, out_y, out_a, out_a64, out_vtp, out_len), out_is_chance, &q);
+  if (rc != LZM_OK) return rc;
+  hipLaunchKernelGGL(stochastic_traverse_kernel, gumbel_grid(h), dim3(256), 0, (hipStream_t)stream, q);
+  LZM_CHECK_LAUNCH();
+  h->walked = true;
+  return LZM_OK;
+}
+
+int lzm_stochastic_backprop(lzm_handle *h, int cur, float discount, float *minmax, const float *rewards,
+                            const float *values, const float *logits, int width, const int32_t *to_play,
+                            const int32_t *leaf_idx, int num_leaves, void *stream) {
+  const char *name = "lzm_stochastic_backprop";
+  int rc = check_kind(name, h, kStochasticKind);
+  if (rc != LZM_OK) return rc;
+  if (!minmax || !rewards || !values || !logits || !to_play) return refuse(LZM_ERR_ARG, name, "null argument");
+  if (width != h->act && width != h->chance)
+    return refuse(LZM_ERR_ARG, name, "the logit rows are action_space or chance_space_size wide");
+  const int n = leaf_idx ? num_leaves : h->B;
+  if (n < 0 || n > h->B) return refuse(LZM_ERR_ARG, name, "at most one list entry per root");
+  if (!h->walked) return refuse(LZM_ERR_STATE, name, "no stochastic traverse has run on this handle");
+  rc = check_cur(h, cur);
+  if (rc != LZM_OK) return rc;
+  if (n == 0) return LZM_OK;
+  StochasticBackpropArgs p;
+  p.t = view(h);
+  p.sv = stochastic_view(h);
+  p.minmax = (float4 *)minmax;
+  p.rewards = rewards; p.values = values; p.logits = logits; p.to_play = to_play; p.leaf_idx = leaf_idx;
+  p.n = n; p.width = width; p.cur = cur; p.disc = discount;
+  hipLaunchKernelGGL(stochastic_backprop_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, p);
+  LZM_CHECK_LAUNCH();
+  return LZM_OK;
+}
+
+int lzm_stochastic_decode_backprop(lzm_handle *h, int cur, float discount, float *minmax, const float *chance_value,
+                                   const float *chance_policy, const float *chance_latent,
+                                   const float *decision_reward, const float *decision_value,
+                                   const float *decision_policy, const float *decision_latent, int support_len,
+                                   int categorical, const int32_t *to_play, float *pool_slot, int64_t row_elems,
+                                   float *out_decoded, void *stream) {
+  const char *name = "lzm_stochastic_decode_backprop";
+  int rc = check_kind(name, h, kStochasticKind);
+  if (rc != LZM_OK) return rc;
+  return stochastic_decode_launch(name, h, cur, discount, minmax, chance_value, chance_policy, chance_latent,
+                                  decision_reward, decision_value, decision_policy, decision_latent, support_len,
+                                  categorical, to_play, pool_slot, row_elems, out_decoded, nullptr,
+                                  (hipStream_t)stream);
+}
+
+int lzm_stochastic_decode_backprop_traverse(lzm_handle *h, int cur, float discount, float *minmax,
+                                            const float *chance_value, const float *chance_policy,
+                                            const float *chance_latent, const float *decision_reward,
+                                            const float *decision_value, const float *decision_policy,
+                                            const float *decision_latent, int support_len, int categorical,
+                                            const int32_t *to_play, float *pool_slot, int64_t row_elems,
+                                            float *out_decoded, int pb_c_base, float pb_c_init, const uint32_t *seed,
+                                            const int32_t *vtp_in, int32_t *out_x, int32_t *out_y, int32_t *out_a,
+                                            int64_t *out_a64, int32_t *out_vtp, int32_t *out_len,
+                                            int32_t *out_is_chance, void *stream) {
+  const char *name = "lzm_stochastic_decode_backprop_traverse";
+  int rc = check_kind(name, h, kStochasticKind);
+  if (rc != LZM_OK) return rc;
+  if (!out_is_chance) return refuse(LZM_ERR_ARG, name, "null argument");
+  StochasticTraverseArgs q;
+  rc = stochastic_traverse_args(name, h, pb_c_base, pb_c_init, discount, minmax, seed, vtp_in,
+                                walk_out(out_x, out_y, out_a, out_a64, out_vtp, out_len), out_is_chance, &q);
+  if (rc != LZM_OK) return rc;
+  return stochastic_decode_launch(name, h, cur, discount, minmax, chance_value, chance_policy, chance_latent,
+                                  decision_reward, decision_value, decision_policy, decision_latent, support_len,
+                                  categorical, to_play, pool_slot, row_elems, out_decoded, &q, (hipStream_t)stream);
 }
 
 int lzm_debug_logf(const float *x, float *out, int64_t n, void *stream) {
@@ -2037,6 +2268,8 @@ int search_mlp(const char *name, MlpFamily fam, lzm_handle *h, int H, int Hl, in
       return refuse(LZM_ERR_STATE, name, "collect-step mode (lzm_search_set_step) has no Gumbel search");
   } else if (h->flags & LZM_TREE_GUMBEL) {
     return refuse(LZM_ERR_STATE, name, "a Gumbel MuZero handle takes lzm_search_mlp_gumbel");
+  } else if (h->flags & LZM_TREE_STOCHASTIC) {
+    return refuse(LZM_ERR_STATE, name, "there is no one-launch search of a Stochastic MuZero handle");
   }
   if ((uintptr_t)weights & 15) {
     snprintf(g_err, sizeof(g_err), "%s: weights must be 16-byte aligned (%s output)", name,
@@ -3670,6 +3903,7 @@ static int search_conv_launch(lzm_handle *h, int num_simulations, int pb_c_base,
     set_err("one-launch searches do not take a Gumbel MuZero handle");
     return LZM_ERR_STATE;
   }
+  if (h->flags & LZM_TREE_STOCHASTIC) return refuse(LZM_ERR_STATE, name, "there is no one-launch search of a Stochastic MuZero handle");
   uintptr_t bits = (uintptr_t)trunk_w | (uintptr_t)actmap | (uintptr_t)w1t | (uintptr_t)w2q | (uintptr_t)latent_pool;
   if (ez)
     bits |= (uintptr_t)ez->hpool | (uintptr_t)ez->cpool | (uintptr_t)ez->lstm_frag | (uintptr_t)ez->vp_s |

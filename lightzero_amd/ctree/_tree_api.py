@@ -420,3 +420,99 @@ def _gumbel_backprop(current_latent_state_index, discount, value_prefixs, values
                       g(np.asarray(value_prefixs).reshape(B), np.float32), g(np.asarray(values).reshape(B), np.float32),
                       g(np.asarray(policies, np.float32).reshape(B, t.A), np.float32),
                       g(np.asarray(to_play_batch, np.int32).reshape(B), np.int32))
+
+
+# ----------------------------------------------------------------------------- Stochastic MuZero (stochastic_mz_tree.pyx)
+class _StochasticRootsBase(_RootsBase):
+    """Roots of stochastic_mz_tree.pyx:27-59: the MuZero surface plus the chance space. The device rows are
+    max(action space, chance space) wide (include/lzmcts.h), padded here."""
+
+    def __init__(self, root_num, legal_actions_list, chance_space_size):
+        _require_int("chance_space_size", chance_space_size)
+        super().__init__(root_num, legal_actions_list, fast_rng=True)
+        self.chance_space_size = int(chance_space_size)
+
+    def _acquire(self, A, device):
+        t = self.tree
+        if t is not None and t.act == A and t.device == device:
+            return t
+        if t is not None:
+            POOL.release(t)
+        self.tree = POOL.acquire(self.root_num, A, self._sims, False, True, device, chance=self.chance_space_size)
+        return self.tree
+
+    def _prepare(self, noise_weight, noises, rewards, logits, to_play, device=None):
+        B = self.root_num
+        logits = np.asarray(logits, dtype=np.float32).reshape(B, -1)
+        A = logits.shape[1]
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        t = self._acquire(A, dev)
+        W = t.A
+        legal, count = np.full((B, W), -1, np.int32), np.zeros(B, np.int32)
+        nz = np.zeros((B, W), np.float32) if noises is not None else None
+        for i in range(B):
+            l = self.legal_actions_list[i] or list(range(A))  # (an empty list: every action, cnode.cpp:125-131)
+            if len(l) > A or any(a < 0 or a >= A for a in l):
+                raise ValueError(f"root {i}: legal actions {l} outside action space {A}")
+            legal[i, :len(l)], count[i] = l, len(l)
+            if nz is not None:
+                row = np.asarray(noises[i], dtype=np.float32).reshape(-1)
+                if row.shape[0] < len(l):
+                    raise IndexError(f"root {i}: {row.shape[0]} noises for {len(l)} legal actions")
+                nz[i, :len(l)] = row[:len(l)]
+        g = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+        t.prepare(g(legal, np.int32), g(count, np.int32), None if nz is None else g(nz, np.float32),
+                  _f32(noise_weight), g(np.asarray(rewards, np.float32).reshape(B), np.float32),
+                  g(np.pad(logits, ((0, 0), (0, W - A))), np.float32),
+                  g(np.asarray(to_play, np.int32).reshape(B), np.int32))
+
+    def prepare_device(self, *a, **k):
+        raise NotImplementedError("stochastic Roots: prepare / prepare_no_noise")
+
+    device_legal = prepare_device
+
+
+def _stochastic_traverse(roots, pb_c_base, pb_c_init, discount_factor, min_max_stats_lst, results,
+                         virtual_to_play_batch, seed=None):
+    """batch_traverse (stochastic_mz_tree.pyx:85-90)."""
+    _require_type("roots", roots, _StochasticRootsBase)
+    _require_int("pb_c_base", pb_c_base)
+    _require_type("min_max_stats_lst", min_max_stats_lst, MinMaxStatsList)
+    _require_type("results", results, ResultsWrapper)
+    _require_list("virtual_to_play_batch", virtual_to_play_batch)
+    t = roots.tree
+    if t is None:
+        raise RuntimeError("batch_traverse: roots not prepared")
+    vtp = torch.tensor(np.asarray(virtual_to_play_batch, np.int32)[:t.B], device=t.device)
+    t.stochastic_traverse(min_max_stats_lst._device(t.device), seed_tensor(next_seed() if seed is None else seed, t.device),
+                          vtp, int(pb_c_base), _f32(pb_c_init), _f32(discount_factor))
+    out = torch.stack([t.x, t.y, t.action, t.vtp, t.search_len, t.is_chance]).cpu().numpy()
+    results._search_lens = out[4].tolist()
+    results._tree = t
+    return [bool(v) for v in out[5]], out[0].tolist(), out[1].tolist(), out[2].tolist(), out[3].tolist()
+
+
+def _stochastic_backprop(current_latent_state_index, discount_factor, value_prefixs, values, policies,
+                         min_max_stats_lst, results, to_play_batch, is_chance_list, leaf_idx_list):
+    """batch_backpropagate (stochastic_mz_tree.pyx:75-83): entry k of the three lists serves root leaf_idx_list[k]
+    (an empty list: root k). is_chance_list is ignored as the reference ignores it (cnode.cpp:116-122): a leaf's
+    kind is the one its walk found."""
+    _require_int("current_latent_state_index", current_latent_state_index)
+    for n, v in (("value_prefixs", value_prefixs), ("values", values), ("policies", policies),
+                 ("to_play_batch", to_play_batch), ("is_chance_list", is_chance_list), ("leaf_idx_list", leaf_idx_list)):
+        _require_list(n, v)
+    _require_type("min_max_stats_lst", min_max_stats_lst, MinMaxStatsList)
+    _require_type("results", results, ResultsWrapper)
+    t = getattr(results, "_tree", None)
+    if t is None:
+        raise RuntimeError("batch_backpropagate: results do not come from batch_traverse")
+    cur = int(current_latent_state_index)
+    if cur + 1 > t.sims_capacity + 1:
+        t.reserve(max(cur + 1, 2 * t.sims_capacity))
+    n = len(leaf_idx_list) or t.B
+    g = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(t.device)
+    t.stochastic_backprop(cur, _f32(discount_factor), min_max_stats_lst._device(t.device),
+                          g(np.asarray(value_prefixs).reshape(n), np.float32), g(np.asarray(values).reshape(n), np.float32),
+                          g(np.asarray(policies, np.float32).reshape(n, -1), np.float32),
+                          g(np.asarray(to_play_batch, np.int32).reshape(t.B), np.int32),
+                          g(np.asarray(leaf_idx_list, np.int32), np.int32) if leaf_idx_list else None)

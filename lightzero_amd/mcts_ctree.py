@@ -1,4 +1,5 @@
-"""Drop-in ``MuZeroMCTSCtree`` / ``EfficientZeroMCTSCtree`` / ``GumbelMuZeroMCTSCtree`` with the search loop on the GPU.
+"""Drop-in ``MuZeroMCTSCtree`` / ``EfficientZeroMCTSCtree`` / ``GumbelMuZeroMCTSCtree`` / ``StochasticMuZeroMCTSCtree``
+with the search loop on the GPU.
 
 Same class surface as /root/reference/lzero/mcts/tree_search/mcts_ctree.py:172-420 (MuZero) and
 :623-827 (EfficientZero): class attribute ``config``, ``default_config()``, ``__init__(cfg)``,
@@ -26,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ctree import ez_tree, gmz_tree, mz_tree
+from .ctree import ez_tree, gmz_tree, mz_tree, stochastic_mz_tree
 from .conv_infer import FoldedCache
 from .fused import NotPackable, PackedCache, pack_efficientzero_mlp
 from .scaling_transform import InverseScalarTransform
@@ -442,8 +443,8 @@ class _MCTSCtree(object):
         t = c.t
         net = _step_net(self, model)
         # warm up every kernel and library handle on a scratch tree (must not touch `t`)
-        scratch = DeviceTree(t.B, t.A, max(c.S, t.sims_capacity), ez=t.ez, fast_rng=t.fast_rng, device=t.device,
-                             gumbel=t.gumbel)
+        scratch = DeviceTree(t.B, t.act, max(c.S, t.sims_capacity), ez=t.ez, fast_rng=t.fast_rng, device=t.device,
+                             gumbel=t.gumbel, chance=t.chance)
         scratch.copy_roots_from(t)
         scratch.set_pb_c(*self._pb_c())
         self._loop(scratch, model, c, net=net)
@@ -946,3 +947,80 @@ class GumbelMuZeroMCTSCtree(_MCTSCtree):
             self._finish(c, roots, None, rec)
             # (independent slices are one search: their count is last_plan["slices"], not part of the path's name)
             self.last_path = "fused-conv" if cz is not None else ("fused-mlp" if fz is not None else "generic")
+
+
+class StochasticMuZeroMCTSCtree(_MCTSCtree):
+    """MCTS for Stochastic MuZero on the GPU (reference: tree_search/mcts_ctree_stochastic.py:26-251). Levels
+    alternate between decision and chance nodes (lzm_stochastic.h), so a simulation's leaves are of two kinds and
+    each kind needs another half of the network. The reference splits the batch by kind on the host — two
+    sub-batches of data-dependent size, two batch_backpropagate calls with index lists. Here a simulation is: gather
+    the leaf latents, run BOTH halves over the whole batch (``recurrent_inference(.., afterstate=False)`` for chance
+    leaves, ``afterstate=True`` for decision leaves; the option index of the branch a root does not use is clamped
+    into that branch's range, so its one-hot stays valid — rows of an eval-mode network are independent, the used
+    rows are unaffected), then one launch that picks each root's rows by its leaf kind, decodes, expands, backs up
+    and walks the next simulation. No host sync, no data-dependent shape: eager, or one HIP graph with
+    cfg.use_hip_graph. Tie and chance draws are per-root Philox streams keyed by the traverse seeds (`seeds` as in
+    MuZeroMCTSCtree.search): the reference's chance draw is seeded from std::random_device, so there is no stream
+    to be in parity with and no rng_mode."""
+
+    config = dict(
+        root_dirichlet_alpha=0.3,
+        root_noise_weight=0.25,
+        pb_c_base=19652,
+        pb_c_init=1.25,
+        value_delta_max=0.01,
+    )  # (the reference's keys)
+    _tree = stochastic_mz_tree
+    reward_name = 'reward'
+    rng_mode = None
+
+    @classmethod
+    def roots(cls: int, active_collect_env_num: int, legal_actions: List[Any],
+              chance_space_size: int = 2) -> "stochastic_mz_tree.Roots":
+        return stochastic_mz_tree.Roots(active_collect_env_num, legal_actions, chance_space_size)
+
+    def _recorder(self, c):
+        if not self.record:
+            return None
+        rec = _Recorder(c.S, c.B, 1, c.dev)
+        rec.is_chance = torch.zeros((c.S, c.B), dtype=torch.int32, device=c.dev)
+        rec.seeds = c.buf.seeds.cpu().numpy().view(np.uint32)
+        return rec
+
+    def _loop(self, t, model, c, rec=None, infer=None, net=None):
+        """The S simulations (mcts_ctree_stochastic.py:116-251) on tree t over c.buf, all enqueued on the current
+        stream: simulation k's backup and simulation k + 1's traverse share a launch."""
+        cfg, buf, S = self._cfg, c.buf, c.S
+        disc, cat, pb_c = self._discount(), self._categorical(), self._pb_c()
+        new_minmax(t.B, cfg.value_delta_max, t.device, out=buf.mm)
+        f = lambda x: x.float().contiguous()
+        for k in range(S):
+            if k == 0:
+                t.stochastic_traverse(buf.mm, buf.seeds[0:1], buf.vtp_in, *pb_c, disc)
+            if rec is not None:
+                for name in ("x", "action", "search_len", "vtp", "is_chance"):
+                    getattr(rec, name)[k].copy_(getattr(t, name))
+            t.gather(buf.pool, c.row, buf.net_in)
+            # a chance leaf was reached by an action, a decision leaf by an outcome
+            oc = model.recurrent_inference(buf.net_in, t.action64.clamp(0, t.act - 1), afterstate=False)
+            od = model.recurrent_inference(buf.net_in, t.action64.clamp(0, t.chance - 1), afterstate=True)
+            walk = (buf.seeds[k + 1:k + 2], buf.vtp_in, *pb_c) if k + 1 < S else None
+            t.stochastic_decode_backprop(
+                k + 1, disc, buf.mm, (f(oc.value), f(oc.policy_logits), f(oc.latent_state)),
+                (f(od.reward), f(od.value), f(od.policy_logits), f(od.latent_state)), cat, t.vtp, buf.pool[k + 1],
+                c.row, walk=walk, out_decoded=None if rec is None else rec.decoded[k])
+
+    def search(self, roots: Any, model: torch.nn.Module, latent_state_roots: List[Any],
+               to_play_batch: Union[int, List[Any]], seeds: torch.Tensor = None) -> None:
+        """seeds (not in the reference): optional device int32 [num_simulations] traverse seeds instead of the host
+        seed source, as in MuZeroMCTSCtree.search."""
+        with torch.no_grad():
+            c = self._begin("search", roots, model, latent_state_roots)
+            if not getattr(c.t, "chance", 0):
+                raise TypeError("StochasticMuZeroMCTSCtree.search: roots must come from StochasticMuZeroMCTSCtree.roots")
+            self._buffers(c, model, graph=not self.record and self._cfg.get('use_hip_graph', False))
+            self._stage(c, to_play_batch, seeds, None)
+            rec = self._recorder(c)
+            self._generic(c, model, rec)
+            self._finish(c, roots, None, rec)
+            self.last_path = "generic"

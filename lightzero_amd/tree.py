@@ -61,20 +61,30 @@ def _rec_ptrs(rec, names=("x", "action", "search_len", "decoded", "policy_logits
 
 
 class DeviceTree:
-    def __init__(self, num_roots, action_space, max_sims=64, ez=False, fast_rng=False, device=None, gumbel=False):
-        """gumbel: a Gumbel MuZero tree (LZM_TREE_GUMBEL; ctree_gumbel_muzero), driven by the gumbel_* methods"""
+    def __init__(self, num_roots, action_space, max_sims=64, ez=False, fast_rng=False, device=None, gumbel=False,
+                 chance=0):
+        """gumbel: a Gumbel MuZero tree (LZM_TREE_GUMBEL; ctree_gumbel_muzero), driven by the gumbel_* methods;
+        chance > 0: a Stochastic MuZero tree with that chance space (lzm_stochastic_create;
+        ctree_stochastic_muzero), driven by the stochastic_* methods — its rows (self.A) are
+        max(action_space, chance) wide, self.act is the action space"""
         _lib.require_gpu()
         if gumbel and ez:
             raise ValueError("DeviceTree: gumbel and ez are mutually exclusive")
+        if chance and (gumbel or ez):
+            raise ValueError("DeviceTree: a stochastic tree is neither gumbel nor ez")
         self.uid = next(_uids)  # never reused (a handle address can be, after lzm_destroy)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.B, self.A = int(num_roots), int(action_space)
+        self.B, self.act, self.chance = int(num_roots), int(action_space), int(chance)
+        self.A = max(self.act, self.chance)
         self.ez, self.fast_rng, self.gumbel = bool(ez), bool(fast_rng), bool(gumbel)
         flags = ((_lib.LZM_TREE_EZ if ez else 0) | (_lib.LZM_RNG_FAST if fast_rng else 0)
                  | (_lib.LZM_TREE_GUMBEL if gumbel else 0))
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            call("lzm_create", self.B, self.A, int(max_sims), flags, ctypes.byref(h))
+            if chance:
+                call("lzm_stochastic_create", self.B, self.act, self.chance, int(max_sims), flags, ctypes.byref(h))
+            else:
+                call("lzm_create", self.B, self.A, int(max_sims), flags, ctypes.byref(h))
         self.h = h
         _lib.register_owner(self)  # closed at exit before the runtime's own teardown
         self.generation = 0
@@ -88,6 +98,7 @@ class DeviceTree:
         self.vtp = torch.zeros(B, **i32)
         self.search_len = torch.zeros(B, **i32)
         self.is_reset = torch.zeros(B, **i32)
+        self.is_chance = torch.zeros(B, **i32)  # (stochastic trees: the last walk's leaf kinds)
         self.seed_buf = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._unchecked = False  # a search ran whose error words no getter has checked yet
 
@@ -256,6 +267,41 @@ class DeviceTree:
              ptr(next_latent), ptr(pool_slot), int(row_elems), ptr(out_decoded), int(num_simulations),
              int(max_num_considered_actions), ptr(vtp_in), ptr(self.x), ptr(self.y), ptr(self.action),
              ptr(self.action64), ptr(self.vtp), ptr(self.search_len), stream_ptr(stream))
+
+    # -- Stochastic MuZero trees (lzm_stochastic_*; LzmError on any other tree, nothing launched) --------
+    def _walk_out(self):
+        return [ptr(self.x), ptr(self.y), ptr(self.action), ptr(self.action64), ptr(self.vtp), ptr(self.search_len),
+                ptr(self.is_chance)]
+
+    def stochastic_traverse(self, minmax, seed, vtp_in, pb_c_base=19652, pb_c_init=1.25, discount=0.997, stream=None):
+        """seed: 1-element device tensor (int32/uint32 bits) keying this walk's Philox draws; also fills is_chance"""
+        call("lzm_stochastic_traverse", self.h, int(pb_c_base), float(pb_c_init), float(discount), ptr(minmax),
+             ptr(seed), ptr(vtp_in), *self._walk_out(), stream_ptr(stream))
+
+    def stochastic_backprop(self, cur, discount, minmax, rewards, values, logits, to_play, leaf_idx=None, stream=None):
+        """raw lists: entry k of rewards / values [n] and logits [n, width] serves root leaf_idx[k] (None: root k)"""
+        call("lzm_stochastic_backprop", self.h, int(cur), float(discount), ptr(minmax), ptr(rewards), ptr(values),
+             ptr(logits), int(logits.shape[-1]), ptr(to_play), ptr(leaf_idx),
+             0 if leaf_idx is None else int(leaf_idx.numel()), stream_ptr(stream))
+
+    def stochastic_decode_backprop(self, cur, discount, minmax, chance_out, decision_out, categorical, to_play,
+                                   pool_slot, row_elems, walk=None, out_decoded=None, stream=None):
+        """One simulation's decode + expand + backup from both head sets over the whole batch: chance_out = (value
+        logits, policy [B, C], afterstate rows), decision_out = (reward logits, value logits, policy [B, A], latent
+        rows). walk = (seed, vtp_in, pb_c_base, pb_c_init): the next simulation's traverse in the same launch."""
+        cv, cp, cl = chance_out
+        dr, dv, dp, dl = decision_out
+        V = dr.shape[-1] if categorical else 1
+        self._value_support(dv.shape[-1] if categorical else 1, V)
+        args = [self.h, int(cur), float(discount), ptr(minmax), ptr(cv), ptr(cp), ptr(cl), ptr(dr), ptr(dv), ptr(dp),
+                ptr(dl), int(V), int(bool(categorical)), ptr(to_play), ptr(pool_slot), int(row_elems),
+                ptr(out_decoded)]
+        if walk is None:
+            call("lzm_stochastic_decode_backprop", *args, stream_ptr(stream))
+        else:
+            seed, vtp_in, pb_c_base, pb_c_init = walk
+            call("lzm_stochastic_decode_backprop_traverse", *args, int(pb_c_base), float(pb_c_init), ptr(seed),
+                 ptr(vtp_in), *self._walk_out(), stream_ptr(stream))
 
     def children_values(self, discount, stream=None):
         """Roots.get_children_values: float32 [B, A], the completed Q in action order, -inf where illegal"""
@@ -535,8 +581,9 @@ class TreePool:
         self._free = {}
         self._lock = threading.Lock()
 
-    def acquire(self, B, A, max_sims, ez, fast_rng, device, gumbel=False):
-        key = (B, A, ez, fast_rng, str(device), bool(gumbel))
+    def acquire(self, B, A, max_sims, ez, fast_rng, device, gumbel=False, chance=0):
+        """A: the action space (a stochastic tree, chance > 0, keeps it in .act)"""
+        key = (B, A, ez, fast_rng, str(device), bool(gumbel), int(chance))
         t = None
         with self._lock:
             lst = self._free.get(key) or []
@@ -547,7 +594,7 @@ class TreePool:
                 if c.h is not None and c.h.value:
                     t = c
         if t is None:
-            t = DeviceTree(B, A, max_sims, ez=ez, fast_rng=fast_rng, device=device, gumbel=gumbel)
+            t = DeviceTree(B, A, max_sims, ez=ez, fast_rng=fast_rng, device=device, gumbel=gumbel, chance=chance)
         else:
             t.reserve(max_sims)
             # the previous owner's sticky error words must not surface in this owner's searches
@@ -560,7 +607,7 @@ class TreePool:
     def release(self, t):
         if t is None or t.h is None:
             return
-        key = (t.B, t.A, t.ez, t.fast_rng, str(t.device), t.gumbel)
+        key = (t.B, t.act, t.ez, t.fast_rng, str(t.device), t.gumbel, t.chance)
         with self._lock:
             self._free.setdefault(key, []).append(t)
 
