@@ -478,6 +478,49 @@ int lzm_az_search_fused(int B, int S, void *ws, int nres, const float *weights, 
  * nres not 1 / 2, null out) return LZM_ERR_ARG before any HIP call. */
 int lzm_az_fused_plan(int B, int S, int nres, int32_t *out);
 
+/* ---- batched AlphaZero for Connect4 (zoo/board_games/connect4/envs/connect4_env.py; the tree of
+ * mcts_alphazero.cpp). The protocol, argument meanings and outputs of lzm_az_begin .. lzm_az_finish above, with
+ *   boards int32[B][42] (row-major 6 x 7, row 0 on top; 0 empty / 1 / 2), state float[B][3][6][7]
+ *   (current_state()[1] with scale=True: the mover's stones 0.5, the opponent's 0.5, 0.5 * player),
+ *   probs float[B][pstride >= 7], visits int32[B][7], probs double[B][7].
+ * Action a is legal iff board[a] == 0; a move fills the highest-index empty cell of its column; a position is
+ * terminal when player 1 has four in a line (winner 1), else player 2 (winner 2), else when the board is full
+ * (winner -1). Every root needs at least one legal action: a full board has no child to visit, and lzm_az_c4_finish
+ * would divide its zero visit counts by their zero sum (NaN probabilities), as the reference does. Paths hold up
+ * to 43 nodes; a tree row has 1 + 7 (S + 1) nodes. `ws` is a device buffer of
+ * lzm_az_c4_workspace_bytes(B, S), filled once by lzm_az_c4_set_constants (synchronous); everything else is
+ * graph-capturable. */
+int lzm_az_c4_workspace_bytes(int B, int S, int64_t *out);
+int lzm_az_c4_set_constants(int B, int S, void *ws, double pb_c_base, double pb_c_init, double alpha, void *stream);
+int lzm_az_c4_begin(int B, int S, void *ws, const int32_t *boards, const int32_t *start_index, float *state,
+                    void *stream);
+int lzm_az_c4_step(int B, int S, void *ws, int sim, const float *probs, int pstride, const float *values, int vstride,
+                   int with_noise, double noise_weight, float *state, void *stream);
+int lzm_az_c4_finish(int B, int S, void *ws, double temperature, int sample, uint32_t seed, const int64_t *counter,
+                     int32_t *visits, double *probs, int32_t *action, void *stream);
+/* test access: node visit / value_sum / first-child rows [B][1 + 7 (S + 1)] and node counts [B] (any may be NULL;
+ * rows past a board's node count read 0 / 0 / -1), and the nodes' priors (the root's children after the noise mix) */
+int lzm_az_c4_export_tree(int B, int S, void *ws, int32_t *visit, float *vsum, int32_t *first, int32_t *nnodes,
+                          void *stream);
+int lzm_az_c4_export_priors(int B, int S, void *ws, float *prior, void *stream);
+/* test access: get_done_winner of n device boards int32[n][42] -> out int32[n][2] = {done, winner} */
+int lzm_az_c4_done_winner(const int32_t *boards, int n, int32_t *out, void *stream);
+
+/* ---- the Connect4 config's AlphaZeroModel (observation (3, 6, 7), 64 channels, num_res_blocks 1 or 2, head
+ * width 32, 7 actions, scalar value) in eval mode, one launch over n positions (lzm_az_c4_net.h).
+ * lzm_az_c4_net_prepare(nres, raw, out) permutes, on the host, `raw` =
+ *   conv0 W[64][27] (out, in*9 + tap), b[64];  4*nres x { conv W[64][576], b[64] } (the representation blocks'
+ *   conv1, conv2, then the prediction's; BatchNorm folded in);  1x1 W[32][64] (value rows, then policy rows),
+ *   b[32];  value head: FC1 [32][672], b[32], LN gamma[32], beta[32], FC2 [32], b[1];  policy head: FC1
+ *   [32][672], b[32], gamma[32], beta[32], FC2 [7][32], b[7]
+ * into lzm_az_c4_net_floats(nres) floats (MFMA B-fragment order, zero padding), to be copied to the device.
+ * lzm_az_c4_net_eval: state float[n][3][6][7] -> probs float[n][7] (softmax), value float[n]. A position's
+ * output bits do not depend on n or on its place in the batch. */
+int64_t lzm_az_c4_net_floats(int nres);
+int lzm_az_c4_net_prepare(int nres, const float *raw, float *out_host);
+int lzm_az_c4_net_eval(int nres, const float *weights, const float *state, int n, float *probs, float *value,
+                       void *stream);
+
 /* ---- convolutional recurrent trunk (configs 3 / 5: conv MuZeroModel / EfficientZeroModel) --------
  * The conv part of recurrent_inference (muzero_model.py:505-530, efficientzero_model.py:526-574,
  * common.py:854-881) with eval BatchNorm folded, one workgroup per env (lzm_conv.h): dynamics conv over

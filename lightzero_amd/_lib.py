@@ -153,6 +153,17 @@ SIGNATURES = {
     "lzm_az_net_eval": [_i, _vp, _vp, _i, _vp, _vp, _vp],
     "lzm_az_search_fused": [_i, _i, _vp, _i, _vp, _vp, _vp, _i, _d, _d, _i, _u32, _vp, _vp, _vp, _vp, _i, _vp],
     "lzm_az_fused_plan": [_i, _i, _i, _vp],
+    "lzm_az_c4_workspace_bytes": [_i, _i, ctypes.POINTER(_i64)],
+    "lzm_az_c4_set_constants": [_i, _i, _vp, _d, _d, _d, _vp],
+    "lzm_az_c4_begin": [_i, _i, _vp, _vp, _vp, _vp, _vp],
+    "lzm_az_c4_step": [_i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _d, _vp, _vp],
+    "lzm_az_c4_finish": [_i, _i, _vp, _d, _i, _u32, _vp, _vp, _vp, _vp, _vp],
+    "lzm_az_c4_export_tree": [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "lzm_az_c4_export_priors": [_i, _i, _vp, _vp, _vp],
+    "lzm_az_c4_done_winner": [_vp, _i, _vp, _vp],
+    "lzm_az_c4_net_floats": [_i],
+    "lzm_az_c4_net_prepare": [_i, _vp, _vp],
+    "lzm_az_c4_net_eval": [_i, _vp, _vp, _i, _vp, _vp, _vp],
     "lzm_conv_trunk_floats": [_i, _i],
     "lzm_conv_trunk_prepare": [_i, _i, _i, _i, _vp, _vp],
     "lzm_conv_trunk": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -195,6 +206,7 @@ SIGNATURES = {
 _RESTYPE = {"lzm_last_error": ctypes.c_char_p, "lzm_mlp_packed_floats": ctypes.c_int64,
             "lzm_mlp_kernel_floats": ctypes.c_int64, "lzm_mlp_ez_packed_floats": ctypes.c_int64,
             "lzm_mlp_ez_kernel_floats": ctypes.c_int64, "lzm_az_net_floats": ctypes.c_int64,
+            "lzm_az_c4_net_floats": ctypes.c_int64,
             "lzm_conv_trunk_floats": ctypes.c_int64, "lzm_conv_trunk_floats_p": ctypes.c_int64,
             "lzm_ez_lstm_frag_floats": ctypes.c_int64, "lzm_ez_lstm_workspace_bytes": ctypes.c_int64,
             "lzm_error_word": ctypes.c_void_p, "lzm_repr_floats": ctypes.c_int64,

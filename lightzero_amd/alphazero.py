@@ -16,6 +16,10 @@ size. Visit counts and action_probs are identical to the reference's for the sam
 with a real-valued network: whole trees of both paths against the restatement fed the fused network's own
 outputs, bit for bit). The sampled action uses a Philox draw (the reference uses std::random_device, which
 has no reproducible stream); tests/test_gpu_az_oracle.py restates the draw on the host.
+
+``game="connect4"`` (or a ``simulate_env`` with 7 actions) searches Connect4 boards [B, 42] the same way through
+lzm_az_c4_begin / step / finish (lzm_az_c4.h); ``Connect4AZNet`` is the Connect4 config's network in one launch
+(lzm_az_c4_net.h), so the whole search is HIP kernels (tests/test_gpu_az_connect4.py: whole trees bit for bit).
 """
 import ctypes
 
@@ -26,6 +30,8 @@ from . import _lib
 from ._lib import call, ptr, stream_ptr
 
 ACTIONS = 9
+# per game: actions, board cells, network input shape, max_moves default, entry-point prefix
+GAMES = {"tictactoe": (9, 9, (3, 3, 3), 9, "lzm_az_"), "connect4": (7, 42, (3, 6, 7), 42, "lzm_az_c4_")}
 
 
 def _fold_bn(conv, bn):
@@ -90,13 +96,69 @@ class FusedAZNet:
         return probs, value
 
 
+class Connect4AZNet:
+    """The Connect4 AlphaZeroModel (model_az.connect4_alphazero_model's structure) packed for lzm_az_c4_net_eval:
+    BatchNorm folded, MFMA B-fragment order (lzm_az_c4_net_prepare). Supported: observation (3, 6, 7), 64
+    channels, 1 or 2 residual blocks per network, head channels 16, head width 32, 7 actions, scalar value (the
+    Connect4 config); anything else raises ValueError."""
+
+    def __init__(self, model, device="cuda"):
+        m = model
+        nres = len(m.rep_blocks)
+        ok = (nres in (1, 2) and len(m.pred_blocks) == nres and m.conv.out_channels == 64 and m.conv.in_channels == 3
+              and m.flat_v == 672 and m.flat_p == 672 and m.conv1x1_value.out_channels == 16
+              and m.conv1x1_policy.out_channels == 16 and len(m.fc_value_head) == 4 and len(m.fc_policy_head) == 4
+              and m.fc_value_head[0].out_features == 32 and m.fc_policy_head[0].out_features == 32
+              and m.fc_policy_head[-1].out_features == 7 and m.fc_value_head[-1].out_features == 1
+              and isinstance(m.fc_value_head[1], torch.nn.LayerNorm))
+        if not ok:
+            raise ValueError("the Connect4 network kernel supports the Connect4 AlphaZeroModel config only")
+        if m.training:
+            raise ValueError("the Connect4 network kernel evaluates the network in eval mode: call model.eval()")
+        self.nres = nres
+        with torch.no_grad():
+            parts = []
+            w, b = _fold_bn(m.conv, m.norm)
+            parts += [w.reshape(64, 27), b]
+            for blk in list(m.rep_blocks) + list(m.pred_blocks):
+                for conv, bn in ((blk.conv1, blk.bn1), (blk.conv2, blk.bn2)):
+                    w, b = _fold_bn(conv, bn)
+                    parts += [w.reshape(64, 576), b]
+            wv, bv = _fold_bn(m.conv1x1_value, m.norm_value)
+            wp, bp = _fold_bn(m.conv1x1_policy, m.norm_policy)
+            parts += [torch.cat([wv.reshape(16, 64), wp.reshape(16, 64)]), torch.cat([bv, bp])]
+            for fc in (m.fc_value_head, m.fc_policy_head):
+                parts += [fc[0].weight, fc[0].bias, fc[1].weight, fc[1].bias, fc[3].weight, fc[3].bias]
+            raw = torch.cat([p.detach().float().cpu().reshape(-1) for p in parts]).contiguous()
+        out = torch.zeros(int(_lib.load().lzm_az_c4_net_floats(nres)), dtype=torch.float32)
+        call("lzm_az_c4_net_prepare", nres, ctypes.c_void_p(raw.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+        self.weights = out.to(device)
+
+    def compute_policy_value(self, state):
+        """state [n, 3, 6, 7] -> (probs [n, 7], value [n, 1]); one launch"""
+        st = state.reshape(-1, 126).to(torch.float32).contiguous()
+        n = st.shape[0]
+        probs = torch.empty((n, 7), dtype=torch.float32, device=st.device)
+        value = torch.empty((n, 1), dtype=torch.float32, device=st.device)
+        call("lzm_az_c4_net_eval", self.nres, ptr(self.weights), ptr(st), n, ptr(probs), ptr(value), stream_ptr())
+        return probs, value
+
+
 class AlphaZeroMCTS:
-    def __init__(self, max_moves=9, num_simulations=50, pb_c_base=19652, pb_c_init=1.25, root_dirichlet_alpha=0.3,
-                 root_noise_weight=0.25, simulate_env=None, device="cuda", graph=False, seed=0):
-        if simulate_env is not None and getattr(getattr(simulate_env, "action_space", None), "n", ACTIONS) != ACTIONS:
-            raise ValueError("the device simulate env is TicTacToe (9 actions)")
+    def __init__(self, max_moves=None, num_simulations=50, pb_c_base=19652, pb_c_init=1.25, root_dirichlet_alpha=0.3,
+                 root_noise_weight=0.25, simulate_env=None, device="cuda", graph=False, seed=0, game=None):
+        env_n = getattr(getattr(simulate_env, "action_space", None), "n", None)
+        if game is None:
+            game = "connect4" if env_n == 7 else "tictactoe"
+        if game not in GAMES:
+            raise ValueError(f"game must be one of {sorted(GAMES)}")
+        self.game = game
+        self.actions, self.cells, self.state_shape, moves, self._fn = GAMES[game]
+        if env_n is not None and env_n != self.actions:
+            raise ValueError("the device simulate env is TicTacToe (9 actions)" if game == "tictactoe" else
+                             "the device simulate env is Connect4 (7 actions)")
         _lib.require_gpu()
-        self.max_moves = int(max_moves)
+        self.max_moves = int(moves if max_moves is None else max_moves)
         self.num_simulations = int(num_simulations)
         self.pb_c_base, self.pb_c_init = float(pb_c_base), float(pb_c_init)
         self.alpha, self.noise_weight = float(root_dirichlet_alpha), float(root_noise_weight)
@@ -113,16 +175,16 @@ class AlphaZeroMCTS:
         if c is not None:
             return c
         nbytes = ctypes.c_int64()
-        call("lzm_az_workspace_bytes", B, self.num_simulations, ctypes.byref(nbytes))
+        call(self._fn + "workspace_bytes", B, self.num_simulations, ctypes.byref(nbytes))
         dev = self.device
         c = dict(ws=torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev),
-                 boards=torch.zeros((B, ACTIONS), dtype=torch.int32, device=dev),
+                 boards=torch.zeros((B, self.cells), dtype=torch.int32, device=dev),
                  start=torch.zeros(B, dtype=torch.int32, device=dev),
-                 state=torch.zeros((B, 3, 3, 3), dtype=torch.float32, device=dev),
-                 visits=torch.zeros((B, ACTIONS), dtype=torch.int32, device=dev),
-                 probs=torch.zeros((B, ACTIONS), dtype=torch.float64, device=dev),
+                 state=torch.zeros((B,) + self.state_shape, dtype=torch.float32, device=dev),
+                 visits=torch.zeros((B, self.actions), dtype=torch.int32, device=dev),
+                 probs=torch.zeros((B, self.actions), dtype=torch.float64, device=dev),
                  action=torch.zeros(B, dtype=torch.int32, device=dev), graphs={})
-        call("lzm_az_set_constants", B, self.num_simulations, ptr(c["ws"]), self.pb_c_base, self.pb_c_init,
+        call(self._fn + "set_constants", B, self.num_simulations, ptr(c["ws"]), self.pb_c_base, self.pb_c_init,
              self.alpha, stream_ptr())
         self._ctx[B] = c
         return c
@@ -131,23 +193,24 @@ class AlphaZeroMCTS:
         probs, value = pv(c["state"])
         probs = probs.reshape(B, -1).to(torch.float32).contiguous()
         value = value.reshape(B).to(torch.float32).contiguous()
-        if probs.shape[1] < ACTIONS:
-            raise ValueError("policy must cover the 9 TicTacToe actions")
+        if probs.shape[1] < self.actions:
+            raise ValueError(f"policy must cover the {self.actions} {self.game} actions")
         return probs, value
 
     def _body(self, B, pv, temperature, sample):
         c = self._buffers(B)
         S, ws, st = self.num_simulations, ptr(c["ws"]), ptr(c["state"])
         s = stream_ptr()
+        begin, step, finish = self._fn + "begin", self._fn + "step", self._fn + "finish"
         with torch.no_grad():
-            call("lzm_az_begin", B, S, ws, ptr(c["boards"]), ptr(c["start"]), st, s)
+            call(begin, B, S, ws, ptr(c["boards"]), ptr(c["start"]), st, s)
             probs, value = self._evaluate(pv, c, B)
-            call("lzm_az_step", B, S, ws, -1, ptr(probs), probs.shape[1], ptr(value), 1, int(bool(sample)),
+            call(step, B, S, ws, -1, ptr(probs), probs.shape[1], ptr(value), 1, int(bool(sample)),
                  self.noise_weight, st, s)
             for k in range(S):
                 probs, value = self._evaluate(pv, c, B)
-                call("lzm_az_step", B, S, ws, k, ptr(probs), probs.shape[1], ptr(value), 1, 0, 0.0, st, s)
-            call("lzm_az_finish", B, S, ws, float(temperature), int(bool(sample)), self.seed, ptr(self._count),
+                call(step, B, S, ws, k, ptr(probs), probs.shape[1], ptr(value), 1, 0, 0.0, st, s)
+            call(finish, B, S, ws, float(temperature), int(bool(sample)), self.seed, ptr(self._count),
                  ptr(c["visits"]), ptr(c["probs"]), ptr(c["action"]), s)
             self._count.add_(1)
 
@@ -182,9 +245,14 @@ class AlphaZeroMCTS:
             g = g[0]
         g.replay()
 
+    def _tictactoe_only(self, what):
+        if self.game != "tictactoe":
+            raise ValueError(f"{what}: the one-launch search exists for TicTacToe only; game is {self.game!r}")
+
     def search_fused(self, boards, start_player_index, net, temperature=1.0, sample=True, export_tree=False):
         """The whole search (root evaluation, S simulations with the network, finalisation) in one
         launch; net: FusedAZNet. Same outputs as get_next_actions."""
+        self._tictactoe_only("search_fused")
         if temperature == 0:
             raise ValueError("Temperature cannot be 0")
         b = torch.as_tensor(boards).reshape(-1, ACTIONS)
@@ -203,18 +271,19 @@ class AlphaZeroMCTS:
         """What search_fused launches for B boards as the process stands (lzm_az_fused_plan; host only):
         dict(rows: boards per workgroup, workgroups, per_cu: workgroups one CU holds (-1: the occupancy
         query failed and 1 was assumed), lds_bytes)."""
+        self._tictactoe_only("fused_plan")
         out = (ctypes.c_int32 * 4)()
         call("lzm_az_fused_plan", int(B), self.num_simulations, net.nres, out)
         return dict(rows=out[0], workgroups=out[1], per_cu=out[2], lds_bytes=out[3])
 
     # ------------------------------------------------------------------ public API
     def get_next_actions(self, boards, start_player_index, compute_policy_value, temperature=1.0, sample=True):
-        """boards [B, 9] (or [B, 3, 3]) with 0 empty / 1 / 2 stones, start_player_index [B] (0: player 1
-        to move, 1: player 2). Returns (actions int32 [B], action_probs float64 [B, 9], device tensors;
-        overwritten by the next call with the same B)."""
+        """boards [B, 9] (or [B, 3, 3]; Connect4: [B, 42] or [B, 6, 7], row 0 on top) with 0 empty / 1 / 2
+        stones, start_player_index [B] (0: player 1 to move, 1: player 2). Returns (actions int32 [B],
+        action_probs float64 [B, actions], device tensors; overwritten by the next call with the same B)."""
         if temperature == 0:
             raise ValueError("Temperature cannot be 0")
-        b = torch.as_tensor(boards).reshape(-1, ACTIONS)
+        b = torch.as_tensor(boards).reshape(-1, self.cells)
         B = int(b.shape[0])
         c = self._buffers(B)
         c["boards"].copy_(b.to(device=self.device, dtype=torch.int32))
@@ -229,7 +298,7 @@ class AlphaZeroMCTS:
         """One board, the reference's signature; policy_value_func is the batched compute_policy_value."""
         cfg = state_config_for_env_reset
         init = cfg.get("init_state")
-        board = np.zeros(ACTIONS, np.int32) if init is None else np.asarray(init, np.int32).reshape(ACTIONS)
+        board = np.zeros(self.cells, np.int32) if init is None else np.asarray(init, np.int32).reshape(self.cells)
         a, p = self.get_next_actions(board[None], [int(cfg["start_player_index"])], policy_value_func, temperature,
                                      sample)
         return int(a[0].item()), p[0].tolist()
@@ -237,20 +306,20 @@ class AlphaZeroMCTS:
     def export_tree(self, B):
         """(visit int32 [B, cap], value_sum float32 [B, cap], first int32 [B, cap], nnodes int32 [B])"""
         c = self._buffers(B)
-        cap = 1 + ACTIONS * (self.num_simulations + 1)
+        cap = 1 + self.actions * (self.num_simulations + 1)
         out = [torch.empty((B, cap), dtype=torch.int32, device=self.device),
                torch.empty((B, cap), dtype=torch.float32, device=self.device),
                torch.empty((B, cap), dtype=torch.int32, device=self.device),
                torch.empty(B, dtype=torch.int32, device=self.device)]
-        call("lzm_az_export_tree", B, self.num_simulations, ptr(c["ws"]), *[ptr(t) for t in out], stream_ptr())
+        call(self._fn + "export_tree", B, self.num_simulations, ptr(c["ws"]), *[ptr(t) for t in out], stream_ptr())
         return out
 
     def export_priors(self, B):
         """the nodes' priors, float32 [B, cap] (rows as export_tree's; the root's children after the noise mix)"""
         c = self._buffers(B)
-        cap = 1 + ACTIONS * (self.num_simulations + 1)
+        cap = 1 + self.actions * (self.num_simulations + 1)
         out = torch.empty((B, cap), dtype=torch.float32, device=self.device)
-        call("lzm_az_export_priors", B, self.num_simulations, ptr(c["ws"]), ptr(out), stream_ptr())
+        call(self._fn + "export_priors", B, self.num_simulations, ptr(c["ws"]), ptr(out), stream_ptr())
         return out
 
 

@@ -3,6 +3,7 @@ import glob
 import os
 import subprocess
 import sys
+import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -15,7 +16,15 @@ ARCH = os.environ.get("LZM_OFFLOAD_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared", "-Wall",
          f"--offload-arch={ARCH}"]
 SOURCES = [os.path.join(HERE, "csrc", "lzm_kernels.hip")]
-DEPS = SOURCES + sorted(glob.glob(os.path.join(HERE, "csrc", "*.h")) +
+# Translation units compiled with the packed-f32 VALU forms (v_pk_add / mul / fma_f32) switched off in the target,
+# then linked in: the Connect4 AlphaZero kernels, whose trees and network bits are pinned to a plain f32 restatement.
+# A guard, not a tuning: the present compiler emits none of these forms there either way (the device assembly is
+# the same with and without the feature). It cannot go on lzm_kernels.hip, which uses packed FMAs on purpose
+# (profiles/EXPERIMENTS.md, "packed FMA") and whose kernels change with it; hence the separate unit.
+# tools/build_variant.sh builds the same two units.
+NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+NO_PK_SOURCES = [os.path.join(HERE, "csrc", "lzm_az_c4.hip")]
+DEPS = SOURCES + NO_PK_SOURCES + sorted(glob.glob(os.path.join(HERE, "csrc", "*.h")) +
                         glob.glob(os.path.join(HERE, "csrc", "*.inc"))) + [os.path.join(REPO, "include", "lzmcts.h")]
 OUT = os.path.join(HERE, "liblzmcts.so")
 
@@ -30,10 +39,19 @@ def needs_build():
 def build(force=False, verbose=True):
     if not force and not needs_build():
         return OUT
-    cmd = [HIPCC] + FLAGS + ["-o", OUT] + SOURCES
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.check_call(cmd)
+    with tempfile.TemporaryDirectory(prefix="lzm_build_") as tmp:
+        objs = []
+        for src in NO_PK_SOURCES:
+            obj = os.path.join(tmp, os.path.splitext(os.path.basename(src))[0] + ".o")
+            cmd = [HIPCC] + [f for f in FLAGS if f != "-shared"] + NO_PK_F32 + ["-c", "-o", obj, src]
+            if verbose:
+                print(" ".join(cmd), file=sys.stderr)
+            subprocess.check_call(cmd)
+            objs.append(obj)
+        cmd = [HIPCC] + FLAGS + ["-o", OUT] + objs + SOURCES  # objects first: hipcc puts -x hip before a .hip file
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.check_call(cmd)
     return OUT
 
 

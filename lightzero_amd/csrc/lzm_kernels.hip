@@ -41,6 +41,7 @@
 #include "lzm_traj.h"
 #include "lzm_az.h"
 #include "lzm_az_fused.h"
+#include "lzm_az_c4_host.h"
 #include "lzm_tree.h"
 #include "lzm_gumbel.h"
 #include "lzm_stochastic.h"
@@ -2976,6 +2977,205 @@ int lzm_az_export_priors(int B, int S, void *ws, float *prior, void *stream) {
   AzTree t;
   az_carve(B, S, ws, &t);
   LZM_HIP(hipMemcpyAsync(prior, t.prior, (size_t)B * t.cap * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+}  // extern "C"
+
+// ---- batched AlphaZero for Connect4 (kernels and launchers: lzm_az_c4.hip). One workspace per (B, S).
+static int64_t c4_carve(int B, int S, void *ws, C4Tree *t) {
+  const int64_t cap = 1 + (int64_t)kC4Cols * (S + 1);
+  char *p = (char *)ws;
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) -> void * {
+    void *r = p ? (void *)(p + off) : nullptr;
+    off += (bytes + 255) & ~(int64_t)255;
+    return r;
+  };
+  C4Tree x;
+  x.B = B; x.S = S; x.cap = (int)cap;
+  x.rec = (int4 *)take((int64_t)B * cap * 16);
+  x.nnodes = (int32_t *)take((int64_t)B * 4);
+  x.root = (uint64_t *)take((int64_t)B * 16);
+  x.root_player = (int32_t *)take((int64_t)B * 4);
+  x.path = (int32_t *)take((int64_t)B * kC4Path * 4);
+  x.leaf = (int32_t *)take((int64_t)B * 4 * 4);
+  x.leaf_bb = (uint64_t *)take((int64_t)B * 16);
+  x.lut_pb = (double *)take((int64_t)(S + 1) * 8);
+  x.lut_sqrt = (double *)take((int64_t)(S + 1) * 8);
+  x.noise = (double *)take((int64_t)kC4Cols * kC4Cols * 8);
+  if (t) *t = x;
+  return off;
+}
+
+#define LZM_C4_LAUNCH(call)                                                                      \
+  do {                                                                                           \
+    hipError_t e_ = (call);                                                                      \
+    if (e_ != hipSuccess) {                                                                      \
+      snprintf(g_err, sizeof(g_err), "%s failed: %s", #call, hipGetErrorString(e_));             \
+      return LZM_ERR_HIP;                                                                        \
+    }                                                                                            \
+  } while (0)
+
+extern "C" {
+
+int lzm_az_c4_workspace_bytes(int B, int S, int64_t *out) {
+  if (B <= 0 || S <= 0 || S > (1 << 20) || !out) {
+    set_err("lzm_az_c4_workspace_bytes: need B > 0, 0 < num_simulations <= 2^20");
+    return LZM_ERR_ARG;
+  }
+  *out = c4_carve(B, S, nullptr, nullptr);
+  return LZM_OK;
+}
+
+int lzm_az_c4_set_constants(int B, int S, void *ws, double pb_c_base, double pb_c_init, double alpha, void *stream) {
+  if (!az_args_ok(B, S, ws, "lzm_az_c4_set_constants")) return LZM_ERR_ARG;
+  if (!(pb_c_base > 0.0) || !(alpha > 0.0)) {
+    set_err("lzm_az_c4_set_constants: need pb_c_base > 0 and alpha > 0");
+    return LZM_ERR_ARG;
+  }
+  C4Tree t;
+  c4_carve(B, S, ws, &t);
+  std::vector<double> pb((size_t)S + 1), sq((size_t)S + 1), nz((size_t)kC4Cols * kC4Cols);
+  for (int n = 0; n <= S; ++n) {
+    pb[(size_t)n] = std::log((n + pb_c_base + 1) / pb_c_base) + pb_c_init;
+    sq[(size_t)n] = std::sqrt((double)n);
+  }
+  lzm_az_noise_table(alpha, kC4Cols, nz.data());  // a position has at most 7 children: the first 7 rows
+  hipStream_t s = (hipStream_t)stream;
+  LZM_HIP(hipMemcpyAsync(t.lut_pb, pb.data(), pb.size() * 8, hipMemcpyHostToDevice, s));
+  LZM_HIP(hipMemcpyAsync(t.lut_sqrt, sq.data(), sq.size() * 8, hipMemcpyHostToDevice, s));
+  LZM_HIP(hipMemcpyAsync(t.noise, nz.data(), nz.size() * 8, hipMemcpyHostToDevice, s));
+  LZM_HIP(hipStreamSynchronize(s));
+  return LZM_OK;
+}
+
+int lzm_az_c4_begin(int B, int S, void *ws, const int32_t *boards, const int32_t *start_index, float *state,
+                    void *stream) {
+  if (!az_args_ok(B, S, ws, "lzm_az_c4_begin")) return LZM_ERR_ARG;
+  if (!boards || !start_index || !state) {
+    set_err("lzm_az_c4_begin: null buffer");
+    return LZM_ERR_ARG;
+  }
+  C4Tree t;
+  c4_carve(B, S, ws, &t);
+  LZM_C4_LAUNCH(c4_launch_begin(t, boards, start_index, state, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int lzm_az_c4_step(int B, int S, void *ws, int sim, const float *probs, int pstride, const float *values, int vstride,
+                   int with_noise, double noise_weight, float *state, void *stream) {
+  if (!az_args_ok(B, S, ws, "lzm_az_c4_step")) return LZM_ERR_ARG;
+  if (sim < -1 || sim >= S || !probs || pstride < kC4Cols || (sim >= 0 && (!values || vstride < 1)) || !state) {
+    set_err("lzm_az_c4_step: need -1 <= sim < num_simulations, probs [B][>=7], values [B] and a state buffer");
+    return LZM_ERR_ARG;
+  }
+  C4Tree t;
+  c4_carve(B, S, ws, &t);
+  C4StepArgs a;
+  a.sim = sim; a.with_noise = with_noise; a.noise_weight = noise_weight;
+  a.probs = probs; a.pstride = pstride; a.values = values ? values : probs; a.vstride = vstride; a.state = state;
+  LZM_C4_LAUNCH(c4_launch_step(t, a, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int lzm_az_c4_finish(int B, int S, void *ws, double temperature, int sample, uint32_t seed, const int64_t *counter,
+                     int32_t *visits, double *probs, int32_t *action, void *stream) {
+  if (!az_args_ok(B, S, ws, "lzm_az_c4_finish")) return LZM_ERR_ARG;
+  if (temperature == 0.0 || !visits || !probs || !action) {
+    set_err("lzm_az_c4_finish: temperature cannot be 0; visits / probs / action buffers required");
+    return LZM_ERR_ARG;
+  }
+  C4Tree t;
+  c4_carve(B, S, ws, &t);
+  LZM_C4_LAUNCH(c4_launch_finish(t, temperature, sample, seed, counter, visits, probs, action, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int lzm_az_c4_export_tree(int B, int S, void *ws, int32_t *visit, float *vsum, int32_t *first, int32_t *nnodes,
+                          void *stream) {
+  if (!az_args_ok(B, S, ws, "lzm_az_c4_export_tree")) return LZM_ERR_ARG;
+  C4Tree t;
+  c4_carve(B, S, ws, &t);
+  LZM_C4_LAUNCH(c4_launch_export(t, visit, vsum, first, nullptr, nnodes, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int lzm_az_c4_export_priors(int B, int S, void *ws, float *prior, void *stream) {
+  if (!az_args_ok(B, S, ws, "lzm_az_c4_export_priors")) return LZM_ERR_ARG;
+  if (!prior) {
+    set_err("lzm_az_c4_export_priors: null output");
+    return LZM_ERR_ARG;
+  }
+  C4Tree t;
+  c4_carve(B, S, ws, &t);
+  LZM_C4_LAUNCH(c4_launch_export(t, nullptr, nullptr, nullptr, prior, nullptr, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int lzm_az_c4_done_winner(const int32_t *boards, int n, int32_t *out, void *stream) {
+  if (!boards || n <= 0 || !out) {
+    set_err("lzm_az_c4_done_winner: need boards [n][42], n > 0 and out [n][2]");
+    return LZM_ERR_ARG;
+  }
+  LZM_C4_LAUNCH(c4_launch_done_winner(boards, n, out, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int64_t lzm_az_c4_net_floats(int nres) { return nres == 1 || nres == 2 ? c4_net_layout(nres).total : -1; }
+
+int lzm_az_c4_net_prepare(int nres, const float *raw, float *out) {
+  if ((nres != 1 && nres != 2) || !raw || !out) {
+    set_err("lzm_az_c4_net_prepare: num_res_blocks must be 1 or 2");
+    return LZM_ERR_ARG;
+  }
+  const C4NetLayout L = c4_net_layout(nres);
+  memset(out, 0, sizeof(float) * (size_t)L.total);
+  const float *p = raw;
+  // B fragment of v_mfma_f32_16x16x4_f32: lane holds B[k = lane / 16][n = lane % 16]; wave w owns out channels 16 w ..
+  const float *w0 = p; p += 64 * 27;
+  for (int wv = 0; wv < 4; ++wv)
+    for (int tap = 0; tap < 9; ++tap)
+      for (int lane = 0; lane < 64; ++lane) {
+        const int cin = lane >> 4;
+        if (cin < 3) out[L.conv0 + (wv * 9 + tap) * 64 + lane] = w0[(16 * wv + (lane & 15)) * 27 + cin * 9 + tap];
+      }
+  memcpy(out + L.conv0_b, p, 64 * sizeof(float)); p += 64;
+  for (int l = 0; l < 4 * nres; ++l) {
+    const float *wl = p; p += 64 * 576;
+    for (int tap = 0; tap < 9; ++tap)
+      for (int wv = 0; wv < 4; ++wv)
+        for (int j = 0; j < 16; ++j)  // K step j of the tap: in channels 4 j .. 4 j + 3
+          for (int lane = 0; lane < 64; ++lane)
+            out[L.conv + (size_t)((((l * 9 + tap) * 4 + wv) * 4 + (j >> 2)) * 64 + lane) * 4 + (j & 3)] =
+                wl[(16 * wv + (lane & 15)) * 576 + (4 * j + (lane >> 4)) * 9 + tap];
+    memcpy(out + L.conv_b + l * 64, p, 64 * sizeof(float)); p += 64;
+  }
+  const float *wh = p; p += 32 * 64;
+  for (int nt = 0; nt < 2; ++nt)
+    for (int k = 0; k < 16; ++k)
+      for (int lane = 0; lane < 64; ++lane)
+        out[L.head + (nt * 16 + k) * 64 + lane] = wh[(16 * nt + (lane & 15)) * 64 + 4 * k + (lane >> 4)];
+  memcpy(out + L.head_b, p, 32 * sizeof(float)); p += 32;
+  for (int head = 0; head < 2; ++head) {
+    const float *f1 = p; p += 32 * 672;
+    for (int i = 0; i < 84; ++i)
+      for (int lane = 0; lane < 64; ++lane)
+        for (int e = 0; e < 4; ++e)
+          out[L.fc1 + ((head * 84 + i) * 64 + lane) * 4 + e] = f1[(lane >> 1) * 672 + (lane & 1) * 336 + 4 * i + e];
+    const int tail = head ? kC4nTp2b + 7 : kC4nTv2b + 1;  // FC1 bias, gamma, beta, FC2, FC2 bias: raw order
+    memcpy(out + (head ? L.tail_p : L.tail_v), p, tail * sizeof(float)); p += tail;
+  }
+  return LZM_OK;
+}
+
+int lzm_az_c4_net_eval(int nres, const float *weights, const float *state, int n, float *probs, float *value,
+                       void *stream) {
+  if ((nres != 1 && nres != 2) || !weights || !state || n <= 0 || !probs || !value) {
+    set_err("lzm_az_c4_net_eval: need num_res_blocks 1 or 2, n > 0 and all buffers");
+    return LZM_ERR_ARG;
+  }
+  LZM_C4_LAUNCH(c4_launch_net_eval(nres, weights, state, n, probs, value, (hipStream_t)stream));
   return LZM_OK;
 }
 

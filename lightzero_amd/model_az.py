@@ -80,3 +80,12 @@ def tictactoe_alphazero_model(random_heads: bool = True) -> AlphaZeroModel:
     layers so an untrained net still gives a non-uniform search."""
     m = AlphaZeroModel(last_linear_layer_init_zero=not random_heads)
     return m.eval()
+
+
+def connect4_alphazero_model(random_heads: bool = True) -> AlphaZeroModel:
+    """The Connect4 config's network in eval mode (zoo/board_games/connect4/config/
+    connect4_alphazero_sp_mode_config.py: observation (3, 6, 7), 7 actions, 1 residual block, 64 channels,
+    value / policy head width 32); random_heads as tictactoe_alphazero_model's."""
+    m = AlphaZeroModel((3, 6, 7), 7, num_res_blocks=1, num_channels=64, fc_value_layers=(32,),
+                       fc_policy_layers=(32,), last_linear_layer_init_zero=not random_heads)
+    return m.eval()

@@ -1,5 +1,7 @@
 # Build lightzero_amd/liblzm_var<NAME>.so from the sources of git revision REV (default: the working tree),
 # for interleaved A/B runs (tools/ab_libs.sh). usage: bash tools/build_variant.sh NAME [REV] [extra hipcc flags]
+# Builds what lightzero_amd/build.py builds: lzm_kernels.hip, and, where the revision has it, lzm_az_c4.hip as a
+# unit of its own with the packed-f32 VALU forms switched off.
 set -e
 name=$1; rev=${2:-}; shift; shift || true
 root=$(cd "$(dirname "$0")/.." && pwd)
@@ -8,6 +10,14 @@ if [ -n "$rev" ]; then
   src=$(mktemp -d /tmp/lzm_var_XXXX)
   git -C "$root" archive "$rev" lightzero_amd/csrc include | tar -x -C "$src"
 fi
-/opt/rocm/bin/hipcc -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -fPIC -shared -Wall --offload-arch=gfx950 "$@" \
-  -o "$root/lightzero_amd/liblzm_var$name.so" "$src/lightzero_amd/csrc/lzm_kernels.hip"
+flags="-O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -fPIC -Wall --offload-arch=gfx950"
+objs=
+if [ -f "$src/lightzero_amd/csrc/lzm_az_c4.hip" ]; then
+  tmp=$(mktemp -d /tmp/lzm_var_obj_XXXX)
+  /opt/rocm/bin/hipcc $flags "$@" -Xclang -target-feature -Xclang -packed-fp32-ops -c -o "$tmp/lzm_az_c4.o" \
+    "$src/lightzero_amd/csrc/lzm_az_c4.hip"
+  objs="$tmp/lzm_az_c4.o"
+fi
+/opt/rocm/bin/hipcc $flags -shared "$@" -o "$root/lightzero_amd/liblzm_var$name.so" $objs \
+  "$src/lightzero_amd/csrc/lzm_kernels.hip"
 echo "built lightzero_amd/liblzm_var$name.so from ${rev:-working tree}"
