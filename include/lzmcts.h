@@ -46,9 +46,12 @@ enum lzm_flags {
                        batch-serial glibc rand() stream of the reference (parity mode) */
   LZM_TREE_GUMBEL = 4, /* Gumbel MuZero tree (ctree_gumbel_muzero) instead of MuZero: driven by the lzm_gumbel_*
                           entry points below; excludes LZM_TREE_EZ; LZM_RNG_FAST is ignored (the tree never draws) */
-  LZM_TREE_STOCHASTIC = 8 /* Stochastic MuZero tree (ctree_stochastic_muzero): set by lzm_stochastic_create, driven
-                             by the lzm_stochastic_* entry points below; excludes LZM_TREE_EZ and LZM_TREE_GUMBEL;
-                             always draws from per-root Philox streams, whatever LZM_RNG_FAST says */
+  LZM_TREE_STOCHASTIC = 8, /* Stochastic MuZero tree (ctree_stochastic_muzero): set by lzm_stochastic_create, driven
+                              by the lzm_stochastic_* entry points below; excludes LZM_TREE_EZ and LZM_TREE_GUMBEL;
+                              always draws from per-root Philox streams, whatever LZM_RNG_FAST says */
+  LZM_TREE_SAMPLED = 16 /* Sampled EfficientZero tree (ctree_sampled_efficientzero): set by lzm_sampled_create, driven
+                           by the lzm_sampled_* entry points below; excludes the three flags above; always draws
+                           from per-root Philox streams */
 };
 
 /* Creates a tree for `num_roots` roots, `action_space` actions, capacity for `max_sims`
@@ -1022,6 +1025,65 @@ int lzm_stochastic_decode_backprop_traverse(lzm_handle *h, int current_latent_st
                                             const int32_t *vtp_in, int32_t *out_x, int32_t *out_y, int32_t *out_a,
                                             int64_t *out_a64, int32_t *out_vtp, int32_t *out_len,
                                             int32_t *out_is_chance, void *stream);
+/* ---- Sampled EfficientZero tree (ctree_sampled_efficientzero; lzm_sampled.h) ----------------------------------
+ * Every expanded node has K = num_of_sampled_actions children ("slots"), each a sampled action: a float vector of
+ * D = action_space_size dimensions (continuous_action_space != 0; the policy row is {mu[D], sigma[D]}, the action
+ * tanh(N(mu, sigma))) or one of action_space_size discrete actions, K of them drawn without replacement (policy row:
+ * the logits). Selection is EfficientZero's value-prefix rule with a uniform prior 1 / K over the slots, as the
+ * reference's cucb_score computes it; its stored child priors and root noise never reach selection, so
+ * lzm_sampled_prepare accepts noises / root_noise_weight and ignores them.
+ *
+ * lzm_sampled_create: K < 1 or K > 64, a continuous D > 32, a discrete action space > 64 or K above it, or another
+ * family's flag is LZM_ERR_ARG. The handle's child blocks are K wide and lzm_action_space returns K.
+ * lzm_get_distributions (rows of K visit counts), lzm_get_values, lzm_get_trajectories (slot indices),
+ * lzm_gather_latent, lzm_copy_tree, lzm_reserve and lzm_minmax_init serve it unchanged. Every other family's
+ * traverse, backprop and one-launch entry point returns LZM_ERR_STATE on it, and the lzm_sampled_* entry points
+ * return LZM_ERR_STATE on any other handle, before any launch.
+ *
+ * Draws: Philox4x32-10 under key (*seed, 0x53414d50). Tie draw of level l of root i: word 0 >> 1 of counter
+ * (l, i, 0, 0) modulo the tie count. Node expanded by simulation L (0: the root), slot j, dims 2m and 2m + 1:
+ * counter (L, i, 2 | j << 8, m), u1 from words 0, 1 and u2 from words 2, 3 (53 bits, + 0.5, * 2^-53), Box-Muller in
+ * double, x = (float)(mu + sigma * z), action = (float)tanh((double)x); an odd D drops the last sine half. Discrete
+ * action a: counter (L, i, 3, a), key pow(u, 1 / p_a) in double with p_a = (float)(expf(l_a) / (sum expf(l) + 1e-6));
+ * slot = the number of larger keys (equal keys: lower action first); slots < K are kept. The expanding entry points
+ * take the seed of the expansion, so the sampled actions are a function of (seed, root, L, slot, dim, policy row). */
+int lzm_sampled_create(int num_roots, int action_space_size, int num_of_sampled_actions, int continuous_action_space,
+                       int max_sims, int flags, lzm_handle **out);
+int lzm_sampled_action_dim(const lzm_handle *h);   /* D of a continuous sampled handle, else (null too) 0 */
+int lzm_sampled_action_space(const lzm_handle *h); /* the action space of a discrete sampled handle, else 0 */
+/* CRoots::prepare / prepare_no_noise: value_prefixs [B], policy [B][2 D] or [B][action_space], to_play [B]; the
+ * root is the node of simulation 0. noises may be null. */
+int lzm_sampled_prepare(lzm_handle *h, const float *noises, float root_noise_weight, const float *value_prefixs,
+                        const float *policy, const int32_t *to_play, const uint32_t *seed, void *stream);
+/* batch_traverse: lzm_traverse's outputs with out_slot int32 [B] (the chosen slot of the leaf's parent) and
+ * out_action, the network's last_actions input: float32 [B][D] (continuous) or int64 [B] (discrete). */
+int lzm_sampled_traverse(lzm_handle *h, int pb_c_base, float pb_c_init, float discount, float *minmax,
+                         const uint32_t *seed, const int32_t *vtp_in, int32_t *out_x, int32_t *out_y,
+                         int32_t *out_slot, void *out_action, int32_t *out_vtp, int32_t *out_len, void *stream);
+/* batch_backpropagate from raw lists, one entry per root: value_prefixs, values [B], policy rows, to_play and
+ * is_reset [B]. LZM_ERR_STATE before the first lzm_sampled_traverse. */
+int lzm_sampled_backprop(lzm_handle *h, int current_latent_state_index, float discount, float *minmax,
+                         const float *value_prefixs, const float *values, const float *policy, const int32_t *to_play,
+                         const int32_t *is_reset, const uint32_t *seed, void *stream);
+/* One simulation's support decode (as lzm_decode_backprop's, is_reset = search_len % lstm_horizon == 0 into
+ * out_is_reset) + expand with sampling + EfficientZero backup in one launch ... */
+int lzm_sampled_decode_backprop(lzm_handle *h, int current_latent_state_index, float discount, float *minmax,
+                                const float *value_prefix_logits, const float *value_logits, int support_len,
+                                int categorical, const float *policy, const int32_t *to_play, int lstm_horizon,
+                                int32_t *out_is_reset, const float *next_latent, float *pool_slot, int64_t row_elems,
+                                float *out_decoded, const uint32_t *seed, void *stream);
+/* ... and the next simulation's lzm_sampled_traverse (keyed by walk_seed) in the same launch, by the wave that
+ * backed the root up. */
+int lzm_sampled_decode_backprop_traverse(lzm_handle *h, int current_latent_state_index, float discount, float *minmax,
+                                         const float *value_prefix_logits, const float *value_logits, int support_len,
+                                         int categorical, const float *policy, const int32_t *to_play,
+                                         int lstm_horizon, int32_t *out_is_reset, const float *next_latent,
+                                         float *pool_slot, int64_t row_elems, float *out_decoded, const uint32_t *seed,
+                                         int pb_c_base, float pb_c_init, const uint32_t *walk_seed,
+                                         const int32_t *vtp_in, int32_t *out_x, int32_t *out_y, int32_t *out_slot,
+                                         void *out_action, int32_t *out_vtp, int32_t *out_len, void *stream);
+/* CRoots::get_sampled_actions: the roots' slots, float32 [B][K][D] or int32 [B][K]. */
+int lzm_sampled_get_sampled_actions(lzm_handle *h, void *out, void *stream);
 /* Device logf port (lzm_numerics.h glibc_logf) exposed for checks against the host libm. */
 int lzm_debug_logf(const float *x, float *out, int64_t n, void *stream);
 

@@ -28,6 +28,7 @@ LZM_TREE_EZ = 1
 LZM_RNG_FAST = 2
 LZM_TREE_GUMBEL = 4
 LZM_TREE_STOCHASTIC = 8
+LZM_TREE_SAMPLED = 16
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -200,6 +201,17 @@ SIGNATURES = {
     "lzm_stochastic_decode_backprop": [_vp, _i, _f] + [_vp] * 8 + [_i, _i, _vp, _vp, _i64, _vp, _vp],
     "lzm_stochastic_decode_backprop_traverse": [_vp, _i, _f] + [_vp] * 8 + [_i, _i, _vp, _vp, _i64, _vp, _i, _f]
                                                + [_vp] * 10,
+    "lzm_sampled_create": [_i, _i, _i, _i, _i, _i, ctypes.POINTER(_vp)],
+    "lzm_sampled_action_dim": [_vp],
+    "lzm_sampled_action_space": [_vp],
+    "lzm_sampled_prepare": [_vp, _vp, _f, _vp, _vp, _vp, _vp, _vp],
+    "lzm_sampled_traverse": [_vp, _i, _f, _f] + [_vp] * 10,
+    "lzm_sampled_backprop": [_vp, _i, _f] + [_vp] * 8,
+    "lzm_sampled_decode_backprop": [_vp, _i, _f, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp, _vp,
+                                    _vp],
+    "lzm_sampled_decode_backprop_traverse": [_vp, _i, _f, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i64,
+                                             _vp, _vp, _i, _f] + [_vp] * 9,
+    "lzm_sampled_get_sampled_actions": [_vp, _vp, _vp],
     "lzm_conv_trunk_xin_p": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp,
                              _vp],
 }

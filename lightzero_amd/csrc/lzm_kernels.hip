@@ -45,6 +45,7 @@
 #include "lzm_tree.h"
 #include "lzm_gumbel.h"
 #include "lzm_stochastic.h"
+#include "lzm_sampled.h"
 #include "lzm_search_mlp.h"
 #include "lzm_search_res.h"
 #include "lzm_conv.h"
@@ -589,6 +590,58 @@ __global__ __launch_bounds__(256) void stochastic_decode_kernel(StochasticDecode
   }
 }
 
+// ---- Sampled EfficientZero tree (lzm_sampled.h): one wave per root, four roots per 256-thread workgroup ----
+template <bool CONT>
+__global__ __launch_bounds__(256) void sampled_prepare_kernel(SampledPrepareArgs p) {
+  const int i = gumbel_wave_root();
+  if (i < p.t.B) sampled_prepare_root<CONT>(p, i);
+}
+
+template <bool CONT>
+__global__ __launch_bounds__(256) void sampled_traverse_kernel(SampledTraverseArgs q) {
+  const int i = gumbel_wave_root();
+  if (i < q.t.B) sampled_traverse_root<CONT>(q, i);
+}
+
+// cbatch_backpropagate from raw lists
+template <bool CONT>
+__global__ __launch_bounds__(256) void sampled_backprop_kernel(SampledBackpropArgs p) {
+  const int i = gumbel_wave_root();
+  if (i >= p.t.B) return;
+  const int width = CONT ? 2 * p.sv.D : p.sv.A;
+  sampled_expand_backup<CONT>(p.t, p.sv, p.minmax, i, p.to_play[i], p.cur, p.value_prefixs[i], p.values[i],
+                              p.policy + (size_t)i * width, p.is_reset[i], *p.seed, p.disc);
+}
+
+// One simulation in one launch, by the wave that owns the root: support decode of value and value prefix, expand
+// (sample, records, action table), the EfficientZero backup with is_reset and, with NEXT_WALK, the next
+// simulation's walk over the records it has just written.
+template <bool CONT, bool NEXT_WALK>
+__global__ __launch_bounds__(256) void sampled_decode_kernel(DecodeArgs p, SampledView sv, const uint32_t *seed,
+                                                             const int32_t *norm_part, SampledTraverseArgs q) {
+  const int i = gumbel_wave_root();
+  if (i >= p.t.B) return;
+  float r, v;
+  decode_heads(p, norm_part, i, &r, &v);
+  const int len = p.t.pathlen[i];
+  const int is_reset = (p.horizon > 0 && len % p.horizon == 0) ? 1 : 0;
+  if (p.out_is_reset && (threadIdx.x & 63) == 0) p.out_is_reset[i] = is_reset;
+  const int width = CONT ? 2 * sv.D : sv.A;
+  sampled_expand_backup<CONT>(p.t, sv, p.minmax, i, p.to_play[i], p.cur, r, v, p.policy_logits + (size_t)i * width,
+                              is_reset, *seed, p.disc);
+  if (NEXT_WALK) {
+    // the backup's stores (other lanes of this wave) complete before the walk reads them
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    sampled_traverse_root<CONT>(q, i);
+  }
+}
+
+__global__ __launch_bounds__(256) void sampled_root_actions_kernel(TreeView t, SampledView sv, void *out) {
+  const int i = gumbel_wave_root();
+  if (i < t.B) sampled_root_actions(t, sv, i, out);
+}
+
 __global__ void debug_logf_kernel(const float *x, float *out, long long n) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = glibc_logf(x[i]);
@@ -674,7 +727,10 @@ struct lzm_handle {
   // Stochastic MuZero handles (LZM_TREE_STOCHASTIC) only: A above is the child-block width max(act, chance)
   int act = 0, chance = 0;        // action space, chance space
   int32_t *is_chance = nullptr;   // [B] kind of the last walk's leaf
-  bool walked = false;            // a stochastic traverse has run (lzm_stochastic_backprop's call order)
+  bool walked = false;            // a stochastic / sampled traverse has run (the backprops' call order)
+  // Sampled EfficientZero handles (LZM_TREE_SAMPLED) only: A above is K, the sampled actions per node
+  int s_dim = 0, s_space = 0;     // continuous: action dimensions D; discrete: action space
+  void *s_act = nullptr;          // the action table, [(sims_cap + 1) * K][B][D] float32 or [..][B] int32
 };
 
 static TreeView view(lzm_handle *h) {
@@ -701,9 +757,9 @@ static void dfree(void *p) {
 
 static void free_tree(lzm_handle *h) {
   dfree(h->stat); dfree(h->meta); dfree(h->path); dfree(h->path_act); dfree(h->lut);
-  dfree(h->step_seeds); dfree(h->raw);
+  dfree(h->step_seeds); dfree(h->raw); dfree(h->s_act);
   h->stat = nullptr; h->meta = nullptr; h->path = nullptr; h->path_act = nullptr; h->lut = nullptr;
-  h->step_seeds = nullptr; h->raw = nullptr;
+  h->step_seeds = nullptr; h->raw = nullptr; h->s_act = nullptr;
   h->step_seeds_n = 0;
 }
 
@@ -763,6 +819,11 @@ int ensure_coef(lzm_handle *h, int positions);
 int ensure_flags(lzm_handle *h, int sims, int G);
 }  // namespace
 
+// elements (4 bytes each) of a sampled handle's action table for `sims` simulations
+static size_t sampled_table_elems(const lzm_handle *h, int sims) {
+  return (size_t)(sims + 1) * h->A * h->B * (h->s_dim > 0 ? h->s_dim : 1);
+}
+
 static int alloc_tree(lzm_handle *h, int sims) {
   h->sims_cap = sims;
   h->cap = 1 + h->A * (sims + 1);
@@ -786,7 +847,12 @@ static int alloc_tree(lzm_handle *h, int sims) {
   // point at the old buffer together with the tree's
   LZM_HIP(hipMalloc(&h->step_seeds, sizeof(int32_t) * (size_t)(sims + 1)));
   h->step_seeds_n = sims + 1;
-  if (!(h->flags & (LZM_RNG_FAST | LZM_TREE_GUMBEL | LZM_TREE_STOCHASTIC))) {
+  if (h->flags & LZM_TREE_SAMPLED) {
+    const size_t bytes = sampled_table_elems(h, sims) * 4;
+    LZM_HIP(hipMalloc(&h->s_act, bytes));
+    LZM_HIP(hipMemset(h->s_act, 0, bytes));
+  }
+  if (!(h->flags & (LZM_RNG_FAST | LZM_TREE_GUMBEL | LZM_TREE_STOCHASTIC | LZM_TREE_SAMPLED))) {
     // parity-mode draw tables and look-back words, allocated here rather than at first use so
     // that a search captured into a HIP graph never allocates
     int rc = ensure_coef(h, h->B * h->depth_cap + 64);
@@ -807,11 +873,16 @@ static int refuse(int code, const char *name, const char *what) {
 
 // the handle is there and of the kind `name` serves (kind 0: the MuZero / EfficientZero entry points, 1 = true: an
 // lzm_gumbel_* entry point, kStochasticKind: an lzm_stochastic_* entry point)
-constexpr int kStochasticKind = 2;
+constexpr int kStochasticKind = 2, kSampledKind = 3;  // (kSampledKind: an lzm_sampled_* entry point)
 static int check_kind(const char *name, const lzm_handle *h, int kind) {
   if (!h) return refuse(LZM_ERR_ARG, name, kind ? "null handle" : "null argument");
-  const int is = (h->flags & LZM_TREE_STOCHASTIC) ? kStochasticKind : (h->flags & LZM_TREE_GUMBEL) ? 1 : 0;
+  const int is = (h->flags & LZM_TREE_SAMPLED) ? kSampledKind
+                 : (h->flags & LZM_TREE_STOCHASTIC) ? kStochasticKind : (h->flags & LZM_TREE_GUMBEL) ? 1 : 0;
   if (is == kind) return LZM_OK;
+  if (is == kSampledKind)
+    return refuse(LZM_ERR_STATE, name, "a Sampled EfficientZero handle takes the lzm_sampled_* entry points");
+  if (kind == kSampledKind)
+    return refuse(LZM_ERR_STATE, name, "not a Sampled EfficientZero handle (create it with lzm_sampled_create)");
   if (is == kStochasticKind)
     return refuse(LZM_ERR_STATE, name, "a Stochastic MuZero handle takes the lzm_stochastic_* entry points");
   if (kind == kStochasticKind)
@@ -914,8 +985,11 @@ extern "C" {
 const char *lzm_last_error(void) { return g_err; }
 
 // lzm_create (chance 0) and lzm_stochastic_create (A: the action space; the handle's block width is max(A, chance))
-static int create_handle(int B, int A, int chance, int max_sims, int flags, lzm_handle **out) {
+static int create_handle(int B, int A, int chance, int max_sims, int flags, lzm_handle **out, int s_dim = 0,
+                         int s_space = 0) {
   lzm_handle *h = new lzm_handle();
+  h->s_dim = s_dim;
+  h->s_space = s_space;
   h->B = B;
   h->A = A > chance ? A : chance;
   h->act = chance ? A : 0;
@@ -961,6 +1035,10 @@ int lzm_create(int B, int A, int max_sims, int flags, lzm_handle **out) {
     set_err("lzm_create: a Stochastic MuZero handle needs its chance space (lzm_stochastic_create)");
     return LZM_ERR_ARG;
   }
+  if (flags & LZM_TREE_SAMPLED) {
+    set_err("lzm_create: a Sampled EfficientZero handle needs its action space (lzm_sampled_create)");
+    return LZM_ERR_ARG;
+  }
   return create_handle(B, A, 0, max_sims, flags, out);
 }
 
@@ -996,13 +1074,15 @@ int lzm_reserve(lzm_handle *h, int max_sims) {
   LZM_HIP(hipDeviceSynchronize());
   lzm_handle old = *h;
   h->stat = nullptr; h->meta = nullptr; h->path = nullptr; h->path_act = nullptr; h->lut = nullptr;
-  h->step_seeds = nullptr; h->raw = nullptr;
+  h->step_seeds = nullptr; h->raw = nullptr; h->s_act = nullptr;
   int rc = alloc_tree(h, max_sims);
   if (rc == LZM_OK) {
     const size_t nodes = (size_t)old.cap * old.B;
     LZM_HIP(hipMemcpy(h->stat, old.stat, nodes * sizeof(NodeStat), hipMemcpyDeviceToDevice));
     LZM_HIP(hipMemcpy(h->meta, old.meta, nodes * sizeof(NodeMeta), hipMemcpyDeviceToDevice));
     if (old.raw) LZM_HIP(hipMemcpy(h->raw, old.raw, nodes * sizeof(float), hipMemcpyDeviceToDevice));
+    if (old.s_act)  // (block-major: the old table is a prefix of the new one)
+      LZM_HIP(hipMemcpy(h->s_act, old.s_act, sampled_table_elems(&old, old.sims_cap) * 4, hipMemcpyDeviceToDevice));
     LZM_HIP(hipMemcpy(h->path, old.path, sizeof(int32_t) * (size_t)old.depth_cap * old.B, hipMemcpyDeviceToDevice));
     LZM_HIP(hipMemcpy(h->path_act, old.path_act, sizeof(int32_t) * (size_t)old.depth_cap * old.B, hipMemcpyDeviceToDevice));
     if (old.lut_base >= 0) rc = fill_lut(h, old.lut_base, old.lut_init);
@@ -1018,8 +1098,8 @@ int lzm_set_pb_c(lzm_handle *h, int pb_c_base, float pb_c_init) {
 
 int lzm_copy_tree(lzm_handle *dst, const lzm_handle *src, void *stream) {
   if (!dst || !src || dst->B != src->B || dst->A != src->A || dst->sims_cap < src->sims_cap ||
-      ((dst->flags ^ src->flags) & (LZM_TREE_GUMBEL | LZM_TREE_STOCHASTIC)) || dst->chance != src->chance ||
-      dst->act != src->act) {
+      ((dst->flags ^ src->flags) & (LZM_TREE_GUMBEL | LZM_TREE_STOCHASTIC | LZM_TREE_SAMPLED)) ||
+      dst->chance != src->chance || dst->act != src->act || dst->s_dim != src->s_dim || dst->s_space != src->s_space) {
     set_err("lzm_copy_tree: handles differ in shape or kind, or destination is smaller");
     return LZM_ERR_ARG;
   }
@@ -1035,6 +1115,10 @@ int lzm_copy_tree(lzm_handle *dst, const lzm_handle *src, void *stream) {
   LZM_HIP(hipMemcpyAsync(dst->pathlen, src->pathlen, sizeof(int32_t) * src->B, hipMemcpyDeviceToDevice, s));
   if (src->is_chance) {
     LZM_HIP(hipMemcpyAsync(dst->is_chance, src->is_chance, sizeof(int32_t) * src->B, hipMemcpyDeviceToDevice, s));
+    dst->walked = src->walked;
+  }
+  if (src->s_act) {
+    LZM_HIP(hipMemcpyAsync(dst->s_act, src->s_act, sampled_table_elems(src, src->sims_cap) * 4, hipMemcpyDeviceToDevice, s));
     dst->walked = src->walked;
   }
   return LZM_OK;
@@ -1620,6 +1704,190 @@ int lzm_stochastic_decode_backprop_traverse(lzm_handle *h, int cur, float discou
   return stochastic_decode_launch(name, h, cur, discount, minmax, chance_value, chance_policy, chance_latent,
                                   decision_reward, decision_value, decision_policy, decision_latent, support_len,
                                   categorical, to_play, pool_slot, row_elems, out_decoded, &q, (hipStream_t)stream);
+}
+
+// ---- Sampled EfficientZero tree (ctree_sampled_efficientzero/lib/cnode.cpp; lzm_sampled.h) ----------------
+}  // extern "C"
+
+static SampledView sampled_view(lzm_handle *h) {
+  return SampledView{h->A, h->s_dim, h->s_space, (float *)h->s_act, (int32_t *)h->s_act};
+}
+
+static int sampled_traverse_args(const char *name, lzm_handle *h, int pb_c_base, float pb_c_init, float discount,
+                                 const float *minmax, const uint32_t *seed, const int32_t *vtp_in, const WalkOut &out,
+                                 void *out_action, SampledTraverseArgs *q) {
+  if (!minmax || !seed || !vtp_in || !walk_out_complete(out) || !out_action)
+    return refuse(LZM_ERR_ARG, name, "null argument");
+  if (pb_c_base <= 0) return refuse(LZM_ERR_ARG, name, "pb_c_base must be positive");
+  const int rc = fill_lut(h, pb_c_base, pb_c_init);
+  if (rc != LZM_OK) return rc;
+  q->t = view(h);
+  q->sv = sampled_view(h);
+  q->minmax = (const float4 *)minmax;
+  q->seed = seed;
+  q->vtp_in = vtp_in;
+  q->out = out;
+  q->out_action = out_action;
+  q->disc = discount;
+  return LZM_OK;
+}
+
+// sampled_decode_kernel for one simulation; walk: the next simulation's traverse arguments, or null
+static int sampled_decode_launch(const char *name, lzm_handle *h, int cur, float discount, float *minmax,
+                                 const float *value_prefix_logits, const float *value_logits, int support_len,
+                                 int categorical, const float *policy, const int32_t *to_play, int lstm_horizon,
+                                 int32_t *out_is_reset, const float *next_latent, float *pool_slot, int64_t row_elems,
+                                 float *out_decoded, const uint32_t *seed, const SampledTraverseArgs *walk,
+                                 hipStream_t s) {
+  if (!seed) return refuse(LZM_ERR_ARG, name, "null argument");
+  DecodeArgs p;
+  const int32_t *nf;
+  const int rc = decode_args(name, h, cur, discount, minmax, value_prefix_logits, value_logits, support_len,
+                             categorical, policy, to_play, lstm_horizon, out_is_reset, next_latent, pool_slot,
+                             row_elems, out_decoded, nullptr, nullptr, s, &p, &nf);
+  if (rc != LZM_OK) return rc;
+  const SampledView sv = sampled_view(h);
+  const SampledTraverseArgs q = walk ? *walk : SampledTraverseArgs{};
+  const dim3 g = gumbel_grid(h), b(256);
+  if (h->s_dim > 0) {
+    if (walk) hipLaunchKernelGGL((sampled_decode_kernel<true, true>), g, b, 0, s, p, sv, seed, nf, q);
+    else hipLaunchKernelGGL((sampled_decode_kernel<true, false>), g, b, 0, s, p, sv, seed, nf, q);
+  } else {
+    if (walk) hipLaunchKernelGGL((sampled_decode_kernel<false, true>), g, b, 0, s, p, sv, seed, nf, q);
+    else hipLaunchKernelGGL((sampled_decode_kernel<false, false>), g, b, 0, s, p, sv, seed, nf, q);
+  }
+  LZM_CHECK_LAUNCH();
+  return LZM_OK;
+}
+
+extern "C" {
+
+int lzm_sampled_create(int B, int action_space_size, int num_of_sampled_actions, int continuous_action_space,
+                       int max_sims, int flags, lzm_handle **out) {
+  const char *name = "lzm_sampled_create";
+  const int K = num_of_sampled_actions;
+  if (!out || B <= 0 || max_sims < 0 || action_space_size < 1)
+    return refuse(LZM_ERR_ARG, name, "need num_roots > 0, action_space_size >= 1, max_sims >= 0");
+  if (K < 1 || K > kMaxActions) return refuse(LZM_ERR_ARG, name, "need 1 <= num_of_sampled_actions <= 64");
+  if (continuous_action_space && action_space_size > kSampledMaxDim)
+    return refuse(LZM_ERR_ARG, name, "a continuous action has at most 32 dimensions");
+  if (!continuous_action_space && action_space_size > kMaxActions)
+    return refuse(LZM_ERR_ARG, name, "a discrete action space has at most 64 actions");
+  if (!continuous_action_space && K > action_space_size)
+    return refuse(LZM_ERR_ARG, name, "cannot sample more actions than the discrete action space holds");
+  if (flags & (LZM_TREE_EZ | LZM_TREE_GUMBEL | LZM_TREE_STOCHASTIC))
+    return refuse(LZM_ERR_ARG, name, "LZM_TREE_SAMPLED excludes LZM_TREE_EZ, LZM_TREE_GUMBEL and LZM_TREE_STOCHASTIC");
+  return create_handle(B, K, 0, max_sims, flags | LZM_TREE_SAMPLED, out, continuous_action_space ? action_space_size : 0,
+                       continuous_action_space ? 0 : action_space_size);
+}
+
+int lzm_sampled_action_dim(const lzm_handle *h) { return h ? h->s_dim : 0; }
+int lzm_sampled_action_space(const lzm_handle *h) { return h ? h->s_space : 0; }
+
+int lzm_sampled_prepare(lzm_handle *h, const float *noises, float root_noise_weight, const float *value_prefixs,
+                        const float *policy, const int32_t *to_play, const uint32_t *seed, void *stream) {
+  const char *name = "lzm_sampled_prepare";
+  const int rc = check_kind(name, h, kSampledKind);
+  if (rc != LZM_OK) return rc;
+  if (!value_prefixs || !policy || !to_play || !seed) return refuse(LZM_ERR_ARG, name, "null argument");
+  (void)noises; (void)root_noise_weight;  // never read by selection (cnode.cpp:454-481, :1076-1079)
+  SampledPrepareArgs p;
+  p.t = view(h);
+  p.sv = sampled_view(h);
+  p.legal = h->legal; p.nlegal = h->nlegal;
+  p.value_prefixs = value_prefixs; p.policy = policy; p.to_play = to_play; p.seed = seed;
+  if (h->s_dim > 0) hipLaunchKernelGGL(sampled_prepare_kernel<true>, gumbel_grid(h), dim3(256), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(sampled_prepare_kernel<false>, gumbel_grid(h), dim3(256), 0, (hipStream_t)stream, p);
+  LZM_CHECK_LAUNCH();
+  h->walked = false;
+  return LZM_OK;
+}
+
+int lzm_sampled_traverse(lzm_handle *h, int pb_c_base, float pb_c_init, float discount, float *minmax,
+                         const uint32_t *seed, const int32_t *vtp_in, int32_t *out_x, int32_t *out_y,
+                         int32_t *out_slot, void *out_action, int32_t *out_vtp, int32_t *out_len, void *stream) {
+  const char *name = "lzm_sampled_traverse";
+  int rc = check_kind(name, h, kSampledKind);
+  if (rc != LZM_OK) return rc;
+  SampledTraverseArgs q;
+  rc = sampled_traverse_args(name, h, pb_c_base, pb_c_init, discount, minmax, seed, vtp_in,
+                             walk_out(out_x, out_y, out_slot, nullptr, out_vtp, out_len), out_action, &q);
+  if (rc != LZM_OK) return rc;
+  if (h->s_dim > 0) hipLaunchKernelGGL(sampled_traverse_kernel<true>, gumbel_grid(h), dim3(256), 0, (hipStream_t)stream, q);
+  else hipLaunchKernelGGL(sampled_traverse_kernel<false>, gumbel_grid(h), dim3(256), 0, (hipStream_t)stream, q);
+  LZM_CHECK_LAUNCH();
+  h->walked = true;
+  return LZM_OK;
+}
+
+int lzm_sampled_backprop(lzm_handle *h, int cur, float discount, float *minmax, const float *value_prefixs,
+                         const float *values, const float *policy, const int32_t *to_play, const int32_t *is_reset,
+                         const uint32_t *seed, void *stream) {
+  const char *name = "lzm_sampled_backprop";
+  int rc = check_kind(name, h, kSampledKind);
+  if (rc != LZM_OK) return rc;
+  if (!minmax || !value_prefixs || !values || !policy || !to_play || !is_reset || !seed)
+    return refuse(LZM_ERR_ARG, name, "null argument");
+  if (!h->walked) return refuse(LZM_ERR_STATE, name, "no sampled traverse has run on this handle");
+  rc = check_cur(h, cur);
+  if (rc != LZM_OK) return rc;
+  SampledBackpropArgs p;
+  p.t = view(h);
+  p.sv = sampled_view(h);
+  p.minmax = (float4 *)minmax;
+  p.value_prefixs = value_prefixs; p.values = values; p.policy = policy; p.to_play = to_play; p.is_reset = is_reset;
+  p.seed = seed; p.cur = cur; p.disc = discount;
+  if (h->s_dim > 0) hipLaunchKernelGGL(sampled_backprop_kernel<true>, gumbel_grid(h), dim3(256), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(sampled_backprop_kernel<false>, gumbel_grid(h), dim3(256), 0, (hipStream_t)stream, p);
+  LZM_CHECK_LAUNCH();
+  return LZM_OK;
+}
+
+int lzm_sampled_decode_backprop(lzm_handle *h, int cur, float discount, float *minmax,
+                                const float *value_prefix_logits, const float *value_logits, int support_len,
+                                int categorical, const float *policy, const int32_t *to_play, int lstm_horizon,
+                                int32_t *out_is_reset, const float *next_latent, float *pool_slot, int64_t row_elems,
+                                float *out_decoded, const uint32_t *seed, void *stream) {
+  const char *name = "lzm_sampled_decode_backprop";
+  const int rc = check_kind(name, h, kSampledKind);
+  if (rc != LZM_OK) return rc;
+  if (!h->walked) return refuse(LZM_ERR_STATE, name, "no sampled traverse has run on this handle");
+  return sampled_decode_launch(name, h, cur, discount, minmax, value_prefix_logits, value_logits, support_len,
+                               categorical, policy, to_play, lstm_horizon, out_is_reset, next_latent, pool_slot,
+                               row_elems, out_decoded, seed, nullptr, (hipStream_t)stream);
+}
+
+int lzm_sampled_decode_backprop_traverse(lzm_handle *h, int cur, float discount, float *minmax,
+                                         const float *value_prefix_logits, const float *value_logits, int support_len,
+                                         int categorical, const float *policy, const int32_t *to_play,
+                                         int lstm_horizon, int32_t *out_is_reset, const float *next_latent,
+                                         float *pool_slot, int64_t row_elems, float *out_decoded, const uint32_t *seed,
+                                         int pb_c_base, float pb_c_init, const uint32_t *walk_seed,
+                                         const int32_t *vtp_in, int32_t *out_x, int32_t *out_y, int32_t *out_slot,
+                                         void *out_action, int32_t *out_vtp, int32_t *out_len, void *stream) {
+  const char *name = "lzm_sampled_decode_backprop_traverse";
+  int rc = check_kind(name, h, kSampledKind);
+  if (rc != LZM_OK) return rc;
+  // (the call-order refusal before the walk's arguments, whose pb_c table refill copies to the device)
+  if (!h->walked) return refuse(LZM_ERR_STATE, name, "no sampled traverse has run on this handle");
+  SampledTraverseArgs q;
+  rc = sampled_traverse_args(name, h, pb_c_base, pb_c_init, discount, minmax, walk_seed, vtp_in,
+                             walk_out(out_x, out_y, out_slot, nullptr, out_vtp, out_len), out_action, &q);
+  if (rc != LZM_OK) return rc;
+  return sampled_decode_launch(name, h, cur, discount, minmax, value_prefix_logits, value_logits, support_len,
+                               categorical, policy, to_play, lstm_horizon, out_is_reset, next_latent, pool_slot,
+                               row_elems, out_decoded, seed, &q, (hipStream_t)stream);
+}
+
+int lzm_sampled_get_sampled_actions(lzm_handle *h, void *out, void *stream) {
+  const char *name = "lzm_sampled_get_sampled_actions";
+  const int rc = check_kind(name, h, kSampledKind);
+  if (rc != LZM_OK) return rc;
+  if (!out) return refuse(LZM_ERR_ARG, name, "null argument");
+  hipLaunchKernelGGL(sampled_root_actions_kernel, gumbel_grid(h), dim3(256), 0, (hipStream_t)stream, view(h),
+                     sampled_view(h), out);
+  LZM_CHECK_LAUNCH();
+  return LZM_OK;
 }
 
 int lzm_debug_logf(const float *x, float *out, int64_t n, void *stream) {
@@ -2271,6 +2539,8 @@ int search_mlp(const char *name, MlpFamily fam, lzm_handle *h, int H, int Hl, in
     return refuse(LZM_ERR_STATE, name, "a Gumbel MuZero handle takes lzm_search_mlp_gumbel");
   } else if (h->flags & LZM_TREE_STOCHASTIC) {
     return refuse(LZM_ERR_STATE, name, "there is no one-launch search of a Stochastic MuZero handle");
+  } else if (h->flags & LZM_TREE_SAMPLED) {
+    return refuse(LZM_ERR_STATE, name, "there is no one-launch search of a Sampled EfficientZero handle");
   }
   if ((uintptr_t)weights & 15) {
     snprintf(g_err, sizeof(g_err), "%s: weights must be 16-byte aligned (%s output)", name,
@@ -4104,6 +4374,7 @@ static int search_conv_launch(lzm_handle *h, int num_simulations, int pb_c_base,
     return LZM_ERR_STATE;
   }
   if (h->flags & LZM_TREE_STOCHASTIC) return refuse(LZM_ERR_STATE, name, "there is no one-launch search of a Stochastic MuZero handle");
+  if (h->flags & LZM_TREE_SAMPLED) return refuse(LZM_ERR_STATE, name, "there is no one-launch search of a Sampled EfficientZero handle");
   uintptr_t bits = (uintptr_t)trunk_w | (uintptr_t)actmap | (uintptr_t)w1t | (uintptr_t)w2q | (uintptr_t)latent_pool;
   if (ez)
     bits |= (uintptr_t)ez->hpool | (uintptr_t)ez->cpool | (uintptr_t)ez->lstm_frag | (uintptr_t)ez->vp_s |

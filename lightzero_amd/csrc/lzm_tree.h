@@ -660,6 +660,9 @@ __device__ inline void backup_wave(const TreeView &t, int i, int li, int ps, flo
 // value_prefix feeds the min-max update, its is_reset form (the node's own value_prefix when the
 // parent is reset) feeds the bootstrap chain. The chain runs leaf to root by readlane in the
 // reference's order; the rest is per level; min-max by an order-free max / min (exact).
+// Contract: lane 0 of the first round holds the leaf (level len) and is the only lane that reads or writes the
+// leaf's record; callers that expand the leaf in the same wave just before (decode_root, lzm_sampled.h) store that
+// record from lane 0 and rely on this, with no fence in between. A change of the lane-to-level mapping must add one.
 __device__ inline void backup_wave_ez(const TreeView &t, int i, int li, int ps, float4 *mm_ptr, int to_play,
                                       float value, float disc) {
   const int lane = threadIdx.x & 63;

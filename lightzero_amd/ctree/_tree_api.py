@@ -516,3 +516,103 @@ def _stochastic_backprop(current_latent_state_index, discount_factor, value_pref
                           g(np.asarray(policies, np.float32).reshape(n, -1), np.float32),
                           g(np.asarray(to_play_batch, np.int32).reshape(t.B), np.int32),
                           g(np.asarray(leaf_idx_list, np.int32), np.int32) if leaf_idx_list else None)
+
+
+# ----------------------------------------------------------------------------- Sampled EfficientZero (ezs_tree.pyx)
+class _SampledRootsBase(_RootsBase):
+    """Roots of ezs_tree.pyx:37-86: every node has num_of_sampled_actions children, each a sampled action (a float
+    vector of action_space_size dimensions, or one discrete action). legal_actions_list is kept and, as in the
+    reference's expand (cnode.cpp:305), not consulted. The noises of prepare never reach selection."""
+
+    def __init__(self, root_num, legal_actions_list, action_space_size, num_of_sampled_actions,
+                 continuous_action_space):
+        _require_int("action_space_size", action_space_size)
+        _require_int("num_of_sampled_actions", num_of_sampled_actions)
+        self.fast_rng, self.root_num = True, int(root_num)
+        self._legal_list, self._mask = [list(l) for l in legal_actions_list], None
+        self.action_space_size, self.num_of_sampled_actions = int(action_space_size), int(num_of_sampled_actions)
+        self.continuous_action_space = bool(continuous_action_space)
+        self.tree, self._sims = None, _DEFAULT_SIMS
+
+    def _prepare(self, noise_weight, noises, rewards, logits, to_play, device=None, seed=None):
+        B = self.root_num
+        width = 2 * self.action_space_size if self.continuous_action_space else self.action_space_size
+        logits = np.asarray(logits, dtype=np.float32).reshape(B, width)
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if self.tree is None or self.tree.device != dev:
+            self.clear()
+            self.tree = POOL.acquire(B, self.action_space_size, self._sims, False, True, dev,
+                                     sampled=self.num_of_sampled_actions, continuous=self.continuous_action_space)
+        g = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+        self.tree.sampled_prepare(g(np.asarray(rewards, np.float32).reshape(B), np.float32), g(logits, np.float32),
+                                  g(np.asarray(to_play, np.int32).reshape(B), np.int32),
+                                  seed_tensor(next_seed() if seed is None else seed, dev))
+
+    def prepare(self, root_noise_weight, noises, value_prefix_pool, policy_logits_pool, to_play_batch, seed=None):
+        """seed (not in the reference): the Philox key of the roots' sampled actions instead of the host seed
+        source"""
+        _require_list("noises", noises)
+        self.prepare_no_noise(value_prefix_pool, policy_logits_pool, to_play_batch, seed)
+
+    def prepare_no_noise(self, value_prefix_pool, policy_logits_pool, to_play_batch, seed=None):
+        _require_list("value_prefix_pool", value_prefix_pool)
+        _require_list("policy_logits_pool", policy_logits_pool)
+        self._prepare(0.0, None, value_prefix_pool, policy_logits_pool, list(to_play_batch), seed=seed)
+
+    def prepare_device(self, *a, **k):
+        raise NotImplementedError("sampled Roots: prepare / prepare_no_noise")
+
+    device_legal = prepare_device
+
+    def get_sampled_actions(self):
+        """ezs_tree.pyx:71-72: per root the K sampled actions, each a list of floats (one float for a discrete action)"""
+        if self.tree is None:
+            return [[] for _ in range(self.root_num)]
+        a = self.tree.sampled_actions().cpu().numpy()
+        return a.reshape(self.root_num, self.num_of_sampled_actions, -1).astype(np.float32).tolist()
+
+
+def _sampled_traverse(roots, pb_c_base, pb_c_init, discount_factor, min_max_stats_lst, results, virtual_to_play_batch,
+                      continuous_action_space, seed=None):
+    """batch_traverse (ezs_tree.pyx:115-121); last_actions: per root the chosen slot's action as a list of floats"""
+    _require_type("roots", roots, _SampledRootsBase)
+    _require_int("pb_c_base", pb_c_base)
+    _require_type("min_max_stats_lst", min_max_stats_lst, MinMaxStatsList)
+    _require_type("results", results, ResultsWrapper)
+    _require_list("virtual_to_play_batch", virtual_to_play_batch)
+    t = roots.tree
+    if t is None:
+        raise RuntimeError("batch_traverse: roots not prepared")
+    if bool(continuous_action_space) != t.continuous:
+        raise ValueError("batch_traverse: continuous_action_space differs from the roots'")
+    vtp = torch.tensor(np.asarray(virtual_to_play_batch, np.int32)[:t.B], device=t.device)
+    results._seed = seed_tensor(next_seed() if seed is None else seed, t.device)
+    t.sampled_traverse(min_max_stats_lst._device(t.device), results._seed, vtp, int(pb_c_base), _f32(pb_c_init),
+                       _f32(discount_factor))
+    out = torch.stack([t.x, t.y, t.vtp, t.search_len, t.action]).cpu().numpy()
+    results._search_lens, results._slots, results._tree = out[3].tolist(), out[4].tolist(), t
+    acts = t.last_actions.cpu().numpy().reshape(t.B, -1).astype(np.float32).tolist()
+    return out[0].tolist(), out[1].tolist(), acts, out[2].tolist()
+
+
+def _sampled_backprop(current_latent_state_index, discount_factor, value_prefixs, values, policies, min_max_stats_lst,
+                      results, is_reset_list, to_play_batch):
+    """batch_backpropagate (ezs_tree.pyx:103-113); the leaves' actions are sampled under the traverse's seed"""
+    _require_int("current_latent_state_index", current_latent_state_index)
+    for n, v in (("value_prefixs", value_prefixs), ("values", values), ("policies", policies),
+                 ("is_reset_list", is_reset_list), ("to_play_batch", to_play_batch)):
+        _require_list(n, v)
+    _require_type("min_max_stats_lst", min_max_stats_lst, MinMaxStatsList)
+    _require_type("results", results, ResultsWrapper)
+    t = getattr(results, "_tree", None)
+    if t is None:
+        raise RuntimeError("batch_backpropagate: results do not come from batch_traverse")
+    cur, B = int(current_latent_state_index), t.B
+    if cur > t.sims_capacity:
+        t.reserve(max(cur, 2 * t.sims_capacity))
+    g = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(t.device)
+    t.sampled_backprop(cur, _f32(discount_factor), min_max_stats_lst._device(t.device),
+                       g(np.asarray(value_prefixs).reshape(B), np.float32), g(np.asarray(values).reshape(B), np.float32),
+                       g(np.asarray(policies, np.float32).reshape(B, -1), np.float32),
+                       g(np.asarray(to_play_batch, np.int32).reshape(B), np.int32),
+                       g(np.asarray(is_reset_list, np.int32).reshape(B), np.int32), results._seed)

@@ -1,5 +1,5 @@
 """Drop-in ``MuZeroMCTSCtree`` / ``EfficientZeroMCTSCtree`` / ``GumbelMuZeroMCTSCtree`` / ``StochasticMuZeroMCTSCtree``
-with the search loop on the GPU.
+/ ``SampledEfficientZeroMCTSCtree`` with the search loop on the GPU.
 
 Same class surface as /root/reference/lzero/mcts/tree_search/mcts_ctree.py:172-420 (MuZero) and
 :623-827 (EfficientZero): class attribute ``config``, ``default_config()``, ``__init__(cfg)``,
@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ctree import ez_tree, gmz_tree, mz_tree, stochastic_mz_tree
+from .ctree import ez_tree, ezs_tree, gmz_tree, mz_tree, stochastic_mz_tree
 from .conv_infer import FoldedCache
 from .fused import NotPackable, PackedCache, pack_efficientzero_mlp
 from .scaling_transform import InverseScalarTransform
@@ -437,14 +437,18 @@ class _MCTSCtree(object):
     def _after_step(self, t, out, c, k, native, rec):
         pass  # (EfficientZero: the is_reset record and the reset mask on the LSTM state)
 
+    def _net(self, model):
+        """the network a captured loop runs and keeps alive"""
+        return _step_net(self, model)
+
     def _capture(self, c, model):
         """Captures the whole S-simulation loop as one HIP graph over c.buf (the static buffers filled just
         before) and the network _step_net picks now; the entry keeps both alive."""
         t = c.t
-        net = _step_net(self, model)
+        net = self._net(model)
         # warm up every kernel and library handle on a scratch tree (must not touch `t`)
         scratch = DeviceTree(t.B, t.act, max(c.S, t.sims_capacity), ez=t.ez, fast_rng=t.fast_rng, device=t.device,
-                             gumbel=t.gumbel, chance=t.chance)
+                             gumbel=t.gumbel, chance=t.chance, sampled=t.sampled, continuous=t.continuous)
         scratch.copy_roots_from(t)
         scratch.set_pb_c(*self._pb_c())
         self._loop(scratch, model, c, net=net)
@@ -605,7 +609,28 @@ class MuZeroMCTSCtree(_MCTSCtree):
                                        reuse_value_list, seeds)
 
 
-class EfficientZeroMCTSCtree(_MCTSCtree):
+class _ValuePrefixLSTM:
+    """What the value-prefix searches (EfficientZero, Sampled EfficientZero) share on the per-simulation path: the
+    reward LSTM's (c, h) state ring in c.buf.extra and the reset rule of lstm_horizon_len."""
+
+    def _horizon(self):
+        horizon = int(self._cfg.lstm_horizon_len)
+        if horizon <= 0:
+            raise ValueError("lstm_horizon_len must be > 0 (mcts_ctree.py:809, 899)")
+        return horizon
+
+    def _after_step(self, t, out, c, k, native, rec):
+        if rec is not None:
+            rec.is_reset[k].copy_(t.is_reset)
+        if native:
+            return  # lzm_ez_lstm_cell already filed the masked state
+        # reset the LSTM state of roots whose search_len % horizon == 0 (mcts_ctree.py:810-816)
+        keep = (1 - t.is_reset).to(torch.float32).unsqueeze(1)
+        for pool, s in zip(c.buf.extra, out.reward_hidden_state):
+            torch.mul(s.reshape(t.B, -1).float(), keep, out=pool[k + 1])
+
+
+class EfficientZeroMCTSCtree(_ValuePrefixLSTM, _MCTSCtree):
     """MCTS for EfficientZero on the GPU (reference: mcts_ctree.py:623-827)."""
 
     _tree = ez_tree
@@ -636,12 +661,6 @@ class EfficientZeroMCTSCtree(_MCTSCtree):
         if t.search_mlp_ez_plan(dims, t.sims_capacity if S is None else S)["kernel"] is None:
             return None
         return packed, dims
-
-    def _horizon(self):
-        horizon = int(self._cfg.lstm_horizon_len)
-        if horizon <= 0:
-            raise ValueError("lstm_horizon_len must be > 0 (mcts_ctree.py:809, 899)")
-        return horizon
 
     def _fused_conv(self, model, t, shape, Hl, S=None):
         """The native split-precision FoldedConvNet (with the fused LSTM step packed) when the whole search of
@@ -677,16 +696,6 @@ class EfficientZeroMCTSCtree(_MCTSCtree):
         hidden = (buf.extra_in[0].unsqueeze(0), buf.extra_in[1].unsqueeze(0))
         t.gather(buf.pool, c.row, buf.net_in)
         return net.recurrent_inference(buf.net_in, hidden, t.action64)
-
-    def _after_step(self, t, out, c, k, native, rec):
-        if rec is not None:
-            rec.is_reset[k].copy_(t.is_reset)
-        if native:
-            return  # lzm_ez_lstm_cell already filed the masked state
-        # reset the LSTM state of roots whose search_len % horizon == 0 (mcts_ctree.py:810-816)
-        keep = (1 - t.is_reset).to(torch.float32).unsqueeze(1)
-        for pool, s in zip(c.buf.extra, out.reward_hidden_state):
-            torch.mul(s.reshape(t.B, -1).float(), keep, out=pool[k + 1])
 
     def search(self, roots: Any, model: torch.nn.Module, latent_state_roots: List[Any],
                reward_hidden_state_roots: List[Any], to_play_batch: Union[int, List[Any]],
@@ -1018,6 +1027,91 @@ class StochasticMuZeroMCTSCtree(_MCTSCtree):
             c = self._begin("search", roots, model, latent_state_roots)
             if not getattr(c.t, "chance", 0):
                 raise TypeError("StochasticMuZeroMCTSCtree.search: roots must come from StochasticMuZeroMCTSCtree.roots")
+            self._buffers(c, model, graph=not self.record and self._cfg.get('use_hip_graph', False))
+            self._stage(c, to_play_batch, seeds, None)
+            rec = self._recorder(c)
+            self._generic(c, model, rec)
+            self._finish(c, roots, None, rec)
+            self.last_path = "generic"
+
+
+class SampledEfficientZeroMCTSCtree(_ValuePrefixLSTM, _MCTSCtree):
+    """MCTS for Sampled EfficientZero on the GPU (reference: tree_search/mcts_ctree_sampled.py:13-233): every node
+    has K sampled actions, float vectors for a continuous action space (lzm_sampled.h). A simulation is: gather the
+    leaf latents and the reward LSTM state (EfficientZero's state ring and reset rule), run
+    ``model.recurrent_inference(latent, (c, h), last_actions)`` with last_actions float [B, D] (long [B] for a
+    discrete space) as the walk wrote them, then one launch that decodes value and value prefix, expands the leaf
+    (sampling its K actions), backs up and walks the next simulation. No host sync: eager, or one HIP graph with
+    cfg.use_hip_graph. Tie draws and sampled actions are per-root Philox streams keyed by the traverse seeds (`seeds`
+    as in MuZeroMCTSCtree.search; simulation k's seed keys its walk and its leaf's sampling): the reference seeds its
+    samplers from the wall clock, so there is no stream to be in parity with and no rng_mode."""
+
+    config = dict(
+        root_dirichlet_alpha=0.3,
+        root_noise_weight=0.25,
+        pb_c_base=19652,
+        pb_c_init=1.25,
+        value_delta_max=0.01,
+    )  # (the reference's keys)
+    _tree = ezs_tree
+    rng_mode = None
+
+    @classmethod
+    def roots(cls, root_num: int, legal_action_lis: List[Any], action_space_size: int,
+              num_of_sampled_actions: int, continuous_action_space: bool) -> "ezs_tree.Roots":
+        return ezs_tree.Roots(root_num, legal_action_lis, action_space_size, num_of_sampled_actions,
+                              continuous_action_space)
+
+    def _net(self, model):
+        return model  # (the user's model as it is: nothing is folded or packed)
+
+    def _recorder(self, c):
+        if not self.record:
+            return None
+        rec = _Recorder(c.S, c.B, 1, c.dev)
+        rec.is_reset = torch.zeros((c.S, c.B), dtype=torch.int32, device=c.dev)
+        la = c.t.last_actions
+        rec.last_actions = torch.zeros((c.S,) + tuple(la.shape), dtype=la.dtype, device=c.dev)
+        rec.seeds = c.buf.seeds.cpu().numpy().view(np.uint32)
+        return rec
+
+    def _loop(self, t, model, c, rec=None, infer=None, net=None):
+        """The S simulations (mcts_ctree_sampled.py:133-232) on tree t over c.buf, all enqueued on the current
+        stream: simulation k's backup and simulation k + 1's traverse share a launch."""
+        cfg, buf, S = self._cfg, c.buf, c.S
+        disc, cat, pb_c, horizon = self._discount(), self._categorical(), self._pb_c(), self._horizon()
+        new_minmax(t.B, cfg.value_delta_max, t.device, out=buf.mm)
+        f = lambda x: x.float().contiguous()
+        net = model if net is None else net
+        for k in range(S):
+            if k == 0:
+                t.sampled_traverse(buf.mm, buf.seeds[0:1], buf.vtp_in, *pb_c, disc)
+            if rec is not None:
+                for name in ("x", "action", "search_len", "vtp", "last_actions"):
+                    getattr(rec, name)[k].copy_(getattr(t, name))
+            t.gather(buf.extra[0], c.extra[0], buf.extra_in[0])
+            t.gather(buf.extra[1], c.extra[1], buf.extra_in[1])
+            t.gather(buf.pool, c.row, buf.net_in)
+            out = net.recurrent_inference(buf.net_in, (buf.extra_in[0].unsqueeze(0), buf.extra_in[1].unsqueeze(0)),
+                                          t.last_actions)
+            walk = (buf.seeds[k + 1:k + 2], buf.vtp_in, *pb_c) if k + 1 < S else None
+            t.sampled_decode_backprop(k + 1, disc, buf.mm, f(out.value_prefix), f(out.value), cat,
+                                      f(out.policy_logits), t.vtp, buf.seeds[k:k + 1], horizon,
+                                      next_latent=f(out.latent_state), pool_slot=buf.pool[k + 1], row_elems=c.row,
+                                      walk=walk, out_decoded=None if rec is None else rec.decoded[k])
+            self._after_step(t, out, c, k, False, rec)  # (the is_reset record, the reset mask on the LSTM state)
+
+    def search(self, roots: Any, model: torch.nn.Module, latent_state_roots: List[Any],
+               reward_hidden_state_roots: List[Any], to_play_batch: Union[int, List[Any]],
+               seeds: torch.Tensor = None) -> None:
+        """seeds (not in the reference): optional device int32 [num_simulations] seeds instead of the host seed
+        source, as in MuZeroMCTSCtree.search."""
+        with torch.no_grad():
+            self._horizon()
+            c = self._begin("search", roots, model, latent_state_roots, reward_hidden_state_roots[:2])
+            if not getattr(c.t, "sampled", 0):
+                raise TypeError("SampledEfficientZeroMCTSCtree.search: roots must come from "
+                                "SampledEfficientZeroMCTSCtree.roots")
             self._buffers(c, model, graph=not self.record and self._cfg.get('use_hip_graph', False))
             self._stage(c, to_play_batch, seeds, None)
             rec = self._recorder(c)

@@ -62,26 +62,36 @@ def _rec_ptrs(rec, names=("x", "action", "search_len", "decoded", "policy_logits
 
 class DeviceTree:
     def __init__(self, num_roots, action_space, max_sims=64, ez=False, fast_rng=False, device=None, gumbel=False,
-                 chance=0):
+                 chance=0, sampled=0, continuous=False):
         """gumbel: a Gumbel MuZero tree (LZM_TREE_GUMBEL; ctree_gumbel_muzero), driven by the gumbel_* methods;
         chance > 0: a Stochastic MuZero tree with that chance space (lzm_stochastic_create;
         ctree_stochastic_muzero), driven by the stochastic_* methods — its rows (self.A) are
-        max(action_space, chance) wide, self.act is the action space"""
+        max(action_space, chance) wide, self.act is the action space;
+        sampled = K > 0: a Sampled EfficientZero tree (lzm_sampled_create; ctree_sampled_efficientzero) with K
+        sampled actions per node, driven by the sampled_* methods — action_space is the number of action
+        dimensions (continuous) or the discrete action space, kept in self.act; its rows (self.A) are K wide"""
         _lib.require_gpu()
         if gumbel and ez:
             raise ValueError("DeviceTree: gumbel and ez are mutually exclusive")
         if chance and (gumbel or ez):
             raise ValueError("DeviceTree: a stochastic tree is neither gumbel nor ez")
+        if sampled and (gumbel or ez or chance):
+            raise ValueError("DeviceTree: a sampled tree is neither gumbel, ez (its value-prefix rule is built in) "
+                             "nor stochastic")
         self.uid = next(_uids)  # never reused (a handle address can be, after lzm_destroy)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.B, self.act, self.chance = int(num_roots), int(action_space), int(chance)
-        self.A = max(self.act, self.chance)
+        self.sampled, self.continuous = int(sampled), bool(continuous)
+        self.A = self.sampled or max(self.act, self.chance)
         self.ez, self.fast_rng, self.gumbel = bool(ez), bool(fast_rng), bool(gumbel)
         flags = ((_lib.LZM_TREE_EZ if ez else 0) | (_lib.LZM_RNG_FAST if fast_rng else 0)
                  | (_lib.LZM_TREE_GUMBEL if gumbel else 0))
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            if chance:
+            if sampled:
+                call("lzm_sampled_create", self.B, self.act, self.sampled, int(self.continuous), int(max_sims), flags,
+                     ctypes.byref(h))
+            elif chance:
                 call("lzm_stochastic_create", self.B, self.act, self.chance, int(max_sims), flags, ctypes.byref(h))
             else:
                 call("lzm_create", self.B, self.A, int(max_sims), flags, ctypes.byref(h))
@@ -100,6 +110,9 @@ class DeviceTree:
         self.is_reset = torch.zeros(B, **i32)
         self.is_chance = torch.zeros(B, **i32)  # (stochastic trees: the last walk's leaf kinds)
         self.seed_buf = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if sampled:  # the network's last_actions input, written by the walk: float [B, D] or long [B]
+            self.last_actions = (torch.zeros((B, self.act), dtype=torch.float32, device=self.device)
+                                 if continuous else self.action64)
         self._unchecked = False  # a search ran whose error words no getter has checked yet
 
     def searched(self):
@@ -302,6 +315,50 @@ class DeviceTree:
             seed, vtp_in, pb_c_base, pb_c_init = walk
             call("lzm_stochastic_decode_backprop_traverse", *args, int(pb_c_base), float(pb_c_init), ptr(seed),
                  ptr(vtp_in), *self._walk_out(), stream_ptr(stream))
+
+    # -- Sampled EfficientZero trees (lzm_sampled_*; LzmError on any other tree, nothing launched) ------
+    def _sampled_walk_out(self):
+        return [ptr(self.x), ptr(self.y), ptr(self.action), ptr(self.last_actions), ptr(self.vtp), ptr(self.search_len)]
+
+    def sampled_prepare(self, value_prefixs, policy, to_play, seed, noises=None, noise_weight=0.0, stream=None):
+        """seed: 1-element device tensor keying the roots' sampled actions; noises never reach selection"""
+        call("lzm_sampled_prepare", self.h, ptr(noises), float(noise_weight), ptr(value_prefixs), ptr(policy),
+             ptr(to_play), ptr(seed), stream_ptr(stream))
+
+    def sampled_traverse(self, minmax, seed, vtp_in, pb_c_base=19652, pb_c_init=1.25, discount=0.997, stream=None):
+        """fills x, y, action (the chosen slot), last_actions (the slot's action), vtp, search_len"""
+        call("lzm_sampled_traverse", self.h, int(pb_c_base), float(pb_c_init), float(discount), ptr(minmax), ptr(seed),
+             ptr(vtp_in), *self._sampled_walk_out(), stream_ptr(stream))
+
+    def sampled_backprop(self, cur, discount, minmax, value_prefixs, values, policy, to_play, is_reset, seed,
+                         stream=None):
+        call("lzm_sampled_backprop", self.h, int(cur), float(discount), ptr(minmax), ptr(value_prefixs), ptr(values),
+             ptr(policy), ptr(to_play), ptr(is_reset), ptr(seed), stream_ptr(stream))
+
+    def sampled_decode_backprop(self, cur, discount, minmax, value_prefix_logits, value_logits, categorical, policy,
+                                to_play, seed, lstm_horizon, next_latent=None, pool_slot=None, row_elems=0, walk=None,
+                                out_decoded=None, stream=None):
+        """One simulation's decode + expand (sampling under `seed`) + backup in one launch; is_reset into
+        self.is_reset. walk = (seed, vtp_in, pb_c_base, pb_c_init): the next simulation's traverse in the same
+        launch."""
+        V = value_prefix_logits.shape[-1] if categorical else 1
+        self._value_support(value_logits.shape[-1] if categorical else 1, V)
+        args = [self.h, int(cur), float(discount), ptr(minmax), ptr(value_prefix_logits), ptr(value_logits), int(V),
+                int(bool(categorical)), ptr(policy), ptr(to_play), int(lstm_horizon), ptr(self.is_reset),
+                ptr(next_latent), ptr(pool_slot), int(row_elems), ptr(out_decoded), ptr(seed)]
+        if walk is None:
+            call("lzm_sampled_decode_backprop", *args, stream_ptr(stream))
+        else:
+            wseed, vtp_in, pb_c_base, pb_c_init = walk
+            call("lzm_sampled_decode_backprop_traverse", *args, int(pb_c_base), float(pb_c_init), ptr(wseed),
+                 ptr(vtp_in), *self._sampled_walk_out(), stream_ptr(stream))
+
+    def sampled_actions(self, stream=None):
+        """Roots.get_sampled_actions: float32 [B, K, D] or int32 [B, K]"""
+        out = (torch.empty((self.B, self.A, self.act), dtype=torch.float32, device=self.device) if self.continuous
+               else torch.empty((self.B, self.A), dtype=torch.int32, device=self.device))
+        call("lzm_sampled_get_sampled_actions", self.h, ptr(out), stream_ptr(stream))
+        return out
 
     def children_values(self, discount, stream=None):
         """Roots.get_children_values: float32 [B, A], the completed Q in action order, -inf where illegal"""
@@ -581,9 +638,9 @@ class TreePool:
         self._free = {}
         self._lock = threading.Lock()
 
-    def acquire(self, B, A, max_sims, ez, fast_rng, device, gumbel=False, chance=0):
-        """A: the action space (a stochastic tree, chance > 0, keeps it in .act)"""
-        key = (B, A, ez, fast_rng, str(device), bool(gumbel), int(chance))
+    def acquire(self, B, A, max_sims, ez, fast_rng, device, gumbel=False, chance=0, sampled=0, continuous=False):
+        """A: the action space (a stochastic tree, chance > 0, or a sampled one, sampled > 0, keeps it in .act)"""
+        key = (B, A, ez, fast_rng, str(device), bool(gumbel), int(chance), int(sampled), bool(continuous))
         t = None
         with self._lock:
             lst = self._free.get(key) or []
@@ -594,7 +651,8 @@ class TreePool:
                 if c.h is not None and c.h.value:
                     t = c
         if t is None:
-            t = DeviceTree(B, A, max_sims, ez=ez, fast_rng=fast_rng, device=device, gumbel=gumbel, chance=chance)
+            t = DeviceTree(B, A, max_sims, ez=ez, fast_rng=fast_rng, device=device, gumbel=gumbel, chance=chance,
+                           sampled=sampled, continuous=continuous)
         else:
             t.reserve(max_sims)
             # the previous owner's sticky error words must not surface in this owner's searches
@@ -607,7 +665,7 @@ class TreePool:
     def release(self, t):
         if t is None or t.h is None:
             return
-        key = (t.B, t.act, t.ez, t.fast_rng, str(t.device), t.gumbel, t.chance)
+        key = (t.B, t.act, t.ez, t.fast_rng, str(t.device), t.gumbel, t.chance, t.sampled, t.continuous)
         with self._lock:
             self._free.setdefault(key, []).append(t)
 
