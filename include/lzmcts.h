@@ -933,6 +933,40 @@ int lzm_search_mlp_gumbel(lzm_handle *h, int hidden, int head_hidden, int suppor
  * need — the raw_value slice included — or a handle of another kind), 0, tree_in_lds}. Host only. */
 int lzm_search_mlp_gumbel_plan(const lzm_handle *h, int num_simulations, int hidden, int head_hidden, int support,
                                int res_dynamics, int32_t *out);
+/* ---- StochasticMuZeroMCTSCtree.search's whole loop over a StochasticMuZeroModelMLP in one launch
+ * (search_stoch_mlp_kernel, lzm_search_stoch_mlp.h). The packed network (lightzero_amd/fused.py pack_stochastic_mlp;
+ * per layer W[K][N] then bias[N], BatchNorm folded): dynamics_network's dynamics layers and reward head,
+ * prediction_network (policy [actions]), afterstate_prediction_network (policy [chance]) and, with shared_dynamics
+ * 0, afterstate_dynamics_network's dynamics layers (with shared_dynamics 1 both branches run dynamics_network's, as
+ * the reference does, and the layers are stored once). Both branches one-hot their option over the action space, so
+ * chance <= actions. lzm_mlp_stoch_packed_floats / _kernel_floats: the packed and the kernel-layout sizes (-1 for a
+ * non-positive width); lzm_mlp_stoch_prepare: packed -> kernel layout (lane order) on `stream`. */
+int64_t lzm_mlp_stoch_packed_floats(int hidden, int actions, int chance, int head_hidden, int support,
+                                    int res_dynamics, int shared_dynamics);
+int64_t lzm_mlp_stoch_kernel_floats(int hidden, int actions, int chance, int head_hidden, int support,
+                                    int res_dynamics, int shared_dynamics);
+int lzm_mlp_stoch_prepare(int hidden, int actions, int chance, int head_hidden, int support, int res_dynamics,
+                          int shared_dynamics, const float *packed, float *out, void *stream);
+/* 1 when the kernel takes the shape: lzm_search_mlp_supported's widths, chance <= actions <= 64 (one lane per child,
+ * an outcome must have a one-hot row), actions <= hidden. Host only. */
+int lzm_search_mlp_stoch_supported(int actions, int chance, int hidden, int head_hidden, int support);
+/* What lzm_search_mlp_stoch launches on this handle as it stands, by the function the launch itself decides with:
+ * out int32[4] = {roots per workgroup, kind: 0 weight-streaming or -1 (refused shape, LDS need, or a handle that is
+ * no Stochastic MuZero tree), 0, tree_in_lds}. Host only. */
+int lzm_search_mlp_stoch_plan(const lzm_handle *h, int num_simulations, int hidden, int head_hidden, int support,
+                              int res_dynamics, int32_t *out);
+/* The search: num_simulations x (walk, the network of each leaf's kind, decode, expand, backup) on a prepared
+ * Stochastic MuZero handle; seeds int32/uint32 [num_simulations] key the Philox draws exactly as
+ * lzm_stochastic_traverse's seed does, so the tree equals the per-simulation path's bit for bit given equal network
+ * outputs. latent_pool [num_simulations + 1][B][hidden], slot 0 = the roots' latents. Optional record (all seven or
+ * none): rec_x / rec_a / rec_len / rec_is_chance / rec_vtp int32 [S][B], rec_decoded [S][B][2] {reward, value} after
+ * h^-1 (reward 0 for a chance leaf), rec_logits [S][B][max(actions, chance)] (zeros past the kind's width).
+ * LZM_ERR_STATE on a handle of another kind, LZM_ERR_ARG for a refused shape or LDS need: nothing is launched. */
+int lzm_search_mlp_stoch(lzm_handle *h, int hidden, int head_hidden, int support, int res_dynamics,
+                         int shared_dynamics, const float *weights, int num_simulations, int pb_c_base,
+                         float pb_c_init, float discount, float *minmax, const uint32_t *seeds, const int32_t *vtp_in,
+                         float *latent_pool, int32_t *rec_x, int32_t *rec_a, int32_t *rec_len, int32_t *rec_is_chance,
+                         int32_t *rec_vtp, float *rec_decoded, float *rec_logits, void *stream);
 /* GumbelMuZeroMCTSCtree.search's whole loop over a conv MuZeroModel (64 x 8 x 8 latent) in one launch per root
  * slice: lzm_search_conv's kernel — trunk, head MLPs, support decode and ensure_softmax verdict unchanged — with the
  * Gumbel walk on the root's tree slice in LDS (its raw_value slice, the Gumbel table and the considered-visits row

@@ -131,6 +131,7 @@ __device__ inline bool cartpole_physics(double *s, int action) {
   return x < -x_threshold || x > x_threshold || theta < -theta_threshold || theta > theta_threshold;
 }
 
+#ifndef LZM_DEVICE_HELPERS_ONLY  // (a second translation unit takes the helpers, not this kernel)
 __global__ void cartpole_reset_kernel(int n, double *state, int32_t *steps, float *obs, uint32_t seed) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -140,6 +141,7 @@ __global__ void cartpole_reset_kernel(int n, double *state, int32_t *steps, floa
   steps[i] = 0;
   for (int j = 0; j < 4; ++j) obs[(size_t)i * 4 + j] = (float)s[j];
 }
+#endif
 
 // GUMBEL: the Gumbel MuZero step — the action is the search's (the first maximum of the improved policy: no purpose-2
 // draw, no temperature), and the improved policy and the mean completed Q are recorded too; all else is the same.

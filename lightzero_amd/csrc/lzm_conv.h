@@ -177,6 +177,7 @@ __device__ __forceinline__ void conv1_layer(const float *in, const float *__rest
   }
 }
 
+#ifndef LZM_DEVICE_HELPERS_ONLY  // (a second translation unit takes the helpers, not this kernel)
 __global__ __launch_bounds__(kCvThreads) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv_trunk_kernel(
     ConvTrunkArgs a) {
   extern __shared__ float cv_lds[];
@@ -233,6 +234,7 @@ __global__ __launch_bounds__(kCvThreads) __attribute__((amdgpu_waves_per_eu(1, 1
   if (ch == 0) conv1_layer(buf(xi), a.w + L.hw, a.w + L.hb, a.h_ch, a.out_h + (int64_t)b * a.h_ch * kCvPix, lane, ph,
                            abase);
 }
+#endif
 
 // ---------------------------------------------------------------------------------------------------
 // Split trunk (precision 1, the default): the same network on v_mfma_f32_16x16x32_f16.

@@ -47,6 +47,7 @@
 #include "lzm_stochastic.h"
 #include "lzm_sampled.h"
 #include "lzm_search_mlp.h"
+#include "lzm_search_stoch_mlp.h"
 #include "lzm_search_res.h"
 #include "lzm_conv.h"
 #include "lzm_repr.h"
@@ -2409,7 +2410,9 @@ int mlp_plan_query(const char *name, const lzm_handle *h, MlpFamily fam, int S, 
 // The network-resident layout (lzm_search_res.h) follows the kernel layout, for the MuZero shape it serves
 bool net_resident(const MlpNet &n) { return n.Hl == 0 && res_shape_ok(n.H, n.A, n.F, n.V, n.res); }
 // packed -> kernel layout: each kernel layer's weights in lane order (swz_source), then its bias
-int mlp_prepare(const MlpNet &net, const float *packed, float *out, hipStream_t stream) {
+// (Net: MlpNet or StochNet — the same fields)
+template <class Net>
+int swizzle_layers(const Net &net, const float *packed, float *out, hipStream_t stream) {
   for (int l = 0; l < net.nk; ++l) {
     const KLayer &q = net.kl[l];
     const size_t n = swz_floats(q.K, q.N);
@@ -2424,6 +2427,11 @@ int mlp_prepare(const MlpNet &net, const float *packed, float *out, hipStream_t 
       LZM_HIP(hipMemcpyAsync(out + net.b_off[l] + q.N0, packed + net.pb[q.src1], (size_t)(q.N - q.N0) * sizeof(float),
                              hipMemcpyDeviceToDevice, stream));
   }
+  return LZM_OK;
+}
+int mlp_prepare(const MlpNet &net, const float *packed, float *out, hipStream_t stream) {
+  const int rc = swizzle_layers(net, packed, out, stream);
+  if (rc != LZM_OK) return rc;
   if (net_resident(net)) {
     ResSrc src;  // res_source numbers the layers in MuZero's packed order: the gate layer's slot skipped
     for (int l = 0; l < 12; ++l) {
@@ -2595,6 +2603,164 @@ int search_mlp(const char *name, MlpFamily fam, lzm_handle *h, int H, int Hl, in
   return launch_stream(name, h, p, plan.R, plan.lds, minmax, stream);
 }
 
+// ---- the one-launch Stochastic MuZero search over StochasticMuZeroModelMLP (lzm_search_stoch_mlp.h)
+// The packed network (lightzero_amd/fused.py pack_stochastic_mlp), layers in packed order: dynamics_network's
+// dynamics layers (2, or 4 with res_connection_in_dynamics) and reward head (2), prediction_network (6: common,
+// value head, policy head [A]), afterstate_prediction_network (6, policy head [C]) and, unless the branches share
+// their dynamics (the reference: _afterstate_dynamics calls dynamics_network), afterstate_dynamics_network's dynamics
+// layers. Both branches one-hot their option over the action space. Kernel layers as MlpNet's: the head hiddens and
+// the head outputs of a prediction network merged; a shared dynamics layer is stored once.
+constexpr int kStochPacked = 22, kStochKernel = 18;
+struct StochNet {
+  int H, A, C, F, V, res, shared, nd;
+  LayerShape s[kStochPacked];
+  size_t pw[kStochPacked], pb[kStochPacked], packed_floats;
+  KLayer kl[kStochKernel];
+  int nk;
+  size_t w_off[kStochKernel], b_off[kStochKernel], kernel_floats;
+  int kdyn[2], krew, kpred[2];  // first kernel layer of branch b's dynamics, of the reward head, of b's prediction
+};
+StochNet stoch_net(int H, int A, int C, int F, int V, int res, int shared) {
+  StochNet n;
+  n.H = H; n.A = A; n.C = C; n.F = F; n.V = V; n.res = res ? 1 : 0; n.shared = shared ? 1 : 0;
+  n.nd = n.res ? 4 : 2;
+  int np = 0;
+  n.nk = 0;
+  auto single = [&](LayerShape l) {
+    n.kl[n.nk++] = KLayer{np, -1, l.K, l.N, l.N};
+    n.s[np++] = l;
+  };
+  auto dynamics = [&]() {
+    single({H + A, (H + A + kKC - 1) / kKC * kKC, H});  // [latent; one-hot option]
+    for (int l = 1; l < n.nd; ++l) single({H, H, H});
+  };
+  auto prediction = [&](int width) {
+    single({H, H, H});  // fc_prediction_common
+    single({H, H, H});
+    n.kl[n.nk++] = KLayer{np, np + 2, H, 2 * F, F};          // [fc_value_head[0] | fc_policy_head[0]]
+    n.kl[n.nk++] = KLayer{np + 1, np + 3, F, V + width, V};  // [fc_value_head[1] | fc_policy_head[1]]
+    n.s[np++] = {H, H, F};
+    n.s[np++] = {F, F, V};
+    n.s[np++] = {H, H, F};
+    n.s[np++] = {F, F, width};
+  };
+  n.kdyn[1] = n.nk; dynamics();
+  n.krew = n.nk; single({H, H, F}); single({F, F, V});
+  n.kpred[1] = n.nk; prediction(A);
+  n.kpred[0] = n.nk; prediction(C);
+  n.kdyn[0] = n.kdyn[1];
+  if (!n.shared) { n.kdyn[0] = n.nk; dynamics(); }
+  size_t off = 0;
+  for (int l = 0; l < np; ++l) {
+    n.pw[l] = off;
+    off += (size_t)n.s[l].krows * n.s[l].N;
+    n.pb[l] = off;
+    off += n.s[l].N;
+  }
+  n.packed_floats = off;
+  off = 0;
+  for (int l = 0; l < n.nk; ++l) {
+    n.w_off[l] = off;
+    off += swz_floats(n.kl[l].K, n.kl[l].N);
+    n.b_off[l] = off;
+    off = (off + n.kl[l].N + 3) & ~(size_t)3;
+  }
+  n.kernel_floats = off;
+  return n;
+}
+// the kernel's limits on top of the dense steps': one lane per action / outcome, and an outcome must have a one-hot
+// row (both branches encode their option over the action space)
+bool stoch_shape_ok(int H, int A, int C, int F, int V) {
+  return mlp_shape_ok(H, A, F, V) && C > 0 && C <= A && A <= kMaxActions;
+}
+bool stoch_args_ok(int H, int A, int C, int F, int V) { return H > 0 && A > 0 && C > 0 && F > 0 && V > 0; }
+
+// LDS plan of search_stoch_mlp_kernel with R roots per workgroup (float offsets, 16-B aligned); returns bytes.
+// x2 / hd: the activation buffers only the schedule names.
+size_t plan_stoch(StochSearchArgs &p, const lzm_handle *h, int R, int S, int H, int F, int V, int *tree_in_lds,
+                  size_t *x2, size_t *hd) {
+  size_t o = 0;
+  const size_t tree_floats = (size_t)h->cap * R * 4;
+  const int tl = (2 * tree_floats * sizeof(float) <= 96 * 1024) ? 1 : 0;
+  *tree_in_lds = tl;
+  p.off_stat = o; if (tl) o += tree_floats;
+  p.off_meta = o; if (tl) o += tree_floats;
+  p.off_lut = o; if (tl) o += round4((size_t)2 * h->lut_n);
+  p.off_legal = o; if (tl) o += round4((size_t)R * h->A + R);
+  p.off_path = o; o += round4((size_t)h->depth_cap * R);
+  p.off_pact = o; o += round4((size_t)h->depth_cap * R);
+  auto tfl = [R](int K) { return (size_t)((K + kKC - 1) / kKC) * (kKC * R + 4); };
+  p.off_x0 = o; o += round4(tfl((H + h->act + kKC - 1) / kKC * kKC));  // [latent; one-hot] rows, zero-padded
+  p.off_x1 = o; o += round4(tfl(H));  // also a pass's policy logits [r][width]
+  *x2 = o; o += round4(tfl(H));
+  p.off_n = o; o += round4(tfl(H));
+  *hd = o; o += round4(tfl(2 * F));
+  p.off_logit = o; if (V < kThreads) o += round4((size_t)(V + 1) * R);
+  p.off_keep = o; o += (size_t)R * kMaxActions;
+  p.off_seeds = o; o += round4((size_t)S);
+  return o * sizeof(float);
+}
+// What lzm_search_mlp_stoch launches for this handle, network shape and search length: the one decision behind the
+// launch and the plan query (MlpPlan's fields; kind 0 weight-streaming, -1 none)
+MlpPlan stoch_plan(const lzm_handle *h, int H, int F, int V, int S, StochSearchArgs &p, size_t *x2, size_t *hd) {
+  MlpPlan pl{roots_per_wg(h->B), -1, 0, 0, 0};
+  if (!(h->flags & LZM_TREE_STOCHASTIC) || !stoch_shape_ok(H, h->act, h->chance, F, V)) return pl;
+  pl.lds = plan_stoch(p, h, pl.R, S, H, F, V, &pl.tree_in_lds, x2, hd);
+  pl.kind = pl.lds <= kMaxLds ? 0 : -1;
+  return pl;
+}
+// Both branches' schedules (build_schedule's routing): dynamics on [latent; one-hot] (+ latent residual,
+// fc_dynamics_2), [branch 1: the reward head, decoded,] fc_prediction_common, the merged head hidden and output
+// (value decoded, policy logits [r][width] into x1); then the idle step. Every schedule has an even length.
+void build_stoch_schedules(StochSearchArgs &p, const StochNet &net, const float *weights, int R, size_t x2s, size_t hds) {
+  const int x0 = (int)p.off_x0, x1 = (int)p.off_x1, x2 = (int)x2s, nl = (int)p.off_n, hd = (int)hds,
+            lg = (int)p.off_logit, V = net.V, F = net.F;
+  for (int b = 0; b < 2; ++b) {
+    int n = 0;
+    auto add = [&](int l, int in, int out, int relu, int resid, int rowmajor, int ldout, int dec) -> StepRec & {
+      const KLayer &k = net.kl[l];
+      StepRec &q = p.sched[b * kStochSteps + n++];
+      q.w = weights + net.w_off[l];
+      q.b = weights + net.b_off[l];
+      q.K = k.K; q.N = k.N;
+      q.wbytes = (int)(swz_floats(k.K, k.N) * sizeof(float));
+      q.in = in; q.out = out; q.relu = relu; q.resid = resid; q.rowmajor = rowmajor; q.ldout = ldout; q.decode = dec;
+      q.ncol1 = k.N;
+      q.in2 = in; q.out2 = out; q.rowmajor2 = rowmajor; q.ldout2 = ldout;
+      const Split sp = layer_split(k.K, k.N);
+      q.Np = sp.Np; q.splits = sp.splits; q.cpl = sp.cpl; q.log2s = sp.log2s;
+      return q;
+    };
+    const int d = net.kdyn[b], pr = net.kpred[b];
+    add(d, x0, x1, 1, -1, 0, 0, 0);
+    add(d + 1, x1, nl, 1, net.res ? x0 : -1, 0, 0, 0);
+    int enc = nl;
+    if (net.res) {
+      enc = x2;
+      add(d + 2, nl, x1, 1, -1, 0, 0, 0);
+      add(d + 3, x1, enc, 1, -1, 0, 0, 0);
+    }
+    if (b == 1) {
+      add(net.krew, enc, hd, 1, -1, 0, 0, 0);
+      add(net.krew + 1, hd, lg, 0, -1, 1, V + 1, 1);
+    }
+    add(pr, nl, x1, 1, -1, 0, 0, 0);
+    add(pr + 1, x1, x2, 1, -1, 0, 0, 0);
+    add(pr + 2, x2, hd, 1, -1, 0, 0, 0);
+    StepRec &o = add(pr + 3, hd, lg, 0, -1, 1, V + 1, 2);
+    o.ncol1 = V;
+    o.in2 = hd + F / kKC * (kKC * R + 4);
+    o.out2 = x1; o.rowmajor2 = 1; o.ldout2 = b == 0 ? net.C : net.A;
+    p.nsteps[b] = n;
+  }
+  StepRec &idle = p.sched[kStochIdle];  // no columns, no weights: every load out of range
+  memset(&idle, 0, sizeof(idle));
+  idle.w = weights; idle.b = weights;
+  idle.resid = -1;
+  const Split sp = layer_split(0, 0);
+  idle.Np = sp.Np; idle.splits = sp.splits; idle.cpl = sp.cpl; idle.log2s = sp.log2s;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2709,6 +2875,90 @@ int lzm_search_mlp_gumbel(lzm_handle *h, int hidden, int head_hidden, int suppor
                     num_simulations, 0, max_num_considered_actions, 19652, 1.25f, discount, minmax, nullptr, vtp_in,
                     latent_pool, nullptr, nullptr, rec_x, rec_a, rec_len, nullptr, rec_decoded, rec_logits,
                     (hipStream_t)stream);
+}
+
+// The StochasticMuZeroModelMLP twins (see include/lzmcts.h)
+int64_t lzm_mlp_stoch_packed_floats(int hidden, int actions, int chance, int head_hidden, int support, int res_dynamics,
+                                    int shared_dynamics) {
+  if (!stoch_args_ok(hidden, actions, chance, head_hidden, support)) return -1;
+  return (int64_t)stoch_net(hidden, actions, chance, head_hidden, support, res_dynamics, shared_dynamics).packed_floats;
+}
+
+int64_t lzm_mlp_stoch_kernel_floats(int hidden, int actions, int chance, int head_hidden, int support, int res_dynamics,
+                                    int shared_dynamics) {
+  if (!stoch_args_ok(hidden, actions, chance, head_hidden, support)) return -1;
+  return (int64_t)stoch_net(hidden, actions, chance, head_hidden, support, res_dynamics, shared_dynamics).kernel_floats;
+}
+
+int lzm_mlp_stoch_prepare(int hidden, int actions, int chance, int head_hidden, int support, int res_dynamics,
+                          int shared_dynamics, const float *packed, float *out, void *stream) {
+  if (!packed || !out || !stoch_args_ok(hidden, actions, chance, head_hidden, support) || hidden % kKC != 0 ||
+      head_hidden % kKC != 0) {
+    set_err("lzm_mlp_stoch_prepare: bad arguments (hidden and head widths must be multiples of 16)");
+    return LZM_ERR_ARG;
+  }
+  return swizzle_layers(stoch_net(hidden, actions, chance, head_hidden, support, res_dynamics, shared_dynamics), packed,
+                        out, (hipStream_t)stream);
+}
+
+int lzm_search_mlp_stoch_supported(int actions, int chance, int hidden, int head_hidden, int support) {
+  return stoch_shape_ok(hidden, actions, chance, head_hidden, support) ? 1 : 0;
+}
+
+int lzm_search_mlp_stoch_plan(const lzm_handle *h, int num_simulations, int hidden, int head_hidden, int support,
+                              int res_dynamics, int32_t *out) {
+  const char *name = "lzm_search_mlp_stoch_plan";
+  (void)res_dynamics;  // (the LDS plan does not depend on it; kept for the plan queries' common shape)
+  if (!h || !out || num_simulations <= 0) return refuse(LZM_ERR_ARG, name, "null argument or no simulations");
+  if (num_simulations > h->sims_cap) return refuse(LZM_ERR_CAPACITY, name, "more simulations than reserved (lzm_reserve)");
+  StochSearchArgs p;
+  memset(&p, 0, sizeof(p));
+  size_t x2, hd;
+  const MlpPlan pl = stoch_plan(h, hidden, head_hidden, support, num_simulations, p, &x2, &hd);
+  out[0] = pl.R; out[1] = pl.kind; out[2] = 0; out[3] = pl.tree_in_lds;
+  return LZM_OK;
+}
+
+int lzm_search_mlp_stoch(lzm_handle *h, int hidden, int head_hidden, int support, int res_dynamics, int shared_dynamics,
+                         const float *weights, int num_simulations, int pb_c_base, float pb_c_init, float discount,
+                         float *minmax, const uint32_t *seeds, const int32_t *vtp_in, float *latent_pool,
+                         int32_t *rec_x, int32_t *rec_a, int32_t *rec_len, int32_t *rec_is_chance, int32_t *rec_vtp,
+                         float *rec_decoded, float *rec_logits, void *stream) {
+  const char *name = "lzm_search_mlp_stoch";
+  const int S = num_simulations;
+  if (!h || !weights || !minmax || !seeds || !vtp_in || !latent_pool || S <= 0)
+    return refuse(LZM_ERR_ARG, name, "null argument or no simulations");
+  int rc = check_kind(name, h, kStochasticKind);
+  if (rc != LZM_OK) return rc;
+  if ((uintptr_t)weights & 15) return refuse(LZM_ERR_ARG, name, "weights must be 16-byte aligned (lzm_mlp_stoch_prepare output)");
+  if (pb_c_base <= 0) return refuse(LZM_ERR_ARG, name, "pb_c_base must be positive");
+  if (rec_x && !(rec_a && rec_len && rec_is_chance && rec_vtp && rec_decoded && rec_logits))
+    return refuse(LZM_ERR_ARG, name, "a record needs all seven record buffers");
+  if (!stoch_shape_ok(hidden, h->act, h->chance, head_hidden, support))
+    return refuse(LZM_ERR_ARG, name, "unsupported network shape (lzm_search_mlp_stoch_supported)");
+  if (S > h->sims_cap) return refuse(LZM_ERR_CAPACITY, name, "more simulations than reserved (lzm_reserve)");
+  StochSearchArgs p;
+  memset(&p, 0, sizeof(p));
+  size_t x2, hd;
+  const MlpPlan plan = stoch_plan(h, hidden, head_hidden, support, S, p, &x2, &hd);
+  if (plan.kind < 0) {
+    snprintf(g_err, sizeof(g_err), "%s: %zu B of LDS needed (network or tree too large)", name, plan.lds);
+    return LZM_ERR_ARG;
+  }
+  if ((rc = fill_lut(h, pb_c_base, pb_c_init)) != LZM_OK) return rc;
+  const StochNet net = stoch_net(hidden, h->act, h->chance, head_hidden, support, res_dynamics, shared_dynamics);
+  p.stat = h->stat; p.meta = h->meta; p.legal = h->legal; p.nlegal = h->nlegal;
+  p.path = h->path; p.path_act = h->path_act; p.pathlen = h->pathlen; p.is_chance = h->is_chance; p.lut = h->lut;
+  p.B = h->B; p.W = h->A; p.A = h->act; p.C = h->chance; p.cap = h->cap; p.lut_n = h->lut_n;
+  p.depth_cap = h->depth_cap;
+  p.S = S; p.disc = discount; p.seeds = seeds; p.vtp_in = vtp_in; p.minmax = (float4 *)minmax; p.pool = latent_pool;
+  p.H = hidden; p.V = support;
+  p.rec_x = rec_x; p.rec_a = rec_a; p.rec_len = rec_len; p.rec_chance = rec_is_chance; p.rec_vtp = rec_vtp;
+  p.rec_dec = rec_decoded; p.rec_logits = rec_logits;
+  build_stoch_schedules(p, net, weights, plan.R, x2, hd);
+  LZM_HIP(stoch_mlp_launch(p, plan.R, plan.tree_in_lds != 0, plan.lds, (hipStream_t)stream));
+  h->walked = true;
+  return LZM_OK;
 }
 
 // Collect-step mode of lzm_search_mlp (sticky on the handle, host state only: a captured launch

@@ -25,6 +25,7 @@
 
 namespace lzm {
 
+#ifndef LZM_DEVICE_HELPERS_ONLY  // (a second translation unit takes the helpers, not this kernel)
 __global__ __launch_bounds__(256) void ez_lstm_input_kernel(int B, int Kr, int H, const float *r, const float *hpool,
                                                             const int32_t *x, float *xin) {
   const int K4 = (Kr + H) >> 2, Kr4 = Kr >> 2, H4 = H >> 2;
@@ -39,9 +40,11 @@ __global__ __launch_bounds__(256) void ez_lstm_input_kernel(int B, int Kr, int H
     reinterpret_cast<float4 *>(xin)[q] = v;
   }
 }
+#endif
 
 __device__ inline float lstm_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 
+#ifndef LZM_DEVICE_HELPERS_ONLY  // (a second translation unit takes the helpers, not this kernel)
 __global__ __launch_bounds__(256) void ez_lstm_cell_kernel(int B, int H, const float *gates, const float *cpool,
                                                            const int32_t *x, const int32_t *search_len, int horizon,
                                                            float *h1, float *c1, float *hslot, float *cslot) {
@@ -69,6 +72,7 @@ __global__ __launch_bounds__(256) void ez_lstm_cell_kernel(int B, int H, const f
     reinterpret_cast<float4 *>(cslot)[q] = reset ? z : c;
   }
 }
+#endif
 
 // ---- the gate GEMM and the cell in one launch, on split-fp16 MFMA (lzm_conv.h's split scheme)
 //
@@ -183,6 +187,7 @@ __device__ __forceinline__ void ls_split_row(const float (&v)[N], float sc, uint
   }
 }
 
+#ifndef LZM_DEVICE_HELPERS_ONLY  // (a second translation unit takes the helpers, not this kernel)
 __global__ __launch_bounds__(kLsThreads) void ez_lstm_gemm_cell_kernel(LstmArgs p) {
   extern __shared__ uint4 ls_lds4[];
   uint16_t *lds = reinterpret_cast<uint16_t *>(ls_lds4);
@@ -395,6 +400,7 @@ __global__ __launch_bounds__(kLsThreads) void ez_lstm_gemm_cell_kernel(LstmArgs 
   }
   stamp(4);
 }
+#endif
 
 // ---- one gate-GEMM + cell tile inside a persistent launch (the EfficientZero one-launch search,
 // lzm_search_conv.h): 256 threads, same tile (64 rows x 16 hidden units, K split in two halves over

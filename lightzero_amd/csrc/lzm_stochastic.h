@@ -69,14 +69,17 @@ __device__ __forceinline__ double stochastic_chance_u(uint32_t seed, int level, 
 
 // cbatch_traverse's walk of root i (:739-772), all 64 lanes of one wave, every argument wave-uniform. Writes path,
 // path_act and best_action (:766) along the walk; the leaf is a chance node iff the returned len is odd.
-__device__ inline Descent stochastic_walk(const TreeView &t, const StochasticView &sv, int i, float4 mm, int players,
-                                          int vtp, float disc, uint32_t seed) {
+// i: the root's index in the tree arrays; col / ps: where its path lives (path[l * ps + col]); root: its index in the
+// batch, which keys the draws. stochastic_walk is the whole-batch form (all three the same, ps = t.B); the one-launch
+// search (lzm_search_stoch_mlp.h) walks a workgroup's slice in LDS (gumbel_walk's li / R addressing).
+__device__ inline Descent stochastic_walk_at(const TreeView &t, const StochasticView &sv, int i, int col, int ps,
+                                             int root, float4 mm, int players, int vtp, float disc, uint32_t seed) {
   const int lane = threadIdx.x & 63;
   int node = 0, len = 0, last_action = -1, parent_latent = -1;
   float parent_q = 0.0f;  // per root; the reference's cross-root carry is 0 wherever it is read
   int latent = __builtin_amdgcn_readfirstlane(t.meta[nidx(t, 0, i)].latent);  // of `node`
   int visit = __builtin_amdgcn_readfirstlane(t.stat[nidx(t, 0, i)].visit);
-  if (lane == 0) t.path[i] = 0;
+  if (lane == 0) t.path[col] = 0;
   while (latent >= 0 && len < t.depth_cap - 1) {
     const bool chance = len & 1;
     // (A + (C - A) rather than a select between the two fields: a select of adjacent argument loads becomes an
@@ -105,7 +108,7 @@ __device__ inline Descent stochastic_walk(const TreeView &t, const StochasticVie
     parent_q = mean_q;
     int jsel;
     if (chance) {
-      jsel = stochastic_chance_pick(c.prior, n, stochastic_chance_u(seed, len, i));
+      jsel = stochastic_chance_pick(c.prior, n, stochastic_chance_u(seed, len, root));
     } else {
       // cucb_score of every child at once, the tie list by SURVEY A7's closed form (descend_wave)
       int N = visit - 1;
@@ -126,7 +129,7 @@ __device__ inline Descent stochastic_walk(const TreeView &t, const StochasticVie
       const float M = wave_max_dpp(valid ? score : -INFINITY);
       const int r = __ffsll((long long)__ballot(valid && score == M)) - 1;
       uint64_t mask = __ballot(valid && lane > r && score >= M - 0.000001f) | (1ull << (r < 0 ? 0 : r));
-      const uint4 o = philox4x32_10(make_uint4((uint32_t)len, (uint32_t)i, 0u, 0u), make_uint2(seed, kStochasticKey));
+      const uint4 o = philox4x32_10(make_uint4((uint32_t)len, (uint32_t)root, 0u, 0u), make_uint2(seed, kStochasticKey));
       int k = (int)((o.x >> 1) % (uint32_t)__popcll(mask));
       for (; k > 0; --k) mask &= mask - 1;
       jsel = __ffsll((long long)mask) - 1;
@@ -136,8 +139,8 @@ __device__ inline Descent stochastic_walk(const TreeView &t, const StochasticVie
     const int child = base + action;
     if (lane == 0) {
       t.meta[nidx(t, node, i)].best = action;
-      t.path_act[(size_t)len * t.B + i] = action;
-      t.path[(size_t)(len + 1) * t.B + i] = child;
+      t.path_act[(size_t)len * ps + col] = action;
+      t.path[(size_t)(len + 1) * ps + col] = child;
     }
     parent_latent = latent;
     node = child;
@@ -149,6 +152,11 @@ __device__ inline Descent stochastic_walk(const TreeView &t, const StochasticVie
   Descent d;
   d.len = len; d.x = parent_latent; d.action = last_action; d.vtp = vtp; d.leaf = node;
   return d;
+}
+
+__device__ inline Descent stochastic_walk(const TreeView &t, const StochasticView &sv, int i, float4 mm, int players,
+                                          int vtp, float disc, uint32_t seed) {
+  return stochastic_walk_at(t, sv, i, i, t.B, i, mm, players, vtp, disc, seed);
 }
 
 struct StochasticTraverseArgs {

@@ -74,9 +74,10 @@ def _fold(lin, bn, dtype=torch.float32):
     return W.to(dtype), b.to(dtype)
 
 
-def describe(model, dtype=torch.float32):
+def describe(model, dtype=torch.float32, policy_is_action_space=True):
     """Returns (layers [((W, b), relu)], dims dict) or raises NotPackable. dtype: of the folded layers (the
-    folding itself runs in float64; the packers take float32)."""
+    folding itself runs in float64; the packers take float32). policy_is_action_space false: the policy head's
+    width is free (Stochastic MuZero's afterstate half: the chance space)."""
     dyn = getattr(model, "dynamics_network", None)
     pred = getattr(model, "prediction_network", None)
     if dyn is None or pred is None:
@@ -104,14 +105,17 @@ def describe(model, dtype=torch.float32):
     off = 4 if res else 2
     F = layers[off][0][0].shape[0]
     V = layers[off + 1][0][0].shape[0]
-    if layers[-1][0][0].shape[0] != A:
+    if policy_is_action_space and layers[-1][0][0].shape[0] != A:
         raise NotPackable("policy head width != action space")
     return layers, dict(hidden=H, actions=A, head_hidden=F, support=V, res=res)
 
 
 def _net_args(dims):
     """(prefix of the library's functions for this network, their shape arguments): lzm_mlp_ez_ for dims with
-    lstm_hidden (describe_ez's), lzm_mlp_ otherwise"""
+    lstm_hidden (describe_ez's), lzm_mlp_stoch_ for dims with chance (describe_stochastic's), lzm_mlp_ otherwise"""
+    if "chance" in dims:
+        return "lzm_mlp_stoch_", (dims["hidden"], dims["actions"], dims["chance"], dims["head_hidden"],
+                                  dims["support"], int(dims["res"]), int(dims["shared"]))
     if "lstm_hidden" in dims:
         return "lzm_mlp_ez_", (dims["hidden"], dims["lstm_hidden"], dims["actions"], dims["head_hidden"],
                                dims["support"], int(dims["res"]))
@@ -125,7 +129,11 @@ def _pack(layers, dims, device):
     ez = "lstm_hidden" in dims
     widths = [dims[k] for k in (("hidden", "lstm_hidden") if ez else ("hidden",)) + ("head_hidden", "support")]
     # the kernels' own limits (widths, support + actions, actions <= hidden), asked of the library
-    if not getattr(L, "lzm_search_mlp_ez_supported" if ez else "lzm_search_mlp_supported")(dims["actions"], *widths):
+    if "chance" in dims:
+        ok = L.lzm_search_mlp_stoch_supported(dims["actions"], dims["chance"], *widths)
+    else:
+        ok = getattr(L, "lzm_search_mlp_ez_supported" if ez else "lzm_search_mlp_supported")(dims["actions"], *widths)
+    if not ok:
         raise NotPackable("network shape outside the search kernels' range: {}".format(dims))
     parts = []
     for (W, b), _ in layers:
@@ -169,6 +177,45 @@ def describe_ez(model, dtype=torch.float32):
 
 def pack_efficientzero_mlp(model, device):
     return _pack(*describe_ez(model), device)
+
+
+class _View:
+    """a (dynamics, prediction) pair under the names describe() reads"""
+
+    def __init__(self, model, dyn, pred):
+        self.dynamics_network, self.prediction_network = getattr(model, dyn, None), getattr(model, pred, None)
+        self.state_norm = getattr(model, "state_norm", False)
+        self.discrete_action_encoding_type = getattr(model, "discrete_action_encoding_type", "one_hot")
+
+
+def describe_stochastic(model, dtype=torch.float32):
+    """describe() for StochasticMuZeroModelMLP: returns (layers [((W, b), relu)], dims dict with chance and shared) in
+    the packed order (lzm_mlp_stoch_packed_floats) — dynamics_network's dynamics layers and reward head,
+    prediction_network, afterstate_prediction_network and, with model.shared_dynamics false,
+    afterstate_dynamics_network's dynamics layers (its reward head feeds nothing: a chance node's reward is 0) — or
+    raises NotPackable: everything describe() refuses of either half, chance_space_size > action_space_size (an
+    outcome is one-hot encoded over the action space) and halves whose latent, head or support widths differ."""
+    if getattr(model, "afterstate_prediction_network", None) is None:
+        raise NotPackable("not a Stochastic MuZero model (no afterstate_prediction_network)")
+    shared = bool(getattr(model, "shared_dynamics", True))
+    dec, dd = describe(_View(model, "dynamics_network", "prediction_network"), dtype)
+    aft, da = describe(_View(model, "dynamics_network" if shared else "afterstate_dynamics_network",
+                             "afterstate_prediction_network"), dtype, policy_is_action_space=False)
+    nd = 4 if dd["res"] else 2
+    A, C = dd["actions"], aft[-1][0][0].shape[0]
+    if C > A:
+        raise NotPackable(f"chance space {C} > action space {A}")
+    for k in ("hidden", "head_hidden", "support", "res"):
+        if dd[k] != da[k]:
+            raise NotPackable(f"{k} differs between the two halves: {dd[k]} != {da[k]}")
+    if dec[nd + 5][0][0].shape[0] != dd["support"] or aft[nd + 5][0][0].shape[0] != dd["support"]:
+        raise NotPackable("reward and value supports differ")
+    layers = dec + aft[nd + 2:] + ([] if shared else aft[:nd])
+    return layers, dict(dd, chance=C, shared=shared)
+
+
+def pack_stochastic_mlp(model, device):
+    return _pack(*describe_stochastic(model), device)
 
 
 def prepare_kernel_weights(flat, dims, out=None):

@@ -29,7 +29,7 @@ import torch
 from . import _lib
 from .ctree import ez_tree, ezs_tree, gmz_tree, mz_tree, stochastic_mz_tree
 from .conv_infer import FoldedCache
-from .fused import NotPackable, PackedCache, pack_efficientzero_mlp
+from .fused import NotPackable, PackedCache, pack_efficientzero_mlp, pack_stochastic_mlp
 from .scaling_transform import InverseScalarTransform
 from .tree import DeviceTree, new_minmax, next_seed
 from .utils import EasyDict
@@ -970,7 +970,10 @@ class StochasticMuZeroMCTSCtree(_MCTSCtree):
     and walks the next simulation. No host sync, no data-dependent shape: eager, or one HIP graph with
     cfg.use_hip_graph. Tie and chance draws are per-root Philox streams keyed by the traverse seeds (`seeds` as in
     MuZeroMCTSCtree.search): the reference's chance draw is seeded from std::random_device, so there is no stream
-    to be in parity with and no rng_mode."""
+    to be in parity with and no rng_mode.
+    With cfg.fused_search (read with default False: opt-in) a StochasticMuZeroModelMLP's whole search runs as one
+    launch (lzm_search_mlp_stoch) where _fused allows it, with the same tree bit for bit given equal network
+    outputs; last_path says which path ran."""
 
     config = dict(
         root_dirichlet_alpha=0.3,
@@ -988,13 +991,37 @@ class StochasticMuZeroMCTSCtree(_MCTSCtree):
               chance_space_size: int = 2) -> "stochastic_mz_tree.Roots":
         return stochastic_mz_tree.Roots(active_collect_env_num, legal_actions, chance_space_size)
 
-    def _recorder(self, c):
+    def __init__(self, cfg: EasyDict = None) -> None:
+        super().__init__(cfg)
+        self._packed = PackedCache(pack=pack_stochastic_mlp)
+
+    def _recorder(self, c, width=1):
+        """width: of the policy_logits rows (the one-launch search records each leaf's row, max(A, C) wide; the
+        per-simulation path records none)"""
         if not self.record:
             return None
-        rec = _Recorder(c.S, c.B, 1, c.dev)
+        rec = _Recorder(c.S, c.B, width, c.dev)
         rec.is_chance = torch.zeros((c.S, c.B), dtype=torch.int32, device=c.dev)
         rec.seeds = c.buf.seeds.cpu().numpy().view(np.uint32)
         return rec
+
+    def _fused(self, model, t, S):
+        """(packed weights, dims) when cfg.fused_search is set (absent: off) and the whole search can run as one
+        lzm_search_mlp_stoch launch: a StochasticMuZeroModelMLP-shaped network with categorical heads, eval-mode
+        BatchNorm and ReLU (fused.describe_stochastic), whose action space, chance space and support match the tree
+        and the config, of a shape the kernel takes on this tree for S simulations by the library's own launch plan
+        (lzm_search_mlp_stoch_plan); None otherwise (the per-simulation path)."""
+        if not self._cfg.get('fused_search', False) or not self._categorical():
+            return None
+        try:
+            packed, dims = self._packed.get(model, t.device)
+        except NotPackable:
+            return None
+        if (dims["actions"], dims["chance"]) != (t.act, t.chance) or \
+                dims["support"] != 2 * int(self._cfg.model.support_scale) + 1:
+            return None
+        self.last_plan = t.search_mlp_stoch_plan(dims, S)
+        return (packed, dims) if self.last_plan["kernel"] is not None else None
 
     def _loop(self, t, model, c, rec=None, infer=None, net=None):
         """The S simulations (mcts_ctree_stochastic.py:116-251) on tree t over c.buf, all enqueued on the current
@@ -1027,12 +1054,19 @@ class StochasticMuZeroMCTSCtree(_MCTSCtree):
             c = self._begin("search", roots, model, latent_state_roots)
             if not getattr(c.t, "chance", 0):
                 raise TypeError("StochasticMuZeroMCTSCtree.search: roots must come from StochasticMuZeroMCTSCtree.roots")
-            self._buffers(c, model, graph=not self.record and self._cfg.get('use_hip_graph', False))
-            self._stage(c, to_play_batch, seeds, None)
-            rec = self._recorder(c)
-            self._generic(c, model, rec)
+            fz = self._fused(model, c.t, c.S)
+            self._buffers(c, model, graph=fz is None and not self.record and self._cfg.get('use_hip_graph', False))
+            vt, sd = self._stage(c, to_play_batch, seeds, None)
+            rec = self._recorder(c, 1 if fz is None else c.t.A)
+            if fz is None:
+                self._generic(c, model, rec)
+            else:  # the whole search in one launch
+                packed, dims = fz
+                new_minmax(c.B, self._cfg.value_delta_max, c.dev, out=c.buf.mm)
+                c.t.search_mlp_stoch(dims, packed, c.S, c.buf.mm, sd, vt, c.buf.pool, *self._pb_c(), self._discount(),
+                                     rec=rec)
             self._finish(c, roots, None, rec)
-            self.last_path = "generic"
+            self.last_path = "generic" if fz is None else "fused-mlp"
 
 
 class SampledEfficientZeroMCTSCtree(_ValuePrefixLSTM, _MCTSCtree):

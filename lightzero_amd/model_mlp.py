@@ -288,6 +288,82 @@ class EfficientZeroModelMLP(nn.Module):
         return EZNetworkOutput(value, value_prefix, policy_logits, next_latent_state, hidden)
 
 
+class StochasticMuZeroModelMLP(nn.Module):
+    """Stochastic MuZero for vector observations (stochastic_muzero_model_mlp.py:14-350, ``initial_inference`` and
+    ``recurrent_inference`` of stochastic_muzero_model.py:201-273), discrete one-hot options. Attribute names and
+    ``state_dict`` keys are the reference's. Not restated: the chance encoder and the self-supervised heads
+    (training only; load such a checkpoint with ``strict=False``).
+
+    Restated as the reference behaves: ``_afterstate_dynamics`` calls ``dynamics_network`` (line 277), so
+    ``afterstate_dynamics_network`` holds parameters nothing reads, and both branches one-hot their option over
+    ``action_space_size``, so ``chance_space_size <= action_space_size``. ``shared_dynamics=False`` (not in the
+    reference) makes ``_afterstate_dynamics`` call ``afterstate_dynamics_network``."""
+
+    def __init__(self, observation_shape: int = 2, action_space_size: int = 6, chance_space_size: int = 2,
+                 latent_state_dim: int = 256, fc_reward_layers=(32,), fc_value_layers=(32,), fc_policy_layers=(32,),
+                 reward_support_size: int = 601, value_support_size: int = 601,
+                 categorical_distribution: bool = True, last_linear_layer_init_zero: bool = True,
+                 state_norm: bool = False, norm_type: Optional[str] = 'BN', res_connection_in_dynamics: bool = False,
+                 shared_dynamics: bool = True, **kwargs):
+        super().__init__()
+        assert chance_space_size <= action_space_size, "an outcome is one-hot encoded over the action space"
+        self.categorical_distribution = categorical_distribution
+        self.reward_support_size = reward_support_size if categorical_distribution else 1
+        self.value_support_size = value_support_size if categorical_distribution else 1
+        self.action_space_size = action_space_size
+        self.chance_space_size = chance_space_size
+        self.discrete_action_encoding_type = 'one_hot'
+        self.action_encoding_dim = action_space_size
+        self.latent_state_dim = latent_state_dim
+        self.state_norm = state_norm
+        self.res_connection_in_dynamics = res_connection_in_dynamics
+        self.shared_dynamics = shared_dynamics
+        dyn = dict(action_encoding_dim=action_space_size, num_channels=latent_state_dim + action_space_size,
+                   common_layer_num=2, fc_reward_layers=fc_reward_layers, output_support_size=self.reward_support_size,
+                   last_linear_layer_init_zero=last_linear_layer_init_zero, norm_type=norm_type,
+                   res_connection_in_dynamics=res_connection_in_dynamics)
+        pred = dict(num_channels=latent_state_dim, fc_value_layers=fc_value_layers, fc_policy_layers=fc_policy_layers,
+                    output_support_size=self.value_support_size,
+                    last_linear_layer_init_zero=last_linear_layer_init_zero, norm_type=norm_type)
+        self.representation_network = RepresentationNetworkMLP(observation_shape, latent_state_dim,
+                                                               norm_type=norm_type)
+        self.dynamics_network = DynamicsNetwork(**dyn)
+        self.prediction_network = PredictionNetworkMLP(action_space_size, **pred)
+        self.afterstate_dynamics_network = DynamicsNetwork(**dyn)
+        self.afterstate_prediction_network = PredictionNetworkMLP(chance_space_size, **pred)
+
+    def initial_inference(self, obs: torch.Tensor) -> MZNetworkOutput:
+        latent_state = self.representation_network(obs)
+        if self.state_norm:
+            latent_state = EfficientZeroModelMLP._renormalize(latent_state)
+        policy_logits, value = self.prediction_network(latent_state)
+        return MZNetworkOutput(value, [0. for _ in range(obs.size(0))], policy_logits, latent_state)
+
+    def _step(self, network, state, option):
+        a = option.long().reshape(-1, 1)
+        one_hot = torch.zeros(a.shape[0], self.action_space_size, device=state.device, dtype=state.dtype)
+        one_hot.scatter_(1, a, 1)
+        next_state, reward = network(torch.cat((state, one_hot), dim=1))
+        return (EfficientZeroModelMLP._renormalize(next_state) if self.state_norm else next_state), reward
+
+    def _dynamics(self, latent_state, action):
+        return self._step(self.dynamics_network, latent_state, action)
+
+    def _afterstate_dynamics(self, latent_state, action):
+        return self._step(self.dynamics_network if self.shared_dynamics else self.afterstate_dynamics_network,
+                          latent_state, action)
+
+    def recurrent_inference(self, state: torch.Tensor, option: torch.Tensor,
+                            afterstate: bool = False) -> MZNetworkOutput:
+        if afterstate:  # state is an afterstate, option a chance outcome
+            next_state, reward = self._dynamics(state, option)
+            policy_logits, value = self.prediction_network(next_state)
+        else:  # state is a latent state, option an action
+            next_state, reward = self._afterstate_dynamics(state, option)
+            policy_logits, value = self.afterstate_prediction_network(next_state)
+        return MZNetworkOutput(value, reward, policy_logits, next_state)
+
+
 def cartpole_efficientzero_model(random_heads: bool = True) -> EfficientZeroModelMLP:
     """The CartPole-v0 EfficientZero network (cartpole_efficientzero_config.py:29-38 over efficientzero.py's
     defaults: latent 128, LSTM 128, one-hot actions, BN, no residual, support 601). ``random_heads`` as in

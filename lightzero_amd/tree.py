@@ -406,6 +406,27 @@ class DeviceTree:
              int(dims["res"]), out)
         return dict(roots_per_wg=out[0], kernel={0: "streaming"}.get(out[1]), mode=out[2], tree_in_lds=bool(out[3]))
 
+    def search_mlp_stoch(self, dims, weights, S, minmax, seeds, vtp_in, pool, pb_c_base=19652, pb_c_init=1.25,
+                         discount=0.997, rec=None, stream=None):
+        """One launch for the whole Stochastic MuZero search of a StochasticMuZeroModelMLP (lzm_search_mlp_stoch;
+        dims / weights: fused.pack_stochastic_mlp's, in the kernel layout); rec: optional _Recorder-like object
+        with is_chance, vtp and policy_logits [S, B, max(A, C)]."""
+        self._unchecked = True
+        rx, ra, rl, rd, rg = _rec_ptrs(rec)
+        call("lzm_search_mlp_stoch", self.h, dims["hidden"], dims["head_hidden"], dims["support"], int(dims["res"]),
+             int(dims["shared"]), ptr(weights), int(S), int(pb_c_base), float(pb_c_init), float(discount),
+             ptr(minmax), ptr(seeds), ptr(vtp_in), ptr(pool), rx, ra, rl, *_rec_ptrs(rec, ("is_chance", "vtp")), rd,
+             rg, stream_ptr(stream))
+
+    def search_mlp_stoch_plan(self, dims, S):
+        """What search_mlp_stoch(dims, ..., S) launches on this handle as it stands (lzm_search_mlp_stoch_plan; host
+        only): dict(roots_per_wg, kernel 'streaming' / None when the kernel refuses the shape, its LDS need or a
+        handle that is no Stochastic MuZero tree, mode 0, tree_in_lds)."""
+        out = (ctypes.c_int32 * 4)()
+        call("lzm_search_mlp_stoch_plan", self.h, int(S), dims["hidden"], dims["head_hidden"], dims["support"],
+             int(dims["res"]), out)
+        return dict(roots_per_wg=out[0], kernel={0: "streaming"}.get(out[1]), mode=out[2], tree_in_lds=bool(out[3]))
+
     def search_conv_gumbel(self, net, S, m, minmax, vtp_in, pool, discount=0.997, categorical=True, rec=None,
                            max_roots=0, stream=None):
         """One launch per root slice for the whole Gumbel MuZero search of a conv MuZeroModel

@@ -22,3 +22,5 @@ echo "# ---- diff parent tree (nothing between this line and the next marker: no
 diff "$old/parent.txt" "$old/tree.txt" || true
 echo "# ---- lzm_az_c4.hip (working tree)"
 lines "$root/lightzero_amd/csrc/lzm_az_c4.hip" -Xclang -target-feature -Xclang -packed-fp32-ops
+echo "# ---- lzm_search_stoch_mlp.hip (working tree)"
+lines "$root/lightzero_amd/csrc/lzm_search_stoch_mlp.hip" -Xclang -target-feature -Xclang -packed-fp32-ops

@@ -97,13 +97,63 @@ def host_search(B, S):
     return run
 
 
+def one_launch_compare(out_path):
+    """--one-launch: the one-launch search (cfg.fused_search, lzm_search_mlp_stoch) against the graph-replayed
+    per-simulation path over a StochasticMuZeroModelMLP of the zoo widths (latent 128, support 601), at 256 roots x
+    50 simulations and 8 x 25, (A, C) = (2, 2) and (4, 2). DESIGN.md 10's protocol: device events around the search
+    call alone (roots prepared outside), medians of five after three warm-up searches, the two paths alternating
+    three times in one session. Every run is kept in out_path."""
+    import numpy as np
+    import torch
+    from lightzero_amd import StochasticMuZeroMCTSCtree
+    from lightzero_amd.model_mlp import StochasticMuZeroModelMLP
+    from lightzero_amd.utils import EasyDict
+    runs = []
+    for (B, S) in ((256, 50), (8, 25)):
+        for (na, nc) in ((2, 2), (4, 2)):
+            torch.manual_seed(0)
+            rng = np.random.default_rng(1)
+            model = StochasticMuZeroModelMLP(observation_shape=4, action_space_size=na, chance_space_size=nc,
+                                             latent_state_dim=128, last_linear_layer_init_zero=False).cuda().eval()
+            lat = torch.from_numpy(rng.normal(size=(B, 128)).astype(np.float32)).cuda()
+            logits = rng.normal(size=(B, na)).astype(np.float32).tolist()
+            paths = {}
+            for name, extra in (("one_launch", dict(fused_search=True)), ("graph", dict(use_hip_graph=True))):
+                mcts = StochasticMuZeroMCTSCtree(EasyDict(
+                    num_simulations=S, discount_factor=0.997, device="cuda",
+                    model=EasyDict(support_scale=300, categorical_distribution=True), **extra))
+                paths[name] = (mcts, mcts.roots(B, [list(range(na))] * B, nc))
+            for rnd in range(3):
+                for name, (mcts, roots) in paths.items():
+                    ms = []
+                    for r in range(8):
+                        roots.prepare_no_noise([0.0] * B, logits, [-1] * B)
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        mcts.search(roots, model, lat, [-1] * B)
+                        e1.record()
+                        torch.cuda.synchronize()
+                        if r >= 3:
+                            ms.append(e0.elapsed_time(e1))
+                    assert mcts.last_path == ("fused-mlp" if name == "one_launch" else "generic"), mcts.last_path
+                    runs.append(dict(roots=B, sims=S, actions=na, chance=nc, path=name, round=rnd,
+                                     median_ms=statistics.median(ms), ms=ms))
+                    print(json.dumps(runs[-1]), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(runs, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--roots", type=int, default=256)
     ap.add_argument("--sims", type=int, default=50)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--child", choices=("host", "device"))
+    ap.add_argument("--one-launch", metavar="OUT.json", help="time the one-launch search against the graph path")
     a = ap.parse_args()
+    if a.one_launch:
+        return one_launch_compare(a.one_launch)
     if a.child == "host":
         print(json.dumps({"host_loop_ms": median_ms(host_search(a.roots, a.sims), a.reps)}))
         return
