@@ -967,6 +967,44 @@ int lzm_search_mlp_stoch(lzm_handle *h, int hidden, int head_hidden, int support
                          float pb_c_init, float discount, float *minmax, const uint32_t *seeds, const int32_t *vtp_in,
                          float *latent_pool, int32_t *rec_x, int32_t *rec_a, int32_t *rec_len, int32_t *rec_is_chance,
                          int32_t *rec_vtp, float *rec_decoded, float *rec_logits, void *stream);
+/* ---- SampledEfficientZeroMCTSCtree.search's whole loop over a continuous SampledEfficientZeroModelMLP in one launch
+ * (search_sampled_mlp_kernel, lzm_search_sampled_mlp.h). The packed network (lightzero_amd/fused.py
+ * pack_sampled_efficientzero_mlp; per layer W[K][N] then bias[N], BatchNorm folded), every layer one dense layer: the
+ * dynamics layers on [latent ; action] (the action as `dim` floats), the reward LSTM's gate layer over [x ; h_prev]
+ * (lzm_mlp_ez_*'s), the value-prefix head, fc_prediction_common, [fc_value_head[0] | main[0]], main[1] and
+ * [fc_value_head[1] | mu | log_sigma] over max(head_hidden, hidden) input rows (a source's rows past its own width
+ * are zeros; a fixed sigma is a zero block with bias log(sigma)). lzm_mlp_sampled_packed_floats / _kernel_floats: the
+ * packed and the kernel-layout sizes (-1 for a non-positive width); lzm_mlp_sampled_prepare: packed -> kernel layout
+ * (lane order) on `stream`. */
+int64_t lzm_mlp_sampled_packed_floats(int hidden, int lstm_hidden, int dim, int head_hidden, int support,
+                                      int res_dynamics);
+int64_t lzm_mlp_sampled_kernel_floats(int hidden, int lstm_hidden, int dim, int head_hidden, int support,
+                                      int res_dynamics);
+int lzm_mlp_sampled_prepare(int hidden, int lstm_hidden, int dim, int head_hidden, int support, int res_dynamics,
+                            const float *packed, float *out, void *stream);
+/* 1 when the kernel takes the shape: lzm_search_mlp_ez_supported's widths with 2 * dim policy columns in the place
+ * of the actions, 1 <= dim <= 32. Host only. */
+int lzm_search_mlp_sampled_supported(int dim, int hidden, int lstm_hidden, int head_hidden, int support);
+/* What lzm_search_mlp_sampled launches on this handle as it stands, by the function the launch itself decides with:
+ * out int32[4] = {roots per workgroup, kind: 0 weight-streaming or -1 (refused shape, LDS need, or a handle that is
+ * no continuous Sampled EfficientZero tree), 0, tree_in_lds}. Host only. */
+int lzm_search_mlp_sampled_plan(const lzm_handle *h, int num_simulations, int hidden, int lstm_hidden, int head_hidden,
+                                int support, int res_dynamics, int32_t *out);
+/* The search: num_simulations x (walk, network, decode, expand with the K x dim Gaussian draws, backup) on a handle
+ * prepared by lzm_sampled_prepare; seeds int32/uint32 [num_simulations]: seeds[k] keys simulation k's tie draws and
+ * its leaf's sampling exactly as lzm_sampled_traverse's and lzm_sampled_decode_backprop's seed do, so the tree and
+ * the action table equal the per-simulation path's given equal policy rows. tanh_mu: bound_type 'tanh'. latent_pool
+ * [num_simulations + 1][B][hidden], h_pool / c_pool [num_simulations + 1][B][lstm_hidden], slot 0 = the roots'.
+ * Optional record (all seven or none): rec_x / rec_slot / rec_len / rec_reset int32 [S][B], rec_decoded [S][B][2]
+ * {value prefix, value} after h^-1, rec_policy [S][B][2 dim] {mu, sigma} as the tree read it, rec_actions
+ * [S][B][dim] the action rows the network was fed. LZM_ERR_STATE on a handle that is no continuous Sampled
+ * EfficientZero tree, LZM_ERR_ARG for a refused shape or LDS need: nothing is launched. */
+int lzm_search_mlp_sampled(lzm_handle *h, int hidden, int lstm_hidden, int head_hidden, int support, int res_dynamics,
+                           int tanh_mu, const float *weights, int num_simulations, int lstm_horizon_len, int pb_c_base,
+                           float pb_c_init, float discount, float *minmax, const uint32_t *seeds, const int32_t *vtp_in,
+                           float *latent_pool, float *h_pool, float *c_pool, int32_t *rec_x, int32_t *rec_slot,
+                           int32_t *rec_len, int32_t *rec_reset, float *rec_decoded, float *rec_policy,
+                           float *rec_actions, void *stream);
 /* GumbelMuZeroMCTSCtree.search's whole loop over a conv MuZeroModel (64 x 8 x 8 latent) in one launch per root
  * slice: lzm_search_conv's kernel — trunk, head MLPs, support decode and ensure_softmax verdict unchanged — with the
  * Gumbel walk on the root's tree slice in LDS (its raw_value slice, the Gumbel table and the considered-visits row

@@ -195,6 +195,12 @@ SIGNATURES = {
     "lzm_search_mlp_stoch_supported": [_i] * 5,
     "lzm_search_mlp_stoch_plan": [_vp, _i, _i, _i, _i, _i, _vp],
     "lzm_search_mlp_stoch": [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _f] + [_vp] * 12,
+    "lzm_mlp_sampled_packed_floats": [_i] * 6,
+    "lzm_mlp_sampled_kernel_floats": [_i] * 6,
+    "lzm_mlp_sampled_prepare": [_i] * 6 + [_vp, _vp, _vp],
+    "lzm_search_mlp_sampled_supported": [_i] * 5,
+    "lzm_search_mlp_sampled_plan": [_vp, _i, _i, _i, _i, _i, _i, _vp],
+    "lzm_search_mlp_sampled": [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _f, _f] + [_vp] * 14,
     "lzm_search_conv_gumbel": [_vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i,
                                _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
     "lzm_search_conv_gumbel_plan": [_vp] + [_i] * 12 + [_vp],
@@ -225,6 +231,7 @@ _RESTYPE = {"lzm_last_error": ctypes.c_char_p, "lzm_mlp_packed_floats": ctypes.c
             "lzm_mlp_kernel_floats": ctypes.c_int64, "lzm_mlp_ez_packed_floats": ctypes.c_int64,
             "lzm_mlp_ez_kernel_floats": ctypes.c_int64, "lzm_az_net_floats": ctypes.c_int64,
             "lzm_mlp_stoch_packed_floats": ctypes.c_int64, "lzm_mlp_stoch_kernel_floats": ctypes.c_int64,
+            "lzm_mlp_sampled_packed_floats": ctypes.c_int64, "lzm_mlp_sampled_kernel_floats": ctypes.c_int64,
             "lzm_az_c4_net_floats": ctypes.c_int64,
             "lzm_conv_trunk_floats": ctypes.c_int64, "lzm_conv_trunk_floats_p": ctypes.c_int64,
             "lzm_ez_lstm_frag_floats": ctypes.c_int64, "lzm_ez_lstm_workspace_bytes": ctypes.c_int64,

@@ -48,6 +48,7 @@
 #include "lzm_sampled.h"
 #include "lzm_search_mlp.h"
 #include "lzm_search_stoch_mlp.h"
+#include "lzm_search_sampled_mlp.h"
 #include "lzm_search_res.h"
 #include "lzm_conv.h"
 #include "lzm_repr.h"
@@ -2761,6 +2762,161 @@ void build_stoch_schedules(StochSearchArgs &p, const StochNet &net, const float 
   idle.Np = sp.Np; idle.splits = sp.splits; idle.cpl = sp.cpl; idle.log2s = sp.log2s;
 }
 
+// ---- the one-launch Sampled EfficientZero search over the continuous SampledEfficientZeroModelMLP
+// (lzm_search_sampled_mlp.h). The packed network (lightzero_amd/fused.py pack_sampled_efficientzero_mlp), layers in
+// packed order, every one a single dense layer (the packer merges the heads): the dynamics layers on
+// [latent ; action] (2, or 4 with res_connection_in_dynamics), the LSTM's gate layer over [x ; h_prev], the
+// value-prefix head (2), fc_prediction_common (2), [fc_value_head[0] | main[0]], main[1] and
+// [fc_value_head[1] | mu | log_sigma] over max(F, H) input rows (each source's rows past its own K are zeros).
+constexpr int kSampledLayers = 12;
+struct SampledNet {
+  int H, Hl, D, F, V, res;
+  LayerShape s[kSampledLayers];
+  size_t pw[kSampledLayers], pb[kSampledLayers], packed_floats;
+  KLayer kl[kSampledLayers];
+  int nk;
+  size_t w_off[kSampledLayers], b_off[kSampledLayers], kernel_floats;
+};
+SampledNet sampled_net(int H, int Hl, int D, int F, int V, int res) {
+  SampledNet n;
+  n.H = H; n.Hl = Hl; n.D = D; n.F = F; n.V = V; n.res = res ? 1 : 0;
+  n.nk = 0;
+  auto add = [&](int krows, int N) {
+    const int K = (krows + kKC - 1) / kKC * kKC;
+    n.kl[n.nk] = KLayer{n.nk, -1, K, N, N};
+    n.s[n.nk++] = {krows, K, N};
+  };
+  add(H + D, H);  // fc_dynamics(_1)[0]: [latent ; action]
+  add(H, H);
+  if (n.res) { add(H, H); add(H, H); }  // fc_dynamics_2
+  add(H + Hl, 4 * Hl);                  // [weight_ih_l0 | weight_hh_l0], bias_ih_l0 + bias_hh_l0
+  add(Hl, F); add(F, V);                // fc_reward_head on h1
+  add(H, H); add(H, H);                 // fc_prediction_common
+  add(H, F + H);                        // [fc_value_head[0] | main[0]]
+  add(H, H);                            // main[1]
+  add(std::max(F, H), V + 2 * D);       // [fc_value_head[1] | mu | log_sigma]
+  size_t off = 0;
+  for (int l = 0; l < n.nk; ++l) {
+    n.pw[l] = off;
+    off += (size_t)n.s[l].krows * n.s[l].N;
+    n.pb[l] = off;
+    off += n.s[l].N;
+  }
+  n.packed_floats = off;
+  off = 0;
+  for (int l = 0; l < n.nk; ++l) {
+    n.w_off[l] = off;
+    off += swz_floats(n.kl[l].K, n.kl[l].N);
+    n.b_off[l] = off;
+    off = (off + n.kl[l].N + 3) & ~(size_t)3;
+  }
+  n.kernel_floats = off;
+  return n;
+}
+// the kernel's limits: the EfficientZero kernel's with the policy row {mu[D], log_sigma[D]} in the place of the
+// logits, and the action table's D <= kSampledMaxDim
+bool sampled_shape_ok(int D, int H, int Hl, int F, int V) {
+  return D > 0 && D <= kSampledMaxDim && ez_shape_ok(H, Hl, 2 * D, F, V);
+}
+bool sampled_args_ok(int H, int Hl, int D, int F, int V) { return H > 0 && Hl > 0 && D > 0 && F > 0 && V > 0; }
+
+// LDS plan of search_sampled_mlp_kernel with R roots per workgroup (float offsets, 16-B aligned); returns bytes.
+// x1 / x2 / hd: the activation buffers only the schedule names.
+size_t plan_sampled(SampledSearchArgs &p, const lzm_handle *h, int R, int S, int H, int Hl, int F, int V, int res,
+                    int tl, size_t *x1, size_t *x2, size_t *hd) {
+  const int D = h->s_dim;
+  size_t o = 0;
+  const size_t tree_floats = (size_t)h->cap * R * 4;
+  p.off_stat = o; if (tl) o += tree_floats;
+  p.off_meta = o; if (tl) o += tree_floats;
+  p.off_lut = o; if (tl) o += round4((size_t)2 * h->lut_n);
+  p.off_path = o; o += round4((size_t)h->depth_cap * R);
+  p.off_pact = o; o += round4((size_t)h->depth_cap * R);
+  auto tfl = [R](int K) { return (size_t)((K + kKC - 1) / kKC) * (kKC * R + 4); };
+  p.off_act = o;
+  p.off_x0 = o; o += round4(tfl((H + D + kKC - 1) / kKC * kKC));  // [latent ; action] rows, zero-padded
+  *x1 = o; o += round4(tfl(std::max(H, F)));  // (rows H .. F stay zero: the merged output layer's K padding)
+  *x2 = o; o += round4(tfl(H));
+  p.off_n = o; o += round4(tfl(H));
+  *hd = o; o += round4(tfl(F + H));           // [value hidden ; main[0]'s output]
+  p.off_logit = o; if (V < kThreads) o += round4((size_t)(V + 1) * R);  // wide supports decode from registers
+  p.off_pol = o; o += round4((size_t)R * 2 * D);
+  p.off_g = o; o += round4(tfl(H + Hl));
+  p.off_gates = o; o += round4(tfl(4 * Hl));
+  p.off_hh = o; o += round4(tfl(Hl));
+  p.off_cp = o; o += round4((size_t)Hl * R);
+  if (!res) p.off_n = p.off_g;  // the next latent is the LSTM's input: the front rows of [x ; h_prev]
+  p.act_floats = o - p.off_act;
+  p.off_seeds = o; o += round4((size_t)S);
+  return o * sizeof(float);
+}
+// What lzm_search_mlp_sampled launches for this handle, network shape and search length: the one decision behind
+// the launch and the plan query (MlpPlan's fields; kind 0 weight-streaming, -1 none). R as the EfficientZero
+// kernel's: 1, 2 or 4. The tree slice is staged in LDS when it is at most 96 KB and the whole plan fits.
+MlpPlan sampled_plan(const lzm_handle *h, int H, int Hl, int F, int V, int res, int S, SampledSearchArgs &p,
+                     size_t *x1, size_t *x2, size_t *hd) {
+  MlpPlan pl{std::min(roots_per_wg(h->B), 4), -1, 0, 0, 0};
+  if (!(h->flags & LZM_TREE_SAMPLED) || h->s_dim <= 0 || !sampled_shape_ok(h->s_dim, H, Hl, F, V)) return pl;
+  pl.tree_in_lds = ((size_t)h->cap * pl.R * 8 * sizeof(float) <= 96 * 1024) ? 1 : 0;
+  pl.lds = plan_sampled(p, h, pl.R, S, H, Hl, F, V, res, pl.tree_in_lds, x1, x2, hd);
+  if (pl.tree_in_lds && pl.lds > kMaxLds) {
+    pl.tree_in_lds = 0;
+    pl.lds = plan_sampled(p, h, pl.R, S, H, Hl, F, V, res, 0, x1, x2, hd);
+  }
+  pl.kind = pl.lds <= kMaxLds ? 0 : -1;
+  return pl;
+}
+// The schedule (build_schedule's routing up to the value-prefix head, then the three-headed tail); padded to an
+// even length with the empty step.
+void build_sampled_schedule(SampledSearchArgs &p, const SampledNet &net, const float *weights, int R, size_t x1s,
+                            size_t x2s, size_t hds) {
+  const int x0 = (int)p.off_x0, x1 = (int)x1s, x2 = (int)x2s, nl = (int)p.off_n, hd = (int)hds, lg = (int)p.off_logit,
+            gx = (int)p.off_g, gt = (int)p.off_gates, hh = (int)p.off_hh, V = net.V, F = net.F;
+  int n = 0;
+  auto add = [&](int in, int out, int relu, int resid, int rowmajor, int ldout, int dec) -> StepRec & {
+    const KLayer &k = net.kl[n];
+    StepRec &q = p.sched[n];
+    q.w = weights + net.w_off[n];
+    q.b = weights + net.b_off[n];
+    q.K = k.K; q.N = k.N;
+    q.wbytes = (int)(swz_floats(k.K, k.N) * sizeof(float));
+    q.in = in; q.out = out; q.relu = relu; q.resid = resid; q.rowmajor = rowmajor; q.ldout = ldout; q.decode = dec;
+    q.ncol1 = k.N;
+    q.in2 = in; q.out2 = out; q.rowmajor2 = rowmajor; q.ldout2 = ldout;
+    const Split sp = layer_split(k.K, k.N);
+    q.Np = sp.Np; q.splits = sp.splits; q.cpl = sp.cpl; q.log2s = sp.log2s;
+    ++n;
+    return q;
+  };
+  add(x0, x1, 1, -1, 0, 0, 0);                   // fc_dynamics(_1)[0] on [latent ; action]
+  add(x1, nl, 1, net.res ? x0 : -1, 0, 0, 0);    // [1] (+ latent: res_connection_in_dynamics)
+  if (net.res) {
+    add(nl, x1, 1, -1, 0, 0, 0);                 // fc_dynamics_2
+    add(x1, gx, 1, -1, 0, 0, 0);
+  }
+  add(gx, gt, 0, -1, 0, 0, 0);                   // gates = [x ; h_prev] . [W_ih | W_hh] + (b_ih + b_hh)
+  p.cell_after = n - 1;
+  add(hh, hd, 1, -1, 0, 0, 0);                   // fc_reward_head on the unmasked h1
+  add(hd, lg, 0, -1, 1, V + 1, 1);
+  add(nl, x1, 1, -1, 0, 0, 0);                   // fc_prediction_common
+  add(x1, x2, 1, -1, 0, 0, 0);
+  add(x2, hd, 1, -1, 0, 0, 0);                   // [fc_value_head[0] | main[0]]: F + H rows of hd
+  add(hd + F / kKC * (kKC * R + 4), x1, 1, -1, 0, 0, 0);  // main[1] on the policy half
+  StepRec &o = add(hd, lg, 0, -1, 1, V + 1, 2);  // [fc_value_head[1] | mu | log_sigma]
+  o.ncol1 = V;                                   // value support columns, decoded
+  o.in2 = x1;                                    // the policy columns read main[1]'s output
+  o.out2 = (int)p.off_pol; o.rowmajor2 = 1; o.ldout2 = 2 * net.D;  // {mu, log_sigma} [r][2 D]
+  if (n & 1) {  // the empty step: no columns, no weights (every load out of range), one barrier
+    StepRec &q = p.sched[n++];
+    memset(&q, 0, sizeof(q));
+    q.w = weights; q.b = weights;
+    q.resid = -1;
+    const Split sp = layer_split(0, 0);
+    q.Np = sp.Np; q.splits = sp.splits; q.cpl = sp.cpl; q.log2s = sp.log2s;
+  }
+  p.nsteps = n;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2957,6 +3113,94 @@ int lzm_search_mlp_stoch(lzm_handle *h, int hidden, int head_hidden, int support
   p.rec_dec = rec_decoded; p.rec_logits = rec_logits;
   build_stoch_schedules(p, net, weights, plan.R, x2, hd);
   LZM_HIP(stoch_mlp_launch(p, plan.R, plan.tree_in_lds != 0, plan.lds, (hipStream_t)stream));
+  h->walked = true;
+  return LZM_OK;
+}
+
+// The continuous SampledEfficientZeroModelMLP twins (see include/lzmcts.h)
+int64_t lzm_mlp_sampled_packed_floats(int hidden, int lstm_hidden, int dim, int head_hidden, int support,
+                                      int res_dynamics) {
+  if (!sampled_args_ok(hidden, lstm_hidden, dim, head_hidden, support)) return -1;
+  return (int64_t)sampled_net(hidden, lstm_hidden, dim, head_hidden, support, res_dynamics).packed_floats;
+}
+
+int64_t lzm_mlp_sampled_kernel_floats(int hidden, int lstm_hidden, int dim, int head_hidden, int support,
+                                      int res_dynamics) {
+  if (!sampled_args_ok(hidden, lstm_hidden, dim, head_hidden, support)) return -1;
+  return (int64_t)sampled_net(hidden, lstm_hidden, dim, head_hidden, support, res_dynamics).kernel_floats;
+}
+
+int lzm_mlp_sampled_prepare(int hidden, int lstm_hidden, int dim, int head_hidden, int support, int res_dynamics,
+                            const float *packed, float *out, void *stream) {
+  if (!packed || !out || !sampled_args_ok(hidden, lstm_hidden, dim, head_hidden, support) || hidden % kKC != 0 ||
+      lstm_hidden % kKC != 0 || head_hidden % kKC != 0) {
+    set_err("lzm_mlp_sampled_prepare: bad arguments (hidden, LSTM and head widths must be multiples of 16)");
+    return LZM_ERR_ARG;
+  }
+  return swizzle_layers(sampled_net(hidden, lstm_hidden, dim, head_hidden, support, res_dynamics), packed, out,
+                        (hipStream_t)stream);
+}
+
+int lzm_search_mlp_sampled_supported(int dim, int hidden, int lstm_hidden, int head_hidden, int support) {
+  return sampled_shape_ok(dim, hidden, lstm_hidden, head_hidden, support) ? 1 : 0;
+}
+
+int lzm_search_mlp_sampled_plan(const lzm_handle *h, int num_simulations, int hidden, int lstm_hidden, int head_hidden,
+                                int support, int res_dynamics, int32_t *out) {
+  const char *name = "lzm_search_mlp_sampled_plan";
+  if (!h || !out || num_simulations <= 0) return refuse(LZM_ERR_ARG, name, "null argument or no simulations");
+  if (num_simulations > h->sims_cap) return refuse(LZM_ERR_CAPACITY, name, "more simulations than reserved (lzm_reserve)");
+  SampledSearchArgs p;
+  memset(&p, 0, sizeof(p));
+  size_t x1, x2, hd;
+  const MlpPlan pl = sampled_plan(h, hidden, lstm_hidden, head_hidden, support, res_dynamics, num_simulations, p, &x1,
+                                  &x2, &hd);
+  out[0] = pl.R; out[1] = pl.kind; out[2] = 0; out[3] = pl.tree_in_lds;
+  return LZM_OK;
+}
+
+int lzm_search_mlp_sampled(lzm_handle *h, int hidden, int lstm_hidden, int head_hidden, int support, int res_dynamics,
+                           int tanh_mu, const float *weights, int num_simulations, int lstm_horizon_len, int pb_c_base,
+                           float pb_c_init, float discount, float *minmax, const uint32_t *seeds, const int32_t *vtp_in,
+                           float *latent_pool, float *h_pool, float *c_pool, int32_t *rec_x, int32_t *rec_slot,
+                           int32_t *rec_len, int32_t *rec_reset, float *rec_decoded, float *rec_policy,
+                           float *rec_actions, void *stream) {
+  const char *name = "lzm_search_mlp_sampled";
+  const int S = num_simulations;
+  if (!h || !weights || !minmax || !seeds || !vtp_in || !latent_pool || !h_pool || !c_pool || S <= 0)
+    return refuse(LZM_ERR_ARG, name, "null argument or no simulations");
+  int rc = check_kind(name, h, kSampledKind);
+  if (rc != LZM_OK) return rc;
+  if (h->s_dim <= 0) return refuse(LZM_ERR_STATE, name, "not a continuous Sampled EfficientZero handle");
+  if ((uintptr_t)weights & 15)
+    return refuse(LZM_ERR_ARG, name, "weights must be 16-byte aligned (lzm_mlp_sampled_prepare output)");
+  if (pb_c_base <= 0) return refuse(LZM_ERR_ARG, name, "pb_c_base must be positive");
+  if (lstm_horizon_len <= 0) return refuse(LZM_ERR_ARG, name, "lstm_horizon_len must be > 0");
+  if (rec_x && !(rec_slot && rec_len && rec_reset && rec_decoded && rec_policy && rec_actions))
+    return refuse(LZM_ERR_ARG, name, "a record needs all seven record buffers");
+  if (!sampled_shape_ok(h->s_dim, hidden, lstm_hidden, head_hidden, support))
+    return refuse(LZM_ERR_ARG, name, "unsupported network shape (lzm_search_mlp_sampled_supported)");
+  if (S > h->sims_cap) return refuse(LZM_ERR_CAPACITY, name, "more simulations than reserved (lzm_reserve)");
+  SampledSearchArgs p;
+  memset(&p, 0, sizeof(p));
+  size_t x1, x2, hd;
+  const MlpPlan plan = sampled_plan(h, hidden, lstm_hidden, head_hidden, support, res_dynamics, S, p, &x1, &x2, &hd);
+  if (plan.kind < 0) {
+    snprintf(g_err, sizeof(g_err), "%s: %zu B of LDS needed (network or tree too large)", name, plan.lds);
+    return LZM_ERR_ARG;
+  }
+  if ((rc = fill_lut(h, pb_c_base, pb_c_init)) != LZM_OK) return rc;
+  const SampledNet net = sampled_net(hidden, lstm_hidden, h->s_dim, head_hidden, support, res_dynamics);
+  p.stat = h->stat; p.meta = h->meta; p.path = h->path; p.path_act = h->path_act; p.pathlen = h->pathlen;
+  p.lut = h->lut; p.act_f = (float *)h->s_act;
+  p.B = h->B; p.K = h->A; p.D = h->s_dim; p.cap = h->cap; p.lut_n = h->lut_n; p.depth_cap = h->depth_cap;
+  p.S = S; p.disc = discount; p.seeds = seeds; p.vtp_in = vtp_in; p.minmax = (float4 *)minmax;
+  p.pool = latent_pool; p.hpool = h_pool; p.cpool = c_pool;
+  p.H = hidden; p.Hl = lstm_hidden; p.V = support; p.horizon = lstm_horizon_len; p.tanh_mu = tanh_mu ? 1 : 0;
+  p.rec_x = rec_x; p.rec_slot = rec_slot; p.rec_len = rec_len; p.rec_reset = rec_reset;
+  p.rec_dec = rec_decoded; p.rec_policy = rec_policy; p.rec_actions = rec_actions;
+  build_sampled_schedule(p, net, weights, plan.R, x1, x2, hd);
+  LZM_HIP(sampled_mlp_launch(p, plan.R, plan.tree_in_lds != 0, plan.lds, (hipStream_t)stream));
   h->walked = true;
   return LZM_OK;
 }

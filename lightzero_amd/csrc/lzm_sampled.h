@@ -64,8 +64,9 @@ __device__ __forceinline__ float sampled_squash(float mu, float sigma, double z)
 }
 
 // The K sampled vectors of root i's node L from its policy row {mu[D], sigma[D]}: one (slot, dim pair) per lane
-// and round, K * ceil(D / 2) items in all.
-__device__ inline void sampled_draw_continuous(const TreeView &t, const SampledView &sv, int i, int L, const float *row,
+// and round, K * ceil(D / 2) items in all. i: the root's index in the batch of tb roots (the draws' counters and the
+// action table's addressing; the one-launch search's tree view is a slice, its table the whole batch's).
+__device__ inline void sampled_draw_continuous(const SampledView &sv, int tb, int i, int L, const float *row,
                                                uint32_t seed) {
   const int D = sv.D, P = (D + 1) >> 1, n = sv.K * P;
   for (int e = threadIdx.x & 63; e < n; e += 64) {
@@ -73,7 +74,7 @@ __device__ inline void sampled_draw_continuous(const TreeView &t, const SampledV
     const uint4 o = philox4x32_10(make_uint4((uint32_t)L, (uint32_t)i, 2u | ((uint32_t)j << 8), (uint32_t)m),
                                   make_uint2(seed, kSampledKey));
     const double r = sqrt(-2.0 * log(u01(o.x, o.y))), a = 6.283185307179586 * u01(o.z, o.w);
-    float *dst = sv.act_f + (((size_t)L * sv.K + j) * t.B + i) * D;
+    float *dst = sv.act_f + (((size_t)L * sv.K + j) * tb + i) * D;
     dst[d0] = sampled_squash(row[d0], row[D + d0], r * cos(a));
     if (d0 + 1 < D) dst[d0 + 1] = sampled_squash(row[d0 + 1], row[D + d0 + 1], r * sin(a));
   }
@@ -101,9 +102,13 @@ __device__ inline void sampled_draw_discrete(const TreeView &t, const SampledVie
 
 // CNode::expand (:194-452) of node `leaf` of root i as the node of simulation `cur` (0: the root, whose own
 // record the caller writes): K fresh children and their sampled actions. All 64 lanes, wave-uniform arguments.
+// i: the root's index in the tree arrays; root / tb: its index in the batch and the batch's size, which key the
+// draws and address the action table. sampled_expand is the whole-batch form (i == root, tb == t.B); the one-launch
+// search (lzm_search_sampled_mlp.h) expands into a workgroup's slice in LDS (continuous actions only).
 template <bool CONT>
-__device__ inline void sampled_expand(const TreeView &t, const SampledView &sv, int i, int leaf, int to_play, int cur,
-                                      float value_prefix, const float *row, int is_reset, uint32_t seed) {
+__device__ inline void sampled_expand_at(const TreeView &t, const SampledView &sv, int i, int root, int tb, int leaf,
+                                         int to_play, int cur, float value_prefix, const float *row, int is_reset,
+                                         uint32_t seed) {
   const int lane = threadIdx.x & 63;
   if (lane == 0 && cur > 0) {
     NodeMeta m = t.meta[nidx(t, leaf, i)];
@@ -122,8 +127,14 @@ __device__ inline void sampled_expand(const TreeView &t, const SampledView &sv, 
     cm.latent = -1; cm.to_play = 0; cm.best = -1; cm.is_reset = 0;
     t.meta[nidx(t, c, i)] = cm;
   }
-  if (CONT) sampled_draw_continuous(t, sv, i, cur, row, seed);
+  if (CONT) sampled_draw_continuous(sv, tb, root, cur, row, seed);
   else sampled_draw_discrete(t, sv, i, cur, row, seed);
+}
+
+template <bool CONT>
+__device__ inline void sampled_expand(const TreeView &t, const SampledView &sv, int i, int leaf, int to_play, int cur,
+                                      float value_prefix, const float *row, int is_reset, uint32_t seed) {
+  sampled_expand_at<CONT>(t, sv, i, i, t.B, leaf, to_play, cur, value_prefix, row, is_reset, seed);
 }
 
 // CRoots::prepare / prepare_no_noise (:677-715) of root i: the root's record, its legal list 0..K-1 (for the
@@ -167,26 +178,21 @@ struct SampledTraverseArgs {
   float disc;
 };
 
-// cbatch_traverse's walk of root i (:1145-1186) and its request rows, all 64 lanes of one wave.
-template <bool CONT>
-__device__ inline void sampled_traverse_root(const SampledTraverseArgs &p, int i) {
-  const TreeView &t = p.t;
+// cbatch_traverse's walk of root i (:1145-1186), all 64 lanes of one wave, every argument wave-uniform. Writes path,
+// path_act and best_action along the walk and returns {len, the leaf's parent's latent index, the chosen slot of
+// that parent, the leaf's to_play, the leaf}. i: the root's index in the tree arrays; col / ps: where its path
+// lives (path[l * ps + col]); root: its index in the batch, which keys the tie draws. sampled_traverse_root is the
+// whole-batch form (all three the same, ps = t.B); the one-launch search (lzm_search_sampled_mlp.h) walks a
+// workgroup's slice in LDS (stochastic_walk_at's addressing).
+__device__ inline Descent sampled_walk_at(const TreeView &t, int K, int i, int col, int ps, int root, float4 mm,
+                                          int players, int vtp, float disc, uint32_t seed) {
   const int lane = threadIdx.x & 63;
-  const int K = p.sv.K;
   const float Kf = (float)K;
-  const float4 mm = p.minmax[i];
-  const uint32_t seed = *p.seed;
-  const float disc = p.disc;
-  // players = (max(virtual_to_play) == -1) ? 1 : 2 (:1138-1143), by every wave for itself
-  int vmax = INT_MIN;
-  for (int j = lane; j < t.B; j += 64) vmax = max(vmax, p.vtp_in[j]);
-  const int players = xor_max(vmax) == -1 ? 1 : 2;
-  int vtp = p.vtp_in[i];
   int node = 0, len = 0, slot = -1, parent_latent = -1;
   float parent_q = 0.0f;  // per root; the reference's cross-root carry is 0 wherever it is read
   NodeStat s = t.stat[nidx(t, 0, i)];
   NodeMeta m = t.meta[nidx(t, 0, i)];
-  if (lane == 0) t.path[i] = 0;
+  if (lane == 0) t.path[col] = 0;
   while (m.latent >= 0 && len < t.depth_cap - 1) {
     const int latent = __builtin_amdgcn_readfirstlane(m.latent);
     const int base = 1 + K * latent;
@@ -232,7 +238,7 @@ __device__ inline void sampled_traverse_root(const SampledTraverseArgs &p, int i
     const float M = wave_max_dpp(valid ? score : -INFINITY);
     const int r = __ffsll((long long)__ballot(valid && score == M)) - 1;
     uint64_t mask = __ballot(valid && lane > r && score >= M - 0.000001f) | (1ull << (r < 0 ? 0 : r));
-    const uint4 o = philox4x32_10(make_uint4((uint32_t)len, (uint32_t)i, 0u, 0u), make_uint2(seed, kSampledKey));
+    const uint4 o = philox4x32_10(make_uint4((uint32_t)len, (uint32_t)root, 0u, 0u), make_uint2(seed, kSampledKey));
     int k = (int)((o.x >> 1) % (uint32_t)__popcll(mask));
     for (; k > 0; --k) mask &= mask - 1;
     slot = __builtin_amdgcn_readfirstlane(__ffsll((long long)mask) - 1);
@@ -240,8 +246,8 @@ __device__ inline void sampled_traverse_root(const SampledTraverseArgs &p, int i
     const int child = base + slot;
     if (lane == 0) {
       t.meta[nidx(t, node, i)].best = slot;
-      t.path_act[(size_t)len * t.B + i] = slot;
-      t.path[(size_t)(len + 1) * t.B + i] = child;
+      t.path_act[(size_t)len * ps + col] = slot;
+      t.path[(size_t)(len + 1) * ps + col] = child;
     }
     parent_latent = latent;
     node = child;
@@ -251,6 +257,23 @@ __device__ inline void sampled_traverse_root(const SampledTraverseArgs &p, int i
     m.latent = __builtin_amdgcn_readlane(cm.latent, slot);
     m.is_reset = __builtin_amdgcn_readlane(cm.is_reset, slot);
   }
+  Descent d;
+  d.len = len; d.x = parent_latent; d.action = slot; d.vtp = vtp; d.leaf = node;
+  return d;
+}
+
+// cbatch_traverse's walk of root i and its request rows, all 64 lanes of one wave.
+template <bool CONT>
+__device__ inline void sampled_traverse_root(const SampledTraverseArgs &p, int i) {
+  const TreeView &t = p.t;
+  const int lane = threadIdx.x & 63;
+  const int K = p.sv.K;
+  // players = (max(virtual_to_play) == -1) ? 1 : 2 (:1138-1143), by every wave for itself
+  int vmax = INT_MIN;
+  for (int j = lane; j < t.B; j += 64) vmax = max(vmax, p.vtp_in[j]);
+  const int players = xor_max(vmax) == -1 ? 1 : 2;
+  const Descent d = sampled_walk_at(t, K, i, i, t.B, i, p.minmax[i], players, p.vtp_in[i], p.disc, *p.seed);
+  const int len = d.len, parent_latent = d.x, slot = d.action, vtp = d.vtp;
   // the chosen slot's action, straight into the network's input row
   if (len > 0) {
     const size_t e = ((size_t)parent_latent * K + slot) * t.B + i;

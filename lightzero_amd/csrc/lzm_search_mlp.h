@@ -689,8 +689,9 @@ __device__ inline void build_pbt(const float2 *lut, int rows, float *lpbt, int t
 // pre-activations are the gate step's output in LDS, c_prev was staged with the gather. The unmasked h1
 // goes to LDS for the value-prefix head; slot k + 1 of both state pools gets h1 / c1, zeroed for rows
 // whose search_len % lstm_horizon_len == 0 (mcts_ctree.py:810-816). The caller's barrier follows.
-template <int R>
-__device__ __forceinline__ void ez_cell(const SearchArgs &p, float *smem, int k, int i0, int nr, const int *s_len) {
+// (Args: SearchArgs, or the one-launch sampled search's argument struct — the same field names)
+template <int R, class Args>
+__device__ __forceinline__ void ez_cell(const Args &p, float *smem, int k, int i0, int nr, const int *s_len) {
   const int Hl = p.Hl, B = p.B;
   const float *GT = smem + p.off_gates, *CP = smem + p.off_cp;
   float *HH = smem + p.off_hh;

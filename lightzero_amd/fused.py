@@ -10,6 +10,7 @@ packer walks ``dynamics_network.fc_dynamics(_1|_2)``, ``fc_reward_head`` and
 ``prediction_network.fc_{prediction_common,value_head,policy_head}`` and accepts any nesting of
 Linear / BatchNorm1d / ReLU inside them (DI-engine's MLP nests fc blocks).
 """
+import math
 import weakref
 from collections import OrderedDict
 
@@ -116,6 +117,9 @@ def _net_args(dims):
     if "chance" in dims:
         return "lzm_mlp_stoch_", (dims["hidden"], dims["actions"], dims["chance"], dims["head_hidden"],
                                   dims["support"], int(dims["res"]), int(dims["shared"]))
+    if "dim" in dims:  # describe_sampled's
+        return "lzm_mlp_sampled_", (dims["hidden"], dims["lstm_hidden"], dims["dim"], dims["head_hidden"],
+                                    dims["support"], int(dims["res"]))
     if "lstm_hidden" in dims:
         return "lzm_mlp_ez_", (dims["hidden"], dims["lstm_hidden"], dims["actions"], dims["head_hidden"],
                                dims["support"], int(dims["res"]))
@@ -131,6 +135,8 @@ def _pack(layers, dims, device):
     # the kernels' own limits (widths, support + actions, actions <= hidden), asked of the library
     if "chance" in dims:
         ok = L.lzm_search_mlp_stoch_supported(dims["actions"], dims["chance"], *widths)
+    elif "dim" in dims:
+        ok = L.lzm_search_mlp_sampled_supported(dims["dim"], *widths)
     else:
         ok = getattr(L, "lzm_search_mlp_ez_supported" if ez else "lzm_search_mlp_supported")(dims["actions"], *widths)
     if not ok:
@@ -216,6 +222,88 @@ def describe_stochastic(model, dtype=torch.float32):
 
 def pack_stochastic_mlp(model, device):
     return _pack(*describe_stochastic(model), device)
+
+
+SAMPLED_MAX_DIM = 32  # kSampledMaxDim (lzm_sampled.h): a continuous action's dimensions at most
+
+
+def describe_sampled(model, dtype=torch.float32):
+    """describe() for the continuous SampledEfficientZeroModelMLP: returns (layers [((W, b), relu)], dims dict with
+    lstm_hidden, dim and tanh) in the packed order (lzm_mlp_sampled_packed_floats), every entry one dense layer —
+    the dynamics layers on [latent ; action], the gate layer as describe_ez builds it, the value-prefix head,
+    fc_prediction_common, then the merged tail: [fc_value_head[0] | main[0]], main[1] and [fc_value_head[1] | mu |
+    log_sigma] over max(head_hidden, hidden) input columns (a source's columns past its own width are zeros). The
+    policy head is DI-engine's ReparameterizationHead by its submodule names (main, mu, log_sigma_layer); its Linear
+    layers are found by walking those modules. sigma_type 'fixed' packs as a zero block with bias
+    log(fixed_sigma_value). Raises NotPackable for a discrete model, sigma_type 'independent', a fixed sigma outside
+    exp of the clamp [-20, 2], D above kSampledMaxDim, state_norm, and whatever describe_ez refuses of the rest."""
+    dyn = getattr(model, "dynamics_network", None)
+    pred = getattr(model, "prediction_network", None)
+    lstm = getattr(dyn, "lstm", None)
+    if pred is None or not isinstance(lstm, nn.LSTM):
+        raise NotPackable("not a SampledEfficientZeroModelMLP (no dynamics_network.lstm / prediction_network)")
+    if not getattr(model, "continuous_action_space", False):
+        raise NotPackable("discrete action space (the one-launch sampled search serves continuous actions)")
+    if lstm.num_layers != 1 or lstm.bidirectional or not lstm.bias or getattr(lstm, "proj_size", 0):
+        raise NotPackable("reward LSTM must be one unidirectional layer with biases")
+    if getattr(model, "state_norm", False):
+        raise NotPackable("state_norm")
+    head = getattr(pred, "fc_policy_head", None)
+    sigma_type = getattr(head, "sigma_type", None)
+    if sigma_type == "independent":
+        raise NotPackable("sigma_type 'independent' (a state-independent log-sigma parameter without the clamp)")
+    if sigma_type not in ("conditioned", "fixed") or getattr(head, "bound_type", None) not in (None, "tanh"):
+        raise NotPackable("policy head is not a ReparameterizationHead with sigma_type 'conditioned' or 'fixed'")
+    res = bool(getattr(dyn, "res_connection_in_dynamics", False))
+    try:
+        seqs = [dyn.fc_dynamics_1, dyn.fc_dynamics_2] if res else [dyn.fc_dynamics]
+        seqs += [dyn.fc_reward_head, pred.fc_prediction_common, pred.fc_value_head, head.main, head.mu]
+        if sigma_type == "conditioned":
+            seqs.append(head.log_sigma_layer)
+    except AttributeError as e:
+        raise NotPackable(f"not a SampledEfficientZeroModelMLP: {e}") from None
+    groups = [_linear_bn_pairs(q) for q in seqs]
+    expect = [[True, True]] * (2 if res else 1) + [[True, False], [True, True], [True, False], [True, True], [False]]
+    expect += [[False]] if sigma_type == "conditioned" else []
+    if [[r for _, _, r in g] for g in groups] != expect:
+        raise NotPackable("unexpected layer counts or activation placement")
+    if any(bn is not None for g in groups[-(3 if sigma_type == "conditioned" else 2):] for _, bn, _ in g):
+        raise NotPackable("a norm inside the policy head")
+    fold = lambda g: [_fold(l, bn, torch.float64) for l, bn, _ in g]
+    nd = 2 if res else 1
+    dynl = [wb for g in groups[:nd] for wb in fold(g)]
+    rew, common, val, main = (fold(g) for g in groups[nd:nd + 4])
+    mu = fold(groups[nd + 4])[0]
+    H, Hl = dynl[0][0].shape[0], lstm.hidden_size
+    D, F, V = dynl[0][0].shape[1] - H, val[0][0].shape[0], val[1][0].shape[0]
+    if D < 1 or mu[0].shape != (D, H):
+        raise NotPackable("mu's width is not the dynamics network's action width")
+    if D > SAMPLED_MAX_DIM:
+        raise NotPackable(f"action dimension {D} > kSampledMaxDim = {SAMPLED_MAX_DIM}")
+    if lstm.input_size != H or rew[0][0].shape[1] != Hl or rew[1][0].shape[0] != V:
+        raise NotPackable("LSTM input / value-prefix head widths do not match the dynamics network")
+    if sigma_type == "conditioned":
+        ls = fold(groups[nd + 5])[0]
+    else:
+        fixed = float(head.fixed_sigma_value)
+        if not (fixed > 0 and -20.0 <= math.log(fixed) <= 2.0):
+            raise NotPackable(f"fixed_sigma_value {fixed} outside exp of the clamp [-20, 2]")
+        ls = (torch.zeros_like(mu[0]), torch.full_like(mu[1], math.log(fixed)))
+    gate = (torch.cat((lstm.weight_ih_l0.detach().double(), lstm.weight_hh_l0.detach().double()), dim=1),
+            lstm.bias_ih_l0.detach().double() + lstm.bias_hh_l0.detach().double())
+    Km = max(F, H)
+    widen = lambda W: torch.cat((W, W.new_zeros(W.shape[0], Km - W.shape[1])), dim=1)
+    hidden = (torch.cat((val[0][0], main[0][0])), torch.cat((val[0][1], main[0][1])))
+    out = (torch.cat((widen(val[1][0]), widen(mu[0]), widen(ls[0]))), torch.cat((val[1][1], mu[1], ls[1])))
+    layers = ([(wb, True) for wb in dynl] + [(gate, False), (rew[0], True), (rew[1], False)] +
+              [(wb, True) for wb in common] + [(hidden, True), (main[1], True), (out, False)])
+    layers = [((W.to(dtype), b.to(dtype)), relu) for (W, b), relu in layers]
+    return layers, dict(hidden=H, lstm_hidden=Hl, dim=D, head_hidden=F, support=V, res=res,
+                        tanh=getattr(head, "bound_type", None) == "tanh")
+
+
+def pack_sampled_efficientzero_mlp(model, device):
+    return _pack(*describe_sampled(model), device)
 
 
 def prepare_kernel_weights(flat, dims, out=None):

@@ -29,7 +29,8 @@ import torch
 from . import _lib
 from .ctree import ez_tree, ezs_tree, gmz_tree, mz_tree, stochastic_mz_tree
 from .conv_infer import FoldedCache
-from .fused import NotPackable, PackedCache, pack_efficientzero_mlp, pack_stochastic_mlp
+from .fused import (NotPackable, PackedCache, pack_efficientzero_mlp, pack_sampled_efficientzero_mlp,
+                    pack_stochastic_mlp)
 from .scaling_transform import InverseScalarTransform
 from .tree import DeviceTree, new_minmax, next_seed
 from .utils import EasyDict
@@ -1078,7 +1079,10 @@ class SampledEfficientZeroMCTSCtree(_ValuePrefixLSTM, _MCTSCtree):
     (sampling its K actions), backs up and walks the next simulation. No host sync: eager, or one HIP graph with
     cfg.use_hip_graph. Tie draws and sampled actions are per-root Philox streams keyed by the traverse seeds (`seeds`
     as in MuZeroMCTSCtree.search; simulation k's seed keys its walk and its leaf's sampling): the reference seeds its
-    samplers from the wall clock, so there is no stream to be in parity with and no rng_mode."""
+    samplers from the wall clock, so there is no stream to be in parity with and no rng_mode.
+    With cfg.fused_search (read with default False: opt-in) a continuous SampledEfficientZeroModelMLP's whole search
+    runs as one launch (lzm_search_mlp_sampled) where _fused allows it: the same draws under the same seeds, so the
+    same tree and sampled actions given equal policy rows; last_path says which path ran."""
 
     config = dict(
         root_dirichlet_alpha=0.3,
@@ -1096,13 +1100,37 @@ class SampledEfficientZeroMCTSCtree(_ValuePrefixLSTM, _MCTSCtree):
         return ezs_tree.Roots(root_num, legal_action_lis, action_space_size, num_of_sampled_actions,
                               continuous_action_space)
 
+    def __init__(self, cfg: EasyDict = None) -> None:
+        super().__init__(cfg)
+        self._packed = PackedCache(pack=pack_sampled_efficientzero_mlp)
+
     def _net(self, model):
         return model  # (the user's model as it is: nothing is folded or packed)
 
-    def _recorder(self, c):
+    def _fused(self, model, t, Hl, S):
+        """(packed weights, dims) when cfg.fused_search is set (absent: off) and the whole search can run as one
+        lzm_search_mlp_sampled launch: a continuous tree, categorical heads, a SampledEfficientZeroModelMLP-shaped
+        network (fused.describe_sampled) whose action dimension, support and LSTM width are the tree's, the
+        config's and the root state's, of a shape the kernel takes on this tree for S simulations by the library's
+        own launch plan (lzm_search_mlp_sampled_plan); None otherwise (the per-simulation path)."""
+        if not self._cfg.get('fused_search', False) or not self._categorical() or not t.continuous:
+            return None
+        try:
+            packed, dims = self._packed.get(model, t.device)
+        except NotPackable:
+            return None
+        if dims["dim"] != t.act or dims["lstm_hidden"] != Hl or \
+                dims["support"] != 2 * int(self._cfg.model.support_scale) + 1:
+            return None
+        self.last_plan = t.search_mlp_sampled_plan(dims, S)
+        return (packed, dims) if self.last_plan["kernel"] is not None else None
+
+    def _recorder(self, c, width=1):
+        """width: of the policy_logits rows (the one-launch search records each leaf's {mu, sigma} row, 2 D wide;
+        the per-simulation path records none)"""
         if not self.record:
             return None
-        rec = _Recorder(c.S, c.B, 1, c.dev)
+        rec = _Recorder(c.S, c.B, width, c.dev)
         rec.is_reset = torch.zeros((c.S, c.B), dtype=torch.int32, device=c.dev)
         la = c.t.last_actions
         rec.last_actions = torch.zeros((c.S,) + tuple(la.shape), dtype=la.dtype, device=c.dev)
@@ -1146,9 +1174,16 @@ class SampledEfficientZeroMCTSCtree(_ValuePrefixLSTM, _MCTSCtree):
             if not getattr(c.t, "sampled", 0):
                 raise TypeError("SampledEfficientZeroMCTSCtree.search: roots must come from "
                                 "SampledEfficientZeroMCTSCtree.roots")
-            self._buffers(c, model, graph=not self.record and self._cfg.get('use_hip_graph', False))
-            self._stage(c, to_play_batch, seeds, None)
-            rec = self._recorder(c)
-            self._generic(c, model, rec)
+            fz = self._fused(model, c.t, c.extra[0], c.S) if len(c.shape) == 1 else None
+            self._buffers(c, model, graph=fz is None and not self.record and self._cfg.get('use_hip_graph', False))
+            vt, sd = self._stage(c, to_play_batch, seeds, None)
+            rec = self._recorder(c, 1 if fz is None else 2 * c.t.act)
+            if fz is None:
+                self._generic(c, model, rec)
+            else:  # the whole search in one launch
+                packed, dims = fz
+                new_minmax(c.B, self._cfg.value_delta_max, c.dev, out=c.buf.mm)
+                c.t.search_mlp_sampled(dims, packed, c.S, c.buf.mm, sd, vt, c.buf.pool, c.buf.extra[0], c.buf.extra[1],
+                                       self._horizon(), *self._pb_c(), self._discount(), rec=rec)
             self._finish(c, roots, None, rec)
-            self.last_path = "generic"
+            self.last_path = "generic" if fz is None else "fused-mlp"

@@ -288,6 +288,149 @@ class EfficientZeroModelMLP(nn.Module):
         return EZNetworkOutput(value, value_prefix, policy_logits, next_latent_state, hidden)
 
 
+class ReparameterizationHead(nn.Module):
+    """DI-engine's ``ding.model.common.head.ReparameterizationHead`` (not installed here), restated from its source
+    as remembered — submodule names, forward order and constants; not checked against an installed DI-engine:
+    ``main`` = ``layer_num`` Linear(H, H) + activation layers without norm, ``mu = Linear(H, D)``, and by
+    ``sigma_type``: 'conditioned' ``log_sigma_layer = Linear(H, D)`` with sigma = exp(clamp(log_sigma, -20, 2));
+    'independent' a parameter ``log_sigma_param`` [1, D] with sigma = exp(log_sigma_param); 'fixed' a constant row of
+    ``fixed_sigma_value``. ``bound_type='tanh'`` applies tanh to mu. Returns {'mu', 'sigma'}."""
+
+    def __init__(self, input_size: int, output_size: int, layer_num: int = 2, sigma_type: str = 'conditioned',
+                 fixed_sigma_value: float = 1.0, activation: nn.Module = nn.ReLU(), norm_type: Optional[str] = None,
+                 bound_type: Optional[str] = None):
+        super().__init__()
+        assert sigma_type in ('fixed', 'independent', 'conditioned'), sigma_type
+        assert bound_type in ('tanh', None), bound_type
+        assert norm_type is None, "the Sampled EfficientZero models build this head without a norm"
+        self.sigma_type, self.bound_type, self.fixed_sigma_value = sigma_type, bound_type, float(fixed_sigma_value)
+        layers = []
+        for _ in range(layer_num):
+            layers += [nn.Linear(input_size, input_size), activation]
+        self.main = nn.Sequential(*layers)
+        self.mu = nn.Linear(input_size, output_size)
+        if sigma_type == 'fixed':
+            self.register_buffer('sigma', torch.full((1, output_size), float(fixed_sigma_value)), persistent=False)
+        elif sigma_type == 'independent':
+            self.log_sigma_param = nn.Parameter(torch.zeros(1, output_size))
+        else:
+            self.log_sigma_layer = nn.Linear(input_size, output_size)
+
+    def forward(self, x):
+        x = self.main(x)
+        mu = self.mu(x)
+        if self.bound_type == 'tanh':
+            mu = torch.tanh(mu)
+        if self.sigma_type == 'fixed':
+            sigma = self.sigma.to(mu) + torch.zeros_like(mu)
+        elif self.sigma_type == 'independent':
+            sigma = torch.exp(self.log_sigma_param + torch.zeros_like(mu))
+        else:
+            sigma = torch.exp(torch.clamp(self.log_sigma_layer(x), -20, 2))
+        return {'mu': mu, 'sigma': sigma}
+
+
+class SampledPredictionNetworkMLP(nn.Module):
+    """sampled_efficientzero_model_mlp.py:386-521: fc_prediction_common, fc_value_head and, for a continuous action
+    space, a ReparameterizationHead as fc_policy_head (policy = cat(mu, sigma)); an MLP head otherwise."""
+
+    def __init__(self, continuous_action_space: bool, action_space_size: int, num_channels: int,
+                 fc_value_layers: Sequence[int] = (32,), fc_policy_layers: Sequence[int] = (32,),
+                 output_support_size: int = 601, last_linear_layer_init_zero: bool = True,
+                 activation: nn.Module = nn.ReLU(inplace=True), norm_type: Optional[str] = 'BN',
+                 sigma_type: str = 'conditioned', fixed_sigma_value: float = 0.3, bound_type: Optional[str] = None):
+        super().__init__()
+        self.continuous_action_space = continuous_action_space
+        self.fc_prediction_common = mlp(num_channels, num_channels, num_channels, 2, activation, norm_type,
+                                        output_activation=True, output_norm=True)
+        self.fc_value_head = mlp(num_channels, fc_value_layers[0], output_support_size, 2, activation, norm_type,
+                                 output_activation=False, output_norm=False,
+                                 last_linear_layer_init_zero=last_linear_layer_init_zero)
+        if continuous_action_space:
+            self.fc_policy_head = ReparameterizationHead(num_channels, action_space_size, 2, sigma_type,
+                                                         fixed_sigma_value, nn.ReLU(), None, bound_type)
+        else:
+            self.fc_policy_head = mlp(num_channels, fc_policy_layers[0], action_space_size, 2, activation, norm_type,
+                                      output_activation=False, output_norm=False,
+                                      last_linear_layer_init_zero=last_linear_layer_init_zero)
+
+    def forward(self, latent_state):
+        x = self.fc_prediction_common(latent_state)
+        value = self.fc_value_head(x)
+        policy = self.fc_policy_head(x)
+        if self.continuous_action_space:
+            policy = torch.cat([policy['mu'], policy['sigma']], dim=-1)
+        return policy, value
+
+
+class SampledEfficientZeroModelMLP(nn.Module):
+    """Sampled EfficientZero for vector observations (sampled_efficientzero_model_mlp.py:14-384): EfficientZeroModelMLP
+    with, for ``continuous_action_space=True``, the dynamics input [latent ; action] (the action as D floats,
+    ``action_encoding_dim = D``) and DI-engine's ReparameterizationHead as the policy head, ``policy_logits =
+    cat(mu, sigma)``; a discrete space keeps EfficientZeroModelMLP's encodings and MLP policy head. The constructor
+    keywords, ``initial_inference`` / ``recurrent_inference`` and the EZNetworkOutput fields are
+    EfficientZeroModelMLP's. The projection / prediction heads of the self-supervised loss are not restated."""
+
+    def __init__(self, observation_shape: int = 2, action_space_size: int = 6, lstm_hidden_size: int = 512,
+                 latent_state_dim: int = 256, fc_reward_layers=(32,), fc_value_layers=(32,), fc_policy_layers=(32,),
+                 reward_support_size: int = 601, value_support_size: int = 601,
+                 categorical_distribution: bool = True, last_linear_layer_init_zero: bool = True,
+                 state_norm: bool = False, norm_type: Optional[str] = 'BN',
+                 discrete_action_encoding_type: str = 'one_hot', res_connection_in_dynamics: bool = False,
+                 continuous_action_space: bool = False, num_of_sampled_actions: int = 6,
+                 sigma_type: str = 'conditioned', fixed_sigma_value: float = 0.3, bound_type: Optional[str] = None,
+                 **kwargs):
+        super().__init__()
+        self.categorical_distribution = categorical_distribution
+        self.reward_support_size = reward_support_size if categorical_distribution else 1
+        self.value_support_size = value_support_size if categorical_distribution else 1
+        self.continuous_action_space = continuous_action_space
+        self.action_space_size = action_space_size
+        self.num_of_sampled_actions = num_of_sampled_actions
+        assert discrete_action_encoding_type in ('one_hot', 'not_one_hot'), discrete_action_encoding_type
+        self.discrete_action_encoding_type = discrete_action_encoding_type
+        self.action_encoding_dim = action_space_size if (
+            continuous_action_space or discrete_action_encoding_type == 'one_hot') else 1
+        self.lstm_hidden_size = lstm_hidden_size
+        self.latent_state_dim = latent_state_dim
+        self.state_norm = state_norm
+        self.res_connection_in_dynamics = res_connection_in_dynamics
+        self.sigma_type, self.fixed_sigma_value, self.bound_type = sigma_type, fixed_sigma_value, bound_type
+        self.representation_network = RepresentationNetworkMLP(observation_shape, latent_state_dim,
+                                                               norm_type=norm_type)
+        self.dynamics_network = DynamicsNetworkMLP(self.action_encoding_dim,
+                                                   latent_state_dim + self.action_encoding_dim, 2,
+                                                   lstm_hidden_size=lstm_hidden_size,
+                                                   fc_reward_layers=fc_reward_layers,
+                                                   output_support_size=self.reward_support_size,
+                                                   last_linear_layer_init_zero=last_linear_layer_init_zero,
+                                                   norm_type=norm_type,
+                                                   res_connection_in_dynamics=res_connection_in_dynamics)
+        self.prediction_network = SampledPredictionNetworkMLP(
+            continuous_action_space, action_space_size, latent_state_dim, fc_value_layers=fc_value_layers,
+            fc_policy_layers=fc_policy_layers, output_support_size=self.value_support_size,
+            last_linear_layer_init_zero=last_linear_layer_init_zero, norm_type=norm_type, sigma_type=sigma_type,
+            fixed_sigma_value=fixed_sigma_value, bound_type=bound_type)
+
+    _renormalize = staticmethod(EfficientZeroModelMLP._renormalize)
+    initial_inference = EfficientZeroModelMLP.initial_inference
+
+    def recurrent_inference(self, latent_state: torch.Tensor, reward_hidden_state, action: torch.Tensor):
+        if not self.continuous_action_space:
+            return EfficientZeroModelMLP.recurrent_inference(self, latent_state, reward_hidden_state, action)
+        from .model_conv import EZNetworkOutput
+        if action.dim() == 1:  # (batch,) -> (batch, 1); (batch, D, 1) -> (batch, D)  (:332-339)
+            action = action.unsqueeze(-1)
+        elif action.dim() == 3:
+            action = action.squeeze(-1)
+        next_latent_state, hidden, value_prefix = self.dynamics_network(
+            torch.cat((latent_state, action.to(latent_state)), dim=1), reward_hidden_state)
+        if self.state_norm:
+            next_latent_state = EfficientZeroModelMLP._renormalize(next_latent_state)
+        policy_logits, value = self.prediction_network(next_latent_state)
+        return EZNetworkOutput(value, value_prefix, policy_logits, next_latent_state, hidden)
+
+
 class StochasticMuZeroModelMLP(nn.Module):
     """Stochastic MuZero for vector observations (stochastic_muzero_model_mlp.py:14-350, ``initial_inference`` and
     ``recurrent_inference`` of stochastic_muzero_model.py:201-273), discrete one-hot options. Attribute names and

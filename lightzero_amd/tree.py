@@ -427,6 +427,30 @@ class DeviceTree:
              int(dims["res"]), out)
         return dict(roots_per_wg=out[0], kernel={0: "streaming"}.get(out[1]), mode=out[2], tree_in_lds=bool(out[3]))
 
+    def search_mlp_sampled(self, dims, weights, S, minmax, seeds, vtp_in, pool, hpool, cpool, horizon,
+                           pb_c_base=19652, pb_c_init=1.25, discount=0.997, rec=None, stream=None):
+        """One launch for the whole Sampled EfficientZero search of a continuous SampledEfficientZeroModelMLP
+        (lzm_search_mlp_sampled; dims / weights: fused.pack_sampled_efficientzero_mlp's, in the kernel layout) on a
+        tree prepared by sampled_prepare; hpool / cpool: the LSTM state pools [S + 1, B, lstm_hidden] with slot 0 =
+        the roots' state; rec: optional _Recorder-like object with is_reset, policy_logits [S, B, 2 D] and
+        last_actions [S, B, D]."""
+        self._unchecked = True
+        rx, ra, rl, rd, rg = _rec_ptrs(rec)
+        call("lzm_search_mlp_sampled", self.h, dims["hidden"], dims["lstm_hidden"], dims["head_hidden"],
+             dims["support"], int(dims["res"]), int(dims["tanh"]), ptr(weights), int(S), int(horizon), int(pb_c_base),
+             float(pb_c_init), float(discount), ptr(minmax), ptr(seeds), ptr(vtp_in), ptr(pool), ptr(hpool),
+             ptr(cpool), rx, ra, rl, *_rec_ptrs(rec, ("is_reset",)), rd, rg, *_rec_ptrs(rec, ("last_actions",)),
+             stream_ptr(stream))
+
+    def search_mlp_sampled_plan(self, dims, S):
+        """What search_mlp_sampled(dims, ..., S) launches on this handle as it stands (lzm_search_mlp_sampled_plan;
+        host only): dict(roots_per_wg, kernel 'streaming' / None when the kernel refuses the shape, its LDS need or
+        a handle that is no continuous sampled tree, mode 0, tree_in_lds)."""
+        out = (ctypes.c_int32 * 4)()
+        call("lzm_search_mlp_sampled_plan", self.h, int(S), dims["hidden"], dims["lstm_hidden"], dims["head_hidden"],
+             dims["support"], int(dims["res"]), out)
+        return dict(roots_per_wg=out[0], kernel={0: "streaming"}.get(out[1]), mode=out[2], tree_in_lds=bool(out[3]))
+
     def search_conv_gumbel(self, net, S, m, minmax, vtp_in, pool, discount=0.997, categorical=True, rec=None,
                            max_roots=0, stream=None):
         """One launch per root slice for the whole Gumbel MuZero search of a conv MuZeroModel

@@ -24,3 +24,5 @@ echo "# ---- lzm_az_c4.hip (working tree)"
 lines "$root/lightzero_amd/csrc/lzm_az_c4.hip" -Xclang -target-feature -Xclang -packed-fp32-ops
 echo "# ---- lzm_search_stoch_mlp.hip (working tree)"
 lines "$root/lightzero_amd/csrc/lzm_search_stoch_mlp.hip" -Xclang -target-feature -Xclang -packed-fp32-ops
+echo "# ---- lzm_search_sampled_mlp.hip (working tree)"
+lines "$root/lightzero_amd/csrc/lzm_search_sampled_mlp.hip" -Xclang -target-feature -Xclang -packed-fp32-ops

@@ -11,7 +11,13 @@ Three ways to run the same search:
 The host loop runs first in a process of its own, then eager and graph in a second one (each child under its own
 time limit; a failure ends the run). One JSON line.
 
+With --latent the network is the package's continuous SampledEfficientZeroModelMLP (support 601, K = 20) at that
+latent / --lstm width, --dim dimensions and --res residual dynamics, and a third way is timed beside eager and graph:
+  one_launch  the same class with cfg.fused_search (lzm_search_mlp_sampled: the whole search in one kernel launch).
+The host loop is skipped there.
+
     python tools/sampled_search_time.py [--discrete] [--roots 256] [--sims 50] [--reps 15]
+    python tools/sampled_search_time.py --latent 256 --lstm 256 --dim 4 --res [--roots 8] [--sims 25]
 """
 import argparse
 import json
@@ -39,6 +45,21 @@ def setup(B, dim, cont):
             rng.normal(size=(B, LATENT)).astype(np.float32), pol.tolist(), hidden)
 
 
+def setup_mlp(B, dim, latent, lstm, res):
+    """setup()'s tuple with the package's continuous SampledEfficientZeroModelMLP (support 601, random heads)"""
+    import numpy as np
+    import torch
+    from lightzero_amd.model_mlp import SampledEfficientZeroModelMLP
+    torch.manual_seed(0)
+    rng = np.random.default_rng(1)
+    pol = np.concatenate([rng.normal(size=(B, dim)), rng.uniform(0.3, 1.0, size=(B, dim))], 1).astype(np.float32)
+    hidden = (np.zeros((1, B, lstm), np.float32), np.zeros((1, B, lstm), np.float32))
+    model = SampledEfficientZeroModelMLP(observation_shape=4, action_space_size=dim, lstm_hidden_size=lstm,
+                                         latent_state_dim=latent, continuous_action_space=True,
+                                         last_linear_layer_init_zero=False, res_connection_in_dynamics=res)
+    return model.cuda().eval(), rng.normal(size=(B, latent)).astype(np.float32), pol.tolist(), hidden
+
+
 def median_ms(fn, reps):
     import torch
     times = []
@@ -52,14 +73,16 @@ def median_ms(fn, reps):
     return statistics.median(times)
 
 
-def class_search(B, S, K, dim, cont, graph, inputs=None, record=False):
-    """run(seeds=None, prepare_seed=None) -> (roots, mcts); inputs, seeds: as host_search's"""
+def class_search(B, S, K, dim, cont, graph, inputs=None, record=False, fused=False, support=SUPPORT):
+    """run(seeds=None, prepare_seed=None) -> (roots, mcts); inputs, seeds: as host_search's; fused: cfg.fused_search;
+    support: the network's support size"""
     from lightzero_amd import SampledEfficientZeroMCTSCtree
     from lightzero_amd.utils import EasyDict
     model, lat, pol, hidden = inputs or setup(B, dim, cont)
     mcts = SampledEfficientZeroMCTSCtree(EasyDict(
         num_simulations=S, discount_factor=0.997, device="cuda", use_hip_graph=graph, lstm_horizon_len=HORIZON,
-        model=EasyDict(support_scale=SUPPORT // 2, categorical_distribution=True, continuous_action_space=cont)))
+        fused_search=fused,
+        model=EasyDict(support_scale=support // 2, categorical_distribution=True, continuous_action_space=cont)))
     roots, mcts.record = mcts.roots(B, [[-1]] * B, dim, K, cont), record
 
     def run(seeds=None, prepare_seed=None):
@@ -114,9 +137,24 @@ def main():
     ap.add_argument("--sims", type=int, default=50)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--discrete", action="store_true")
+    ap.add_argument("--latent", type=int, default=0)
+    ap.add_argument("--lstm", type=int, default=128)
+    ap.add_argument("--dim", type=int, default=3)
+    ap.add_argument("--res", action="store_true")
     ap.add_argument("--child", choices=("host", "device"))
     a = ap.parse_args()
     K, dim, cont = (5, 18, False) if a.discrete else (20, 3, True)
+    if a.latent:  # the package's MLP model: eager, graph and the one launch in this process
+        inputs = setup_mlp(a.roots, a.dim, a.latent, a.lstm, a.res)
+        out = {"roots": a.roots, "sims": a.sims, "K": 20, "dim": a.dim, "latent": a.latent, "lstm": a.lstm,
+               "res": a.res, "reps": a.reps}
+        for name, graph, fused in (("eager_ms", False, False), ("graph_ms", True, False), ("one_launch_ms", False, True)):
+            run = class_search(a.roots, a.sims, 20, a.dim, True, graph, inputs, fused=fused, support=601)
+            out[name] = median_ms(run, a.reps)
+            out[name.replace("_ms", "_path")] = run()[1].last_path
+        out["graph_vs_one_launch"] = out["graph_ms"] / out["one_launch_ms"]
+        print(json.dumps(out))
+        return
     if a.child == "host":
         print(json.dumps({"host_loop_ms": median_ms(host_search(a.roots, a.sims, K, dim, cont), a.reps)}))
         return
