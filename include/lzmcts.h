@@ -523,6 +523,17 @@ int64_t lzm_az_c4_net_floats(int nres);
 int lzm_az_c4_net_prepare(int nres, const float *raw, float *out_host);
 int lzm_az_c4_net_eval(int nres, const float *weights, const float *state, int n, float *probs, float *value,
                        void *stream);
+/* The same network with its 64 -> 64 3x3 layers and 1x1 heads on split-fp16 MFMA (lzm_az_c4_net_split.h; every
+ * f32 operand as two fp16 terms, three products per term pair, error at the f32 level). lzm_az_c4_net_split_prepare
+ * takes the same `raw` and writes lzm_az_c4_net_split_floats(nres) floats: the fragments, each weight row's 2^-e_c
+ * and each layer's {max row L1 norm, max |bias|}. lzm_az_c4_net_split_eval is graph-capturable like
+ * lzm_az_c4_net_eval; range_err (device int32, caller-zeroed, required) gains 1 per position whose activations
+ * left the split's range (non-finite, or beyond ~2^114); such a position's outputs are not meaningful. A position's
+ * output bits do not depend on n or on its place in the batch. */
+int64_t lzm_az_c4_net_split_floats(int nres);
+int lzm_az_c4_net_split_prepare(int nres, const float *raw, float *out_host);
+int lzm_az_c4_net_split_eval(int nres, const float *weights, const float *state, int n, float *probs, float *value,
+                             int32_t *range_err, void *stream);
 
 /* ---- convolutional recurrent trunk (configs 3 / 5: conv MuZeroModel / EfficientZeroModel) --------
  * The conv part of recurrent_inference (muzero_model.py:505-530, efficientzero_model.py:526-574,

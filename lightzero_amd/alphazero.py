@@ -100,9 +100,17 @@ class Connect4AZNet:
     """The Connect4 AlphaZeroModel (model_az.connect4_alphazero_model's structure) packed for lzm_az_c4_net_eval:
     BatchNorm folded, MFMA B-fragment order (lzm_az_c4_net_prepare). Supported: observation (3, 6, 7), 64
     channels, 1 or 2 residual blocks per network, head channels 16, head width 32, 7 actions, scalar value (the
-    Connect4 config); anything else raises ValueError."""
+    Connect4 config); anything else raises ValueError.
 
-    def __init__(self, model, device="cuda"):
+    precision="f32" (the default) is the exact-f32 MFMA kernel; "split" packs with lzm_az_c4_net_split_prepare and
+    runs lzm_az_c4_net_split_eval (lzm_az_c4_net_split.h: the 64 -> 64 layers on fp16 MFMA, every operand as two
+    fp16 terms, error at the f32 level). range_errors() then counts the positions whose activations left the split's
+    range since construction (non-finite weights or inputs, magnitudes beyond ~2^114); always 0 for "f32"."""
+
+    def __init__(self, model, device="cuda", precision="f32"):
+        if precision not in ("f32", "split"):
+            raise ValueError(f"precision must be 'f32' or 'split', not {precision!r}")
+        self.precision = precision
         m = model
         nres = len(m.rep_blocks)
         ok = (nres in (1, 2) and len(m.pred_blocks) == nres and m.conv.out_channels == 64 and m.conv.in_channels == 3
@@ -130,9 +138,11 @@ class Connect4AZNet:
             for fc in (m.fc_value_head, m.fc_policy_head):
                 parts += [fc[0].weight, fc[0].bias, fc[1].weight, fc[1].bias, fc[3].weight, fc[3].bias]
             raw = torch.cat([p.detach().float().cpu().reshape(-1) for p in parts]).contiguous()
-        out = torch.zeros(int(_lib.load().lzm_az_c4_net_floats(nres)), dtype=torch.float32)
-        call("lzm_az_c4_net_prepare", nres, ctypes.c_void_p(raw.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+        fn = "lzm_az_c4_net_split_" if precision == "split" else "lzm_az_c4_net_"
+        out = torch.zeros(int(getattr(_lib.load(), fn + "floats")(nres)), dtype=torch.float32)
+        call(fn + "prepare", nres, ctypes.c_void_p(raw.data_ptr()), ctypes.c_void_p(out.data_ptr()))
         self.weights = out.to(device)
+        self._range_err = torch.zeros(1, dtype=torch.int32, device=device) if precision == "split" else None
 
     def compute_policy_value(self, state):
         """state [n, 3, 6, 7] -> (probs [n, 7], value [n, 1]); one launch"""
@@ -140,8 +150,16 @@ class Connect4AZNet:
         n = st.shape[0]
         probs = torch.empty((n, 7), dtype=torch.float32, device=st.device)
         value = torch.empty((n, 1), dtype=torch.float32, device=st.device)
-        call("lzm_az_c4_net_eval", self.nres, ptr(self.weights), ptr(st), n, ptr(probs), ptr(value), stream_ptr())
+        if self.precision == "split":
+            call("lzm_az_c4_net_split_eval", self.nres, ptr(self.weights), ptr(st), n, ptr(probs), ptr(value),
+                 ptr(self._range_err), stream_ptr())
+        else:
+            call("lzm_az_c4_net_eval", self.nres, ptr(self.weights), ptr(st), n, ptr(probs), ptr(value), stream_ptr())
         return probs, value
+
+    def range_errors(self):
+        """positions whose activations left the split kernel's range so far (synchronises)"""
+        return 0 if self._range_err is None else int(self._range_err.item())
 
 
 class AlphaZeroMCTS:

@@ -1,4 +1,4 @@
-// lzm_az_c4.hip — the Connect4 AlphaZero kernels (lzm_az_c4.h, lzm_az_c4_net.h) and their launchers. Argument
+// lzm_az_c4.hip — the Connect4 AlphaZero kernels (lzm_az_c4.h, lzm_az_c4_net.h, lzm_az_c4_net_split.h) and their launchers. Argument
 // checks, the workspace carve and the error text live with the C entry points in lzm_kernels.hip.
 #include <hip/hip_runtime.h>
 
@@ -6,6 +6,8 @@
 
 #include "lzm_az_c4.h"
 #include "lzm_az_c4_net.h"
+#define LZM_DEVICE_HELPERS_ONLY  // lzm_conv.h's split-scheme helpers without its kernels (lzm_kernels.hip's)
+#include "lzm_az_c4_net_split.h"
 
 namespace lzm {
 
@@ -67,6 +69,35 @@ static hipError_t c4_net_launch(const float *w, const float *state, int n, float
 hipError_t c4_launch_net_eval(int nres, const float *w, const float *state, int n, float *probs, float *value,
                               hipStream_t s) {
   return nres == 1 ? c4_net_launch<1>(w, state, n, probs, value, s) : c4_net_launch<2>(w, state, n, probs, value, s);
+}
+
+template <int NRES, int P>
+static hipError_t c4_net_split_launch(const float *w, const float *state, int n, float *probs, float *value,
+                                      int32_t *err, hipStream_t s) {
+  constexpr size_t lds = (size_t)C4s<P>::lds_bytes;
+  static std::atomic<bool> attr[64];  // per device ordinal, as c4_net_launch
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (dev < 0 || dev >= 64 || !attr[dev].load(std::memory_order_acquire)) {
+    e = hipFuncSetAttribute((const void *)c4_net_eval_split_kernel<NRES, P>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds);
+    if (e != hipSuccess) return e;
+    if (dev >= 0 && dev < 64) attr[dev].store(true, std::memory_order_release);
+  }
+  hipLaunchKernelGGL((c4_net_eval_split_kernel<NRES, P>), dim3((n + P - 1) / P), dim3(kC4nThreads), lds, s, w, state, n,
+                     probs, value, err);
+  return hipGetLastError();
+}
+
+hipError_t c4_launch_net_split_eval(int nres, int boards, const float *w, const float *state, int n, float *probs,
+                                    float *value, int32_t *err, hipStream_t s) {
+  if (boards == 0) boards = kC4sBoards;
+  if (boards == 2)
+    return nres == 1 ? c4_net_split_launch<1, 2>(w, state, n, probs, value, err, s)
+                     : c4_net_split_launch<2, 2>(w, state, n, probs, value, err, s);
+  return nres == 1 ? c4_net_split_launch<1, 4>(w, state, n, probs, value, err, s)
+                   : c4_net_split_launch<2, 4>(w, state, n, probs, value, err, s);
 }
 
 }  // namespace lzm

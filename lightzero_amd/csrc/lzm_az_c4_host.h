@@ -63,6 +63,36 @@ __host__ __device__ inline C4NetLayout c4_net_layout(int nres) {
   return L;
 }
 
+// prepared weight buffer of the split-fp16 network (lzm_az_c4_net_split.h, lzm_az_c4_net_split_prepare): conv0,
+// fc1 and the tails as above; the 64 -> 64 layers and the 1x1 heads as lzm_conv.h's split fragments
+constexpr int kC4sFrag3 = 4 * 18 * 2 * 64 * 4;  // floats: [wave 4][chunk 18][term 2][lane 64][8 fp16]
+constexpr int kC4sFrag1 = 2 * 2 * 2 * 64 * 4;   // floats: [N tile 2][chunk 2][term 2][lane 64][8 fp16]
+constexpr int kC4sWExp = 48;                    // weight-row scale exponents within +-48 (lzm_az_c4_net_split.h)
+constexpr int kC4sBoards = 2;                   // positions per workgroup by default
+struct C4SplitLayout {
+  int conv0, conv0_b;
+  int conv;               // [layer] kC4sFrag3
+  int conv_b, conv_inv;   // bias [layers][64], 2^-e_c [layers][64]
+  int conv_bd;            // [layers] {Wb = max row L1 norm, Bb = max |bias|, 0, 0}
+  int head, head_b, head_inv;  // kC4sFrag1, bias [32], 2^-e_c [32]
+  int fc1, tail_v, tail_p;
+  int total;
+};
+
+__host__ __device__ inline C4SplitLayout c4_split_layout(int nres) {
+  C4SplitLayout L;
+  int o = 0;
+  auto take = [&](int n) { int r = o; o += (n + 3) & ~3; return r; };
+  L.conv0 = take(4 * 9 * 64); L.conv0_b = take(64);
+  L.conv = take(4 * nres * kC4sFrag3);
+  L.conv_b = take(4 * nres * 64); L.conv_inv = take(4 * nres * 64); L.conv_bd = take(4 * nres * 4);
+  L.head = take(kC4sFrag1); L.head_b = take(32); L.head_inv = take(32);
+  L.fc1 = take(2 * 84 * 64 * 4);
+  L.tail_v = take(kC4nTv2b + 1); L.tail_p = take(kC4nTp2b + 7);
+  L.total = o;
+  return L;
+}
+
 // launchers (lzm_az_c4.hip); each returns the launch's status
 hipError_t c4_launch_begin(const C4Tree &t, const int32_t *boards, const int32_t *start_index, float *state,
                            hipStream_t s);
@@ -74,5 +104,8 @@ hipError_t c4_launch_export(const C4Tree &t, int32_t *visit, float *vsum, int32_
 hipError_t c4_launch_done_winner(const int32_t *boards, int n, int32_t *out, hipStream_t s);
 hipError_t c4_launch_net_eval(int nres, const float *w, const float *state, int n, float *probs, float *value,
                               hipStream_t s);
+// boards: positions per workgroup, 2 or 4 (0: the default)
+hipError_t c4_launch_net_split_eval(int nres, int boards, const float *w, const float *state, int n, float *probs,
+                                    float *value, int32_t *err, hipStream_t s);
 
 }  // namespace lzm

@@ -736,7 +736,7 @@ __global__ __launch_bounds__(kCvThreads) __attribute__((amdgpu_waves_per_eu(1, 1
 // host packing for the split trunk (every weight row scaled, the layer's bounds). 3x3: W[64 out][64 in][9] ->
 // [wave][chunk s][term][lane][8]: chunk s = 2 * tap + j, lane -> (out 16 * wave + (lane & 15), in 32 j + 8 (lane >>
 // 4) + e); inv[64] = 2^-e_c; bd[0] = Wb
-inline int bx_row_exp(const float *row, int n, double *l1) {
+inline int bx_row_exp(const float *row, int n, double *l1, int lim = kBxWExp) {
   float m = 0.f;
   double s = 0.0;
   for (int k = 0; k < n; ++k) {
@@ -745,18 +745,18 @@ inline int bx_row_exp(const float *row, int n, double *l1) {
     s += v;
   }
   *l1 = s;
-  return m > 0.f ? bx_scale_exp(m, kBxWExp) : 0;
+  return m > 0.f ? bx_scale_exp(m, lim) : 0;
 }
 // a float >= the double x (the bounds are upper bounds)
 inline float bx_round_up(double x) { return (float)(x * (1.0 + 1e-6)); }
 
-inline void bx_pack3(const float *W, float *outf, float *inv, float *bd) {
+inline void bx_pack3(const float *W, float *outf, float *inv, float *bd, int lim = kBxWExp) {
   uint16_t *out = reinterpret_cast<uint16_t *>(outf);
   int e[64];
   double wb = 0.0;
   for (int co = 0; co < 64; ++co) {
     double l1;
-    e[co] = bx_row_exp(W + co * 64 * 9, 64 * 9, &l1);
+    e[co] = bx_row_exp(W + co * 64 * 9, 64 * 9, &l1, lim);
     inv[co] = bx_pow2(-e[co]);
     wb = l1 > wb ? l1 : wb;
   }

@@ -3943,6 +3943,51 @@ int lzm_az_c4_net_eval(int nres, const float *weights, const float *state, int n
   return LZM_OK;
 }
 
+int64_t lzm_az_c4_net_split_floats(int nres) { return nres == 1 || nres == 2 ? c4_split_layout(nres).total : -1; }
+
+int lzm_az_c4_net_split_prepare(int nres, const float *raw, float *out) {
+  if ((nres != 1 && nres != 2) || !raw || !out) {
+    set_err("lzm_az_c4_net_split_prepare: num_res_blocks must be 1 or 2");
+    return LZM_ERR_ARG;
+  }
+  // conv0, the biases, FC1 and the tails are the f32 network's blocks
+  const C4NetLayout F = c4_net_layout(nres);
+  const C4SplitLayout L = c4_split_layout(nres);
+  std::vector<float> f32((size_t)F.total);
+  if (lzm_az_c4_net_prepare(nres, raw, f32.data()) != LZM_OK) return LZM_ERR_ARG;
+  memset(out, 0, sizeof(float) * (size_t)L.total);
+  auto copy = [&](int dst, int src, int nf) { memcpy(out + dst, f32.data() + src, sizeof(float) * (size_t)nf); };
+  copy(L.conv0, F.conv0, 4 * 9 * 64);
+  copy(L.conv0_b, F.conv0_b, 64);
+  copy(L.conv_b, F.conv_b, 4 * nres * 64);
+  copy(L.head_b, F.head_b, 32);
+  copy(L.fc1, F.fc1, 2 * 84 * 64 * 4);
+  copy(L.tail_v, F.tail_v, kC4nTv2b + 1);
+  copy(L.tail_p, F.tail_p, kC4nTp2b + 7);
+  const float *p = raw + 64 * 27 + 64;
+  for (int l = 0; l < 4 * nres; ++l) {  // W [64 out][64 in][9], bias [64]
+    float *bd = out + L.conv_bd + 4 * l;
+    bx_pack3(p, out + L.conv + (size_t)l * kC4sFrag3, out + L.conv_inv + l * 64, bd, kC4sWExp);
+    bd[1] = bx_bias_bound(p + 64 * 576, 64);
+    p += 64 * 576 + 64;
+  }
+  float hbd[4];
+  bx_pack1(p, 32, out + L.head, out + L.head_inv, hbd);
+  return LZM_OK;
+}
+
+int lzm_az_c4_net_split_eval(int nres, const float *weights, const float *state, int n, float *probs, float *value,
+                             int32_t *range_err, void *stream) {
+  if ((nres != 1 && nres != 2) || !weights || !state || n <= 0 || !probs || !value || !range_err) {
+    set_err("lzm_az_c4_net_split_eval: need num_res_blocks 1 or 2, n > 0 and all buffers (range_err included)");
+    return LZM_ERR_ARG;
+  }
+  const char *e = getenv("LZM_C4_SPLIT_BOARDS");  // "2" / "4": that instantiation (timing experiments)
+  const int boards = e && (atoi(e) == 2 || atoi(e) == 4) ? atoi(e) : 0;
+  LZM_C4_LAUNCH(c4_launch_net_split_eval(nres, boards, weights, state, n, probs, value, range_err, (hipStream_t)stream));
+  return LZM_OK;
+}
+
 }  // extern "C"
 
 // ---- fused AlphaZero search (lzm_az_fused.h)

@@ -2,7 +2,7 @@
 (Connect4AZNet.compute_policy_value) and with the torch module's compute_policy_value on the GPU.
 
 Per shape the two variants alternate three times; each turn times five searches with device events and keeps
-their median. Raw runs go to --out as JSON, the summary to stdout. With --net-only N it only runs the HIP
+their median. With --precision split the two variants are the f32 and the split-fp16 HIP networks (five turns). Raw runs go to --out as JSON, the summary to stdout. With --net-only N it only runs the HIP
 network N times at --positions (512) positions (for a kernel trace: rocprofv3 --kernel-trace --stats -- python ...
 --net-only 50).
 """
@@ -53,10 +53,12 @@ def main():
     ap.add_argument("--out", default="az_connect4_time.json")
     ap.add_argument("--net-only", type=int, default=0)
     ap.add_argument("--positions", type=int, default=512, help="batch of the --net-only calls")
+    ap.add_argument("--precision", choices=["f32", "split"], default="f32",
+                    help="the HIP network's kernel; split: the searches alternate f32 and split instead of hip and torch")
     args = ap.parse_args()
     torch.manual_seed(0)
     model = connect4_alphazero_model().cuda()
-    net = Connect4AZNet(model)
+    net = Connect4AZNet(model, precision=args.precision)
     if args.net_only:
         x = torch.rand(args.positions, 3, 6, 7, device="cuda")
         for _ in range(args.net_only):
@@ -64,6 +66,8 @@ def main():
         torch.cuda.synchronize()
         return
     variants = {"hip": net.compute_policy_value, "torch": model.compute_policy_value}
+    if args.precision == "split":
+        variants = {"f32": Connect4AZNet(model).compute_policy_value, "split": net.compute_policy_value}
     result = {"sims": SIMS, "flop_per_call_512": 512 * FLOP_PER_POSITION, "runs": []}
     for B in (512, 8):
         bd, st = boards(B)
@@ -72,7 +76,7 @@ def main():
             for _ in range(3):
                 mcts[k].get_next_actions(bd, st, pv, 1.0, True)
         torch.cuda.synchronize()
-        for turn in range(3):
+        for turn in range(5 if args.precision == "split" else 3):
             for k, pv in variants.items():
                 ms = time_search(mcts[k], bd, st, pv)
                 result["runs"].append({"B": B, "variant": k, "turn": turn, "ms": ms})
