@@ -535,6 +535,32 @@ int lzm_az_c4_net_split_prepare(int nres, const float *raw, float *out_host);
 int lzm_az_c4_net_split_eval(int nres, const float *weights, const float *state, int n, float *probs, float *value,
                              int32_t *range_err, void *stream);
 
+/* ---- the conv StochasticMuZeroModel's recurrent step (the 2048 config: latent 64 x 4 x 4, num_res_blocks 1 or 2
+ * per sub-network, head channels 16, one hidden layer of 32, 1 <= A, C <= 64, categorical heads with odd V <= 601,
+ * eval-mode BatchNorm and ReLU), one launch per simulation over B roots (lzm_smz_conv.h).
+ * lzm_smz_conv_net_prepare(nres, A, C, V, raw, out) folds nothing: it permutes, on the host, `raw` = two sets, the
+ * decision leaves' (dynamics_network + prediction_network) then the chance leaves' (afterstate_dynamics_network +
+ * afterstate_prediction_network), each
+ *   (1 + 4 nres) x { conv W[64][64][9] (out, in, tap; BatchNorm folded), b[64] } (the dynamics convolution over the
+ *   64 latent channels, the dynamics blocks' conv1, conv2, then the prediction's);  edge[16][64] (cell, out: the sum
+ *   of the option plane's folded taps that fall inside the board at that cell);  per head (decision: reward, value,
+ *   policy; chance: value, policy): 1x1 W[16][64], b[16] (folded), FC1 W[32][256], b[32] (BatchNorm1d folded),
+ *   FC2 W[n][32], b[n] with n = V, V and A (decision) or C (chance)
+ * into lzm_smz_conv_net_floats(nres, A, C, V) floats (MFMA B-fragment order, zero padding; -1: a refused shape),
+ * to be copied to the device.
+ * lzm_smz_conv_net_step: root i's leaf latent is pool[x[i]][i] (pool float[nslots][B][1024]; a root whose x[i] is
+ * outside [0, nslots) is skipped), its kind is_chance[i], its option option[i] (entering as option / A for a chance
+ * leaf, option / C for a decision leaf, divided in f32). Written per root: latent[i] (1024), value[i] (V), and
+ * reward[i] (V), policy_d[i] (A) for a decision leaf or policy_c[i] (C) for a chance leaf; the other rows stay
+ * as they were. positions: per workgroup, 1 or 2 (0: the default, or LZM_SMZ_CONV_POSITIONS for experiments). A
+ * root's output bits do not depend on B, on positions, on its place in the batch or on its neighbours' kinds.
+ * Graph-capturable. LZM_ERR_ARG, nothing launched, for a refused shape or a null buffer. */
+int64_t lzm_smz_conv_net_floats(int nres, int A, int C, int V);
+int lzm_smz_conv_net_prepare(int nres, int A, int C, int V, const float *raw, float *out_host);
+int lzm_smz_conv_net_step(int nres, int A, int C, int V, const float *weights, const float *pool, int nslots, int B,
+                          const int32_t *x, const int32_t *option, const int32_t *is_chance, float *latent,
+                          float *value, float *reward, float *policy_d, float *policy_c, int positions, void *stream);
+
 /* ---- convolutional recurrent trunk (configs 3 / 5: conv MuZeroModel / EfficientZeroModel) --------
  * The conv part of recurrent_inference (muzero_model.py:505-530, efficientzero_model.py:526-574,
  * common.py:854-881) with eval BatchNorm folded, one workgroup per env (lzm_conv.h): dynamics conv over

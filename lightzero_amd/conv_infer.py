@@ -45,6 +45,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from .fused import NotPackable
 
 
 class NotFoldable(Exception):
@@ -743,6 +744,121 @@ class FoldedConvInitial:
             return EZNetworkOutput(value, [0. for _ in range(B)], policy, latent, (z, z.clone()))
         from .model_mlp import MZNetworkOutput
         return MZNetworkOutput(value, [0. for _ in range(B)], policy, latent)
+
+
+def fold_stochastic_conv(model):
+    """The conv StochasticMuZeroModel's recurrent step with every BatchNorm folded (in float64), as the two sets
+    lzm_smz_conv_net_prepare takes: [decision, chance], each a dict with ``convs`` [(W [64, 64, 3, 3], b [64])] (the
+    dynamics convolution over the 64 latent channels, the dynamics blocks' conv1 / conv2, the prediction's), ``edge``
+    [16, 64] (cell, out: the option plane's folded taps that fall inside the board), ``heads`` {name: (1x1 W
+    [16, 64], b, FC1 W [32, 256], b, FC2 W [n, 32], b)} (decision: reward, value, policy; chance: value, policy) and
+    ``space`` (what the option is divided by). Raises NotPackable for a model the kernel does not take."""
+    try:
+        pairs = ((model.dynamics_network, model.prediction_network, model.chance_space_size),
+                 (model.afterstate_dynamics_network, model.afterstate_prediction_network, model.action_space_size))
+        if model.training:
+            raise NotPackable("eval-mode BatchNorm only")
+        if not getattr(model, "categorical_distribution", True) or getattr(model, "state_norm", False):
+            raise NotPackable("categorical heads without state_norm only")
+        sets = []
+        for kind, (dyn, pred, space) in enumerate(pairs):
+            if tuple(dyn.conv.weight.shape) != (64, 65, 3, 3) or len(dyn.resblocks) not in (1, 2) \
+                    or len(pred.resblocks) != len(dyn.resblocks) or not isinstance(dyn.activation, torch.nn.ReLU) \
+                    or not isinstance(pred.activation, torch.nn.ReLU):
+                raise NotPackable("64 channels, 1 or 2 ReLU residual blocks per sub-network")
+            bn_v, bn_p = (pred.bn_value, pred.bn_policy) if kind else (pred.norm_value, pred.norm_policy)
+            w, b = _fold(dyn.conv.weight, None, dyn.bn)
+            convs = [(w[:, :64], b)]
+            for blocks in (dyn.resblocks, pred.resblocks):
+                for c1, c2 in _resblocks(blocks):
+                    convs += [c1, c2]
+            ones = torch.ones(1, 1, 4, 4, dtype=torch.float64, device=w.device)
+            edge = F.conv2d(ones, w[:, 64:], None, padding=1)[0].reshape(64, 16).t().contiguous()
+            heads = OrderedDict()
+            for name, conv, bn, fc in (("reward", dyn.conv1x1_reward, dyn.bn_reward, dyn.fc_reward_head),
+                                       ("value", pred.conv1x1_value, bn_v, pred.fc_value),
+                                       ("policy", pred.conv1x1_policy, bn_p, pred.fc_policy)):
+                if kind and name == "reward":
+                    continue  # (a chance node's reward is 0)
+                cw, cb = _fold(conv.weight, conv.bias, bn)
+                (w1, b1), (w2, b2) = _mlp_linears(fc)
+                if tuple(cw.shape[:2]) != (16, 64) or tuple(w1.shape) != (32, 256) or w2.shape[1] != 32:
+                    raise NotPackable("head channels 16 on a 4 x 4 latent, one hidden layer of 32")
+                heads[name] = (cw.reshape(16, 64), cb, w1, b1, w2, b2)
+            sets.append(dict(convs=convs, edge=edge, heads=heads, space=int(space)))
+    except (AttributeError, NotFoldable) as e:
+        raise NotPackable(f"not a conv StochasticMuZeroModel the kernel takes: {e}")
+    A, C = sets[0]["heads"]["policy"][4].shape[0], sets[1]["heads"]["policy"][4].shape[0]
+    V = sets[0]["heads"]["value"][4].shape[0]
+    if sets[0]["heads"]["reward"][4].shape[0] != V or sets[1]["heads"]["value"][4].shape[0] != V \
+            or len(sets[0]["convs"]) != len(sets[1]["convs"]) or (sets[0]["space"], sets[1]["space"]) != (C, A):
+        raise NotPackable("the two halves' depths, supports or option spaces differ")
+    dims = dict(nres=(len(sets[0]["convs"]) - 1) // 4, A=int(A), C=int(C), V=int(V))
+    if _lib.load().lzm_smz_conv_net_floats(dims["nres"], dims["A"], dims["C"], dims["V"]) < 0:
+        raise NotPackable(f"shape outside the kernel's range: {dims}")
+    return sets, dims
+
+
+class StochasticConvNet:
+    """The conv StochasticMuZeroModel's recurrent step as one HIP launch per simulation (csrc/lzm_smz_conv.h):
+    ``step`` reads each root's leaf kind, leaf latent (straight from the search's latent pool) and option on the
+    device and runs that kind's half only. Raises NotPackable for a model the kernel does not take. The device blob
+    is re-prepared in place when the model's tensors change (``refresh``), so captured graphs keep valid pointers."""
+
+    def __init__(self, model, device=None):
+        self.model = weakref.ref(model)
+        self.device = torch.device(device) if device is not None else next(model.parameters()).device
+        self.blob = None
+        self._pack(model)
+
+    @staticmethod
+    def _version(model):
+        return tuple(t._version for t in list(model.parameters()) + list(model.buffers()))
+
+    def _pack(self, model):
+        sets, dims = fold_stochastic_conv(model)
+        raw = torch.cat([t.reshape(-1) for s in sets for t in
+                         [x for wb in s["convs"] for x in wb] + [s["edge"]] + [x for h in s["heads"].values() for x in h]]
+                        ).float().cpu().contiguous()
+        d = (dims["nres"], dims["A"], dims["C"], dims["V"])
+        host = torch.empty(_lib.load().lzm_smz_conv_net_floats(*d), dtype=torch.float32)
+        _lib.call("lzm_smz_conv_net_prepare", *d, _lib.ptr(raw), _lib.ptr(host))
+        if self.blob is None or dims != self.dims:
+            self.blob = host.to(self.device)
+        else:
+            self.blob.copy_(host)
+        self.dims, self._d, self.version = dims, d, self._version(model)
+
+    def refresh(self):
+        model = self.model()
+        if model is not None and self._version(model) != self.version:
+            self._pack(model)
+
+    def step(self, pool, x, option, is_chance, latent, value, reward, policy_d, policy_c, positions=0, stream=None):
+        """pool float [slots, B, 64, 4, 4]; x, option, is_chance int32 [B]; outputs latent [B, 64, 4, 4], value
+        [B, V], reward [B, V] and policy_d [B, A] (decision rows), policy_c [B, C] (chance rows)"""
+        B = int(x.numel())
+        _lib.call("lzm_smz_conv_net_step", *self._d, _lib.ptr(self.blob), _lib.ptr(pool), int(pool.shape[0]), B,
+                  _lib.ptr(x), _lib.ptr(option), _lib.ptr(is_chance), _lib.ptr(latent), _lib.ptr(value),
+                  _lib.ptr(reward), _lib.ptr(policy_d), _lib.ptr(policy_c), int(positions), _lib.stream_ptr(stream))
+
+    def outputs(self, B):
+        """fresh output buffers for B roots: (latent, value, reward, policy_d, policy_c); rows a step does not
+        write stay zero"""
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=self.device)
+        d = self.dims
+        return z(B, 64, 4, 4), z(B, d["V"]), z(B, d["V"]), z(B, d["A"]), z(B, d["C"])
+
+    def recurrent_inference(self, state, option, afterstate=False, positions=0):
+        """the module's recurrent_inference on a batch of one kind (afterstate=False: the reward rows are zero)"""
+        from .model_mlp import MZNetworkOutput
+        B = state.shape[0]
+        pool = state.to(device=self.device, dtype=torch.float32).contiguous().reshape(1, B, 64, 4, 4)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        lat, value, reward, pd, pc = self.outputs(B)
+        self.step(pool, torch.zeros(B, **i32), option.to(**i32).reshape(B).contiguous(),
+                  torch.full((B,), 0 if afterstate else 1, **i32), lat, value, reward, pd, pc, positions)
+        return MZNetworkOutput(value, reward, pd if afterstate else pc, lat)
 
 
 def folded_initial_or_none(model):

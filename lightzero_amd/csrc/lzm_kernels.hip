@@ -42,6 +42,7 @@
 #include "lzm_az.h"
 #include "lzm_az_fused.h"
 #include "lzm_az_c4_host.h"
+#include "lzm_smz_conv_host.h"
 #include "lzm_tree.h"
 #include "lzm_gumbel.h"
 #include "lzm_stochastic.h"
@@ -3985,6 +3986,78 @@ int lzm_az_c4_net_split_eval(int nres, const float *weights, const float *state,
   const char *e = getenv("LZM_C4_SPLIT_BOARDS");  // "2" / "4": that instantiation (timing experiments)
   const int boards = e && (atoi(e) == 2 || atoi(e) == 4) ? atoi(e) : 0;
   LZM_C4_LAUNCH(c4_launch_net_split_eval(nres, boards, weights, state, n, probs, value, range_err, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int64_t lzm_smz_conv_net_floats(int nres, int A, int C, int V) {
+  return smz_conv_shape_ok(nres, A, C, V) ? smz_conv_layout(nres, V).total : -1;
+}
+
+int lzm_smz_conv_net_prepare(int nres, int A, int C, int V, const float *raw, float *out) {
+  if (!smz_conv_shape_ok(nres, A, C, V) || !raw || !out) {
+    set_err("lzm_smz_conv_net_prepare: need num_res_blocks 1 or 2, 1 <= A, C <= 64, odd V <= 601 and both buffers");
+    return LZM_ERR_ARG;
+  }
+  const SmzConvLayout L = smz_conv_layout(nres, V);
+  memset(out, 0, sizeof(float) * (size_t)L.total);
+  const float *p = raw;
+  for (int kind = 0; kind < 2; ++kind) {
+    float *o = out + (size_t)kind * L.set;
+    // B fragment of v_mfma_f32_16x16x4_f32: lane holds B[k = lane / 16][n = lane % 16]; wave w owns out channels 16 w ..
+    for (int l = 0; l < L.layers; ++l) {
+      const float *wl = p; p += 64 * 576;
+      for (int tap = 0; tap < 9; ++tap)
+        for (int wv = 0; wv < 4; ++wv)
+          for (int j = 0; j < 16; ++j)  // K step j of the tap: in channels 4 j .. 4 j + 3
+            for (int lane = 0; lane < 64; ++lane)
+              o[L.conv + (size_t)((((l * 9 + tap) * 4 + wv) * 4 + (j >> 2)) * 64 + lane) * 4 + (j & 3)] =
+                  wl[(16 * wv + (lane & 15)) * 576 + (4 * j + (lane >> 4)) * 9 + tap];
+      memcpy(o + L.conv_b + l * 64, p, 64 * sizeof(float)); p += 64;
+    }
+    for (int cell = 0; cell < 16; ++cell)
+      for (int ch = 0; ch < 64; ++ch) o[L.edge + ch * 16 + cell] = p[cell * 64 + ch];
+    p += 1024;
+    for (int head = kind ? 1 : 0; head < 3; ++head) {
+      const int n = head < 2 ? V : (kind ? C : A), np = smz_fc2_np(L, head);
+      for (int k = 0; k < 16; ++k)
+        for (int lane = 0; lane < 64; ++lane)
+          o[L.hconv + (head * 16 + k) * 64 + lane] = p[(lane & 15) * 64 + 4 * k + (lane >> 4)];
+      p += 16 * 64;
+      memcpy(o + L.hconv_b + head * 16, p, 16 * sizeof(float)); p += 16;
+      for (int i = 0; i < 32; ++i)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int e = 0; e < 4; ++e)
+            o[L.fc1 + ((head * 32 + i) * 64 + lane) * 4 + e] = p[(lane >> 1) * 256 + (lane & 1) * 128 + 4 * i + e];
+      p += 32 * 256;
+      memcpy(o + L.fc1_b + head * 32, p, 32 * sizeof(float)); p += 32;
+      float *f2 = o + smz_fc2_at(L, head);
+      for (int r = 0; r < n; ++r)
+        for (int u = 0; u < 32; ++u) f2[u * np + r] = p[r * 32 + u];
+      p += n * 32;
+      memcpy(f2 + 32 * np, p, n * sizeof(float)); p += n;
+    }
+  }
+  return LZM_OK;
+}
+
+int lzm_smz_conv_net_step(int nres, int A, int C, int V, const float *weights, const float *pool, int nslots, int B,
+                          const int32_t *x, const int32_t *option, const int32_t *is_chance, float *latent,
+                          float *value, float *reward, float *policy_d, float *policy_c, int positions, void *stream) {
+  if (!smz_conv_shape_ok(nres, A, C, V) || !weights || !pool || nslots <= 0 || B <= 0 || !x || !option || !is_chance ||
+      !latent || !value || !reward || !policy_d || !policy_c || (positions != 0 && positions != 1 && positions != 2)) {
+    set_err("lzm_smz_conv_net_step: need num_res_blocks 1 or 2, 1 <= A, C <= 64, odd V <= 601, nslots > 0, B > 0, "
+            "positions 0, 1 or 2 and all buffers");
+    return LZM_ERR_ARG;
+  }
+  if (positions == 0) {
+    const char *e = getenv("LZM_SMZ_CONV_POSITIONS");  // "1" / "2": that instantiation (timing experiments)
+    if (e && (atoi(e) == 1 || atoi(e) == 2)) positions = atoi(e);
+  }
+  SmzConvArgs a;
+  a.w = weights; a.pool = pool; a.x = x; a.option = option; a.is_chance = is_chance;
+  a.latent = latent; a.value = value; a.reward = reward; a.policy_d = policy_d; a.policy_c = policy_c;
+  a.nslots = nslots; a.B = B; a.A = A; a.C = C; a.V = V;
+  LZM_C4_LAUNCH(smz_conv_launch_step(nres, positions, a, (hipStream_t)stream));
   return LZM_OK;
 }
 

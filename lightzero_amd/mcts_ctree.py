@@ -28,7 +28,7 @@ import torch
 
 from . import _lib
 from .ctree import ez_tree, ezs_tree, gmz_tree, mz_tree, stochastic_mz_tree
-from .conv_infer import FoldedCache
+from .conv_infer import FoldedCache, StochasticConvNet
 from .fused import (NotPackable, PackedCache, pack_efficientzero_mlp, pack_sampled_efficientzero_mlp,
                     pack_stochastic_mlp)
 from .scaling_transform import InverseScalarTransform
@@ -974,7 +974,10 @@ class StochasticMuZeroMCTSCtree(_MCTSCtree):
     to be in parity with and no rng_mode.
     With cfg.fused_search (read with default False: opt-in) a StochasticMuZeroModelMLP's whole search runs as one
     launch (lzm_search_mlp_stoch) where _fused allows it, with the same tree bit for bit given equal network
-    outputs; last_path says which path ran."""
+    outputs; last_path says which path ran.
+    With cfg.native_network (read with default False: opt-in) a conv StochasticMuZeroModel's recurrent step is one
+    launch per simulation (conv_infer.StochasticConvNet: the gather and both recurrent_inference calls become one
+    kernel that runs each root's own half), eager or graph-replayed as the generic path; last_path "native-conv"."""
 
     config = dict(
         root_dirichlet_alpha=0.3,
@@ -986,6 +989,7 @@ class StochasticMuZeroMCTSCtree(_MCTSCtree):
     _tree = stochastic_mz_tree
     reward_name = 'reward'
     rng_mode = None
+    _step_net = None  # the StochasticConvNet of the search in progress (cfg.native_network), else None
 
     @classmethod
     def roots(cls: int, active_collect_env_num: int, legal_actions: List[Any],
@@ -995,10 +999,36 @@ class StochasticMuZeroMCTSCtree(_MCTSCtree):
     def __init__(self, cfg: EasyDict = None) -> None:
         super().__init__(cfg)
         self._packed = PackedCache(pack=pack_stochastic_mlp)
+        self._native_nets = OrderedDict()  # id(model) -> (model weakref, StochasticConvNet or None)
+
+    def _native(self, model, t):
+        """the StochasticConvNet of a model the lzm_smz_conv kernel takes, whose action space, chance space and
+        support are the tree's and the config's, when cfg.native_network is set (absent: off); None otherwise"""
+        if not self._cfg.get('native_network', False) or not self._categorical():
+            return None
+        e = self._native_nets.get(id(model))
+        if e is None or e[0]() is not model:
+            try:
+                net = StochasticConvNet(model, t.device)
+            except NotPackable:
+                net = None
+            e = self._native_nets[id(model)] = (weakref.ref(model), net)
+            while len(self._native_nets) > 4:
+                self._native_nets.popitem(last=False)
+        elif e[1] is not None:
+            e[1].refresh()
+        net = e[1]
+        if net is None or (net.dims["A"], net.dims["C"]) != (t.act, t.chance) or \
+                net.dims["V"] != 2 * int(self._cfg.model.support_scale) + 1:
+            return None
+        return net
+
+    def _net(self, model):
+        return self._step_net if self._step_net is not None else model
 
     def _recorder(self, c, width=1):
-        """width: of the policy_logits rows (the one-launch search records each leaf's row, max(A, C) wide; the
-        per-simulation path records none)"""
+        """width: of the policy_logits rows (the one-launch search and the native conv step record each leaf's row,
+        max(A, C) wide and zero past the kind's width; the generic path records none)"""
         if not self.record:
             return None
         rec = _Recorder(c.S, c.B, width, c.dev)
@@ -1031,17 +1061,33 @@ class StochasticMuZeroMCTSCtree(_MCTSCtree):
         disc, cat, pb_c = self._discount(), self._categorical(), self._pb_c()
         new_minmax(t.B, cfg.value_delta_max, t.device, out=buf.mm)
         f = lambda x: x.float().contiguous()
+        net = self._net(model) if net is None else net
+        if isinstance(net, StochasticConvNet):
+            if getattr(buf, "smz_dims", None) != net.dims:  # one set of head rows for both kinds
+                buf.smz_out, buf.smz_dims = net.outputs(t.B)[1:], dict(net.dims)
+            value, reward, pd, pc = buf.smz_out
+            A, C = net.dims["A"], net.dims["C"]
         for k in range(S):
             if k == 0:
                 t.stochastic_traverse(buf.mm, buf.seeds[0:1], buf.vtp_in, *pb_c, disc)
             if rec is not None:
                 for name in ("x", "action", "search_len", "vtp", "is_chance"):
                     getattr(rec, name)[k].copy_(getattr(t, name))
+            walk = (buf.seeds[k + 1:k + 2], buf.vtp_in, *pb_c) if k + 1 < S else None
+            if isinstance(net, StochasticConvNet):
+                net.step(buf.pool, t.x, t.action, t.is_chance, buf.net_in, value, reward, pd, pc)
+                if rec is not None:
+                    ch, row = t.is_chance.bool().unsqueeze(1), rec.policy_logits[k]
+                    row[:, :C] = torch.where(ch, pc, row[:, :C])
+                    row[:, :A] = torch.where(ch, row[:, :A], pd)
+                t.stochastic_decode_backprop(
+                    k + 1, disc, buf.mm, (value, pc, buf.net_in), (reward, value, pd, buf.net_in), cat, t.vtp,
+                    buf.pool[k + 1], c.row, walk=walk, out_decoded=None if rec is None else rec.decoded[k])
+                continue
             t.gather(buf.pool, c.row, buf.net_in)
             # a chance leaf was reached by an action, a decision leaf by an outcome
             oc = model.recurrent_inference(buf.net_in, t.action64.clamp(0, t.act - 1), afterstate=False)
             od = model.recurrent_inference(buf.net_in, t.action64.clamp(0, t.chance - 1), afterstate=True)
-            walk = (buf.seeds[k + 1:k + 2], buf.vtp_in, *pb_c) if k + 1 < S else None
             t.stochastic_decode_backprop(
                 k + 1, disc, buf.mm, (f(oc.value), f(oc.policy_logits), f(oc.latent_state)),
                 (f(od.reward), f(od.value), f(od.policy_logits), f(od.latent_state)), cat, t.vtp, buf.pool[k + 1],
@@ -1056,9 +1102,10 @@ class StochasticMuZeroMCTSCtree(_MCTSCtree):
             if not getattr(c.t, "chance", 0):
                 raise TypeError("StochasticMuZeroMCTSCtree.search: roots must come from StochasticMuZeroMCTSCtree.roots")
             fz = self._fused(model, c.t, c.S)
+            self._step_net = self._native(model, c.t) if fz is None and c.shape == (64, 4, 4) else None
             self._buffers(c, model, graph=fz is None and not self.record and self._cfg.get('use_hip_graph', False))
             vt, sd = self._stage(c, to_play_batch, seeds, None)
-            rec = self._recorder(c, 1 if fz is None else c.t.A)
+            rec = self._recorder(c, 1 if fz is None and self._step_net is None else c.t.A)
             if fz is None:
                 self._generic(c, model, rec)
             else:  # the whole search in one launch
@@ -1067,7 +1114,7 @@ class StochasticMuZeroMCTSCtree(_MCTSCtree):
                 c.t.search_mlp_stoch(dims, packed, c.S, c.buf.mm, sd, vt, c.buf.pool, *self._pb_c(), self._discount(),
                                      rec=rec)
             self._finish(c, roots, None, rec)
-            self.last_path = "generic" if fz is None else "fused-mlp"
+            self.last_path = "fused-mlp" if fz is not None else ("generic" if self._step_net is None else "native-conv")
 
 
 class SampledEfficientZeroMCTSCtree(_ValuePrefixLSTM, _MCTSCtree):

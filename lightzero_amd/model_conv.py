@@ -12,6 +12,9 @@ DI-engine's ``ResBlock`` (not installed) is restated from its known structure:
 ``basic``: conv3x3-BN-act, conv3x3-BN, + x, act; ``downsample``: conv3x3/2-BN-act, conv3x3-BN,
 + conv3x3/2(x) (no norm), act. All convolutions are bias-free except the 1x1 head convolutions.
 DI-engine's ``MLP`` is ``model_mlp.mlp``.
+- ``StochasticMuZeroModel`` lzero/model/stochastic_muzero_model.py:15-273 (the 2048 config,
+  zoo/game_2048/config/stochastic_muzero_2048_config.py), its ``DynamicsNetwork`` :481-573 and
+  ``AfterstatePredictionNetwork`` :586-689.
 
 Shapes at the Atari configs (observation (4, 64, 64), ``downsample=True``): conv3x3/2 4->32 (32x32),
 basic(32), downsample 32->64 (16x16), basic(64), avgpool3/2 (8x8), basic(64), then
@@ -344,6 +347,107 @@ class EfficientZeroModel(_ConvModelBase):
         nxt, hidden, value_prefix = self.dynamics_network(self._encode(latent_state, action), reward_hidden_state)
         policy_logits, value = self._prediction(nxt)
         return EZNetworkOutput(value, value_prefix, policy_logits, nxt, hidden)
+
+
+class StochasticDynamicsNetwork(DynamicsNetwork):
+    """stochastic_muzero_model.py:481-573 (``AfterstateDynamicsNetwork`` is the same class, :583): MuZero's
+    dynamics over [latent | one scalar option plane], with the reference's norm names ``bn`` / ``bn_reward``."""
+
+    def __init__(self, num_res_blocks, num_channels, reward_head_channels, fc_reward_layers, output_support_size,
+                 flatten_reward, activation, last_linear_layer_init_zero=True):
+        super().__init__(1, num_res_blocks, num_channels, reward_head_channels, fc_reward_layers, output_support_size,
+                         flatten_reward, activation, last_linear_layer_init_zero, 'BN')
+        self.bn = self._modules.pop('norm_common')
+        self.bn_reward = self._modules.pop('norm_reward')
+
+    def trunk(self, state_action_encoding):  # :553-567
+        x = self.bn(self.conv(state_action_encoding))
+        x = self.activation(x + state_action_encoding[:, :-1, :, :])
+        for b in self.resblocks:
+            x = b(x)
+        return x, self.activation(self.bn_reward(self.conv1x1_reward(x)))
+
+
+class AfterstatePredictionNetwork(PredictionNetwork):
+    """stochastic_muzero_model.py:586-689: the prediction network over the chance space, norms named
+    ``bn_value`` / ``bn_policy``."""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.bn_value = self._modules.pop('norm_value')
+        self.bn_policy = self._modules.pop('norm_policy')
+
+    def forward(self, afterstate):  # :673-689
+        for b in self.resblocks:
+            afterstate = b(afterstate)
+        value = self.activation(self.bn_value(self.conv1x1_value(afterstate)))
+        policy = self.activation(self.bn_policy(self.conv1x1_policy(afterstate)))
+        value = self.fc_value(value.reshape(-1, self.flatten_output_size_for_value_head))
+        policy = self.fc_policy(policy.reshape(-1, self.flatten_output_size_for_policy_head))
+        return policy, value
+
+
+class StochasticMuZeroModel(nn.Module):
+    """lzero/model/stochastic_muzero_model.py:15-273 for image-shaped observations (2048: observation (16, 4, 4),
+    4 actions, ``chance_space_size`` 32, no downsample). ``recurrent_inference(state, option, afterstate)`` :233-273:
+    ``afterstate=False`` takes a latent state and an action to the afterstate, its value and the chance logits;
+    ``afterstate=True`` takes an afterstate and an outcome to the next latent state, reward, value and policy
+    logits. The option enters as one constant plane ``option / space`` (:354-377, :408-431; the space is
+    ``chance_space_size`` in ``_dynamics``, ``action_space_size`` in ``_afterstate_dynamics``), divided in float32.
+    Attribute names and ``state_dict`` keys are the reference's. Not restated: the chance encoder (:127) and the
+    self-supervised heads (:177-199), training only; load such a checkpoint with ``strict=False``."""
+
+    def __init__(self, observation_shape=(16, 4, 4), action_space_size=4, chance_space_size=32, num_res_blocks=1,
+                 num_channels=64, reward_head_channels=16, value_head_channels=16, policy_head_channels=16,
+                 fc_reward_layers=(32,), fc_value_layers=(32,), fc_policy_layers=(32,), reward_support_size=601,
+                 value_support_size=601, categorical_distribution=True,
+                 activation: nn.Module = nn.ReLU(inplace=True), last_linear_layer_init_zero=True, state_norm=False,
+                 downsample=False, **kwargs):
+        super().__init__()
+        if state_norm:  # (the reference's renormalize raises on any input, lzero/model/utils.py:120)
+            raise NotImplementedError("StochasticMuZeroModel: state_norm")
+        self.categorical_distribution = categorical_distribution
+        self.reward_support_size = reward_support_size if categorical_distribution else 1
+        self.value_support_size = value_support_size if categorical_distribution else 1
+        self.action_space_size = action_space_size
+        self.chance_space_size = chance_space_size
+        self.state_norm = False
+        self.downsample = downsample
+        if downsample:  # :104-118 (the head inputs after a /16 downsample)
+            latent = math.ceil(observation_shape[1] / 16) * math.ceil(observation_shape[2] / 16)
+        else:
+            latent = observation_shape[1] * observation_shape[2]
+        self.representation_network = RepresentationNetwork(observation_shape, num_res_blocks, num_channels,
+                                                            downsample, activation)
+        dyn = (num_res_blocks, num_channels + 1, reward_head_channels, fc_reward_layers, self.reward_support_size,
+               reward_head_channels * latent, activation, last_linear_layer_init_zero)
+        pred = (num_res_blocks, num_channels, value_head_channels, policy_head_channels, fc_value_layers,
+                fc_policy_layers, self.value_support_size, value_head_channels * latent,
+                policy_head_channels * latent, activation, last_linear_layer_init_zero)
+        self.dynamics_network = StochasticDynamicsNetwork(*dyn)
+        self.prediction_network = PredictionNetwork(action_space_size, *pred)
+        self.afterstate_dynamics_network = StochasticDynamicsNetwork(*dyn)
+        self.afterstate_prediction_network = AfterstatePredictionNetwork(chance_space_size, *pred)
+
+    def initial_inference(self, obs):  # :201-231
+        latent_state = self.representation_network(obs)
+        policy_logits, value = self.prediction_network(latent_state)
+        return MZNetworkOutput(value, [0. for _ in range(obs.size(0))], policy_logits, latent_state)
+
+    def _step(self, network, space, state, option):
+        plane = (option.reshape(-1).float() / space).to(state.dtype).reshape(-1, 1, 1, 1).expand(
+            state.shape[0], 1, state.shape[2], state.shape[3])
+        next_state, reward = network(torch.cat((state, plane), dim=1))
+        return next_state, reward
+
+    def recurrent_inference(self, state, option, afterstate=False):
+        if afterstate:  # state is an afterstate, option a chance outcome
+            next_state, reward = self._step(self.dynamics_network, self.chance_space_size, state, option)
+            policy_logits, value = self.prediction_network(next_state)
+        else:  # state is a latent state, option an action
+            next_state, reward = self._step(self.afterstate_dynamics_network, self.action_space_size, state, option)
+            policy_logits, value = self.afterstate_prediction_network(next_state)
+        return MZNetworkOutput(value, reward, policy_logits, next_state)
 
 
 def atari_efficientzero_model(action_space_size=6, **kw):
