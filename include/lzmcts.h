@@ -535,6 +535,48 @@ int lzm_az_c4_net_split_prepare(int nres, const float *raw, float *out_host);
 int lzm_az_c4_net_split_eval(int nres, const float *weights, const float *state, int n, float *probs, float *value,
                              int32_t *range_err, void *stream);
 
+/* ---- batched AlphaZero for Gomoku 6 x 6 (zoo/board_games/gomoku/envs/gomoku_env.py, get_done_winner_cython.pyx;
+ * the tree of mcts_alphazero.cpp). The protocol, argument meanings and outputs of lzm_az_c4_begin ..
+ * lzm_az_c4_export_priors above, with
+ *   boards int32[B][36] (row-major 6 x 6; 0 empty / 1 / 2), state float[B][3][6][6] (current_state()[1] with
+ *   scale=True: the mover's stones 0.5, the other player's 0.5, 0.5 * player to move),
+ *   probs float[B][pstride >= 36], visits int32[B][36], probs double[B][36].
+ * Action a puts a stone on cell a and is legal iff the cell is empty. A position is terminal when some stone
+ * starts a run of five of its colour (down-left, down, down-right or right) that fits on the board: the winner is
+ * the owner of the first such stone in row-major order (six in a row wins; with fives of both colours the earlier
+ * start cell decides), else when the board is full (winner -1). Every root needs at least one empty cell. Paths
+ * hold up to 37 nodes; a tree row has 1 + 36 (S + 1) nodes. */
+int lzm_az_gmk_workspace_bytes(int B, int S, int64_t *out);
+int lzm_az_gmk_set_constants(int B, int S, void *ws, double pb_c_base, double pb_c_init, double alpha, void *stream);
+int lzm_az_gmk_begin(int B, int S, void *ws, const int32_t *boards, const int32_t *start_index, float *state,
+                     void *stream);
+int lzm_az_gmk_step(int B, int S, void *ws, int sim, const float *probs, int pstride, const float *values, int vstride,
+                    int with_noise, double noise_weight, float *state, void *stream);
+int lzm_az_gmk_finish(int B, int S, void *ws, double temperature, int sample, uint32_t seed, const int64_t *counter,
+                      int32_t *visits, double *probs, int32_t *action, void *stream);
+int lzm_az_gmk_export_tree(int B, int S, void *ws, int32_t *visit, float *vsum, int32_t *first, int32_t *nnodes,
+                           void *stream);
+int lzm_az_gmk_export_priors(int B, int S, void *ws, float *prior, void *stream);
+/* test access: get_done_winner of n device boards int32[n][36] -> out int32[n][2] = {done, winner} */
+int lzm_az_gmk_done_winner(const int32_t *boards, int n, int32_t *out, void *stream);
+
+/* ---- the Gomoku config's AlphaZeroModel (observation (3, 6, 6), 32 channels, num_res_blocks 1 or 2, head channels
+ * 16, head width 32, 36 actions, scalar value) in eval mode, one launch over n positions (lzm_az_gomoku_net.h).
+ * lzm_az_gmk_net_prepare(nres, raw, out) permutes, on the host, `raw` =
+ *   conv0 W[32][27] (out, in*9 + tap), b[32];  4*nres x { conv W[32][288], b[32] } (the representation blocks'
+ *   conv1, conv2, then the prediction's; BatchNorm folded in);  1x1 W[32][32] (value rows, then policy rows),
+ *   b[32];  value head: FC1 [32][576], b[32], LN gamma[32], beta[32], FC2 [32], b[1];  policy head: FC1
+ *   [32][576], b[32], gamma[32], beta[32], FC2 [36][32], b[36]
+ * into lzm_az_gmk_net_floats(nres) floats (MFMA B-fragment order, zero padding), to be copied to the device; nres
+ * outside {1, 2} gives -1. lzm_az_gmk_net_eval: state float[n][3][6][6] -> probs float[n][36] (softmax), value
+ * float[n]; graph-capturable. It runs 1 or 2 positions per workgroup, chosen from n (LZM_GMK_NET_POSITIONS =
+ * 1 / 2 forces one, for timing experiments); a position's output bits do not depend on that choice, on n or on
+ * its place in the batch. */
+int64_t lzm_az_gmk_net_floats(int nres);
+int lzm_az_gmk_net_prepare(int nres, const float *raw, float *out_host);
+int lzm_az_gmk_net_eval(int nres, const float *weights, const float *state, int n, float *probs, float *value,
+                        void *stream);
+
 /* ---- the conv StochasticMuZeroModel's recurrent step (the 2048 config: latent 64 x 4 x 4, num_res_blocks 1 or 2
  * per sub-network, head channels 16, one hidden layer of 32, 1 <= A, C <= 64, categorical heads with odd V <= 601,
  * eval-mode BatchNorm and ReLU), one launch per simulation over B roots (lzm_smz_conv.h).

@@ -20,6 +20,10 @@ has no reproducible stream); tests/test_gpu_az_oracle.py restates the draw on th
 ``game="connect4"`` (or a ``simulate_env`` with 7 actions) searches Connect4 boards [B, 42] the same way through
 lzm_az_c4_begin / step / finish (lzm_az_c4.h); ``Connect4AZNet`` is the Connect4 config's network in one launch
 (lzm_az_c4_net.h), so the whole search is HIP kernels (tests/test_gpu_az_connect4.py: whole trees bit for bit).
+
+``game="gomoku"`` (or a ``simulate_env`` with 36 actions) searches Gomoku 6 x 6 boards [B, 36] through
+lzm_az_gmk_begin / step / finish (lzm_az_gomoku.h), and ``GomokuAZNet`` is the Gomoku config's network in one
+launch (lzm_az_gomoku_net.h; tests/test_gpu_az_gomoku.py: whole trees bit for bit).
 """
 import ctypes
 
@@ -31,7 +35,8 @@ from ._lib import call, ptr, stream_ptr
 
 ACTIONS = 9
 # per game: actions, board cells, network input shape, max_moves default, entry-point prefix
-GAMES = {"tictactoe": (9, 9, (3, 3, 3), 9, "lzm_az_"), "connect4": (7, 42, (3, 6, 7), 42, "lzm_az_c4_")}
+GAMES = {"tictactoe": (9, 9, (3, 3, 3), 9, "lzm_az_"), "connect4": (7, 42, (3, 6, 7), 42, "lzm_az_c4_"),
+         "gomoku": (36, 36, (3, 6, 6), 36, "lzm_az_gmk_")}
 
 
 def _fold_bn(conv, bn):
@@ -162,19 +167,69 @@ class Connect4AZNet:
         return 0 if self._range_err is None else int(self._range_err.item())
 
 
+class GomokuAZNet:
+    """The Gomoku AlphaZeroModel (model_az.gomoku_alphazero_model's structure) packed for lzm_az_gmk_net_eval:
+    BatchNorm folded, MFMA B-fragment order (lzm_az_gmk_net_prepare). Supported: observation (3, 6, 6), 32
+    channels, 1 or 2 residual blocks per network, head channels 16, head width 32, 36 actions, scalar value (the
+    Gomoku config, board_size 6); anything else raises ValueError."""
+
+    def __init__(self, model, device="cuda"):
+        m = model
+        nres = len(m.rep_blocks)
+        ok = (nres in (1, 2) and len(m.pred_blocks) == nres and m.conv.out_channels == 32 and m.conv.in_channels == 3
+              and m.flat_v == 576 and m.flat_p == 576 and m.conv1x1_value.out_channels == 16
+              and m.conv1x1_policy.out_channels == 16 and len(m.fc_value_head) == 4 and len(m.fc_policy_head) == 4
+              and m.fc_value_head[0].out_features == 32 and m.fc_policy_head[0].out_features == 32
+              and m.fc_policy_head[-1].out_features == 36 and m.fc_value_head[-1].out_features == 1
+              and isinstance(m.fc_value_head[1], torch.nn.LayerNorm))
+        if not ok:
+            raise ValueError("the Gomoku network kernel supports the Gomoku AlphaZeroModel config only "
+                             "(observation (3, 6, 6), 32 channels, 1 or 2 residual blocks, 36 actions)")
+        if m.training:
+            raise ValueError("the Gomoku network kernel evaluates the network in eval mode: call model.eval()")
+        self.nres = nres
+        with torch.no_grad():
+            parts = []
+            w, b = _fold_bn(m.conv, m.norm)
+            parts += [w.reshape(32, 27), b]
+            for blk in list(m.rep_blocks) + list(m.pred_blocks):
+                for conv, bn in ((blk.conv1, blk.bn1), (blk.conv2, blk.bn2)):
+                    w, b = _fold_bn(conv, bn)
+                    parts += [w.reshape(32, 288), b]
+            wv, bv = _fold_bn(m.conv1x1_value, m.norm_value)
+            wp, bp = _fold_bn(m.conv1x1_policy, m.norm_policy)
+            parts += [torch.cat([wv.reshape(16, 32), wp.reshape(16, 32)]), torch.cat([bv, bp])]
+            for fc in (m.fc_value_head, m.fc_policy_head):
+                parts += [fc[0].weight, fc[0].bias, fc[1].weight, fc[1].bias, fc[3].weight, fc[3].bias]
+            raw = torch.cat([p.detach().float().cpu().reshape(-1) for p in parts]).contiguous()
+        out = torch.zeros(int(_lib.load().lzm_az_gmk_net_floats(nres)), dtype=torch.float32)
+        call("lzm_az_gmk_net_prepare", nres, ctypes.c_void_p(raw.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+        self.weights = out.to(device)
+
+    def compute_policy_value(self, state):
+        """state [n, 3, 6, 6] -> (probs [n, 36], value [n, 1]); one launch"""
+        st = state.reshape(-1, 108).to(torch.float32).contiguous()
+        n = st.shape[0]
+        probs = torch.empty((n, 36), dtype=torch.float32, device=st.device)
+        value = torch.empty((n, 1), dtype=torch.float32, device=st.device)
+        call("lzm_az_gmk_net_eval", self.nres, ptr(self.weights), ptr(st), n, ptr(probs), ptr(value), stream_ptr())
+        return probs, value
+
+
 class AlphaZeroMCTS:
     def __init__(self, max_moves=None, num_simulations=50, pb_c_base=19652, pb_c_init=1.25, root_dirichlet_alpha=0.3,
                  root_noise_weight=0.25, simulate_env=None, device="cuda", graph=False, seed=0, game=None):
         env_n = getattr(getattr(simulate_env, "action_space", None), "n", None)
         if game is None:
-            game = "connect4" if env_n == 7 else "tictactoe"
+            game = {7: "connect4", 36: "gomoku"}.get(env_n, "tictactoe")
         if game not in GAMES:
             raise ValueError(f"game must be one of {sorted(GAMES)}")
         self.game = game
         self.actions, self.cells, self.state_shape, moves, self._fn = GAMES[game]
         if env_n is not None and env_n != self.actions:
-            raise ValueError("the device simulate env is TicTacToe (9 actions)" if game == "tictactoe" else
-                             "the device simulate env is Connect4 (7 actions)")
+            raise ValueError({"tictactoe": "the device simulate env is TicTacToe (9 actions)",
+                              "connect4": "the device simulate env is Connect4 (7 actions)",
+                              "gomoku": "the device simulate env is Gomoku 6 x 6 (36 actions)"}[game])
         _lib.require_gpu()
         self.max_moves = int(moves if max_moves is None else max_moves)
         self.num_simulations = int(num_simulations)
@@ -296,7 +351,7 @@ class AlphaZeroMCTS:
 
     # ------------------------------------------------------------------ public API
     def get_next_actions(self, boards, start_player_index, compute_policy_value, temperature=1.0, sample=True):
-        """boards [B, 9] (or [B, 3, 3]; Connect4: [B, 42] or [B, 6, 7], row 0 on top) with 0 empty / 1 / 2
+        """boards [B, 9] (or [B, 3, 3]; Connect4: [B, 42] or [B, 6, 7], row 0 on top; Gomoku: [B, 36] or [B, 6, 6]) with 0 empty / 1 / 2
         stones, start_player_index [B] (0: player 1 to move, 1: player 2). Returns (actions int32 [B],
         action_probs float64 [B, actions], device tensors; overwritten by the next call with the same B)."""
         if temperature == 0:

@@ -23,11 +23,13 @@ SOURCES = [os.path.join(HERE, "csrc", "lzm_kernels.hip")]
 # (profiles/EXPERIMENTS.md, "packed FMA") and whose kernels change with it; hence the separate unit.
 # The one-launch Stochastic MuZero and Sampled EfficientZero searches' kernels (lzm_search_stoch_mlp.hip,
 # lzm_search_sampled_mlp.hip) and the Stochastic MuZero conv step (lzm_smz_conv.hip) are built the same way: they
-# use no packed form, and the feature keeps it so.
+# use no packed form, and the feature keeps it so. The Gomoku AlphaZero kernels (lzm_az_gomoku.hip) are pinned like
+# the Connect4 ones and built like them.
 # tools/build_variant.sh builds the same units.
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-NO_PK_SOURCES = [os.path.join(HERE, "csrc", n) for n in ("lzm_az_c4.hip", "lzm_search_stoch_mlp.hip",
-                                                         "lzm_search_sampled_mlp.hip", "lzm_smz_conv.hip")]
+NO_PK_SOURCES = [os.path.join(HERE, "csrc", n) for n in ("lzm_az_c4.hip", "lzm_az_gomoku.hip",
+                                                         "lzm_search_stoch_mlp.hip", "lzm_search_sampled_mlp.hip",
+                                                         "lzm_smz_conv.hip")]
 DEPS = SOURCES + NO_PK_SOURCES + sorted(glob.glob(os.path.join(HERE, "csrc", "*.h")) +
                         glob.glob(os.path.join(HERE, "csrc", "*.inc"))) + [os.path.join(REPO, "include", "lzmcts.h")]
 OUT = os.path.join(HERE, "liblzmcts.so")

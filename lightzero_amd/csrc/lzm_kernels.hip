@@ -42,6 +42,7 @@
 #include "lzm_az.h"
 #include "lzm_az_fused.h"
 #include "lzm_az_c4_host.h"
+#include "lzm_az_gomoku_host.h"
 #include "lzm_smz_conv_host.h"
 #include "lzm_tree.h"
 #include "lzm_gumbel.h"
@@ -3986,6 +3987,162 @@ int lzm_az_c4_net_split_eval(int nres, const float *weights, const float *state,
   const char *e = getenv("LZM_C4_SPLIT_BOARDS");  // "2" / "4": that instantiation (timing experiments)
   const int boards = e && (atoi(e) == 2 || atoi(e) == 4) ? atoi(e) : 0;
   LZM_C4_LAUNCH(c4_launch_net_split_eval(nres, boards, weights, state, n, probs, value, range_err, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+}  // extern "C"
+
+// ---- batched AlphaZero for Gomoku 6 x 6 (kernels and launchers: lzm_az_gomoku.hip). One workspace per (B, S).
+static int64_t gmk_carve(int B, int S, void *ws, GmkTree *t) {
+  const int64_t cap = 1 + (int64_t)kGmkCells * (S + 1);
+  char *p = (char *)ws;
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) -> void * {
+    void *r = p ? (void *)(p + off) : nullptr;
+    off += (bytes + 255) & ~(int64_t)255;
+    return r;
+  };
+  GmkTree x;
+  x.B = B; x.S = S; x.cap = (int)cap;
+  x.rec = (int4 *)take((int64_t)B * cap * 16);
+  x.nnodes = (int32_t *)take((int64_t)B * 4);
+  x.root = (uint64_t *)take((int64_t)B * 16);
+  x.root_player = (int32_t *)take((int64_t)B * 4);
+  x.path = (int32_t *)take((int64_t)B * kGmkPath * 4);
+  x.leaf = (int32_t *)take((int64_t)B * 4 * 4);
+  x.leaf_bb = (uint64_t *)take((int64_t)B * 16);
+  x.lut_pb = (double *)take((int64_t)(S + 1) * 8);
+  x.lut_sqrt = (double *)take((int64_t)(S + 1) * 8);
+  x.noise = (double *)take((int64_t)kGmkCells * kGmkCells * 8);
+  if (t) *t = x;
+  return off;
+}
+
+extern "C" {
+
+int lzm_az_gmk_workspace_bytes(int B, int S, int64_t *out) {
+  if (B <= 0 || S <= 0 || S > (1 << 20) || !out) {
+    set_err("lzm_az_gmk_workspace_bytes: need B > 0, 0 < num_simulations <= 2^20");
+    return LZM_ERR_ARG;
+  }
+  *out = gmk_carve(B, S, nullptr, nullptr);
+  return LZM_OK;
+}
+
+int lzm_az_gmk_set_constants(int B, int S, void *ws, double pb_c_base, double pb_c_init, double alpha, void *stream) {
+  if (!az_args_ok(B, S, ws, "lzm_az_gmk_set_constants")) return LZM_ERR_ARG;
+  if (!(pb_c_base > 0.0) || !(alpha > 0.0)) {
+    set_err("lzm_az_gmk_set_constants: need pb_c_base > 0 and alpha > 0");
+    return LZM_ERR_ARG;
+  }
+  GmkTree t;
+  gmk_carve(B, S, ws, &t);
+  std::vector<double> pb((size_t)S + 1), sq((size_t)S + 1), nz((size_t)kGmkCells * kGmkCells);
+  for (int n = 0; n <= S; ++n) {
+    pb[(size_t)n] = std::log((n + pb_c_base + 1) / pb_c_base) + pb_c_init;
+    sq[(size_t)n] = std::sqrt((double)n);
+  }
+  lzm_az_noise_table(alpha, kGmkCells, nz.data());  // a position has at most 36 children: the first 36 rows
+  hipStream_t s = (hipStream_t)stream;
+  LZM_HIP(hipMemcpyAsync(t.lut_pb, pb.data(), pb.size() * 8, hipMemcpyHostToDevice, s));
+  LZM_HIP(hipMemcpyAsync(t.lut_sqrt, sq.data(), sq.size() * 8, hipMemcpyHostToDevice, s));
+  LZM_HIP(hipMemcpyAsync(t.noise, nz.data(), nz.size() * 8, hipMemcpyHostToDevice, s));
+  LZM_HIP(hipStreamSynchronize(s));
+  return LZM_OK;
+}
+
+int lzm_az_gmk_begin(int B, int S, void *ws, const int32_t *boards, const int32_t *start_index, float *state,
+                     void *stream) {
+  if (!az_args_ok(B, S, ws, "lzm_az_gmk_begin")) return LZM_ERR_ARG;
+  if (!boards || !start_index || !state) {
+    set_err("lzm_az_gmk_begin: null buffer");
+    return LZM_ERR_ARG;
+  }
+  GmkTree t;
+  gmk_carve(B, S, ws, &t);
+  LZM_C4_LAUNCH(gmk_launch_begin(t, boards, start_index, state, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int lzm_az_gmk_step(int B, int S, void *ws, int sim, const float *probs, int pstride, const float *values, int vstride,
+                    int with_noise, double noise_weight, float *state, void *stream) {
+  if (!az_args_ok(B, S, ws, "lzm_az_gmk_step")) return LZM_ERR_ARG;
+  if (sim < -1 || sim >= S || !probs || pstride < kGmkCells || (sim >= 0 && (!values || vstride < 1)) || !state) {
+    set_err("lzm_az_gmk_step: need -1 <= sim < num_simulations, probs [B][>=36], values [B] and a state buffer");
+    return LZM_ERR_ARG;
+  }
+  GmkTree t;
+  gmk_carve(B, S, ws, &t);
+  GmkStepArgs a;
+  a.sim = sim; a.with_noise = with_noise; a.noise_weight = noise_weight;
+  a.probs = probs; a.pstride = pstride; a.values = values ? values : probs; a.vstride = vstride; a.state = state;
+  LZM_C4_LAUNCH(gmk_launch_step(t, a, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int lzm_az_gmk_finish(int B, int S, void *ws, double temperature, int sample, uint32_t seed, const int64_t *counter,
+                      int32_t *visits, double *probs, int32_t *action, void *stream) {
+  if (!az_args_ok(B, S, ws, "lzm_az_gmk_finish")) return LZM_ERR_ARG;
+  if (temperature == 0.0 || !visits || !probs || !action) {
+    set_err("lzm_az_gmk_finish: temperature cannot be 0; visits / probs / action buffers required");
+    return LZM_ERR_ARG;
+  }
+  GmkTree t;
+  gmk_carve(B, S, ws, &t);
+  LZM_C4_LAUNCH(gmk_launch_finish(t, temperature, sample, seed, counter, visits, probs, action, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int lzm_az_gmk_export_tree(int B, int S, void *ws, int32_t *visit, float *vsum, int32_t *first, int32_t *nnodes,
+                           void *stream) {
+  if (!az_args_ok(B, S, ws, "lzm_az_gmk_export_tree")) return LZM_ERR_ARG;
+  GmkTree t;
+  gmk_carve(B, S, ws, &t);
+  LZM_C4_LAUNCH(gmk_launch_export(t, visit, vsum, first, nullptr, nnodes, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int lzm_az_gmk_export_priors(int B, int S, void *ws, float *prior, void *stream) {
+  if (!az_args_ok(B, S, ws, "lzm_az_gmk_export_priors")) return LZM_ERR_ARG;
+  if (!prior) {
+    set_err("lzm_az_gmk_export_priors: null output");
+    return LZM_ERR_ARG;
+  }
+  GmkTree t;
+  gmk_carve(B, S, ws, &t);
+  LZM_C4_LAUNCH(gmk_launch_export(t, nullptr, nullptr, nullptr, prior, nullptr, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int lzm_az_gmk_done_winner(const int32_t *boards, int n, int32_t *out, void *stream) {
+  if (!boards || n <= 0 || !out) {
+    set_err("lzm_az_gmk_done_winner: need boards [n][36], n > 0 and out [n][2]");
+    return LZM_ERR_ARG;
+  }
+  LZM_C4_LAUNCH(gmk_launch_done_winner(boards, n, out, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int64_t lzm_az_gmk_net_floats(int nres) { return nres == 1 || nres == 2 ? gmk_net_layout(nres).total : -1; }
+
+int lzm_az_gmk_net_prepare(int nres, const float *raw, float *out) {
+  if ((nres != 1 && nres != 2) || !raw || !out) {
+    set_err("lzm_az_gmk_net_prepare: num_res_blocks must be 1 or 2");
+    return LZM_ERR_ARG;
+  }
+  gmk_net_pack(nres, raw, out);
+  return LZM_OK;
+}
+
+int lzm_az_gmk_net_eval(int nres, const float *weights, const float *state, int n, float *probs, float *value,
+                        void *stream) {
+  if ((nres != 1 && nres != 2) || !weights || !state || n <= 0 || !probs || !value) {
+    set_err("lzm_az_gmk_net_eval: need num_res_blocks 1 or 2, n > 0 and all buffers");
+    return LZM_ERR_ARG;
+  }
+  const char *e = getenv("LZM_GMK_NET_POSITIONS");  // "1" / "2": that instantiation (timing experiments)
+  const int pos = e && (atoi(e) == 1 || atoi(e) == 2) ? atoi(e) : 0;
+  LZM_C4_LAUNCH(gmk_launch_net_eval(nres, pos, weights, state, n, probs, value, (hipStream_t)stream));
   return LZM_OK;
 }
 
