@@ -577,6 +577,42 @@ int lzm_az_gmk_net_prepare(int nres, const float *raw, float *out_host);
 int lzm_az_gmk_net_eval(int nres, const float *weights, const float *state, int n, float *probs, float *value,
                         void *stream);
 
+/* ---- batched AlphaZero for Gomoku 9 x 9 and 15 x 15 (lzm_az_gomoku_n.h): the lzm_az_gmk_* family above with the
+ * board size N = n_board as the first argument. boards int32[B][N^2] (row-major N x N), state float[B][3][N][N],
+ * probs float[B][>= N^2], visits int32[B][N^2], probs_out double[B][N^2]; same rules, protocol and outputs. One
+ * workspace per (n_board, B, S). Paths hold up to min(N^2, S + 1) + 1 nodes; a tree row has 1 + N^2 (S + 1) nodes.
+ * An n_board outside {9, 15} gives LZM_ERR_ARG before any device call (6 x 6 is the lzm_az_gmk_* family). */
+int lzm_az_gmkn_workspace_bytes(int n_board, int B, int S, int64_t *out);
+int lzm_az_gmkn_set_constants(int n_board, int B, int S, void *ws, double pb_c_base, double pb_c_init, double alpha,
+                              void *stream);
+int lzm_az_gmkn_begin(int n_board, int B, int S, void *ws, const int32_t *boards, const int32_t *start_index,
+                      float *state, void *stream);
+int lzm_az_gmkn_step(int n_board, int B, int S, void *ws, int sim, const float *probs, int pstride, const float *values,
+                     int vstride, int with_noise, double noise_weight, float *state, void *stream);
+int lzm_az_gmkn_finish(int n_board, int B, int S, void *ws, double temperature, int sample, uint32_t seed,
+                       const int64_t *counter, int32_t *visits, double *probs, int32_t *action, void *stream);
+int lzm_az_gmkn_export_tree(int n_board, int B, int S, void *ws, int32_t *visit, float *vsum, int32_t *first,
+                            int32_t *nnodes, void *stream);
+int lzm_az_gmkn_export_priors(int n_board, int B, int S, void *ws, float *prior, void *stream);
+/* test access: get_done_winner of n device boards int32[n][N^2] -> out int32[n][2] = {done, winner} */
+int lzm_az_gmkn_done_winner(int n_board, const int32_t *boards, int n, int32_t *out, void *stream);
+
+/* ---- the Gomoku AlphaZeroModel at observation (3, N, N), N = n_board in {9, 15} (32 channels, num_res_blocks 1 or
+ * 2, head channels 16, head width 32, N^2 actions, scalar value) in eval mode, one launch over n positions
+ * (lzm_az_gomoku_n_net.h). lzm_az_gmkn_net_prepare(n_board, nres, raw, out) permutes, on the host, `raw` =
+ *   conv0 W[32][27] (out, in*9 + tap), b[32];  4*nres x { conv W[32][288], b[32] } (the representation blocks'
+ *   conv1, conv2, then the prediction's; BatchNorm folded in);  1x1 W[32][32] (value rows, then policy rows),
+ *   b[32];  value head: FC1 [32][16 N^2], b[32], LN gamma[32], beta[32], FC2 [32], b[1];  policy head: FC1
+ *   [32][16 N^2], b[32], gamma[32], beta[32], FC2 [N^2][32], b[N^2]
+ * into lzm_az_gmkn_net_floats(n_board, nres) floats (MFMA B-fragment order, zero padding), to be copied to the
+ * device; a board size outside {9, 15} or nres outside {1, 2} gives -1 / LZM_ERR_ARG. lzm_az_gmkn_net_eval: state
+ * float[n][3][N][N] -> probs float[n][N^2] (softmax), value float[n]; graph-capturable. One position per workgroup;
+ * a position's output bits do not depend on n or on its place in the batch. */
+int64_t lzm_az_gmkn_net_floats(int n_board, int nres);
+int lzm_az_gmkn_net_prepare(int n_board, int nres, const float *raw, float *out_host);
+int lzm_az_gmkn_net_eval(int n_board, int nres, const float *weights, const float *state, int n, float *probs,
+                         float *value, void *stream);
+
 /* ---- the conv StochasticMuZeroModel's recurrent step (the 2048 config: latent 64 x 4 x 4, num_res_blocks 1 or 2
  * per sub-network, head channels 16, one hidden layer of 32, 1 <= A, C <= 64, categorical heads with odd V <= 601,
  * eval-mode BatchNorm and ReLU), one launch per simulation over B roots (lzm_smz_conv.h).

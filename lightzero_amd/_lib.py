@@ -179,6 +179,17 @@ SIGNATURES = {
     "lzm_az_gmk_net_floats": [_i],
     "lzm_az_gmk_net_prepare": [_i, _vp, _vp],
     "lzm_az_gmk_net_eval": [_i, _vp, _vp, _i, _vp, _vp, _vp],
+    "lzm_az_gmkn_workspace_bytes": [_i, _i, _i, ctypes.POINTER(_i64)],
+    "lzm_az_gmkn_set_constants": [_i, _i, _i, _vp, _d, _d, _d, _vp],
+    "lzm_az_gmkn_begin": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "lzm_az_gmkn_step": [_i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _d, _vp, _vp],
+    "lzm_az_gmkn_finish": [_i, _i, _i, _vp, _d, _i, _u32, _vp, _vp, _vp, _vp, _vp],
+    "lzm_az_gmkn_export_tree": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "lzm_az_gmkn_export_priors": [_i, _i, _i, _vp, _vp, _vp],
+    "lzm_az_gmkn_done_winner": [_i, _vp, _i, _vp, _vp],
+    "lzm_az_gmkn_net_floats": [_i, _i],
+    "lzm_az_gmkn_net_prepare": [_i, _i, _vp, _vp],
+    "lzm_az_gmkn_net_eval": [_i, _i, _vp, _vp, _i, _vp, _vp, _vp],
     "lzm_smz_conv_net_floats": [_i] * 4,
     "lzm_smz_conv_net_prepare": [_i] * 4 + [_vp, _vp],
     "lzm_smz_conv_net_step": [_i] * 4 + [_vp, _vp, _i, _i] + [_vp] * 8 + [_i, _vp],
@@ -250,7 +261,7 @@ _RESTYPE = {"lzm_last_error": ctypes.c_char_p, "lzm_mlp_packed_floats": ctypes.c
             "lzm_mlp_stoch_packed_floats": ctypes.c_int64, "lzm_mlp_stoch_kernel_floats": ctypes.c_int64,
             "lzm_mlp_sampled_packed_floats": ctypes.c_int64, "lzm_mlp_sampled_kernel_floats": ctypes.c_int64,
             "lzm_az_c4_net_floats": ctypes.c_int64, "lzm_az_c4_net_split_floats": ctypes.c_int64,
-            "lzm_az_gmk_net_floats": ctypes.c_int64,
+            "lzm_az_gmk_net_floats": ctypes.c_int64, "lzm_az_gmkn_net_floats": ctypes.c_int64,
             "lzm_smz_conv_net_floats": ctypes.c_int64,
             "lzm_conv_trunk_floats": ctypes.c_int64, "lzm_conv_trunk_floats_p": ctypes.c_int64,
             "lzm_ez_lstm_frag_floats": ctypes.c_int64, "lzm_ez_lstm_workspace_bytes": ctypes.c_int64,

@@ -23,7 +23,10 @@ lzm_az_c4_begin / step / finish (lzm_az_c4.h); ``Connect4AZNet`` is the Connect4
 
 ``game="gomoku"`` (or a ``simulate_env`` with 36 actions) searches Gomoku 6 x 6 boards [B, 36] through
 lzm_az_gmk_begin / step / finish (lzm_az_gomoku.h), and ``GomokuAZNet`` is the Gomoku config's network in one
-launch (lzm_az_gomoku_net.h; tests/test_gpu_az_gomoku.py: whole trees bit for bit).
+launch (lzm_az_gomoku_net.h; tests/test_gpu_az_gomoku.py: whole trees bit for bit). ``board_size=9`` or ``15`` (or a
+``simulate_env`` with 81 or 225 actions) searches boards [B, N^2] through lzm_az_gmkn_begin / step / finish
+(lzm_az_gomoku_n.h), and ``GomokuAZNet`` of a (3, N, N) model runs lzm_az_gomoku_n_net.h
+(tests/test_gpu_az_gomoku_n.py: whole trees bit for bit).
 """
 import ctypes
 
@@ -37,6 +40,7 @@ ACTIONS = 9
 # per game: actions, board cells, network input shape, max_moves default, entry-point prefix
 GAMES = {"tictactoe": (9, 9, (3, 3, 3), 9, "lzm_az_"), "connect4": (7, 42, (3, 6, 7), 42, "lzm_az_c4_"),
          "gomoku": (36, 36, (3, 6, 6), 36, "lzm_az_gmk_")}
+GOMOKU_SIZES = (6, 9, 15)  # 6: lzm_az_gmk_*; 9, 15: lzm_az_gmkn_* with the board size as the first argument
 
 
 def _fold_bn(conv, bn):
@@ -168,26 +172,32 @@ class Connect4AZNet:
 
 
 class GomokuAZNet:
-    """The Gomoku AlphaZeroModel (model_az.gomoku_alphazero_model's structure) packed for lzm_az_gmk_net_eval:
-    BatchNorm folded, MFMA B-fragment order (lzm_az_gmk_net_prepare). Supported: observation (3, 6, 6), 32
-    channels, 1 or 2 residual blocks per network, head channels 16, head width 32, 36 actions, scalar value (the
-    Gomoku config, board_size 6); anything else raises ValueError."""
+    """The Gomoku AlphaZeroModel (model_az.gomoku_alphazero_model's structure) packed for lzm_az_gmk_net_eval
+    (board_size 6) or lzm_az_gmkn_net_eval (board_size 9, 15): BatchNorm folded, MFMA B-fragment order
+    (lzm_az_gmk_net_prepare / lzm_az_gmkn_net_prepare). Supported: observation (3, N, N) with N in {6, 9, 15}, 32
+    channels, 1 or 2 residual blocks per network, head channels 16, head width 32, N^2 actions, scalar value (the
+    Gomoku config); anything else raises ValueError."""
 
     def __init__(self, model, device="cuda"):
         m = model
         nres = len(m.rep_blocks)
+        cells = int(m.fc_policy_head[-1].out_features) if len(m.fc_policy_head) == 4 else 0
+        size = {n * n: n for n in GOMOKU_SIZES}.get(cells, 0)
         ok = (nres in (1, 2) and len(m.pred_blocks) == nres and m.conv.out_channels == 32 and m.conv.in_channels == 3
-              and m.flat_v == 576 and m.flat_p == 576 and m.conv1x1_value.out_channels == 16
+              and size != 0 and m.flat_v == 16 * cells and m.flat_p == 16 * cells
+              and m.conv1x1_value.out_channels == 16
               and m.conv1x1_policy.out_channels == 16 and len(m.fc_value_head) == 4 and len(m.fc_policy_head) == 4
               and m.fc_value_head[0].out_features == 32 and m.fc_policy_head[0].out_features == 32
-              and m.fc_policy_head[-1].out_features == 36 and m.fc_value_head[-1].out_features == 1
-              and isinstance(m.fc_value_head[1], torch.nn.LayerNorm))
+              and m.fc_value_head[-1].out_features == 1 and isinstance(m.fc_value_head[1], torch.nn.LayerNorm))
         if not ok:
             raise ValueError("the Gomoku network kernel supports the Gomoku AlphaZeroModel config only "
-                             "(observation (3, 6, 6), 32 channels, 1 or 2 residual blocks, 36 actions)")
+                             "(observation (3, N, N) with N in 6, 9, 15, 32 channels, 1 or 2 residual blocks, "
+                             "N * N actions)")
         if m.training:
             raise ValueError("the Gomoku network kernel evaluates the network in eval mode: call model.eval()")
-        self.nres = nres
+        self.nres, self.board_size, self.cells = nres, size, cells
+        # the entry points and their leading arguments: the 9 x 9 / 15 x 15 family carries the board size
+        self._fn, self._lead = ("lzm_az_gmk_net_", (nres,)) if size == 6 else ("lzm_az_gmkn_net_", (size, nres))
         with torch.no_grad():
             parts = []
             w, b = _fold_bn(m.conv, m.norm)
@@ -202,34 +212,49 @@ class GomokuAZNet:
             for fc in (m.fc_value_head, m.fc_policy_head):
                 parts += [fc[0].weight, fc[0].bias, fc[1].weight, fc[1].bias, fc[3].weight, fc[3].bias]
             raw = torch.cat([p.detach().float().cpu().reshape(-1) for p in parts]).contiguous()
-        out = torch.zeros(int(_lib.load().lzm_az_gmk_net_floats(nres)), dtype=torch.float32)
-        call("lzm_az_gmk_net_prepare", nres, ctypes.c_void_p(raw.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+        out = torch.zeros(int(getattr(_lib.load(), self._fn + "floats")(*self._lead)), dtype=torch.float32)
+        call(self._fn + "prepare", *self._lead, ctypes.c_void_p(raw.data_ptr()), ctypes.c_void_p(out.data_ptr()))
         self.weights = out.to(device)
 
     def compute_policy_value(self, state):
-        """state [n, 3, 6, 6] -> (probs [n, 36], value [n, 1]); one launch"""
-        st = state.reshape(-1, 108).to(torch.float32).contiguous()
+        """state [n, 3, N, N] -> (probs [n, N^2], value [n, 1]); one launch"""
+        st = state.reshape(-1, 3 * self.cells).to(torch.float32).contiguous()
         n = st.shape[0]
-        probs = torch.empty((n, 36), dtype=torch.float32, device=st.device)
+        probs = torch.empty((n, self.cells), dtype=torch.float32, device=st.device)
         value = torch.empty((n, 1), dtype=torch.float32, device=st.device)
-        call("lzm_az_gmk_net_eval", self.nres, ptr(self.weights), ptr(st), n, ptr(probs), ptr(value), stream_ptr())
+        call(self._fn + "eval", *self._lead, ptr(self.weights), ptr(st), n, ptr(probs), ptr(value), stream_ptr())
         return probs, value
 
 
 class AlphaZeroMCTS:
     def __init__(self, max_moves=None, num_simulations=50, pb_c_base=19652, pb_c_init=1.25, root_dirichlet_alpha=0.3,
-                 root_noise_weight=0.25, simulate_env=None, device="cuda", graph=False, seed=0, game=None):
+                 root_noise_weight=0.25, simulate_env=None, device="cuda", graph=False, seed=0, game=None,
+                 board_size=None):
         env_n = getattr(getattr(simulate_env, "action_space", None), "n", None)
         if game is None:
-            game = {7: "connect4", 36: "gomoku"}.get(env_n, "tictactoe")
+            game = {7: "connect4", 36: "gomoku", 81: "gomoku", 225: "gomoku"}.get(env_n, "tictactoe")
         if game not in GAMES:
             raise ValueError(f"game must be one of {sorted(GAMES)}")
         self.game = game
         self.actions, self.cells, self.state_shape, moves, self._fn = GAMES[game]
+        self._lead = ()  # arguments in front of (B, S, ...): the board size for Gomoku 9 x 9 / 15 x 15
+        if game == "gomoku":
+            if board_size is None:
+                board_size = {81: 9, 225: 15}.get(env_n, 6)
+            if board_size not in GOMOKU_SIZES:
+                raise ValueError(f"Gomoku board_size must be one of {GOMOKU_SIZES}, not {board_size!r}")
+            if board_size != 6:
+                n = int(board_size)
+                self.actions, self.cells, self.state_shape, moves = n * n, n * n, (3, n, n), n * n
+                self._fn, self._lead = "lzm_az_gmkn_", (n,)
+        elif board_size is not None:
+            raise ValueError("board_size belongs to game='gomoku'")
+        self.board_size = board_size
         if env_n is not None and env_n != self.actions:
             raise ValueError({"tictactoe": "the device simulate env is TicTacToe (9 actions)",
                               "connect4": "the device simulate env is Connect4 (7 actions)",
-                              "gomoku": "the device simulate env is Gomoku 6 x 6 (36 actions)"}[game])
+                              "gomoku": f"the device simulate env is Gomoku {board_size} x {board_size} "
+                                        f"({self.actions} actions)"}[game])
         _lib.require_gpu()
         self.max_moves = int(moves if max_moves is None else max_moves)
         self.num_simulations = int(num_simulations)
@@ -248,7 +273,7 @@ class AlphaZeroMCTS:
         if c is not None:
             return c
         nbytes = ctypes.c_int64()
-        call(self._fn + "workspace_bytes", B, self.num_simulations, ctypes.byref(nbytes))
+        call(self._fn + "workspace_bytes", *self._lead, B, self.num_simulations, ctypes.byref(nbytes))
         dev = self.device
         c = dict(ws=torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev),
                  boards=torch.zeros((B, self.cells), dtype=torch.int32, device=dev),
@@ -257,8 +282,8 @@ class AlphaZeroMCTS:
                  visits=torch.zeros((B, self.actions), dtype=torch.int32, device=dev),
                  probs=torch.zeros((B, self.actions), dtype=torch.float64, device=dev),
                  action=torch.zeros(B, dtype=torch.int32, device=dev), graphs={})
-        call(self._fn + "set_constants", B, self.num_simulations, ptr(c["ws"]), self.pb_c_base, self.pb_c_init,
-             self.alpha, stream_ptr())
+        call(self._fn + "set_constants", *self._lead, B, self.num_simulations, ptr(c["ws"]), self.pb_c_base,
+             self.pb_c_init, self.alpha, stream_ptr())
         self._ctx[B] = c
         return c
 
@@ -276,14 +301,14 @@ class AlphaZeroMCTS:
         s = stream_ptr()
         begin, step, finish = self._fn + "begin", self._fn + "step", self._fn + "finish"
         with torch.no_grad():
-            call(begin, B, S, ws, ptr(c["boards"]), ptr(c["start"]), st, s)
+            call(begin, *self._lead, B, S, ws, ptr(c["boards"]), ptr(c["start"]), st, s)
             probs, value = self._evaluate(pv, c, B)
-            call(step, B, S, ws, -1, ptr(probs), probs.shape[1], ptr(value), 1, int(bool(sample)),
+            call(step, *self._lead, B, S, ws, -1, ptr(probs), probs.shape[1], ptr(value), 1, int(bool(sample)),
                  self.noise_weight, st, s)
             for k in range(S):
                 probs, value = self._evaluate(pv, c, B)
-                call(step, B, S, ws, k, ptr(probs), probs.shape[1], ptr(value), 1, 0, 0.0, st, s)
-            call(finish, B, S, ws, float(temperature), int(bool(sample)), self.seed, ptr(self._count),
+                call(step, *self._lead, B, S, ws, k, ptr(probs), probs.shape[1], ptr(value), 1, 0, 0.0, st, s)
+            call(finish, *self._lead, B, S, ws, float(temperature), int(bool(sample)), self.seed, ptr(self._count),
                  ptr(c["visits"]), ptr(c["probs"]), ptr(c["action"]), s)
             self._count.add_(1)
 
@@ -351,7 +376,7 @@ class AlphaZeroMCTS:
 
     # ------------------------------------------------------------------ public API
     def get_next_actions(self, boards, start_player_index, compute_policy_value, temperature=1.0, sample=True):
-        """boards [B, 9] (or [B, 3, 3]; Connect4: [B, 42] or [B, 6, 7], row 0 on top; Gomoku: [B, 36] or [B, 6, 6]) with 0 empty / 1 / 2
+        """boards [B, 9] (or [B, 3, 3]; Connect4: [B, 42] or [B, 6, 7], row 0 on top; Gomoku: [B, N^2] or [B, N, N]) with 0 empty / 1 / 2
         stones, start_player_index [B] (0: player 1 to move, 1: player 2). Returns (actions int32 [B],
         action_probs float64 [B, actions], device tensors; overwritten by the next call with the same B)."""
         if temperature == 0:
@@ -384,7 +409,8 @@ class AlphaZeroMCTS:
                torch.empty((B, cap), dtype=torch.float32, device=self.device),
                torch.empty((B, cap), dtype=torch.int32, device=self.device),
                torch.empty(B, dtype=torch.int32, device=self.device)]
-        call(self._fn + "export_tree", B, self.num_simulations, ptr(c["ws"]), *[ptr(t) for t in out], stream_ptr())
+        call(self._fn + "export_tree", *self._lead, B, self.num_simulations, ptr(c["ws"]), *[ptr(t) for t in out],
+             stream_ptr())
         return out
 
     def export_priors(self, B):
@@ -392,7 +418,7 @@ class AlphaZeroMCTS:
         c = self._buffers(B)
         cap = 1 + self.actions * (self.num_simulations + 1)
         out = torch.empty((B, cap), dtype=torch.float32, device=self.device)
-        call(self._fn + "export_priors", B, self.num_simulations, ptr(c["ws"]), ptr(out), stream_ptr())
+        call(self._fn + "export_priors", *self._lead, B, self.num_simulations, ptr(c["ws"]), ptr(out), stream_ptr())
         return out
 
 

@@ -43,6 +43,7 @@
 #include "lzm_az_fused.h"
 #include "lzm_az_c4_host.h"
 #include "lzm_az_gomoku_host.h"
+#include "lzm_az_gomoku_n_host.h"
 #include "lzm_smz_conv_host.h"
 #include "lzm_tree.h"
 #include "lzm_gumbel.h"
@@ -4143,6 +4144,193 @@ int lzm_az_gmk_net_eval(int nres, const float *weights, const float *state, int 
   const char *e = getenv("LZM_GMK_NET_POSITIONS");  // "1" / "2": that instantiation (timing experiments)
   const int pos = e && (atoi(e) == 1 || atoi(e) == 2) ? atoi(e) : 0;
   LZM_C4_LAUNCH(gmk_launch_net_eval(nres, pos, weights, state, n, probs, value, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+}  // extern "C"
+
+// ---- batched AlphaZero for Gomoku 9 x 9 and 15 x 15 (kernels and launchers: lzm_az_gomoku_n.hip). One workspace per
+// (board size, B, S).
+static int64_t gmkn_carve(int n_board, int B, int S, void *ws, GmkNTree *t) {
+  const int cells = n_board * n_board;
+  const int64_t cap = 1 + (int64_t)cells * (S + 1);
+  char *p = (char *)ws;
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) -> void * {
+    void *r = p ? (void *)(p + off) : nullptr;
+    off += (bytes + 255) & ~(int64_t)255;
+    return r;
+  };
+  GmkNTree x;
+  x.B = B; x.S = S; x.cap = (int)cap; x.path_len = gmkn_path_len(cells, S);
+  x.rec = (int4 *)take((int64_t)B * cap * 16);
+  x.nnodes = (int32_t *)take((int64_t)B * 4);
+  x.root = (uint64_t *)take((int64_t)B * 2 * kGmkNWords * 8);
+  x.root_player = (int32_t *)take((int64_t)B * 4);
+  x.path = (int32_t *)take((int64_t)B * x.path_len * 4);
+  x.leaf = (int32_t *)take((int64_t)B * 4 * 4);
+  x.leaf_bb = (uint64_t *)take((int64_t)B * 2 * kGmkNWords * 8);
+  x.lut_pb = (double *)take((int64_t)(S + 1) * 8);
+  x.lut_sqrt = (double *)take((int64_t)(S + 1) * 8);
+  x.noise = (double *)take((int64_t)cells * cells * 8);
+  if (t) *t = x;
+  return off;
+}
+
+// the board size and the (B, S, workspace) triple; S is bounded so that a tree row's node indices stay in int
+static bool gmkn_args_ok(int n_board, int B, int S, const void *ws, bool need_ws, const char *what) {
+  if (!gmkn_size_ok(n_board)) {
+    snprintf(g_err, sizeof(g_err), "%s: board size %d is not supported: the supported sizes are 9 and 15 (6: lzm_az_gmk_*)",
+             what, n_board);
+    return false;
+  }
+  if (B <= 0 || S <= 0 || S > (1 << 20) || (need_ws && !ws)) {
+    snprintf(g_err, sizeof(g_err), "%s: need B > 0, 0 < num_simulations <= 2^20%s", what, need_ws ? " and a workspace" : "");
+    return false;
+  }
+  return true;
+}
+
+static bool gmkn_net_args_ok(int n_board, int nres, const char *what) {
+  if (!gmkn_size_ok(n_board) || (nres != 1 && nres != 2)) {
+    snprintf(g_err, sizeof(g_err), "%s: the supported board sizes are 9 and 15 (got %d), num_res_blocks 1 or 2 (got %d)",
+             what, n_board, nres);
+    return false;
+  }
+  return true;
+}
+
+extern "C" {
+
+int lzm_az_gmkn_workspace_bytes(int n_board, int B, int S, int64_t *out) {
+  if (!gmkn_args_ok(n_board, B, S, nullptr, false, "lzm_az_gmkn_workspace_bytes")) return LZM_ERR_ARG;
+  if (!out) {
+    set_err("lzm_az_gmkn_workspace_bytes: null output");
+    return LZM_ERR_ARG;
+  }
+  *out = gmkn_carve(n_board, B, S, nullptr, nullptr);
+  return LZM_OK;
+}
+
+int lzm_az_gmkn_set_constants(int n_board, int B, int S, void *ws, double pb_c_base, double pb_c_init, double alpha,
+                              void *stream) {
+  if (!gmkn_args_ok(n_board, B, S, ws, true, "lzm_az_gmkn_set_constants")) return LZM_ERR_ARG;
+  if (!(pb_c_base > 0.0) || !(alpha > 0.0)) {
+    set_err("lzm_az_gmkn_set_constants: need pb_c_base > 0 and alpha > 0");
+    return LZM_ERR_ARG;
+  }
+  const int cells = n_board * n_board;
+  GmkNTree t;
+  gmkn_carve(n_board, B, S, ws, &t);
+  std::vector<double> pb((size_t)S + 1), sq((size_t)S + 1), nz((size_t)cells * cells);
+  for (int n = 0; n <= S; ++n) {
+    pb[(size_t)n] = std::log((n + pb_c_base + 1) / pb_c_base) + pb_c_init;
+    sq[(size_t)n] = std::sqrt((double)n);
+  }
+  lzm_az_noise_table(alpha, cells, nz.data());  // a position has at most N^2 children: the first N^2 rows
+  hipStream_t s = (hipStream_t)stream;
+  LZM_HIP(hipMemcpyAsync(t.lut_pb, pb.data(), pb.size() * 8, hipMemcpyHostToDevice, s));
+  LZM_HIP(hipMemcpyAsync(t.lut_sqrt, sq.data(), sq.size() * 8, hipMemcpyHostToDevice, s));
+  LZM_HIP(hipMemcpyAsync(t.noise, nz.data(), nz.size() * 8, hipMemcpyHostToDevice, s));
+  LZM_HIP(hipStreamSynchronize(s));
+  return LZM_OK;
+}
+
+int lzm_az_gmkn_begin(int n_board, int B, int S, void *ws, const int32_t *boards, const int32_t *start_index,
+                      float *state, void *stream) {
+  if (!gmkn_args_ok(n_board, B, S, ws, true, "lzm_az_gmkn_begin")) return LZM_ERR_ARG;
+  if (!boards || !start_index || !state) {
+    set_err("lzm_az_gmkn_begin: null buffer");
+    return LZM_ERR_ARG;
+  }
+  GmkNTree t;
+  gmkn_carve(n_board, B, S, ws, &t);
+  LZM_C4_LAUNCH(gmkn_launch_begin(n_board, t, boards, start_index, state, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int lzm_az_gmkn_step(int n_board, int B, int S, void *ws, int sim, const float *probs, int pstride, const float *values,
+                     int vstride, int with_noise, double noise_weight, float *state, void *stream) {
+  if (!gmkn_args_ok(n_board, B, S, ws, true, "lzm_az_gmkn_step")) return LZM_ERR_ARG;
+  if (sim < -1 || sim >= S || !probs || pstride < n_board * n_board || (sim >= 0 && (!values || vstride < 1)) || !state) {
+    set_err("lzm_az_gmkn_step: need -1 <= sim < num_simulations, probs [B][>= N^2], values [B] and a state buffer");
+    return LZM_ERR_ARG;
+  }
+  GmkNTree t;
+  gmkn_carve(n_board, B, S, ws, &t);
+  GmkNStepArgs a;
+  a.sim = sim; a.with_noise = with_noise; a.noise_weight = noise_weight;
+  a.probs = probs; a.pstride = pstride; a.values = values ? values : probs; a.vstride = vstride; a.state = state;
+  LZM_C4_LAUNCH(gmkn_launch_step(n_board, t, a, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int lzm_az_gmkn_finish(int n_board, int B, int S, void *ws, double temperature, int sample, uint32_t seed,
+                       const int64_t *counter, int32_t *visits, double *probs, int32_t *action, void *stream) {
+  if (!gmkn_args_ok(n_board, B, S, ws, true, "lzm_az_gmkn_finish")) return LZM_ERR_ARG;
+  if (temperature == 0.0 || !visits || !probs || !action) {
+    set_err("lzm_az_gmkn_finish: temperature cannot be 0; visits / probs / action buffers required");
+    return LZM_ERR_ARG;
+  }
+  GmkNTree t;
+  gmkn_carve(n_board, B, S, ws, &t);
+  LZM_C4_LAUNCH(gmkn_launch_finish(n_board, t, temperature, sample, seed, counter, visits, probs, action,
+                                   (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int lzm_az_gmkn_export_tree(int n_board, int B, int S, void *ws, int32_t *visit, float *vsum, int32_t *first,
+                            int32_t *nnodes, void *stream) {
+  if (!gmkn_args_ok(n_board, B, S, ws, true, "lzm_az_gmkn_export_tree")) return LZM_ERR_ARG;
+  GmkNTree t;
+  gmkn_carve(n_board, B, S, ws, &t);
+  LZM_C4_LAUNCH(gmkn_launch_export(t, visit, vsum, first, nullptr, nnodes, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int lzm_az_gmkn_export_priors(int n_board, int B, int S, void *ws, float *prior, void *stream) {
+  if (!gmkn_args_ok(n_board, B, S, ws, true, "lzm_az_gmkn_export_priors")) return LZM_ERR_ARG;
+  if (!prior) {
+    set_err("lzm_az_gmkn_export_priors: null output");
+    return LZM_ERR_ARG;
+  }
+  GmkNTree t;
+  gmkn_carve(n_board, B, S, ws, &t);
+  LZM_C4_LAUNCH(gmkn_launch_export(t, nullptr, nullptr, nullptr, prior, nullptr, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int lzm_az_gmkn_done_winner(int n_board, const int32_t *boards, int n, int32_t *out, void *stream) {
+  if (!gmkn_size_ok(n_board) || !boards || n <= 0 || !out) {
+    set_err("lzm_az_gmkn_done_winner: the supported board sizes are 9 and 15; need boards [n][N^2], n > 0 and out [n][2]");
+    return LZM_ERR_ARG;
+  }
+  LZM_C4_LAUNCH(gmkn_launch_done_winner(n_board, boards, n, out, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int64_t lzm_az_gmkn_net_floats(int n_board, int nres) {
+  return gmkn_size_ok(n_board) && (nres == 1 || nres == 2) ? gmkn_net_layout(nres, n_board).total : -1;
+}
+
+int lzm_az_gmkn_net_prepare(int n_board, int nres, const float *raw, float *out) {
+  if (!gmkn_net_args_ok(n_board, nres, "lzm_az_gmkn_net_prepare")) return LZM_ERR_ARG;
+  if (!raw || !out) {
+    set_err("lzm_az_gmkn_net_prepare: null buffer");
+    return LZM_ERR_ARG;
+  }
+  gmkn_net_pack(nres, n_board, raw, out);
+  return LZM_OK;
+}
+
+int lzm_az_gmkn_net_eval(int n_board, int nres, const float *weights, const float *state, int n, float *probs,
+                         float *value, void *stream) {
+  if (!gmkn_net_args_ok(n_board, nres, "lzm_az_gmkn_net_eval")) return LZM_ERR_ARG;
+  if (!weights || !state || n <= 0 || !probs || !value) {
+    set_err("lzm_az_gmkn_net_eval: need n > 0 and all buffers");
+    return LZM_ERR_ARG;
+  }
+  LZM_C4_LAUNCH(gmkn_launch_net_eval(n_board, nres, weights, state, n, probs, value, (hipStream_t)stream));
   return LZM_OK;
 }
 

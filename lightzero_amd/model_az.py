@@ -91,10 +91,12 @@ def connect4_alphazero_model(random_heads: bool = True) -> AlphaZeroModel:
     return m.eval()
 
 
-def gomoku_alphazero_model(random_heads: bool = True) -> AlphaZeroModel:
+def gomoku_alphazero_model(random_heads: bool = True, board_size: int = 6) -> AlphaZeroModel:
     """The Gomoku config's network in eval mode (zoo/board_games/gomoku/config/
     gomoku_alphazero_sp_mode_config.py: board_size 6, observation (3, 6, 6), 36 actions, 1 residual block, 32
-    channels, head channels 16, value / policy head width 32); random_heads as tictactoe_alphazero_model's."""
-    m = AlphaZeroModel((3, 6, 6), 36, num_res_blocks=1, num_channels=32, fc_value_layers=(32,),
+    channels, head channels 16, value / policy head width 32); random_heads as tictactoe_alphazero_model's.
+    board_size N gives the same network at observation (3, N, N) with N^2 actions, as the config does."""
+    n = int(board_size)
+    m = AlphaZeroModel((3, n, n), n * n, num_res_blocks=1, num_channels=32, fc_value_layers=(32,),
                        fc_policy_layers=(32,), last_linear_layer_init_zero=not random_heads)
     return m.eval()

@@ -7,7 +7,8 @@ median. Raw runs go to --out as JSON, the summary to stdout. --instantiations al
 events around 200 launches) at --net-batches for every built positions-per-workgroup instantiation
 (LZM_GMK_NET_POSITIONS), alternating three times. With --net-only N it only runs the HIP network N times at
 --positions positions under the environment's instantiation (for a kernel trace: rocprofv3 --kernel-trace --stats
--- python ... --net-only 50).
+-- python ... --net-only 50). --board-size 9 / 15 times the lzm_az_gmkn_* family, which builds one position per
+workgroup only.
 """
 import argparse
 import json
@@ -24,16 +25,19 @@ from lightzero_amd.alphazero import AlphaZeroMCTS, GomokuAZNet  # noqa: E402
 from lightzero_amd.model_az import gomoku_alphazero_model  # noqa: E402
 
 SIMS = 50
-# conv0 + 4 conv3x3 32->32 + 1x1 heads + the two FC1 per position, multiply-adds x 2
-FLOP_PER_POSITION = 2 * (36 * 27 * 32 + 4 * 36 * 288 * 32 + 36 * 32 * 32 + 2 * 576 * 32)
 
 
-def boards(B, seed=0):
+def flop_per_position(cells):
+    """conv0 + 4 conv3x3 32->32 + 1x1 heads + the two FC1 per position, multiply-adds x 2"""
+    return 2 * (cells * 27 * 32 + 4 * cells * 288 * 32 + cells * 32 * 32 + 2 * 16 * cells * 32)
+
+
+def boards(B, seed=0, cells=36):
     """positions 0..15 random stones into a game"""
     rng = np.random.default_rng(seed)
-    out = np.zeros((B, 36), np.int32)
+    out = np.zeros((B, cells), np.int32)
     for b in range(B):
-        for k, c in enumerate(rng.permutation(36)[:int(rng.integers(0, 16))]):
+        for k, c in enumerate(rng.permutation(cells)[:int(rng.integers(0, 16))]):
             out[b, c] = 1 + k % 2
     return out, np.zeros(B, np.int32)
 
@@ -65,37 +69,41 @@ def main():
     ap.add_argument("--positions", type=int, default=512, help="batch of the --net-only calls")
     ap.add_argument("--instantiations", action="store_true")
     ap.add_argument("--net-batches", type=int, nargs="*", default=[32, 128, 256, 512, 1024, 2048, 4096])
+    ap.add_argument("--board-size", type=int, default=6, choices=[6, 9, 15])
     args = ap.parse_args()
+    N = args.board_size
+    env = "LZM_GMK_NET_POSITIONS"  # read by the 6 x 6 family only
+    built = ("1", "2") if N == 6 else ("1",)
     torch.manual_seed(0)
-    model = gomoku_alphazero_model().cuda()
+    model = gomoku_alphazero_model(board_size=N).cuda()
     net = GomokuAZNet(model)
     if args.net_only:
-        x = torch.rand(args.positions, 3, 6, 6, device="cuda")
+        x = torch.rand(args.positions, 3, N, N, device="cuda")
         for _ in range(args.net_only):
             net.compute_policy_value(x)
         torch.cuda.synchronize()
         return
-    result = {"sims": SIMS, "flop_per_position": FLOP_PER_POSITION, "runs": [], "net_us": []}
+    result = {"sims": SIMS, "board_size": N, "flop_per_position": flop_per_position(N * N), "runs": [], "net_us": []}
     if args.instantiations:
-        forced = os.environ.pop("LZM_GMK_NET_POSITIONS", None)
+        forced = os.environ.pop(env, None)
         for n in args.net_batches:
-            x = torch.rand(n, 3, 6, 6, device="cuda")
+            x = torch.rand(n, 3, N, N, device="cuda")
             for turn in range(3):
-                for p in ("1", "2"):
-                    os.environ["LZM_GMK_NET_POSITIONS"] = p
+                for p in built:
+                    os.environ[env] = p
                     if turn == 0:
                         time_net(net, x, 20)
                     result["net_us"].append({"n": n, "positions": int(p), "turn": turn, "us": time_net(net, x)})
-            os.environ.pop("LZM_GMK_NET_POSITIONS")
-            for p in (1, 2):
+            os.environ.pop(env)
+            for p in map(int, built):
                 us = [r["us"] for r in result["net_us"] if r["n"] == n and r["positions"] == p]
                 print(f"net n={n} positions/workgroup={p}: {['%.2f' % u for u in us]} us per launch")
         if forced is not None:
-            os.environ["LZM_GMK_NET_POSITIONS"] = forced
+            os.environ[env] = forced
     variants = {"hip": net.compute_policy_value, "torch": model.compute_policy_value}
     for B in (32, 512):
-        bd, st = boards(B)
-        mcts = {k: AlphaZeroMCTS(None, SIMS, game="gomoku", graph=True) for k in variants}
+        bd, st = boards(B, cells=N * N)
+        mcts = {k: AlphaZeroMCTS(None, SIMS, game="gomoku", graph=True, board_size=N) for k in variants}
         for k, pv in variants.items():  # capture and warm up
             for _ in range(3):
                 mcts[k].get_next_actions(bd, st, pv, 1.0, True)

@@ -28,3 +28,5 @@ echo "# ---- lzm_search_sampled_mlp.hip (working tree)"
 lines "$root/lightzero_amd/csrc/lzm_search_sampled_mlp.hip" -Xclang -target-feature -Xclang -packed-fp32-ops
 echo "# ---- lzm_az_gomoku.hip (working tree)"
 lines "$root/lightzero_amd/csrc/lzm_az_gomoku.hip" -Xclang -target-feature -Xclang -packed-fp32-ops
+echo "# ---- lzm_az_gomoku_n.hip (working tree)"
+lines "$root/lightzero_amd/csrc/lzm_az_gomoku_n.hip" -Xclang -target-feature -Xclang -packed-fp32-ops
