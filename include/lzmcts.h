@@ -612,6 +612,18 @@ int64_t lzm_az_gmkn_net_floats(int n_board, int nres);
 int lzm_az_gmkn_net_prepare(int n_board, int nres, const float *raw, float *out_host);
 int lzm_az_gmkn_net_eval(int n_board, int nres, const float *weights, const float *state, int n, float *probs,
                          float *value, void *stream);
+/* The same network with its 32 -> 32 3x3 layers and 1x1 heads on split-fp16 MFMA (lzm_az_gomoku_n_net_split.h; every
+ * f32 operand as two fp16 terms, three products per term pair, error at the f32 level). lzm_az_gmkn_net_split_prepare
+ * takes the same `raw` and writes lzm_az_gmkn_net_split_floats(n_board, nres) floats: the fragments, each weight
+ * row's 2^-e_c and each layer's {max row L1 norm, max |bias|}. lzm_az_gmkn_net_split_eval is graph-capturable like
+ * lzm_az_gmkn_net_eval; range_err (device int32, caller-zeroed, required) gains 1 per position whose activations
+ * left the split's range (non-finite, or beyond ~2^114); such a position's outputs are not meaningful. One position
+ * per workgroup; a position's output bits do not depend on n or on its place in the batch. A board size outside
+ * {9, 15} or nres outside {1, 2} gives -1 / LZM_ERR_ARG before any device call. */
+int64_t lzm_az_gmkn_net_split_floats(int n_board, int nres);
+int lzm_az_gmkn_net_split_prepare(int n_board, int nres, const float *raw, float *out_host);
+int lzm_az_gmkn_net_split_eval(int n_board, int nres, const float *weights, const float *state, int n, float *probs,
+                               float *value, int32_t *range_err, void *stream);
 
 /* ---- the conv StochasticMuZeroModel's recurrent step (the 2048 config: latent 64 x 4 x 4, num_res_blocks 1 or 2
  * per sub-network, head channels 16, one hidden layer of 32, 1 <= A, C <= 64, categorical heads with odd V <= 601,

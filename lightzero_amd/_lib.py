@@ -190,6 +190,9 @@ SIGNATURES = {
     "lzm_az_gmkn_net_floats": [_i, _i],
     "lzm_az_gmkn_net_prepare": [_i, _i, _vp, _vp],
     "lzm_az_gmkn_net_eval": [_i, _i, _vp, _vp, _i, _vp, _vp, _vp],
+    "lzm_az_gmkn_net_split_floats": [_i, _i],
+    "lzm_az_gmkn_net_split_prepare": [_i, _i, _vp, _vp],
+    "lzm_az_gmkn_net_split_eval": [_i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp],
     "lzm_smz_conv_net_floats": [_i] * 4,
     "lzm_smz_conv_net_prepare": [_i] * 4 + [_vp, _vp],
     "lzm_smz_conv_net_step": [_i] * 4 + [_vp, _vp, _i, _i] + [_vp] * 8 + [_i, _vp],
@@ -262,6 +265,7 @@ _RESTYPE = {"lzm_last_error": ctypes.c_char_p, "lzm_mlp_packed_floats": ctypes.c
             "lzm_mlp_sampled_packed_floats": ctypes.c_int64, "lzm_mlp_sampled_kernel_floats": ctypes.c_int64,
             "lzm_az_c4_net_floats": ctypes.c_int64, "lzm_az_c4_net_split_floats": ctypes.c_int64,
             "lzm_az_gmk_net_floats": ctypes.c_int64, "lzm_az_gmkn_net_floats": ctypes.c_int64,
+            "lzm_az_gmkn_net_split_floats": ctypes.c_int64,
             "lzm_smz_conv_net_floats": ctypes.c_int64,
             "lzm_conv_trunk_floats": ctypes.c_int64, "lzm_conv_trunk_floats_p": ctypes.c_int64,
             "lzm_ez_lstm_frag_floats": ctypes.c_int64, "lzm_ez_lstm_workspace_bytes": ctypes.c_int64,

@@ -176,9 +176,18 @@ class GomokuAZNet:
     (board_size 6) or lzm_az_gmkn_net_eval (board_size 9, 15): BatchNorm folded, MFMA B-fragment order
     (lzm_az_gmk_net_prepare / lzm_az_gmkn_net_prepare). Supported: observation (3, N, N) with N in {6, 9, 15}, 32
     channels, 1 or 2 residual blocks per network, head channels 16, head width 32, N^2 actions, scalar value (the
-    Gomoku config); anything else raises ValueError."""
+    Gomoku config); anything else raises ValueError.
 
-    def __init__(self, model, device="cuda"):
+    precision="f32" (the default) is the exact-f32 MFMA kernel; "split" (board_size 9 and 15 only) packs with
+    lzm_az_gmkn_net_split_prepare and runs lzm_az_gmkn_net_split_eval (lzm_az_gomoku_n_net_split.h: the 32 -> 32
+    layers on fp16 MFMA, every operand as two fp16 terms, error at the f32 level). range_errors() then counts the
+    positions whose activations left the split's range since construction (non-finite weights or inputs, magnitudes
+    beyond ~2^114); always 0 for "f32"."""
+
+    def __init__(self, model, device="cuda", precision="f32"):
+        if precision not in ("f32", "split"):
+            raise ValueError(f"precision must be 'f32' or 'split', not {precision!r}")
+        self.precision = precision
         m = model
         nres = len(m.rep_blocks)
         cells = int(m.fc_policy_head[-1].out_features) if len(m.fc_policy_head) == 4 else 0
@@ -198,6 +207,10 @@ class GomokuAZNet:
         self.nres, self.board_size, self.cells = nres, size, cells
         # the entry points and their leading arguments: the 9 x 9 / 15 x 15 family carries the board size
         self._fn, self._lead = ("lzm_az_gmk_net_", (nres,)) if size == 6 else ("lzm_az_gmkn_net_", (size, nres))
+        if precision == "split":
+            if size == 6:
+                raise ValueError("precision='split' supports board sizes 9 and 15; the 6 x 6 network is f32 only")
+            self._fn = "lzm_az_gmkn_net_split_"
         with torch.no_grad():
             parts = []
             w, b = _fold_bn(m.conv, m.norm)
@@ -215,6 +228,7 @@ class GomokuAZNet:
         out = torch.zeros(int(getattr(_lib.load(), self._fn + "floats")(*self._lead)), dtype=torch.float32)
         call(self._fn + "prepare", *self._lead, ctypes.c_void_p(raw.data_ptr()), ctypes.c_void_p(out.data_ptr()))
         self.weights = out.to(device)
+        self._range_err = torch.zeros(1, dtype=torch.int32, device=device) if precision == "split" else None
 
     def compute_policy_value(self, state):
         """state [n, 3, N, N] -> (probs [n, N^2], value [n, 1]); one launch"""
@@ -222,8 +236,13 @@ class GomokuAZNet:
         n = st.shape[0]
         probs = torch.empty((n, self.cells), dtype=torch.float32, device=st.device)
         value = torch.empty((n, 1), dtype=torch.float32, device=st.device)
-        call(self._fn + "eval", *self._lead, ptr(self.weights), ptr(st), n, ptr(probs), ptr(value), stream_ptr())
+        err = () if self._range_err is None else (ptr(self._range_err),)
+        call(self._fn + "eval", *self._lead, ptr(self.weights), ptr(st), n, ptr(probs), ptr(value), *err, stream_ptr())
         return probs, value
+
+    def range_errors(self):
+        """positions whose activations left the split kernel's range so far (synchronises)"""
+        return 0 if self._range_err is None else int(self._range_err.item())
 
 
 class AlphaZeroMCTS:

@@ -24,10 +24,12 @@ SOURCES = [os.path.join(HERE, "csrc", "lzm_kernels.hip")]
 # The one-launch Stochastic MuZero and Sampled EfficientZero searches' kernels (lzm_search_stoch_mlp.hip,
 # lzm_search_sampled_mlp.hip) and the Stochastic MuZero conv step (lzm_smz_conv.hip) are built the same way: they
 # use no packed form, and the feature keeps it so. The Gomoku AlphaZero kernels (lzm_az_gomoku.hip) are pinned like
-# the Connect4 ones and built like them, and so are the 9 x 9 / 15 x 15 ones (lzm_az_gomoku_n.hip).
+# the Connect4 ones and built like them, and so are the 9 x 9 / 15 x 15 ones (lzm_az_gomoku_n.hip) and their
+# split-fp16 network (lzm_az_gomoku_n_split.hip, a unit of its own so that the f32 kernels' unit compiles as before).
 # tools/build_variant.sh builds the same units.
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 NO_PK_SOURCES = [os.path.join(HERE, "csrc", n) for n in ("lzm_az_c4.hip", "lzm_az_gomoku.hip", "lzm_az_gomoku_n.hip",
+                                                         "lzm_az_gomoku_n_split.hip",
                                                          "lzm_search_stoch_mlp.hip", "lzm_search_sampled_mlp.hip",
                                                          "lzm_smz_conv.hip")]
 DEPS = SOURCES + NO_PK_SOURCES + sorted(glob.glob(os.path.join(HERE, "csrc", "*.h")) +

@@ -54,6 +54,7 @@
 #include "lzm_search_sampled_mlp.h"
 #include "lzm_search_res.h"
 #include "lzm_conv.h"
+#include "lzm_az_gomoku_n_split_host.h"
 #include "lzm_repr.h"
 #include "lzm_heads.h"
 #include "lzm_lstm.h"
@@ -4331,6 +4332,32 @@ int lzm_az_gmkn_net_eval(int n_board, int nres, const float *weights, const floa
     return LZM_ERR_ARG;
   }
   LZM_C4_LAUNCH(gmkn_launch_net_eval(n_board, nres, weights, state, n, probs, value, (hipStream_t)stream));
+  return LZM_OK;
+}
+
+int64_t lzm_az_gmkn_net_split_floats(int n_board, int nres) {
+  return gmkn_size_ok(n_board) && (nres == 1 || nres == 2) ? gmkn_split_layout(nres, n_board).total : -1;
+}
+
+int lzm_az_gmkn_net_split_prepare(int n_board, int nres, const float *raw, float *out) {
+  if (!gmkn_net_args_ok(n_board, nres, "lzm_az_gmkn_net_split_prepare")) return LZM_ERR_ARG;
+  if (!raw || !out) {
+    set_err("lzm_az_gmkn_net_split_prepare: null buffer");
+    return LZM_ERR_ARG;
+  }
+  gmkn_split_pack(nres, n_board, raw, out);
+  return LZM_OK;
+}
+
+int lzm_az_gmkn_net_split_eval(int n_board, int nres, const float *weights, const float *state, int n, float *probs,
+                               float *value, int32_t *range_err, void *stream) {
+  if (!gmkn_net_args_ok(n_board, nres, "lzm_az_gmkn_net_split_eval")) return LZM_ERR_ARG;
+  if (!weights || !state || n <= 0 || !probs || !value || !range_err) {
+    set_err("lzm_az_gmkn_net_split_eval: need n > 0 and all buffers (range_err included)");
+    return LZM_ERR_ARG;
+  }
+  LZM_C4_LAUNCH(gmkn_launch_net_split_eval(n_board, nres, weights, state, n, probs, value, range_err,
+                                           (hipStream_t)stream));
   return LZM_OK;
 }
 

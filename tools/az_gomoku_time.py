@@ -8,7 +8,9 @@ events around 200 launches) at --net-batches for every built positions-per-workg
 (LZM_GMK_NET_POSITIONS), alternating three times. With --net-only N it only runs the HIP network N times at
 --positions positions under the environment's instantiation (for a kernel trace: rocprofv3 --kernel-trace --stats
 -- python ... --net-only 50). --board-size 9 / 15 times the lzm_az_gmkn_* family, which builds one position per
-workgroup only.
+workgroup only. With --precision split (board sizes 9 and 15) the two search variants are the f32 and the split-fp16
+HIP networks, alternating five times, and the network alone is timed at --net-batches for both, alternating three
+times.
 """
 import argparse
 import json
@@ -70,13 +72,16 @@ def main():
     ap.add_argument("--instantiations", action="store_true")
     ap.add_argument("--net-batches", type=int, nargs="*", default=[32, 128, 256, 512, 1024, 2048, 4096])
     ap.add_argument("--board-size", type=int, default=6, choices=[6, 9, 15])
+    ap.add_argument("--precision", choices=["f32", "split"], default="f32",
+                    help="the HIP network's kernel; split: the searches alternate f32 and split instead of hip and torch")
     args = ap.parse_args()
     N = args.board_size
+    split = args.precision == "split"
     env = "LZM_GMK_NET_POSITIONS"  # read by the 6 x 6 family only
     built = ("1", "2") if N == 6 else ("1",)
     torch.manual_seed(0)
     model = gomoku_alphazero_model(board_size=N).cuda()
-    net = GomokuAZNet(model)
+    net = GomokuAZNet(model, precision=args.precision)
     if args.net_only:
         x = torch.rand(args.positions, 3, N, N, device="cuda")
         for _ in range(args.net_only):
@@ -101,6 +106,19 @@ def main():
         if forced is not None:
             os.environ[env] = forced
     variants = {"hip": net.compute_policy_value, "torch": model.compute_policy_value}
+    if split:
+        nets = {"f32": GomokuAZNet(model), "split": net}
+        variants = {k: v.compute_policy_value for k, v in nets.items()}
+        for n in args.net_batches:
+            x = torch.rand(n, 3, N, N, device="cuda")
+            for turn in range(3):
+                for k, v in nets.items():
+                    if turn == 0:
+                        time_net(v, x, 20)
+                    result["net_us"].append({"n": n, "variant": k, "turn": turn, "us": time_net(v, x)})
+            for k in nets:
+                us = [r["us"] for r in result["net_us"] if r["n"] == n and r.get("variant") == k]
+                print(f"net n={n} {k}: {['%.2f' % u for u in us]} us per launch")
     for B in (32, 512):
         bd, st = boards(B, cells=N * N)
         mcts = {k: AlphaZeroMCTS(None, SIMS, game="gomoku", graph=True, board_size=N) for k in variants}
@@ -108,7 +126,7 @@ def main():
             for _ in range(3):
                 mcts[k].get_next_actions(bd, st, pv, 1.0, True)
         torch.cuda.synchronize()
-        for turn in range(3):
+        for turn in range(5 if split else 3):
             for k, pv in variants.items():
                 ms = time_search(mcts[k], bd, st, pv)
                 result["runs"].append({"B": B, "variant": k, "turn": turn, "ms": ms})
@@ -117,6 +135,9 @@ def main():
             allms = [m for r in result["runs"] if r["B"] == B and r["variant"] == k for m in r["ms"]]
             print(f"B={B} sims={SIMS} {k}: median of 5 per turn {['%.3f' % m for m in med]} ms, "
                   f"median {statistics.median(med):.3f} ms, all runs {min(allms):.3f} .. {max(allms):.3f} ms")
+    if split:
+        result["range_errors"] = net.range_errors()
+        print(f"range errors: {result['range_errors']}")
     os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1)

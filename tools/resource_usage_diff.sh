@@ -30,3 +30,5 @@ echo "# ---- lzm_az_gomoku.hip (working tree)"
 lines "$root/lightzero_amd/csrc/lzm_az_gomoku.hip" -Xclang -target-feature -Xclang -packed-fp32-ops
 echo "# ---- lzm_az_gomoku_n.hip (working tree)"
 lines "$root/lightzero_amd/csrc/lzm_az_gomoku_n.hip" -Xclang -target-feature -Xclang -packed-fp32-ops
+echo "# ---- lzm_az_gomoku_n_split.hip (working tree)"
+lines "$root/lightzero_amd/csrc/lzm_az_gomoku_n_split.hip" -Xclang -target-feature -Xclang -packed-fp32-ops
